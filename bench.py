@@ -11,7 +11,7 @@ close -- is measured at N = 1 by running the `twopaco` CLI as a child process on
 written out as FASTA files (`e2e` in the JSON line).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload m2|m1] [--scale S]
-                  [--decomposition ranges|address] [--cpu-baseline sample|full|none] [--e2e-runs R]
+                  [--decomposition ranges|address] [--cpu-baseline sample|full|none] [--e2e-runs R] [--dump-outputs DIR]
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) starts
 `python -m torch.distributed.run --nproc-per-node N` on this file as a CHILD process (before anything
@@ -82,6 +82,39 @@ def one_step(ctx, abundance=(1 << 64) - 1):
     J = ctx.junctions_finalize()
     n_marked, n_valid = ctx.emit()
     return marks, st, J, n_valid
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: all arrays together, .npy headers included
+
+
+def dump_outputs(ctx, out_dir, marks, st, J, n_valid):
+    """--dump-outputs DIR: what the last timed step left for its caller, as float64 .npy files that two builds can be compared by.
+      counters.npy            candidate marks, distinct junctions, junction occurrences, true / false junctions, exact-filter table
+                              size, length of the (position, id) lists
+      junction_positions.npy  text positions of the emit lists (tpc_emit_fetch), in position order
+      junction_ids.npy        their ids, same rows (an id beyond 2^53 is rounded; INVALID_VERTEX marks a Bloom false positive)
+      junction_keys.npy       the sorted junction keys (tpc_junction_keys), every 64-bit word as two exact 32-bit halves, low first
+    Lists too long for DUMP_BYTES are cut to a fixed sample of rows (seeded, in order), the same for the same list lengths."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    counters = np.array([marks, J, n_valid, st["true"], st["false"], st["table"], ctx.n_marked], dtype=np.float64)
+    g, ids = ctx.emit_fetch()
+    order = np.argsort(g, kind="stable")
+    g, ids = g[order], ids[order]
+    keys = ctx.junction_keys()
+    halves = np.stack([keys & np.uint64(0xFFFFFFFF), keys >> np.uint64(32)], axis=-1).reshape(keys.shape[0], 2 * keys.shape[1])
+    budget = (DUMP_BYTES - counters.nbytes - 4 * 4096) // 2  # half to the emit lists, half to the keys (4 KiB per header, generously)
+    rng = np.random.default_rng(GOLDEN_SEED)
+
+    def rows(n, row_bytes):
+        m = budget // row_bytes
+        return slice(None) if n <= m else np.sort(rng.choice(n, size=m, replace=False))
+
+    pick = rows(g.size, 2 * 8)
+    arrays = {"counters": counters, "junction_positions": g[pick].astype(np.float64), "junction_ids": ids[pick].astype(np.float64),
+              "junction_keys": halves[rows(halves.shape[0], 8 * halves.shape[1])].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def write_fasta_files(recs, tmp, n=None, p=None):
@@ -271,7 +304,13 @@ def main():
                          "power-of-two N), or vertex-hash ranges (the reference's rounds side by side, no data-path exchange).  auto: "
                          "address at every power-of-two N (the scaling curve is one decomposition); below 8 GPUs the range "
                          "decomposition is timed as well and reported under the key 'ranges' (DESIGN.md section 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: after the timed steps write what the last one computed to DIR/*.npy (float64, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("TPC_FORCE_DIST")):
+        ap.error("--dump-outputs covers the single-GPU path (--gpus 1) only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -341,6 +380,8 @@ def main():
     # bytes per level-2 entry as the passes ran them (tpc_binsp.h: 48-bit query entries in lines of 20, 24-bit insert entries in lines of 40)
     q_l2_bytes = 128 / 20 if ctx.stat("query_entry_fmt") == 6 else 8.0
     i_l2_bytes = 128 / 40 if ctx.stat("insert_entry_fmt") == 3 else 4.0
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, marks, st, J, n_valid)
     result = {"candidate_marks": marks, "junctions": J, "junction_occurrences": n_valid, **st}
     result_ok = None
     if golden:  # the reference's own counters for this workload (VE.h:384-388), tests/golden/cases.json

@@ -6,6 +6,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+# rank processes of one test that share a GPU: with the test process itself that keeps five processes on a device.
+# combined_worker puts rank r on GPU r // RANKS_PER_GPU, so a world of eight needs two GPUs.
+RANKS_PER_GPU = 4
+
 
 class OracleBackend:
     """CPU stand-in for the HIP backend -- TEST ONLY: lets the rank orchestration (ranges, key
@@ -138,9 +142,9 @@ def addr_worker(rank, world, port, spec, result_path):
 
 
 def combined_worker(rank, world, port, spec, result_path):
-    """The combined exchange (twopaco_amd/dist.py:Combined; include/twopaco_hip.h tpc_combine_*): `world` ranks over gloo, every context
-    on GPU 0 with option replicate_filter.  Each rank reports its WHOLE filter and its round mask after every round's query, and the
-    final (position, id) list.  spec["peek"]: the filter is also downloaded between insert and query (the imported lists are then
+    """The combined exchange (twopaco_amd/dist.py:Combined; include/twopaco_hip.h tpc_combine_*): `world` ranks over gloo, the context of
+    rank r on GPU r // RANKS_PER_GPU with option replicate_filter.  Each rank reports its WHOLE filter and its round mask after every
+    round's query, and the final (position, id) list.  spec["peek"]: the filter is also downloaded between insert and query (the imported lists are then
     applied without a lookup riding along, and the query reads the dense filter)."""
     import pickle
 
@@ -154,7 +158,8 @@ def combined_worker(rank, world, port, spec, result_path):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    torch.cuda.set_device(0)
+    gpu = rank // RANKS_PER_GPU
+    torch.cuda.set_device(gpu)
     letters = np.frombuffer(b"ACGTN", dtype=np.uint8)
     code_of = np.zeros(256, dtype=np.uint8)
     code_of[letters] = np.arange(5, dtype=np.uint8)
@@ -167,7 +172,7 @@ def combined_worker(rank, world, port, spec, result_path):
         else:
             recs, _ = synth.workload(sp["workload"], scale=sp["scale"])
             text = capi.PackedText.from_codes(recs)
-        ctx = capi.Context(0)
+        ctx = capi.Context(gpu)
         for opt, val in sp.get("options", {}).items():
             ctx.set_option(opt, val)
         ctx.set_option("replicate_filter", 1)
@@ -177,7 +182,7 @@ def combined_worker(rank, world, port, spec, result_path):
         ctx.shard_config(rank, world)  # before the upload (the window) and the parameters (the filter stays whole)
         ctx.set_params(sp["k"], sp["L"], sp["q"], capi.seed_table(sp["q"], sp["L"], seed=sp["seed"]))
         ctx.seq_upload(text)
-        sh = tdist.Combined(ctx, dist, torch.device("cuda", 0), configure=False, mode=sp.get("mode"))
+        sh = tdist.Combined(ctx, dist, torch.device("cuda", gpu), configure=False, mode=sp.get("mode"))
         out = {"rounds": []}
         for lo, hi in sp["ranges"]:
             sh.insert(lo, hi)

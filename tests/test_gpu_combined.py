@@ -1,5 +1,5 @@
 """GPU (-m gpu): the combined multi-GPU exchange -- the Bloom filter REPLICATED through set-bit lists (include/twopaco_hip.h
-tpc_combine_*, csrc/tpc_combine.hip, twopaco_amd/dist.py:Combined) -- on 2, 4 and 8 ranks sharing GPU 0 over a gloo rendezvous.
+tpc_combine_*, csrc/tpc_combine.hip, twopaco_amd/dist.py:Combined) -- on 2, 4 and 8 ranks over a gloo rendezvous, at most four of them on one GPU.
 What the reference's threads get from one shared ConcurrentBitVector (concurrentbitvector.cpp:31-45, MergeOr :115-122) every rank
 must end up with here: after a round's query EVERY rank holds the oracle's whole filter bit for bit, the round masks of the ranks
 together are the oracle's candidate mask (each rank marks only the positions it hashed), and the final (position, id) list is the
@@ -9,6 +9,7 @@ import pickle
 
 import numpy as np
 import pytest
+import torch
 import torch.multiprocessing as mp
 
 from helpers import case_files, golden_cases
@@ -17,6 +18,15 @@ from test_dist_cpu import free_port
 
 pytestmark = pytest.mark.gpu
 CASES = {c["name"]: c for c in golden_cases()}
+
+
+def need_gpus(world):
+    """A world of more than RANKS_PER_GPU ranks spreads its rank processes over several GPUs (dist_worker.combined_worker)."""
+    from dist_worker import RANKS_PER_GPU
+    need = -(-world // RANKS_PER_GPU)
+    found = torch.cuda.device_count()
+    if found < need:
+        pytest.skip("needs %d GPUs for %d ranks at %d ranks per GPU, found %d" % (need, world, RANKS_PER_GPU, found))
 
 
 def run(spec, world, tmp_path):
@@ -88,6 +98,7 @@ MODES = {"gather": "all-gather of the exports", "scatter": "reduce-scatter", "de
 def test_combined_golden_cases(name, slice_bits, world, mode, tmp_path):
     """Golden inputs of the real reference (N runs, IUPAC, sequence ends, multi-word keys, several rounds with their exact ranges, an
     abundance cut): filter, masks and ids through every form of the exchange."""
+    need_gpus(world)
     spec, o = golden_spec(name, slice_bits, tmp_path, mode=mode)
     check(spec, o, run(spec, world, tmp_path), world, MODES[mode])
 
@@ -130,6 +141,7 @@ def _synthetic(workload, scale, L, seed, options, **extra):
 def test_combined_synthetic(world, slice_bits, mode, tmp_path):
     """8 x 50 kbp genomes with 1 % SNPs, filter of 2^26 bits: slices of one, four and sixteen 2^16-bit windows; the automatic choice
     of the bytes model (all-gather at two ranks, reduce-scatter beyond) and both forms forced."""
+    need_gpus(world)
     spec, o = _synthetic("m1", 0.01, 26, 11, {"slice_bits": slice_bits, "part_min_tiles": 1}, mode=mode, sharded_pass2="records", text_window=True)
     gathered = run(spec, world, tmp_path)
     want = MODES[mode] if mode else (MODES["gather"] if world == 2 else MODES["scatter"])
@@ -183,5 +195,6 @@ def test_combined_more_than_16_hash_functions(name, world, tmp_path):
 
 def test_combined_more_ranks_than_tiles(tmp_path):
     """example.fa is one tile: seven of eight ranks hash nothing and still build the whole filter from the one export."""
+    need_gpus(8)
     spec, o = golden_spec("example_k15_dbg", 8, tmp_path, mode="scatter")
     check(spec, o, run(spec, 8, tmp_path), 8, "reduce-scatter")
