@@ -55,3 +55,42 @@ def text_codes(bases, nmask, length):
     isn = ((nmask[g >> np.uint64(5)] >> (g & np.uint64(31)).astype(np.uint32)) & np.uint32(1)).astype(bool)
     codes[isn] = 4
     return codes
+
+
+_BAND = {}
+
+
+def band_case():
+    """A random text of 16 M positions (almost every k-mer distinct) under a 2^30-bit filter of 16384 slices of 2^16 bits: each of two
+    ranks exports about 2400 distinct bits per slice -- the list density at which the long-lived export used to claim more than the
+    block size tpc_combine_info promised.  The FASTA file and the oracle's results are made once per test session."""
+    if _BAND:
+        return _BAND
+    import tempfile
+
+    from oracle import oracle as O
+    k, L, q, seed = 25, 30, 5, 7
+    d = tempfile.mkdtemp(prefix="tpc_band_")
+    path = os.path.join(d, "band.fa")
+    rng = np.random.default_rng(2400)
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)
+    with open(path, "wb") as f:
+        for r in range(4):
+            lines = letters[rng.integers(0, 4, 4000000)].reshape(-1, 80)
+            f.write(b">band%d\n" % r)
+            f.write(np.hstack([lines, np.full((lines.shape[0], 1), ord("\n"), dtype=np.uint8)]).tobytes())
+    o = O.Oracle(k, L, q, O.seed_table(seed, q, L))
+    o.add_fasta(path)
+    o.fill_only()
+    marks = o.check_only()
+    filt, mask = o.filter.copy(), o.round_mask.copy()
+    o.enumerate(rounds=1)
+    seqs, pos, ids = o.records
+    start = np.asarray(o.rec_start, dtype=np.int64)
+    want = sorted((int(start[s] + p), int(i)) for s, p, i in zip(seqs.tolist(), pos.tolist(), ids.tolist()) if abs(i) <= len(o.keys))
+    o.write_bin(os.path.join(d, "oracle.bin"))
+    with open(os.path.join(d, "oracle.bin"), "rb") as f:
+        out = f.read()
+    _BAND.update(files=[path], k=k, L=L, q=q, seed=seed, marks=marks, filter=filt, round_mask=mask, junctions=len(o.keys), want=want, bin=out)
+    o.close()
+    return _BAND

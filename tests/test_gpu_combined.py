@@ -169,6 +169,41 @@ def test_combined_several_batches_take_the_dense_road(world, budget, tmp_path):
     check(spec, o, gathered, world, "dense")
 
 
+def test_combined_blocked_insert_entries_take_the_dense_road(tmp_path):
+    """Blocked 24-bit level-2 insert entries (option insert_entry_fmt = 3) in one batch: not sparse, so the dense OR all-reduce, with
+    the query begun once the still pending insert is in the dense filter (dist.py:_dense_reduce)."""
+    spec, o = _synthetic("m1", 0.01, 26, 11, {"slice_bits": 14, "part_min_tiles": 1, "insert_entry_fmt": 3})
+    gathered = run(spec, 2, tmp_path)
+    assert gathered[0]["rounds"][0]["insert_batches"] == 1
+    check(spec, o, gathered, 2, "dense")
+
+
+@pytest.mark.parametrize("mode", ["gather", "scatter"])
+def test_combined_lists_at_the_failing_density(mode, tmp_path):
+    """Low-duplicate input at about 2400 distinct bits per 2^16-bit slice and rank over 16384 slices (helpers.band_case): the long-lived
+    export's chunks waste the most there, and its blocks must still hold what tpc_combine_info sized them for; both forms of the
+    exchange, filter, masks and ids against the oracle."""
+    from helpers import band_case
+    b = band_case()
+    spec = {"files": b["files"], "k": b["k"], "L": b["L"], "q": b["q"], "seed": b["seed"], "ranges": [(0, 1 << b["L"])], "abundance": (1 << 64) - 1,
+            "options": {"slice_bits": 16}, "mode": mode}
+    gathered = run(spec, 2, tmp_path)
+    union = np.zeros_like(b["round_mask"])
+    for g in gathered:
+        r = g["rounds"][0]
+        assert MODES[mode] in r["combine"]["mode"] and r["fused"] >= 1, r["combine"]
+        assert (r["filter"] == b["filter"]).all()
+        assert (r["mask"] == b["round_mask"]).all()
+        union |= r["mask"]
+        assert g["junctions"] == b["junctions"]
+        keep = g["ids"] != (1 << 63) - 1
+        assert sorted(zip(g["g"][keep].tolist(), g["ids"][keep].tolist())) == b["want"]
+    assert int(np.unpackbits(union.view(np.uint8)).sum()) == b["marks"]
+    # the density of the case: about 2400 distinct bits = 300 units per slice and rank
+    units = gathered[0]["rounds"][0]["combine"]["export_units"]
+    assert sum(units) > 16384 * 250, units
+
+
 def test_combined_three_levels_take_the_dense_road(tmp_path):
     """The three-level geometry (f = 39 / 40), forced on a small filter: no deferred apply, so the dense OR all-reduce."""
     spec, o = golden_spec("rand6_k25_q3", 12, tmp_path)

@@ -96,6 +96,21 @@ def test_m1_full_four_emulated_ranks(capi, tmp_path):
     e.close()
 
 
+def test_emulated_ranks_at_the_failing_density(capi, tmp_path, monkeypatch):
+    """The C++ host on the low-duplicate input of helpers.band_case (about 2400 distinct bits per slice and rank; slices of 2^16 bits,
+    so 16384 of them): the long-lived export must fit the blocks it sized, and the output is the oracle's bytes."""
+    from helpers import band_case
+    b = band_case()
+    monkeypatch.setenv("TWOPACO_SLICE_BITS", "16")
+    out = str(tmp_path / "band.bin")
+    e = capi.Enumerator(b["files"], b["k"], b["L"], q=b["q"], rounds=1, tmpdir=str(tmp_path), out=out, seed=b["seed"], gpus=2, emulate_ranks=True)
+    with open(out, "rb") as f:
+        assert f.read() == b["bin"]
+    assert e.vertices_count() == b["junctions"]
+    assert "replicated through set-bit lists" in e.log and "GPUs = 2" in e.log
+    e.close()
+
+
 def test_cli_checkpoint_roundtrip(tmp_path):
     """--save-filter / --load-filter with --gpus N under the combined exchange: every rank holds the WHOLE filter, so rank 0 writes
     one unsharded file per round and every rank reads it back instead of inserting; a one-GPU run reads the same files."""

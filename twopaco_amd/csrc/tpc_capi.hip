@@ -124,6 +124,7 @@ int flush_pending_apply(tpc_ctx *c)
         HIPCHK(c, hipGetLastError());
         return 0;
     }
+    c->qb_valid = false;  // (both applies below write an overflow list and cursor that a begun query's first batch may own: pbuf[4] / pbuf[5])
     if (c->pending_shard) {  // the sharded insert: level-2 regions kept aside, the overflow entries still in the apply-side list the plan points at
         c->pending_shard = false;
         Timed t(c, TPC_K_SHARD_APPLY);
@@ -161,6 +162,7 @@ double range_mass(const tpc_ctx *c, uint64_t lo, uint64_t hi)
 bool ensure_pbuf(tpc_ctx *c, int i, size_t need)
 {
     if (need <= c->pbytes[i]) return true;
+    c->qb_valid = false;  // (a begun query's binned first batch may live in this buffer)
     if (c->pbuf[i]) (void)hipFree(c->pbuf[i]);
     c->pbuf[i] = nullptr; c->pbytes[i] = 0;
     if (i == 8) c->off2_uploaded.clear();
@@ -178,6 +180,7 @@ bool release_partition_buffers(tpc_ctx *c)
     for (void *p : c->ikeep) if (p) held += 1;
     if (!held) return false;
     (void)hipStreamSynchronize(c->stream);
+    c->qb_valid = false;
     for (int i = 0; i < tpc_ctx::NPBUF; i++) {
         if (c->pbuf[i]) (void)hipFree(c->pbuf[i]);
         c->pbuf[i] = nullptr; c->pbytes[i] = 0;
@@ -406,6 +409,10 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "query_entry_fmt")) return c->stat_fmt[1];
     if (!strcmp(name, "insert_batches")) return c->stat_batches[0];
     if (!strcmp(name, "query_batches")) return c->stat_batches[1];
+    if (!strcmp(name, "query_tiles_per_batch")) return c->stat_q_plan[0];  // plan of the last partitioned query: 512-word tiles per batch, level-1 / level-2 bits
+    if (!strcmp(name, "query_b1")) return c->stat_q_plan[1];
+    if (!strcmp(name, "query_b2")) return c->stat_q_plan[2];
+    if (!strcmp(name, "query_begun")) return c->stat_q_begun;  // 1: the last query's first batch was binned by tpc_pass1_query_begin
     if (!strcmp(name, "filter2_retries")) return c->stat_filter2_retries;
     if (!strcmp(name, "fused_lookups")) return c->stat_fused;
     if (!strcmp(name, "query_overflow_entries")) return c->stat_query_overflow;
@@ -455,6 +462,7 @@ int tpc_set_params(tpc_ctx *c, int k, int L, int q, const uint64_t *seed_table)
     c->have_params = true;
     c->periodic_valid = false;  // (k)
     c->pending_apply = false;
+    c->qb_valid = false;
     c->n_keys = 0; c->finalized = false; c->rounds_done = 0; c->mask_dirty = false; c->marks_valid = false; c->rmask_sums_valid = false;
     return 0;
 }
@@ -464,6 +472,7 @@ int tpc_seq_upload(tpc_ctx *c, const uint64_t *bases, const uint32_t *nmask, uin
     if (!c || !bases || !nmask || n_text < 2) return fail(c, -1, "bad text");
     HIPCHK(c, hipSetDevice(c->device));
     const auto t_begin = std::chrono::steady_clock::now();
+    c->qb_valid = false;  // (a begun query hashed the text this call replaces)
     const uint64_t nw = (n_text + 31) / 32;
     if (!((nmask[0] & 1u) && ((nmask[(n_text - 1) >> 5] >> ((n_text - 1) & 31)) & 1u)))
         return fail(c, -1, "text must start and end with the N separator");
@@ -551,6 +560,7 @@ int tpc_pass1_insert(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_kmers)
     HIPCHK(c, hipSetDevice(c->device));
     const bool gated = !(lo == 0 && hi >= c->P.lmask);
     { int rc0 = flush_pending_apply(c); if (rc0) return rc0; }
+    c->qb_valid = false;  // (the insert bins into the buffers a begun query's first batch lives in)
     ensure_periodic(c);
     if (n_kmers) HIPCHK(c, hipMemsetAsync(c->counters, 0, sizeof(unsigned long long), c->stream));
     uint64_t t_begin, t_end;
@@ -808,14 +818,27 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
     if (c->sh_world > 1 && !c->opt_replicate) return fail(c, -1, "the filter is sharded: use tpc_shard_hash / tpc_shard_apply");
     HIPCHK(c, hipSetDevice(c->device));
     const bool gated = !(lo == 0 && hi >= c->P.lmask);
-    const bool begun = !begin_only && c->qb_valid && c->qb_lo == lo && c->qb_hi == hi;  // the first batch's hash and binning are on the stream already
+    bool begun = !begin_only && c->qb_valid && c->qb_lo == lo && c->qb_hi == hi;  // the first batch's hash and binning are on the stream already
     c->qb_valid = false;
+    // deferred apply of this round's insert: the lookup builds the slices (k_apply_lookup) when the geometry still matches
+    auto fuses = [c](const TpcQPlan &p) {
+        return c->pending_apply && !c->pending_shard && p.b3 == 0 && p.slice_bits == c->pending_pl.slice_bits && p.b1 == c->pending_pl.b1 && p.b2 == c->pending_pl.b2 &&
+               (p.fmt == 6 || c->pending_pl.fmt2 == 0);
+    };
+    if (begun && c->pending_apply && !fuses(c->qb_pl)) {  // the insert is applied first, into the overflow list and cursor the begun batch owns: hash and bin again
+        int rc0 = materialize_reset(c);
+        if (rc0) return rc0;
+        begun = false;
+    }
+    c->stat_q_begun = begun ? 1 : 0;
     c->marks_valid = false; c->rmask_sums_valid = false;
     ensure_periodic(c);
     TpcQPlan pl;
     uint64_t t_begin, t_end;
     pass_tiles(c, t_begin, t_end);  // every tile, or this rank's chunk (option replicate_filter on a sharded context: the marks of the chunk only)
-    bool part = plan_query(c, lo, hi, gated, pl);
+    // a begun first batch was binned under the plan of tpc_pass1_query_begin: planning again could pick other batches, caps or region
+    // offsets (the automatic budget follows the device's free memory, and the caller allocates between the two calls)
+    bool part = begun ? (pl = c->qb_pl, true) : plan_query(c, lo, hi, gated, pl);
     if (replicated(c)) {
         if (!part && c->P.q <= TPC_KERNEL_MAXQ) return fail(c, -1, "a replicated multi-GPU pass needs the partitioned query (q=%d, L=%d, slice_bits=%d)", c->P.q, c->P.L, c->opt_slice_bits);
         if (!begun) HIPCHK(c, hipMemsetAsync(c->rmask, 0, c->n_words_alloc * sizeof(uint32_t), c->stream));  // the hash kernel rewrites the words of this rank's tiles only
@@ -823,9 +846,7 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
     if (begin_only && !part) return 0;  // (the direct kernel needs the filter from its first instruction: nothing to start early)
     if (part)
         for (int i = 0; i < tpc_ctx::NPBUF && part; i++) if (qpart_need(pl, i)) part = ensure_pbuf(c, i, qpart_need(pl, i));  // not enough HBM: direct path
-    // deferred apply of this round's insert: the lookup builds the slices (k_apply_lookup) when the geometry still matches
-    const bool fused = !begin_only && c->pending_apply && !c->pending_shard && part && pl.b3 == 0 && pl.slice_bits == c->pending_pl.slice_bits &&
-                       pl.b1 == c->pending_pl.b1 && pl.b2 == c->pending_pl.b2 && (pl.fmt == 6 || c->pending_pl.fmt2 == 0);
+    const bool fused = !begin_only && part && fuses(pl);
     if (!fused && !begin_only) { int rc0 = materialize_reset(c); if (rc0) return rc0; }
     if (part) {
         pl.buf1 = (uint64_t *)c->pbuf[0]; pl.cnt1 = (uint32_t *)c->pbuf[1]; pl.buf2 = (uint64_t *)c->pbuf[2]; pl.cnt2 = (uint32_t *)c->pbuf[3];
@@ -865,6 +886,7 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
                         return fail(c, -1, "partitioned query launch failed");
                     HIPCHK(c, hipGetLastError());
                     c->qb_valid = true; c->qb_lo = lo; c->qb_hi = hi;
+                    c->qb_pl = pl; c->qb_pl.n_tiles = per;
                     return 0;
                 }
                 if (fused && t0 == t_begin) {  // the first batch's lookup kernel also builds and writes the filter slices; later batches read them
@@ -923,6 +945,7 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
         c->stat_path[1] = (pl.b3 ? 3 : 2) + (overflowed ? 10 : 0);
         c->stat_fmt[1] = pl.fmt;
         c->stat_batches[1] = (int64_t)((pass_tile_count(c) + per_batch - 1) / per_batch);
+        c->stat_q_plan[0] = (int64_t)per_batch; c->stat_q_plan[1] = pl.b1; c->stat_q_plan[2] = pl.b2;
         if (c->dbg_ovf) {
             unsigned long long sc[65];
             (void)hipMemcpy(sc, pl.surv_cur, sizeof sc, hipMemcpyDeviceToHost);

@@ -37,7 +37,9 @@ int tpc_combine_info(tpc_ctx *c, uint32_t n_dest, uint64_t *info)
         HIPCHK(c, hipMemcpyAsync(ovf_off.data(), c->iovf_off, ovf_off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<uint64_t> units(n_dest, 0);
+    // per destination: the lists (u = units of a slice at most), the largest slice, and what the chunks may leave unused
+    std::vector<uint64_t> units(n_dest, 0), most(n_dest, 0), waste(n_dest, 0);
+    const bool chunked = n_slices >= TPC_COMBINE_PERSIST_SLICES;  // the long-lived export (tpc_combine.hip:k_slice_export_p) places slices in chunks
     for (uint32_t b1 = 0; b1 < (1u << g.b1); b1++)
         for (uint32_t b2 = 0; b2 < nb2; b2++) {
             uint64_t e = 0;
@@ -45,10 +47,26 @@ int tpc_combine_info(tpc_ctx *c, uint32_t n_dest, uint64_t *info)
             const uint32_t sp = (b1 << g.b2) | b2;
             if (c->pending_novf) e += ovf_off[sp + 1] - ovf_off[sp];
             e = std::min<uint64_t>(e, (uint64_t)1 << g.slice_bits);
-            units[b1 & (n_dest - 1)] += (e + 7) / 8 + n_win;
+            const uint64_t u = (e + 7) / 8 + n_win;
+            const uint32_t d = b1 & (n_dest - 1);
+            units[d] += u;
+            most[d] = std::max(most[d], u);
+            waste[d] += std::min<uint64_t>(u, TPC_COMBINE_CHUNK);
         }
-    // (+ the chunks the persistent export claims per workgroup and destination: tpc_combine.hip:CB_CHUNK = 512 units, at most 1024 workgroups)
-    info[0] = 1; info[1] = n_slices; info[2] = n_win; info[3] = *std::max_element(units.begin(), units.end()) + 1024 * 512;
+    uint64_t cap = 0;
+    for (uint32_t d = 0; d < n_dest; d++) {
+        // chunked: a slice whose lists do not fit what is left of the chunk at hand takes a new chunk and leaves that rest unused -- less
+        // than its lists and less than a chunk.  With slices of at most m < CHUNK units, a chunk left behind also holds more than CHUNK - m
+        // units of lists, so at most units / (CHUNK - m + 1) chunks are left, each with less than m unused.
+        uint64_t w = 0;
+        if (chunked) {
+            w = waste[d];
+            if (most[d] < TPC_COMBINE_CHUNK) w = std::min<uint64_t>(w, units[d] / (TPC_COMBINE_CHUNK - most[d] + 1) * most[d]);
+        }
+        cap = std::max(cap, units[d] + w);
+    }
+    // (+ the tail of the last chunk of every workgroup and destination)
+    info[0] = 1; info[1] = n_slices; info[2] = n_win; info[3] = cap + (uint64_t)TPC_COMBINE_MAX_WG * TPC_COMBINE_CHUNK;
     info[4] = (uint64_t)g.slice_bits; info[5] = (uint64_t)g.b1; info[6] = (uint64_t)g.b2; info[7] = (uint64_t)(n_slices / n_dest) * n_win;
     return 0;
 }

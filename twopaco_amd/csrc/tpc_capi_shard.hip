@@ -26,6 +26,7 @@ int tpc_shard_config(tpc_ctx *c, uint32_t rank, uint32_t world)
 int tpc_shard_plan(tpc_ctx *c, int pass, uint64_t lo, uint64_t hi, uint64_t *geom)
 {
     if (!c || !c->have_params || !c->bases || !geom) return fail(c, -1, "set_params and seq_upload first");
+    c->qb_valid = false;  // (the sharded passes share the partition buffers with a begun query)
     if (pass != TPC_SHARD_INSERT && pass != TPC_SHARD_QUERY) return fail(c, -1, "bad pass");
     HIPCHK(c, hipSetDevice(c->device));
     if (!part_hash_supported(c))
@@ -137,6 +138,7 @@ namespace {
 int shard_hash_impl(tpc_ctx *c, int pass, uint64_t batch, uint64_t lo, uint64_t hi, void *send_regions, void *send_counts, uint64_t *n_overflow, bool async)
 {
     if (!c || (pass != TPC_SHARD_INSERT && pass != TPC_SHARD_QUERY) || !c->sh_have[pass]) return fail(c, -1, "tpc_shard_plan for this pass first");
+    c->qb_valid = false;  // (the sharded passes share the partition buffers with a begun query)
     if (!send_regions || !send_counts || batch >= c->sh_batches[pass]) return fail(c, -1, "bad arguments");
     if (c->sh_async[pass]) return fail(c, -1, "a hash of this pass is still in flight: tpc_shard_hash_end first");
     HIPCHK(c, hipSetDevice(c->device));
@@ -246,6 +248,7 @@ int tpc_shard_overflow_get(tpc_ctx *c, int pass, void *dst, uint64_t n)
 int tpc_shard_overflow_set(tpc_ctx *c, int pass, const void *src, uint64_t n)
 {
     if (!c || (pass != TPC_SHARD_INSERT && pass != TPC_SHARD_QUERY) || !c->sh_have[pass] || (!src && n)) return fail(c, -1, "bad arguments");
+    c->qb_valid = false;  // (the sharded passes share the partition buffers with a begun query)
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t cap = pass == TPC_SHARD_INSERT ? c->sh_ipl.ovf_cap : c->sh_qpl.ovf_cap;
     if (n > cap) return fail(c, -1, "gathered overflow lists (%llu entries) exceed the capacity %llu: skew beyond what the sharded path handles",
@@ -327,6 +330,7 @@ int shard_apply_impl(tpc_ctx *c, int pass, uint64_t batch, const void *recv_regi
                      const void *own_regions, const void *own_counts)
 {
     if (!c || (pass != TPC_SHARD_INSERT && pass != TPC_SHARD_QUERY) || !c->sh_have[pass]) return fail(c, -1, "tpc_shard_plan for this pass first");
+    c->qb_valid = false;  // (the sharded passes share the partition buffers with a begun query)
     if (!recv_regions || !recv_counts || batch >= c->sh_batches[pass]) return fail(c, -1, "bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t *roff1 = nullptr;

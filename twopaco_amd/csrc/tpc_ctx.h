@@ -149,7 +149,10 @@ struct tpc_ctx {
     // context (sh_world > 1); tpc_pass1_insert / tpc_pass1_query then run the one-GPU passes over this rank's chunk of the tiles
     int opt_replicate = 0;
     bool qb_valid = false;               // tpc_pass1_query_begin enqueued the first batch's hash and binning of the query of [qb_lo, qb_hi]
-    uint64_t qb_lo = 0, qb_hi = 0;
+    uint64_t qb_lo = 0, qb_hi = 0;       //   (anything that reallocates or writes a partition buffer, or changes the text, clears it)
+    TpcQPlan qb_pl;                      // ... under this plan (geometry, tiles per batch, buffers): the query reuses it, never plans again
+    int64_t stat_q_plan[3] = {0, 0, 0};  // tiles per batch, b1, b2 of the last partitioned query
+    int stat_q_begun = 0;                // the last query's first batch was the one tpc_pass1_query_begin binned
     bool pending_lists = false;          // the pending (deferred) insert lives in imported set-bit lists (cmb_ls), not in level-2 regions
     TpcListSrc cmb_ls;                   // ... these (payload and directories are the caller's device buffers)
     TpcPartPlan cmb_geo;                 // slice geometry of the last deferred insert (tpc_combine_export / _merge / _import agree on it)

@@ -243,6 +243,11 @@ __host__ __device__ __forceinline__ uint32_t tpc_list_windows(int slice_bits) { 
 // what a pass of k_slice_combine produces: n_dest blocks of `cap` 16-byte units each in payload, cur[d] = units used of block d
 // (cur[n_dest] != 0: a block was too small), dir = [n_dest][slices per destination][windows] (tpc_lists.h)
 struct TpcCombineOut { uint16_t *payload; uint64_t cap; unsigned long long *cur; uint64_t *dir; uint32_t n_dest; };
+// The export of a rank's own insert over at least TPC_COMBINE_PERSIST_SLICES slices runs as long-lived workgroups (at most
+// TPC_COMBINE_MAX_WG of them) that place a slice's lists in chunks of at least TPC_COMBINE_CHUNK units claimed per destination: a slice
+// whose lists do not fit what is left of the chunk at hand takes a new one, so a block holds, beyond the lists, less than
+// min(units of the slice, TPC_COMBINE_CHUNK) per slice plus less than TPC_COMBINE_CHUNK per workgroup (tpc_combine_info sizes for that).
+constexpr uint32_t TPC_COMBINE_PERSIST_SLICES = 16384, TPC_COMBINE_CHUNK = 512, TPC_COMBINE_MAX_WG = 1024;
 int tpc_launch_slice_combine(const TpcLaunch &a, int slice_bits, int b1, int b2, uint32_t perm_mult, uint32_t perm_inv, const TpcPartPlan *ipl, const uint64_t *iovf,
                              const uint64_t *iovf_off, const TpcListSrc &ls, bool dense, bool fresh, const TpcCombineOut *out, uint32_t rank, uint32_t world);
 

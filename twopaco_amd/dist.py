@@ -947,8 +947,6 @@ class Combined(AddressSharded):
             self.stats["combine"].update(mode="one rank: nothing to exchange", exchange_bytes_received=0)
             return {"mode": "one rank"}
         info = self._try(ctx.combine_info, W, default=None) or {"sparse": 0}
-        if not info["sparse"]:
-            self._begin_query(lo, hi)  # (the insert went to the dense filter: the query's hash and binning run under the filters' OR-reduce)
         # every rank must take the same road: sparse lists only if every rank's insert stayed in its regions
         dense = comm.max_ints([0 if info["sparse"] else 1])[0] == 1 or self.mode == "dense"
         st = self.stats["combine"]
@@ -979,7 +977,9 @@ class Combined(AddressSharded):
                 self._try(ctx.combine_import, W, W, payload.data_ptr(), [d * cap for d in range(W)], cdir.data_ptr(), spd * n_win)
         if dense:
             st.setdefault("mode", "dense OR all-reduce")
-            self._dense_reduce()
+            # (not sparse: the query begins once the insert is in the dense filter -- applying a still pending insert writes the
+            # overflow list and cursor a begun first batch would own -- and its hash and binning run under the filters' OR-reduce)
+            self._dense_reduce(begin=None if info["sparse"] else (lo, hi))
             self._tick("insert_exchange", t0)
             return {"mode": st["mode"]}
         pay64 = payload.view(torch.int64)  # (2 x int64 per unit)
@@ -1054,8 +1054,9 @@ class Combined(AddressSharded):
                 torch.cuda.synchronize()
         self._try(pass1_query_begin)
 
-    def _dense_reduce(self):
-        """OR all-reduce of the ranks' dense filters by word ranges (the mask union's scheme on 2^L / 8 bytes)."""
+    def _dense_reduce(self, begin=None):
+        """OR all-reduce of the ranks' dense filters by word ranges (the mask union's scheme on 2^L / 8 bytes).  begin: (lo, hi) of a
+        query to begin once this rank's filter is complete (tpc_filter_copy_out applies a pending insert)."""
         torch, ctx, W, comm = self.torch, self.ctx, self.world, self.comm
         if W == 1:
             return
@@ -1064,6 +1065,8 @@ class Combined(AddressSharded):
         chunk = words // W
         mine = self._buf("c_dense", words * 4).view(torch.int32)
         self._try(ctx.filter_copy_out, 0, words, mine.data_ptr())
+        if begin is not None:
+            self._begin_query(*begin)
         comm.agree()
         parts = comm.a2a_equal(mine).contiguous()
         folded = self._buf("c_fold", chunk * 4).view(torch.int32)

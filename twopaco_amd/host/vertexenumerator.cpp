@@ -253,7 +253,11 @@ namespace TwoPaCo
 				// the fan-out 2^(L - slice_bits) is split over two levels and the first must have at least `gpus` buckets
 				int logGpus = 0;
 				while ((1 << logGpus) < gpus) ++logGpus;
-				const int shardSliceBits = int(std::min<int64_t>(20, std::max<int64_t>(6, int64_t(filterSize) - std::max(2, 2 * logGpus))));
+				int shardSliceBits = int(std::min<int64_t>(20, std::max<int64_t>(6, int64_t(filterSize) - std::max(2, 2 * logGpus))));
+				if (const char * sliceEnv = std::getenv("TWOPACO_SLICE_BITS"))  // smaller slices only (tests: the combined export's long-lived kernel from 16384 slices on)
+				{
+					shardSliceBits = std::max(6, std::min(shardSliceBits, std::atoi(sliceEnv)));
+				}
 				const char * shardPeriodicEnv = std::getenv("TWOPACO_SHARD_PERIODIC");
 				const bool shardPeriodic = !(shardPeriodicEnv && shardPeriodicEnv[0] == '0');
 				if (gpus > 64 || (gpus & (gpus - 1)))
