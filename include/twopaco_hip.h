@@ -447,7 +447,12 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "insert_batches" / "query_batches" = tile batches; "filter2_retries" = exact-filter passes repeated
  * with the full-size table by the last tpc_pass2_filter; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
  * tpc_pass2_filter consumed (what tpc_pass1_query reports; the sharded first pass has no single call that does);
- * "device_free_bytes" / "device_total_bytes" = hipMemGetInfo of the context's device, now.
+ * "device_free_bytes" / "device_total_bytes" = hipMemGetInfo of the context's device, now;
+ * which kernels the last first pass ran (after a "+10" path: those of the partitioned pass the direct kernel completed):
+ * "insert_hash_kernel" = 0 none (the direct rolling kernel), 1 the instruction-lean hash with its seed table in LDS, 2 the same
+ * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);
+ * "query_hash_kernel" = 0 none (direct), 1 the lean k_q_hash2, 2 k_q_hash, 4 the closed form;
+ * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify.
  * -1: unknown name. */
 int64_t tpc_get_stat(const tpc_ctx *ctx, const char *name);
 

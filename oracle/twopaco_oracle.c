@@ -556,7 +556,7 @@ static void fill_pass(orc_run *R, const uint32_t *run, uint64_t low, uint64_t hi
         if (!have) { vh_init(R, &v, w, R->q); have = 1; }
         int prev = w[-1], next = w[R->k];
         uint64_t first = vh_vertex(&v);
-        uint64_t set[64];
+        uint64_t set[4 * ORC_MAXQ];  /* an edge out and one in, each both dummy letters beside N: 4 q addresses */
         int ns = 0;
         if (next != ORC_N) { edge_out(R, &v, next, addr); for (int i = 0; i < R->q; i++) set[ns++] = addr[i]; }
         else {

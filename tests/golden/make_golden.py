@@ -222,6 +222,12 @@ def main():
     # _fp: a filter small enough for Bloom false positives, two rounds (the split pass with 20 functions)
     case("rand6_k9_q20", "rand6.fa", 9, 22, q=20)
     case("rand6_k9_q20_fp_r2", "rand6.fa", 9, 18, q=20, rounds=2)
+    # hash-function counts between and beyond those above: 16 with k past the insert seed table and the 31-letter verification limit,
+    # 11 (odd, two emit batches) gated in two rounds, 9 with a k of three key words, 64 (the last count the closed form takes)
+    case("rand6_k33_q16", "rand6.fa", 33, 20, q=16)
+    case("rand6_k21_q11_r2", "rand6.fa", 21, 20, q=11, rounds=2)
+    case("c2_k65_q9", "c2.fa", 65, 22, q=9)
+    case("rand6_k31_q64", "rand6.fa", 31, 22, q=64)
     # collision-free multi-round runs: "first seen" in the split pass (VE.h:559-570) is then order independent,
     # so the round ranges (VE.h:206-254) below are what ANY correct implementation must print
     case("rand6_k9_L24_r4", "rand6.fa", 9, 24, rounds=4)

@@ -286,3 +286,31 @@ def test_address_sharded_randomized(world, tmp_path):
             o.add_record(r)
         check(sp, o, gathered, world)
         o.close()
+
+
+def test_address_sharded_hash_counts_beyond_8(tmp_path):
+    """Entry routing at q = 8, 9, 12, 16 (the sharded path takes q <= 16) with k on both sides of 31: the sharded verification's address
+    kernels (k_v_addrs2 / k_v_addrs) for more than 7 functions, fused and step by step, in one process group."""
+    rng = np.random.default_rng(916)
+    alphabet = np.frombuffer(b"ACGT", dtype=np.uint8)
+    specs = []
+    for i, (q, k) in enumerate([(q, k) for q in (8, 9, 12, 16) for k in (25, 47)]):
+        base = alphabet[rng.integers(0, 4, 20000)].copy()
+        recs = []
+        for r in range(3):
+            s = base.copy()
+            hits = rng.random(s.size) < 0.02
+            s[hits] = alphabet[rng.integers(0, 4, int(hits.sum()))]
+            if r == 1:
+                a = int(rng.integers(0, s.size)); s[a:a + 40] = ord("N")
+            recs.append(s.tobytes())
+        L = 20
+        specs.append({"records": recs, "k": k, "L": L, "q": q, "seed": 5 + i, "ranges": [(0, 1 << L), (1 << 18, 3 << 18)],
+                      "abundance": (1 << 64) - 1, "fused_verify": i % 2 == 0, "options": {"slice_bits": 10}})
+    results = run(specs, 2, tmp_path)
+    for sp, gathered in zip(specs, results):
+        o = O.Oracle(sp["k"], sp["L"], sp["q"], O.seed_table(sp["seed"], sp["q"], sp["L"]))
+        for r in sp["records"]:
+            o.add_record(r)
+        check(sp, o, gathered, 2)
+        o.close()

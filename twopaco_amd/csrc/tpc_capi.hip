@@ -24,6 +24,7 @@ TpcLaunch make_launch(const tpc_ctx *c)
     TpcLaunch a;
     a.P = c->P; a.tab = c->tab; a.bases = c->bases; a.nmask = c->nmask; a.n_text = c->n_text;
     a.n_tiles = c->n_tiles; a.filter = c->filter; a.stream = c->stream;
+    a.stat_kernel = c->stat_kernel;
     return a;
 }
 
@@ -407,6 +408,9 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "query_path")) return c->stat_path[1];
     if (!strcmp(name, "insert_entry_fmt")) return c->stat_fmt[0];
     if (!strcmp(name, "query_entry_fmt")) return c->stat_fmt[1];
+    if (!strcmp(name, "insert_hash_kernel")) return c->stat_kernel[0];
+    if (!strcmp(name, "query_hash_kernel")) return c->stat_kernel[1];
+    if (!strcmp(name, "query_verify_kernel")) return c->stat_kernel[2];
     if (!strcmp(name, "insert_batches")) return c->stat_batches[0];
     if (!strcmp(name, "query_batches")) return c->stat_batches[1];
     if (!strcmp(name, "query_tiles_per_batch")) return c->stat_q_plan[0];  // plan of the last partitioned query: 512-word tiles per batch, level-1 / level-2 bits
@@ -701,6 +705,7 @@ int tpc_pass1_insert(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_kmers)
         Timed t(c, TPC_K_INSERT);
         TpcLaunch ad = make_launch(c);
         if (replicated(c)) { ad.g_begin = t_begin * 512ull * TPC_RUN; ad.g_end = t_end * 512ull * TPC_RUN; }  // (q > 16 only: see above)
+        if (part) ad.stat_kernel = nullptr;  // (completing an overflowed partitioned pass: the stats keep its hash kernel)
         if (tpc_launch_insert(ad, lo, hi, gated, c->opt_test_first != 0, n_kmers ? c->counters : nullptr))
             return fail(c, -1, "insert launch failed");
     }
@@ -1022,6 +1027,7 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
         Timed t(c, TPC_K_QUERY);
         TpcLaunch ad = make_launch(c);
         if (replicated(c)) { ad.g_begin = t_begin * 512ull * TPC_RUN; ad.g_end = t_end * 512ull * TPC_RUN; }  // (q > 16: the closed-form kernel over this rank's chunk)
+        if (part) ad.stat_kernel = nullptr;  // (completing an overflowed partitioned pass: the stats keep its kernels)
         if (tpc_launch_query(ad, c->rmask, lo, hi, gated, c->counters + 1)) return fail(c, -1, "query launch failed");
     }
     HIPCHK(c, hipGetLastError());

@@ -68,6 +68,9 @@ struct TpcLaunch {
     uint64_t g_begin = 0, g_end = ~0ull;
     // measurement: recorded around the k_apply_lookup launch of tpc_launch_query_part_fused_lookup when set (TPC_K_LOOKUP)
     hipEvent_t ev_lookup0 = nullptr, ev_lookup1 = nullptr;
+    // when set: the launchers record which hash / verification kernel they chose, [0] insert hash, [1] query hash, [2] query
+    // verification (tpc_ctx::stat_kernel, the values of tpc_get_stat "insert_hash_kernel" / "query_hash_kernel" / "query_verify_kernel")
+    int *stat_kernel = nullptr;
 };
 constexpr int TPC_PER_MAXP = 63;    // periods of the periodic windows the first pass skips (tpc_qpartition.hip:k_periodic_build)
 constexpr int TPC_PER_PLANES = 6;   // bit planes of the copy distance; the masks of a text are [2 + TPC_PER_PLANES][n_words_alloc]: per_qs, the planes, per_i

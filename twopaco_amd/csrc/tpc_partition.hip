@@ -594,6 +594,7 @@ int launch_hash_q(const TpcLaunch &a, const TpcPartPlan &pl, bool gated, uint64_
         const size_t seed = (size_t)a.P.k * 5 * Q * 16;  // the seed table, when it fits beside the rings (160 KB per workgroup)
         const int seed_rows = fixed + seed <= (size_t)160 * 1024 - 256 ? a.P.k : 0;
         const size_t lds = fixed + (seed_rows ? seed : 0);
+        if (a.stat_kernel) a.stat_kernel[0] = seed_rows ? 1 : 2;
 #define TPC_HASH2_GO(G, S, H)                                                                                                               \
     do {                                                                                                                                    \
         (void)hipFuncSetAttribute((const void *)k_part_hash2<Q, G, S, H>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
@@ -618,6 +619,7 @@ int launch_hash_q(const TpcLaunch &a, const TpcPartPlan &pl, bool gated, uint64_
     if constexpr (Q > 8) return -1;  // 9..16 functions: instantiated for the lean kernel only (the caller falls back to the direct kernel)
     else {
     const size_t lds = Bins3<uint32_t, PH_THREADS>::lds_bytes(pl.b1) + (size_t)(PT_THREADS + 1 + TPC_XW_MAX) * 24 + (size_t)Q * 5 * 16 + 64;
+    if (a.stat_kernel) a.stat_kernel[0] = 3;
 #define TPC_HASH_GO(G, S)                                                                                                                   \
     do {                                                                                                                                    \
         (void)hipFuncSetAttribute((const void *)k_part_hash<Q, G, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \

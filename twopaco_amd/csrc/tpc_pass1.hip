@@ -381,7 +381,9 @@ int tpc_test_force_anyq = 0;  // option "test_force_anyq" (tests only, process-w
 
 int tpc_launch_insert(const TpcLaunch &a, uint64_t lo, uint64_t hi, bool gated, bool test, unsigned long long *n_kmers)
 {
-    if (a.P.q > TPC_KERNEL_MAXQ || tpc_test_force_anyq) return tpc_launch_insert_anyq(a, lo, hi, gated, test, n_kmers);
+    const bool anyq = a.P.q > TPC_KERNEL_MAXQ || tpc_test_force_anyq;
+    if (a.stat_kernel) a.stat_kernel[0] = anyq ? 4 : 0;
+    if (anyq) return tpc_launch_insert_anyq(a, lo, hi, gated, test, n_kmers);
 #define CALL(Q) launch_insert_q<Q>(a, lo, hi, gated, test, n_kmers)
     TPC_DISPATCH_Q(a.P.q, CALL)
 #undef CALL
@@ -390,7 +392,9 @@ int tpc_launch_insert(const TpcLaunch &a, uint64_t lo, uint64_t hi, bool gated, 
 
 int tpc_launch_query(const TpcLaunch &a, uint32_t *rmask, uint64_t lo, uint64_t hi, bool gated, unsigned long long *n_marks)
 {
-    if (a.P.q > TPC_KERNEL_MAXQ || tpc_test_force_anyq) return tpc_launch_query_anyq(a, rmask, lo, hi, gated, n_marks);
+    const bool anyq = a.P.q > TPC_KERNEL_MAXQ || tpc_test_force_anyq;
+    if (a.stat_kernel) { a.stat_kernel[1] = anyq ? 4 : 0; a.stat_kernel[2] = 0; }  // (the direct kernels verify in place)
+    if (anyq) return tpc_launch_query_anyq(a, rmask, lo, hi, gated, n_marks);
 #define CALL(Q) launch_query_q<Q>(a, rmask, lo, hi, gated, n_marks)
     TPC_DISPATCH_Q(a.P.q, CALL)
 #undef CALL

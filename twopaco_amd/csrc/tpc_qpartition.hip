@@ -1516,6 +1516,7 @@ void launch_qhash(const TpcLaunch &a, const TpcQPlan &pl, bool gated, uint64_t l
     const bool rb = q_use_rbins(pl.b1);
     // the instruction-lean kernel: flush-per-round bins (two rounds per position at 512 bins), a 24-bit slice index
     const bool lean = pl.b1 <= 9 && pl.sub_rounds <= 2 && perm.F <= 24 && !TpcEnv::get().no_lean && !(rb && TpcEnv::get().rb_hash);
+    if (a.stat_kernel) a.stat_kernel[1] = lean ? 1 : 2;
     if (lean) {
         const size_t lds = Bins3<uint64_t, QH_THREADS>::lds_bytes(pl.b1) + (size_t)(PT_THREADS + 1 + TPC_XW_MAX) * 12 + 160 + (size_t)QT_MAXK * 80 + 64;
 #define TPC_QHASH2_GO(G, S, H, X)                                                                                                           \
@@ -1777,6 +1778,7 @@ void launch_qverify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
     const size_t table = (size_t)(a.P.k + 1) * 4 * Q * 16;  // k_q_verify2's letter table
     if (a.P.k <= 31 && table <= 48 * 1024 && !TpcEnv::get().no_lean) {
         const bool lazy = !TpcEnv::get().verify_eager;  // (TPC_VERIFY_LAZY=0, measurements: all Q - 1 probes at once)
+        if (a.stat_kernel) a.stat_kernel[2] = lazy ? 1 : 2;
         if (lazy) {
             (void)hipFuncSetAttribute((const void *)k_q_verify2<Q, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table);
             hipLaunchKernelGGL((k_q_verify2<Q, true>), dim3(256, QS_LISTS), dim3(256), table, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase,
@@ -1788,6 +1790,7 @@ void launch_qverify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
         }
         return;
     }
+    if (a.stat_kernel) a.stat_kernel[2] = 3;
     hipLaunchKernelGGL((k_q_verify<Q>), dim3(256, QS_LISTS), dim3(256), 0, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase, rmask);
 }
 
