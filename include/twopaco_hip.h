@@ -148,7 +148,8 @@ int tpc_pass2_filter_records(tpc_ctx *ctx, const uint64_t *records_dev, uint64_t
  * far fewer rows travel (M2 at two ranks: 22 M marks -> ~1 M records per rank).  The rows are routed as before and
  * tpc_pass2_filter_aggregated merges what a rank received: sets OR-ed, counts added, the reference's verdict (isBif, abundance cut) on
  * the sums.  Occurrences are counted whenever `abundance` is a real cut (< 2^40) -- pass the same value to both calls on every rank.
- * tpc_pass2_filter_records takes aggregated and per-position records alike; what differs is how the table is sized and that rule. */
+ * tpc_pass2_filter_records takes aggregated and per-position records alike (under a cut below 2^40 it counts, as the aggregated call does);
+ * what differs is how the table is sized. */
 int tpc_pass2_aggregate_records(tpc_ctx *ctx, uint32_t world, uint64_t abundance, uint64_t *records_dev, int32_t *owner_dev, uint64_t *n_records);
 int tpc_pass2_filter_aggregated(tpc_ctx *ctx, const uint64_t *records_dev, uint64_t n, uint64_t abundance, uint64_t *n_true, uint64_t *n_false,
                                 uint64_t *table_size);
@@ -445,7 +446,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
 /* What the last first-pass calls ran: "insert_path" / "query_path" = 1 direct kernel, 2 or 3 = LDS
  * write-combining with that many levels (+10: it overflowed and the direct kernel completed the pass);
  * "insert_batches" / "query_batches" = tile batches; "filter2_retries" = exact-filter passes repeated
- * with the full-size table by the last tpc_pass2_filter; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
+ * with the full-size table by the last exact filter (tpc_pass2_filter*), "aggregate_retries" those of the last tpc_pass2_aggregate_records;
+ * "filter2_counted" = 1 when the last exact-filter launch (either call) counted occurrences (an abundance cut applies), 0 when it kept
+ * only "seen twice"; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
  * tpc_pass2_filter consumed (what tpc_pass1_query reports; the sharded first pass has no single call that does);
  * "device_free_bytes" / "device_total_bytes" = hipMemGetInfo of the context's device, now;
  * which kernels the last first pass ran (after a "+10" path: those of the partitioned pass the direct kernel completed):

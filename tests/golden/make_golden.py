@@ -123,6 +123,19 @@ def write_tracts_fa(path, seed=17):
     synth.write_fasta(path, [base, c1, c2, c3, c4], width=80)
 
 
+def write_width_fa(path, seed=23):
+    """Keys of 4, 9 and 14 words with junctions: chr0 random, chr1 = chr0 with a substitution every ~900 bases, chr2 = chr0 rotated
+    (one breakpoint), chr3 random around a 1500-base copy of chr0's middle, chr4 shorter than k = 413."""
+    base = synth.random_genome(6000, seed)
+    c1 = base.copy()
+    for i in range(450, 6000, 900):
+        c1[i] = (c1[i] + 1) & 3
+    c2 = np.concatenate([base[3700:], base[:3700]])
+    c3 = np.concatenate([synth.random_genome(700, seed + 1), base[2000:3500], synth.random_genome(700, seed + 2)])
+    c4 = base[4000:4300]
+    synth.write_fasta(path, [base, c1, c2, c3, c4], width=70)
+
+
 def parse_log(log):
     rounds = []
     for m in re.finditer(r"Round (\d+), (\d+):(\d+)", log):
@@ -152,6 +165,8 @@ def main():
         write_longk_fa(os.path.join(HERE, "lk.fa"))
     if only is None or any(n.startswith("tr_") for n in only):
         write_tracts_fa(os.path.join(HERE, "tracts.fa"))
+    if only is None or any(n.startswith("wd_") for n in only):
+        write_width_fa(os.path.join(HERE, "width.fa"))
 
     cases = []
 
@@ -232,6 +247,13 @@ def main():
     # so the round ranges (VE.h:206-254) below are what ANY correct implementation must print
     case("rand6_k9_L24_r4", "rand6.fa", 9, 24, rounds=4)
     case("c2_k29_L26_r3", "c2.fa", 29, 26, rounds=3)
+
+    # key widths no other case reaches (4, 9 and 14 words) on a saturated filter (L = 10: strand-hash ties), and an abundance cut on
+    # keys of more than one word
+    case("wd_k93_L10", "width.fa", 93, 10)
+    case("wd_k253_L10", "width.fa", 253, 10)
+    case("wd_k413_L10", "width.fa", 413, 10)
+    case("wd_k93_a3", "width.fa", 93, 20, abundance=3)
 
     # low-complexity tracts (periodic windows) at filter sizes that take the partitioned passes (L >= 28); _r2: gated rounds, collision free
     case("tr_k25_L28", "tracts.fa", 25, 28)

@@ -418,6 +418,8 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "query_b2")) return c->stat_q_plan[2];
     if (!strcmp(name, "query_begun")) return c->stat_q_begun;  // 1: the last query's first batch was binned by tpc_pass1_query_begin
     if (!strcmp(name, "filter2_retries")) return c->stat_filter2_retries;
+    if (!strcmp(name, "aggregate_retries")) return c->stat_aggregate_retries;
+    if (!strcmp(name, "filter2_counted")) return c->stat_filter2_counted;
     if (!strcmp(name, "fused_lookups")) return c->stat_fused;
     if (!strcmp(name, "query_overflow_entries")) return c->stat_query_overflow;
     if (!strcmp(name, "insert_overflow_entries")) return c->stat_insert_overflow;

@@ -75,6 +75,8 @@ int tpc_pass2_aggregate_records(tpc_ctx *c, uint32_t world, uint64_t abundance, 
     while (full < 2 * c->n_marks + 2) full <<= 1;
     uint64_t cap = 1024;
     while (cap < c->n_marks / 4 + 2) cap <<= 1;
+    c->stat_filter2_counted = counted ? 1 : 0;
+    c->stat_aggregate_retries = 0;
     for (;;) {  // as pass2_filter_impl: sized for the usual ratio of marks to distinct keys, repeated at full size when a probe sequence says so
         if (cap > c->table_alloc) {
             if (c->table) (void)hipFree(c->table);
@@ -100,6 +102,7 @@ int tpc_pass2_aggregate_records(tpc_ctx *c, uint32_t world, uint64_t abundance, 
         }
         if (cap >= full) return fail(c, -1, "exact-filter table overflow at full size");
         cap = full;
+        c->stat_aggregate_retries++;
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -147,7 +150,9 @@ int pass2_filter_impl(tpc_ctx *c, const uint64_t *fmarks, uint64_t n_fmarks, boo
     // is repeated with 2 x marks slots, which always suffices.
     const size_t sb = tpc_table_slot_bytes(c->C);
     TpcLaunch a = make_launch(c);
-    const bool counted = aggregated ? aggregated_counted(abundance) : abundance < n_marks;  // otherwise no key can exceed the abundance cut
+    // otherwise no key can exceed the abundance cut.  Records may be aggregated ones (tpc_pass2_filter_records takes both): such a record
+    // carries a count that can exceed the number of records received, so for records the aggregated rule applies as well
+    const bool counted = (records && aggregated_counted(abundance)) || (!aggregated && abundance < n_marks);
     if (!c->scan_blocks) HIPCHK(c, hipMalloc((void **)&c->scan_blocks, 2 * TPC_SCAN2_BLOCKS * sizeof(uint64_t)));
     uint64_t full = 1024;
     while (full < 2 * n_marks + 2) full <<= 1;
@@ -156,6 +161,7 @@ int pass2_filter_impl(tpc_ctx *c, const uint64_t *fmarks, uint64_t n_fmarks, boo
     if (aggregated) cap = full;               // a rank sends a key once: the records are distinct up to the number of ranks
     uint64_t tp = 0, used = 0;
     c->stat_filter2_retries = 0;
+    c->stat_filter2_counted = counted ? 1 : 0;
     for (;;) {
         if (cap > c->table_alloc) {
             if (c->table) (void)hipFree(c->table);

@@ -108,6 +108,8 @@ struct tpc_ctx {
     mutable int stat_kernel[3] = {0, 0, 0};  // hash kernel of the last insert / query and the query's verification kernel (TpcLaunch::stat_kernel)
     int stat_fmt[2] = {0, 0};        // entry format of the last partitioned insert (level 2: 0 = 32-bit, 3 = planar 24-bit) / query (0 = 8-byte, 6 = planar 48-bit)
     int64_t stat_filter2_retries = 0;  // exact-filter passes repeated with the full-size table (last tpc_pass2_filter)
+    int64_t stat_aggregate_retries = 0;  // ... by the last tpc_pass2_aggregate_records
+    int stat_filter2_counted = 0;        // the last exact-filter launch counted occurrences (k_filter2 / k_filter2_rec <C, true>)
     int64_t opt_part_min_tiles = 256;  // never cut batches smaller than this many 512-word tiles
     int64_t opt_part_budget = 0;  // bytes of partition buffers per batch; 0 = automatic (part_budget())
     int opt_query_mode = 0;    // 0 auto, 1 direct loads, 2 partitioned

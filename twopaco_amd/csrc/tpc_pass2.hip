@@ -596,7 +596,8 @@ k_table_records(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_
             }
 #pragma unroll
             for (int w = 0; w < C; w++) records[o * (C + 1) + w] = ck[w];
-            records[o * (C + 1) + C] = sl.meta | (1ull << 63);
+            // a counted slot (abundance cut) holds no META_MULTI: set it from the count, so that the record says "seen twice" either way
+            records[o * (C + 1) + C] = sl.meta | ((sl.meta >> META_COUNT_SHIFT) >= 2 ? META_MULTI : 0ull) | (1ull << 63);
             owner[o] = (int32_t)((key_hash<C>(ck) >> 40) % world);
         }
         base += total;
