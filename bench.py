@@ -10,8 +10,12 @@ The second half of the metric -- end-to-end junction occurrences per second, pro
 close -- is measured at N = 1 by running the `twopaco` CLI as a child process on the same workload
 written out as FASTA files (`e2e` in the JSON line).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload m2|m1] [--scale S]
-                  [--decomposition ranges|address] [--cpu-baseline sample|full|none] [--e2e-runs R] [--dump-outputs DIR]
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  What the
+headline figure does not need runs with --full only: the end-to-end CLI runs, the CPU baseline (the
+reference binary), and at N > 1 the vertex-hash ranges timed beside the address-sharded filter.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload m2|m1] [--scale S] [--dump-outputs DIR]
+                  [--decomposition ranges|address] [--full [--cpu-baseline sample|full|none] [--e2e-runs R]]
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) starts
 `python -m torch.distributed.run --nproc-per-node N` on this file as a CHILD process (before anything
@@ -292,9 +296,12 @@ def main():
                                                       "two reverse-complemented genomes and 50-300 contigs per genome (synth.py)")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--test-first", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the twopaco CLI end to end (e2e, e2e_back_to_back), "
+                         "the CPU baseline, and at N > 1 with --decomposition auto the vertex-hash ranges (key 'ranges')")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full", "none"])
-    ap.add_argument("--e2e-runs", type=int, default=5, help="runs of the twopaco CLI for the end-to-end figure (0 = skip)")
+    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full", "none"], help="with --full")
+    ap.add_argument("--e2e-runs", type=int, default=5, help="with --full: runs of the twopaco CLI for the end-to-end figure (0 = skip)")
     ap.add_argument("--e2e-settle", type=float, default=3.5,
                     help="seconds between two CLI runs of the headline series: the driver wipes a finished process's device memory "
                          "asynchronously (~3 s for the 59 GB of one run) and an allocation that is handed one of those blocks waits for it (profiles/r04f_e2e_back_to_back.txt)")
@@ -302,7 +309,7 @@ def main():
     ap.add_argument("--decomposition", default="auto", choices=["auto", "ranges", "address"],
                     help="multi-GPU: the Bloom filter sharded by bit address with an all-to-all per pass (the north-star decomposition; "
                          "power-of-two N), or vertex-hash ranges (the reference's rounds side by side, no data-path exchange).  auto: "
-                         "address at every power-of-two N (the scaling curve is one decomposition); below 8 GPUs the range "
+                         "address at every power-of-two N (the scaling curve is one decomposition); with --full the range "
                          "decomposition is timed as well and reported under the key 'ranges' (DESIGN.md section 5)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="single GPU: after the timed steps write what the last one computed to DIR/*.npy (float64, at most 64 MB; see dump_outputs)")
@@ -325,8 +332,10 @@ def main():
         s.close()
     if world > 1 or os.environ.get("TPC_FORCE_DIST"):  # TPC_FORCE_DIST: exercise the distributed path with one rank
         from twopaco_amd import dist as tdist
+        if not args.full and args.decomposition == "auto":  # the line's own decomposition alone: under auto, bench_main times the ranges beside it
+            args.decomposition = "address" if world & (world - 1) == 0 else "ranges"  # (auto's choice in bench_main)
         base = None
-        if not args.no_cpu_baseline and args.cpu_baseline != "none":
+        if args.full and not args.no_cpu_baseline and args.cpu_baseline != "none":
             def base(recs, p):
                 tmp = tempfile.mkdtemp(prefix="tpc_bench_")
                 try:
@@ -334,7 +343,7 @@ def main():
                 finally:
                     shutil.rmtree(tmp, ignore_errors=True)
         e2e = None
-        if args.e2e_runs > 0:
+        if args.full and args.e2e_runs > 0:
             def e2e(recs, p, gpus):
                 tmp = tempfile.mkdtemp(prefix="tpc_bench_")
                 try:
@@ -478,30 +487,31 @@ def main():
         # the north star's roofline kernel: first-pass Bloom insert
         "roofline_insert": roof("first-pass insert (k_part_hash, k_part_split, k_part_apply / its share of k_apply_lookup)", ins_ms, design_ins, traffic_ins, 0.25 + q * 2 * G_BYTES, 0.25 + 8 * q),
     }
-    tmp = tempfile.mkdtemp(prefix="tpc_bench_")
-    try:
-        if args.e2e_runs > 0:
-            files = write_fasta_files(recs, tmp, p=p)
-            time.sleep(args.e2e_settle)  # this process's own context (60 GB) has just been closed
-            out["e2e"] = e2e_cli(files, p, golden, args.e2e_runs, tmp, settle_s=args.e2e_settle)
-            if "error" in out["e2e"]:
-                print("bench: " + out["e2e"]["error"], file=sys.stderr)
-                sys.exit(4)
-            if args.e2e_b2b_runs > 0:  # the same CLI run started right behind its predecessor: p50 / max and the slowest run's own timers
-                b2b = e2e_cli(files, p, golden, args.e2e_b2b_runs, tmp, settle_s=0.0)
-                if "error" in b2b:
-                    print("bench: " + b2b["error"], file=sys.stderr)
+    if args.full:
+        tmp = tempfile.mkdtemp(prefix="tpc_bench_")
+        try:
+            if args.e2e_runs > 0:
+                files = write_fasta_files(recs, tmp, p=p)
+                time.sleep(args.e2e_settle)  # this process's own context (60 GB) has just been closed
+                out["e2e"] = e2e_cli(files, p, golden, args.e2e_runs, tmp, settle_s=args.e2e_settle)
+                if "error" in out["e2e"]:
+                    print("bench: " + out["e2e"]["error"], file=sys.stderr)
                     sys.exit(4)
-                out["e2e_back_to_back"] = {k: b2b[k] for k in ("e2e_wall_s_p50", "e2e_wall_s_min", "e2e_wall_s_max", "e2e_wall_s_all", "breakdown_ms",
-                                                              "slowest_run_breakdown_ms", "runs", "output_sha256_equals_reference")}
-                out["e2e_back_to_back"]["what"] = ("the same CLI runs with no pause between them: an allocation of a run that is handed device memory the driver is still "
-                                                    "wiping for the process before it waits for that wipe (~3 s for 59 GB; profiles/r04e_e2e_budget_sweep.txt)")
-            out["e2e_junction_occurrences_per_sec"] = out["e2e"]["e2e_junction_occurrences_per_sec"]
-            out["e2e_wall_s"] = out["e2e"]["e2e_wall_s"]
-        if not args.no_cpu_baseline and args.cpu_baseline != "none":
-            out["cpu_baseline"] = cpu_baseline(recs, p, tmp, args.cpu_baseline)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+                if args.e2e_b2b_runs > 0:  # the same CLI run started right behind its predecessor: p50 / max and the slowest run's own timers
+                    b2b = e2e_cli(files, p, golden, args.e2e_b2b_runs, tmp, settle_s=0.0)
+                    if "error" in b2b:
+                        print("bench: " + b2b["error"], file=sys.stderr)
+                        sys.exit(4)
+                    out["e2e_back_to_back"] = {k: b2b[k] for k in ("e2e_wall_s_p50", "e2e_wall_s_min", "e2e_wall_s_max", "e2e_wall_s_all", "breakdown_ms",
+                                                                  "slowest_run_breakdown_ms", "runs", "output_sha256_equals_reference")}
+                    out["e2e_back_to_back"]["what"] = ("the same CLI runs with no pause between them: an allocation of a run that is handed device memory the driver is still "
+                                                        "wiping for the process before it waits for that wipe (~3 s for 59 GB; profiles/r04e_e2e_budget_sweep.txt)")
+                out["e2e_junction_occurrences_per_sec"] = out["e2e"]["e2e_junction_occurrences_per_sec"]
+                out["e2e_wall_s"] = out["e2e"]["e2e_wall_s"]
+            if not args.no_cpu_baseline and args.cpu_baseline != "none":
+                out["cpu_baseline"] = cpu_baseline(recs, p, tmp, args.cpu_baseline)
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
     print(json.dumps(out))
 
 

@@ -58,7 +58,7 @@ def test_bench_single_rank_over_rccl(decomposition):
 
 
 def test_bench_auto_value_is_the_address_sharded_filter_and_ranges_keep_their_record():
-    """`--decomposition auto` times both decompositions; the line's value is ALWAYS the address-sharded filter's (one decomposition at
+    """`--decomposition auto --full` times both decompositions; the line's value is ALWAYS the address-sharded filter's (one decomposition at
     every N: the per-N values are a scaling curve of the north-star design), the vertex-hash ranges keep their full record under
     "ranges", and both carry the same (reference) counters."""
     import json
@@ -69,7 +69,7 @@ def test_bench_auto_value_is_the_address_sharded_filter_and_ranges_keep_their_re
     env = dict(os.environ, TPC_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29545", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", TPC_MULTIGPU="entries")
     env.pop("TPC_DIST_BACKEND", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "m1", "--scale", "0.1",
-                          "--no-cpu-baseline", "--e2e-runs", "0"], env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--e2e-runs", "0"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["headline_decomposition"] == "address" == line["config"]["decomposition"]
@@ -93,7 +93,7 @@ def test_bench_two_ranks_on_one_gpu_whole_line():
     env["TPC_MULTIGPU"] = env["TWOPACO_MULTIGPU"] = "entries"  # this test pins the entry-routing exchange (filters beyond one GPU); the default is below
     env["TPC_E2E_EMULATE_RANKS"] = "1"  # the end-to-end leg: `twopaco --gpus 2 --emulate-ranks` (both ranks of the C++ host on this one device)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "m1", "--scale", "0.1",
-                          "--no-cpu-baseline", "--e2e-runs", "1", "--e2e-settle", "0.5"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--e2e-runs", "1", "--e2e-settle", "0.5"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -127,7 +127,7 @@ def test_bench_combined_exchange_whole_line(ranks, tmp_path):
     env["TPC_DIST_SERIALIZE"] = str(tmp_path / "device.lock")
     env["TPC_E2E_EMULATE_RANKS"] = "1"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--workload", "m1", "--scale", "0.1",
-                          "--no-cpu-baseline", "--e2e-runs", "1", "--e2e-settle", "0.5"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline", "--e2e-runs", "1", "--e2e-settle", "0.5"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 passes behind profiles/: kernel trace + stats, then FETCH_SIZE and WRITE_SIZE in their own runs (the guide's
-# HBM section: separate --pmc passes), then the plain bench line of the same build.  Any failing step fails the script.
+# HBM section: separate --pmc passes), then the full bench line of the same build.  Any failing step fails the script.
 # Usage (on the GPU box, from the repo root): bash tools/profile_round.sh <tag>
 set -euo pipefail
 tag=${1:-r03}
@@ -21,6 +21,6 @@ python3 tools/pmc_traffic.py $fdb $wdb > $out/${tag}_pmc_traffic.json
 # carries `traffic` / `frac` of THIS build (round 4's kept line said "stale" because this copy came after)
 pmc_name=$(python3 -c "import re;print(re.search(r'PMC_PROFILE = \"(.*?)\"', open('bench.py').read()).group(1))")
 cp $out/${tag}_pmc_traffic.json profiles/$pmc_name
-python3 bench.py "${@:2}" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full "${@:2}" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cp profiles/$pmc_name $out/$pmc_name
 head -14 $out/${tag}_kernel_stats.csv
