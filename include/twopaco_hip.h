@@ -242,8 +242,17 @@ int tpc_shard_verify_local(tpc_ctx *ctx);
  * of the sharded calls opts in with tpc_set_option(ctx, "shard_periodic_skip", 1) before tpc_shard_plan -- tpc_shard_hash then skips them
  * too -- and MUST call tpc_shard_periodic_copy once per round, after the marks of the round's last query batch (tpc_shard_finish /
  * tpc_shard_mark / tpc_shard_verify_local) and before anything reads the round mask (mask union, tpc_pass2_marks).  The source of a copy
- * lies in the same 512-word tile, i.e. on the same rank.  Without the option nothing is skipped and the call does nothing. */
+ * lies in the same 512-word tile, i.e. on the same rank.  Without the option nothing is skipped and the call does nothing.
+ * The call is k_periodic_copy alone over whatever the round mask holds: mark(i) = mark(i - distance(i)) at every copying position, in
+ * ascending order, every other position unchanged -- on a one-rank context with the option set, after tpc_mask_import, it can be driven
+ * with any marks (tests/test_gpu_periodic.py). */
 int tpc_shard_periodic_copy(tpc_ctx *ctx);
+/* Read-out of the periodic-window masks (tests): builds them for this text and k if they are not built, as the first partitioned pass
+ * would, and copies to the host the bits of the copying positions (qs_host, tpc_mask_words words), the six bit planes of their copy
+ * distance 1 .. 63 (planes_host, plane b at b * tpc_mask_words) and the bits of the positions whose insert is dropped (ins_host); bit b of
+ * word w = position 32 w + b, as in the round mask.  All zero when the text has no such position, when option periodic_skip is 0, and on
+ * a sharded context that did not opt in.  Changes nothing a pass would not have changed. */
+int tpc_periodic_download(tpc_ctx *ctx, uint32_t *qs_host, uint32_t *planes_host, uint32_t *ins_host);
 
 /* ---- address-sharded filter (multi-GPU) -------------------------------------------------
  * The Bloom filter (ConcurrentBitVector bitVector, VE.h:257) is cut over `world` ranks (a power of
@@ -455,7 +464,10 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "insert_hash_kernel" = 0 none (the direct rolling kernel), 1 the instruction-lean hash with its seed table in LDS, 2 the same
  * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);
  * "query_hash_kernel" = 0 none (direct), 1 the lean k_q_hash2, 2 k_q_hash, 4 the closed form;
- * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify.
+ * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify;
+ * "text_word_begin" / "text_word_end" = the packed words [begin, end) of the text this context holds ("text_words" is their difference);
+ * "periodic_any_query" / "periodic_any_insert" = 1 when the detection-only launch of the periodic-window masks found a position that
+ * copies its verdict / drops its insert (0 before the masks of this text and k were asked for, or with the option off).
  * -1: unknown name. */
 int64_t tpc_get_stat(const tpc_ctx *ctx, const char *name);
 

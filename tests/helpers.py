@@ -94,3 +94,88 @@ def band_case():
     _BAND.update(files=[path], k=k, L=L, q=q, seed=seed, marks=marks, filter=filt, round_mask=mask, junctions=len(o.keys), want=want, bin=out)
     o.close()
     return _BAND
+
+
+# ---------------------------------------------------------------------------------------------- periodic windows: the definition
+PER_MAXP = 63      # periods 1 .. 63 (csrc/tpc_internal.h: TPC_PER_MAXP)
+PER_TILE = 16384   # positions of a 512-word tile: its first PER_MAXP positions never copy
+
+
+def periodic_reference(codes, k, lo=0, hi=None):
+    """The periodic-window masks of a text by their definition (csrc/tpc_qpartition.hip: k_periodic_build), in numpy.
+
+    codes: the position codes of the global text (0..3, 4 = N and every separator).  A context that holds only the characters
+    [lo, hi) sees every other one as 4; so does everything before the text and behind it.  With
+        eq_p[j] = T[j] < 4 and T[j - p] < 4 and T[j] == T[j - p]          p = 1 .. 63
+    ins[i]  = some p with eq_p true on all of i .. i + k       (the k + 1 characters of the out-edge repeat: the insert adds nothing)
+    qs[i]   = some p with eq_p true on all of i - 1 .. i + k   (the k + 2 characters of the vertex repeat: it takes the verdict of
+              position i - p), and i mod 16384 >= 63 (a copy never leaves its tile); dist[i] = the smallest such p, 0 where qs is clear.
+    Returns (qs bool, dist uint8, ins bool), one entry per position."""
+    T = np.array(codes, dtype=np.uint8)
+    n = T.size
+    hi = n if hi is None else min(int(hi), n)
+    T[:max(0, int(lo))] = 4
+    T[hi:] = 4
+    idx = np.arange(n, dtype=np.int64)
+    ins = np.zeros(n, dtype=bool)
+    qs = np.zeros(n, dtype=bool)
+    dist = np.zeros(n, dtype=np.uint8)
+    if n <= k:
+        return qs, dist, ins
+    for p in range(PER_MAXP, 0, -1):   # descending: the smallest period is written last
+        eq = np.zeros(n, dtype=bool)
+        eq[p:] = (T[p:] == T[:n - p]) & (T[p:] < 4)
+        # run[j] = length of the stretch of true eq that ends at j (0 where eq[j] is false)
+        run = idx - np.maximum.accumulate(np.where(eq, -1, idx))
+        end = run[k:]                   # end[i] = run at the window's last character i + k; windows past the text's end hold a 4
+        ins[:n - k] |= end >= k + 1
+        two = end >= k + 2
+        qs[:n - k] |= two
+        dist[:n - k][two] = p
+    tile = (idx % PER_TILE) >= PER_MAXP
+    qs &= tile
+    dist[~qs] = 0
+    return qs, dist, ins
+
+
+def periodic_reference_bruteforce(codes, k, lo=0, hi=None):
+    """The same definition by comparing windows of the text as strings, one position and one period at a time (the check of
+    periodic_reference; a few thousand positions at most)."""
+    n = len(codes)
+    hi = n if hi is None else min(int(hi), n)
+    s = "".join("ACGT"[c] if c < 4 and lo <= j < hi else "N" for j, c in enumerate(np.asarray(codes).tolist()))
+    pad = "N" * (PER_MAXP + 1)
+    s = pad + s + "N" * (k + 2)
+    qs = np.zeros(n, dtype=bool)
+    dist = np.zeros(n, dtype=np.uint8)
+    ins = np.zeros(n, dtype=bool)
+    for i in range(n):
+        a = i + len(pad)
+        edge, vertex = s[a:a + k + 1], s[a - 1:a + k + 1]
+        for p in range(1, PER_MAXP + 1):
+            if "N" not in edge and edge == s[a - p:a - p + k + 1]:
+                ins[i] = True
+            if "N" not in vertex and vertex == s[a - 1 - p:a - p + k + 1] and i % PER_TILE >= PER_MAXP and not qs[i]:
+                qs[i] = True
+                dist[i] = p
+    return qs, dist, ins
+
+
+def periodic_copy_reference(marks, qs, dist):
+    """k_periodic_copy's result, one position after the other: for i ascending, where qs[i], mark[i] = mark[i - dist[i]]."""
+    m = np.array(marks, dtype=bool)
+    d = dist.astype(np.int64)
+    for i in np.nonzero(qs)[0].tolist():
+        m[i] = m[i - d[i]]
+    return m
+
+
+def bits_of_words(words, n):
+    """One bool per position from a mask of 32-bit words (bit b of word w = position 32 w + b)."""
+    return np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")[:n].astype(bool)
+
+
+def words_of_bits(bits, n_words):
+    b = np.zeros(n_words * 32, dtype=np.uint8)
+    b[:len(bits)] = np.asarray(bits, dtype=np.uint8)
+    return np.packbits(b, bitorder="little").view("<u4").astype(np.uint32)

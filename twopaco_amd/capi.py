@@ -25,7 +25,7 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_shard_route", "tpc_shard_permute64", "tpc_shard_select", "tpc_mask_export_padded", "tpc_mask_or_blocks", "tpc_mask_import",
                "tpc_emit_stream", "tpc_emit_stream_fetch", "tpc_host_alloc", "tpc_host_free", "tpc_get_stat", "tpc_filter_upload",
                "tpc_junction_keys_export", "tpc_junction_keys_import", "tpc_warmup", "tpc_preload", "tpc_reserve", "tpc_shard_chunk", "tpc_emit_stream_partial", "tpc_emit_stream_part",
-               "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy",
+               "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in"]
 
 _hip = None
@@ -114,6 +114,7 @@ def hip():
         L.tpc_shard_finish.argtypes = [p, p, u64, ci, p, p, p]
         L.tpc_shard_verify_local.argtypes = [p]
         L.tpc_shard_periodic_copy.argtypes = [p]
+        L.tpc_periodic_download.argtypes = [p, p, p, p]
         L.tpc_pass1_query_begin.argtypes = [p, u64, u64]
         L.tpc_combine_info.argtypes = [p, u32, p]
         L.tpc_combine_export.argtypes = [p, u32, p, u64, p, p]
@@ -510,6 +511,21 @@ class Context:
     def shard_periodic_copy(self):
         """After a round's last query batch on a context with option shard_periodic_skip: positions that sent no probes take their twin's verdict."""
         self._ck(hip().tpc_shard_periodic_copy(self._h))
+
+    def periodic_download(self):
+        """The periodic-window masks of this text and k (built now if they are not), one entry per position of the mask words:
+        qs (bool: the position copies its verdict), dist (uint8: from how many positions back, 0 where qs is clear), ins (bool: its insert is dropped)."""
+        nw = hip().tpc_mask_words(self._h)
+        qs, planes, ins = np.zeros(nw, dtype=np.uint32), np.zeros((6, nw), dtype=np.uint32), np.zeros(nw, dtype=np.uint32)
+        self._ck(hip().tpc_periodic_download(self._h, qs.ctypes.data, planes.ctypes.data, ins.ctypes.data))
+
+        def bits(w):
+            return np.unpackbits(w.astype("<u4").view(np.uint8), bitorder="little")
+
+        dist = np.zeros(nw * 32, dtype=np.uint8)
+        for b in range(6):
+            dist |= bits(planes[b]) << b
+        return bits(qs).astype(bool), dist, bits(ins).astype(bool)
 
     def shard_verify_local(self):
         """One rank: verifies and marks the survivors of the last shard_apply(QUERY) where they are."""

@@ -426,6 +426,10 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "periodic_skip")) return c->periodic_valid ? 1 : 0;
     if (!strcmp(name, "pbuf_releases")) return c->stat_pbuf_releases;
     if (!strcmp(name, "text_words")) return (int64_t)(c->text_w1 - c->text_w0);  // packed words of the text this context holds
+    if (!strcmp(name, "text_word_begin")) return (int64_t)c->text_w0;  // ... words [begin, end) of the packed text (a windowed context: its tiles and their halo)
+    if (!strcmp(name, "text_word_end")) return (int64_t)c->text_w1;
+    if (!strcmp(name, "periodic_any_query")) return c->periodic_valid && c->periodic_any_q ? 1 : 0;   // what the detection-only launch of ensure_periodic answered:
+    if (!strcmp(name, "periodic_any_insert")) return c->periodic_valid && c->periodic_any_i ? 1 : 0;  // some position copies its verdict / drops its insert
     if (!strcmp(name, "device_free_bytes") || !strcmp(name, "device_total_bytes")) {  // hipMemGetInfo of the context's device, now
         size_t free_b = 0, total_b = 0;
         if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return -1; }
@@ -1073,6 +1077,24 @@ int tpc_mask_download(tpc_ctx *c, int run_wide, uint32_t *words_host)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(words_host, run_wide ? c->mask : c->rmask, c->n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tpc_periodic_download(tpc_ctx *c, uint32_t *qs_host, uint32_t *planes_host, uint32_t *ins_host)
+{   // the masks as the hash kernels and k_periodic_copy read them; zeros where ensure_periodic built none (no periodic position, option off)
+    if (!c || !c->have_params || !c->bases || !qs_host || !planes_host || !ins_host) return fail(c, -1, "set_params and seq_upload first");
+    HIPCHK(c, hipSetDevice(c->device));
+    ensure_periodic(c);
+    const size_t nw = c->n_words, stride = c->n_words_alloc;
+    memset(qs_host, 0, nw * sizeof(uint32_t));
+    memset(planes_host, 0, nw * TPC_PER_PLANES * sizeof(uint32_t));
+    memset(ins_host, 0, nw * sizeof(uint32_t));
+    if (!(c->periodic_valid && c->periodic && (c->periodic_any_q || c->periodic_any_i))) return 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(qs_host, c->periodic, nw * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < TPC_PER_PLANES; b++)
+        HIPCHK(c, hipMemcpy(planes_host + (size_t)b * nw, c->periodic + (size_t)(1 + b) * stride, nw * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ins_host, c->periodic + (size_t)(1 + TPC_PER_PLANES) * stride, nw * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
