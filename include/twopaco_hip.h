@@ -55,7 +55,8 @@ enum {
     TPC_K_FUSED = 12,       /* deferred apply: k_q_split + k_apply_lookup (inside TPC_K_QUERY), or the apply alone when it was flushed */
     TPC_K_LOOKUP = 13,      /* the k_apply_lookup launch of TPC_K_FUSED alone (the one kernel insert and query share: its time is split by bytes) */
     TPC_K_COMBINE = 14,     /* tpc_combine_export / tpc_combine_merge: k_slice_combine                                        */
-    TPC_K_COUNT = 15
+    TPC_K_SEGMENTS = 15,    /* tpc_segments_build_*: names and first-sight bits of the compacted graph's segments, graphdump.cpp:44-113, 398-480 */
+    TPC_K_COUNT = 16
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -414,6 +415,48 @@ int tpc_combine_choose(uint32_t world, int L, uint64_t mean_export_units, double
 /* Words [word0, word0 + n_words) of the filter to / from a device buffer (the dense form of the exchange; a pending insert is applied first). */
 int tpc_filter_copy_out(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uint32_t *dst_dev);
 int tpc_filter_copy_in(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, const uint32_t *src_dev);
+
+/* ---- segment table of the compacted graph (graphdump's walk on the device) ----------------------------------------------------
+ * graphdump's gfa1 / gfa2 / fasta formats walk the junction stream one record at a time: every pair of consecutive records of one
+ * sequence is a segment occurrence (an EVENT), named by its end junctions and one character of the text, and printed in full
+ * at the first sight of its name (graphdump.cpp:44-113 the naming, :398-480 the walk).  The walk is serial because of "first
+ * sight" and because segments whose deciding character is 'N' get fresh names 2^34, 2^34 + 1, ... in file order; both are a
+ * minimum / a scan over all events.  This group builds, for a stream of n_bytes / 12 slots (the bytes of de_bruijn.bin: a
+ * slot is a separator when its position OR its id field holds the separator value, junctionapi.h:91; trailing bytes that do
+ * not fill a slot are ignored), one entry per event e in file order:
+ *   name[e]   signed segment name, SegmentNamer::Name of twopaco_amd/host/junctiondump.cpp (graphdump.cpp:44-113)
+ *   first[e]  bit e % 32 of word e / 32: e is the smallest event index with this |name| (exact: a direct-addressed table of
+ *             32-bit event indices filled with atomicMin; 'N'-named events are always first)
+ * and the walk's first error in file order.  The text comes from tpc_seq_upload (tpc_set_params is not needed: a context used only
+ * for this holds no filter and no partition buffers); rec_start / rec_len are those of EVERY input sequence, as for tpc_emit_stream;
+ * amb_pos (n_amb entries, ascending, may be NULL when n_amb = 0) lists the global text positions that hold a valid letter other
+ * than A C G T N: the packed text cannot tell them from 'N', the namer can (graphdump.cpp:75-92: such a letter after the left
+ * junction of a forward segment gives the name -1, an 'N' there a fresh name).
+ * Memory: the stream (12 B / slot), 8 B / slot of scan scratch, 13 B / event, and the table of 4 x (largest |name| + 1) bytes,
+ * at most 32 x (largest |id| + 1).  A stream of 2^32 - 1 slots or more, or one whose buffers do not fit the free device memory,
+ * is refused with an error text (never a fault).
+ *   tpc_segments_build_host      from the stream's bytes in host memory (what graphdump reads from the file)
+ *   tpc_segments_build_resident  from the stream tpc_emit_stream left on the device in this context; same table
+ *   tpc_segments_counts          counts[0] events, [1] distinct segments (first bits set), [2] 'N'-named events, [3] bytes of the
+ *                                first-sight table, [4] slots, [5] peak bytes of device memory in use during the build
+ *   tpc_segments_error           the first failing pair of consecutive records in file order (what the serial walk would have
+ *                                thrown): *slot = slot index of the pair's second record (of the first record of the stream when its
+ *                                sequence id is not 0), *kind = 0 none, 1 "The input is corrupted", 2 "A vertex id is too large,
+ *                                cannot generate GFA" (|id| >= 2^31 in an event; inside one pair the corruption checks come first).
+ *                                The table is built all the same: an event that fails its own checks gets the name 0, every
+ *                                other entry is what the rule gives (sequence ids being the count of separators before a slot)
+ *   tpc_segments_fetch_names / _first   name[e0 .. e0 + n) / words [word0, word0 + n_words) of first[] to the host */
+#define TPC_SEG_OK 0
+#define TPC_SEG_CORRUPTED 1
+#define TPC_SEG_ID_TOO_LARGE 2
+int tpc_segments_build_host(tpc_ctx *ctx, const void *stream_host, uint64_t n_bytes, int k, const uint64_t *rec_start, const uint64_t *rec_len,
+                            uint32_t n_rec, const uint64_t *amb_pos, uint64_t n_amb);
+int tpc_segments_build_resident(tpc_ctx *ctx, int k, const uint64_t *rec_start, const uint64_t *rec_len, uint32_t n_rec, const uint64_t *amb_pos,
+                                uint64_t n_amb);
+int tpc_segments_counts(const tpc_ctx *ctx, uint64_t *counts /* [6] */);
+int tpc_segments_error(const tpc_ctx *ctx, uint64_t *slot, int *kind);
+int tpc_segments_fetch_names(tpc_ctx *ctx, uint64_t e0, uint64_t n, int64_t *name_host);
+int tpc_segments_fetch_first(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uint32_t *first_host);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -26,7 +26,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_emit_stream", "tpc_emit_stream_fetch", "tpc_host_alloc", "tpc_host_free", "tpc_get_stat", "tpc_filter_upload",
                "tpc_junction_keys_export", "tpc_junction_keys_import", "tpc_warmup", "tpc_preload", "tpc_reserve", "tpc_shard_chunk", "tpc_emit_stream_partial", "tpc_emit_stream_part",
                "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
-               "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in"]
+               "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
+               "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first"]
+SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
 _host = None
@@ -138,6 +140,12 @@ def hip():
         L.tpc_mask_import.argtypes = [p, p]
         L.tpc_emit_stream.argtypes = [p, p, p, u32, p, p]
         L.tpc_emit_stream_fetch.argtypes = [p, u64, u64, p]
+        L.tpc_segments_build_host.argtypes = [p, p, u64, ci, p, p, u32, p, u64]
+        L.tpc_segments_build_resident.argtypes = [p, ci, p, p, u32, p, u64]
+        L.tpc_segments_counts.argtypes = [p, p]
+        L.tpc_segments_error.argtypes = [p, p, p]
+        L.tpc_segments_fetch_names.argtypes = [p, u64, u64, p]
+        L.tpc_segments_fetch_first.argtypes = [p, u64, u64, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
         L.tpc_get_stat.restype = i64
@@ -419,6 +427,44 @@ class Context:
         if hip().tpc_emit_stream_fetch(self._h, 0, nb.value, buf.ctypes.data) != 0:
             raise RuntimeError("tpc_emit_stream_fetch failed")
         return buf.tobytes(), nr.value
+
+    def segments_build(self, stream, k, rec_start, rec_len, ambiguous=()):
+        """The segment table of graphdump's gfa1 / gfa2 / fasta walk (csrc/tpc_segments.hip) over the text of seq_upload.
+        stream: the bytes of de_bruijn.bin, or None for the stream emit_stream left on the device.  ambiguous: ascending
+        global text positions of the valid letters other than A C G T N.  Returns segments_counts()."""
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        amb = np.ascontiguousarray(ambiguous, dtype=np.uint64)
+        if stream is None:
+            self._ck(hip().tpc_segments_build_resident(self._h, k, rs.ctypes.data, rl.ctypes.data, rs.size, amb.ctypes.data, amb.size))
+        else:
+            buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+            self._ck(hip().tpc_segments_build_host(self._h, buf.ctypes.data, buf.size, k, rs.ctypes.data, rl.ctypes.data, rs.size, amb.ctypes.data, amb.size))
+        return self.segments_counts()
+
+    def segments_counts(self):
+        """dict: events, segments (first bits set), n_named ('N'-named events), table_bytes, slots, peak_device_bytes."""
+        c = np.zeros(6, dtype=np.uint64)
+        self._ck(hip().tpc_segments_counts(self._h, c.ctypes.data))
+        return dict(zip(("events", "segments", "n_named", "table_bytes", "slots", "peak_device_bytes"), (int(x) for x in c)))
+
+    def segments_error(self):
+        """(slot of the failing pair's second record, text of the serial walk's error) or None."""
+        slot, kind = ctypes.c_uint64(0), ctypes.c_int(0)
+        self._ck(hip().tpc_segments_error(self._h, ctypes.byref(slot), ctypes.byref(kind)))
+        return None if kind.value == 0 else (slot.value, SEGMENT_ERRORS[kind.value])
+
+    def segments_fetch(self, e0=0, n=None):
+        """(name[e0 : e0 + n] as int64, first[e0 : e0 + n] as bool); n = None: to the last event."""
+        events = self.segments_counts()["events"]
+        n = events - e0 if n is None else n
+        name = np.zeros(n, dtype=np.int64)
+        self._ck(hip().tpc_segments_fetch_names(self._h, e0, n, name.ctypes.data))
+        w0, w1 = e0 // 32, (e0 + n + 31) // 32
+        words = np.zeros(max(w1 - w0, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_fetch_first(self._h, w0, words.size, words.ctypes.data))
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[e0 - 32 * w0:e0 - 32 * w0 + n].astype(bool)
+        return name, bits
 
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))

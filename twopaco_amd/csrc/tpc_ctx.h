@@ -3,6 +3,7 @@
 //   tpc_capi_pass2.hip    second pass, junction keys, ids, junction stream (tpc_pass2_*, tpc_junction*, tpc_emit*)
 //   tpc_capi_shard.hip    the filter cut by address over ranks (tpc_shard_*), mask unions
 //   tpc_capi_combine.hip  the filter replicated through set-bit lists (tpc_combine_*)
+//   tpc_capi_segments.hip the segment table of the compacted graph (tpc_segments_*)
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
 #include "../../include/twopaco_hip.h"
@@ -85,6 +86,13 @@ struct tpc_ctx {
     uint64_t *sp_rec = nullptr, *sp_vscan = nullptr, *sp_cnt = nullptr, *sp_lo = nullptr;
     uint32_t *sp_flags = nullptr;
     uint32_t sp_n_rec = 0;
+    // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed, of the last build
+    int64_t *seg_name = nullptr;
+    uint32_t *seg_first = nullptr;
+    uint64_t seg_events = 0, seg_segments = 0, seg_named = 0, seg_table_bytes = 0, seg_slots = 0, seg_peak_bytes = 0;
+    uint64_t seg_err_slot = 0;
+    int seg_err_kind = 0;
+    bool seg_valid = false;
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors

@@ -320,3 +320,9 @@ int tpc_warm_partition();
 int tpc_warm_qpartition();
 int tpc_warm_pass2();
 int tpc_warm_stream();
+// tpc_segments.hip
+#define TPC_SEG_ERR_TEXT 256
+struct TpcSegResult { uint64_t events, segments, named, table_bytes, peak_bytes, err_slot; int err_kind; };
+int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, int k, const uint64_t *bases, const uint32_t *nmask,
+                        const uint64_t *d_rec_start, const uint64_t *d_rec_len, uint32_t n_rec, const uint64_t *d_amb, uint64_t n_amb,
+                        int64_t **name_out, uint32_t **first_out, TpcSegResult *res, char *err);

@@ -2,7 +2,7 @@
 //
 // Downstream consumer of the junction stream, kept flag- and byte-compatible with the reference's
 // graphdump (reference src/graphdump/graphdump.cpp) so that pipelines built on it are unchanged:
-//   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix]
+//   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>]
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -16,20 +16,36 @@
 // 2^35-bit vector (4 GiB), and output is buffered.  Where the reference reads out of bounds (a .bin whose first
 // sequences were too short to be dispatched, so that sequence ids and FASTA records get out of step) it prints
 // garbage before its "The input is corrupted"; this tool reports the error without the garbage.
+// --gpu (an addition; without it nothing changes): for gfa1 / gfa2 / fasta the serial part of the walk -- segment names,
+// fresh names of 'N' segments, first sight -- is computed on the device (csrc/tpc_segments.hip through the tpc_segments_*
+// group of include/twopaco_hip.h, loaded with dlopen: the binary has no link-time dependency on the device library), after
+// which every output line depends only on its own event and the one before it, and `--threads` workers format contiguous
+// chunks of events that go to stdout in order.  No device or no library with --gpu is an error: there is no fallback.
 #include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <unordered_set>
 #include <vector>
 
+#include <dlfcn.h>
+#include <unistd.h>
+
+#include "../../include/twopaco_hip.h"
 #include "dnachar.h"
 #include "junctionapi.h"
 #include "streamfastaparser.h"
+#include "textpack.h"
 
 namespace
 {
@@ -40,7 +56,10 @@ namespace
 	class Out
 	{
 	public:
-		~Out() { Flush(); }
+		// toStdout = false: the text only collects in Text() (a chunk of the parallel formatter)
+		explicit Out(bool toStdout = true) : toStdout_(toStdout) {}
+		~Out() { if (toStdout_) Flush(); }
+		std::string & Text() { return buf_; }
 		Out & operator << (const std::string & s) { buf_ += s; return Check(); }
 		Out & operator << (const char * s) { buf_ += s; return Check(); }
 		Out & operator << (char c) { buf_ += c; return Check(); }
@@ -57,7 +76,7 @@ namespace
 	private:
 		Out & Check()
 		{
-			if (buf_.size() > (1u << 20))
+			if (toStdout_ && buf_.size() > (1u << 20))
 			{
 				std::fwrite(buf_.data(), 1, buf_.size(), stdout);
 				buf_.clear();
@@ -66,6 +85,7 @@ namespace
 			return *this;
 		}
 
+		bool toStdout_;
 		std::string buf_;
 	};
 
@@ -349,6 +369,21 @@ namespace
 			prevId_ = 0;
 		}
 
+		// The parallel formatter enters a sequence in the middle (Resume: the event before the chunk's first one, 0 when that
+		// begins its sequence) and hands the whole path to the worker that holds the sequence's last event.
+		void Resume(int64_t prevId, uint64_t prevSize)
+		{
+			path_.clear();
+			prevId_ = prevId;
+			prevSize_ = prevSize;
+		}
+
+		void EndOfSequence(size_t sequence, const int64_t * name, size_t count)
+		{
+			path_.assign(name, name + count);
+			EndOfSequence(sequence);
+		}
+
 	protected:
 		virtual void SegmentLine(const SegmentEvent & e, const std::string & body) = 0;
 		virtual void Occurrence(const SegmentEvent & e, size_t k) = 0;
@@ -439,6 +474,409 @@ namespace
 		Out & out_;
 	};
 
+	// ---------------------------------------------------------------------------------------- --gpu
+	double MsSince(const std::chrono::steady_clock::time_point & t0)
+	{
+		return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	}
+
+	struct DumpStats
+	{
+		std::string path;
+		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
+		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs;
+		size_t threads;
+		DumpStats() : path("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), threads(1) {}
+
+		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
+		void Write() const
+		{
+			const char * file = std::getenv("TWOPACO_GRAPHDUMP_STATS");
+			if (!file || !*file) return;
+			FILE * f = std::fopen(file, "w");
+			if (!f) return;
+			std::fprintf(f, "{\"path\": \"%s\", \"events\": %llu, \"segments\": %llu, \"n_named\": %llu, \"device_ms\": %.3f, \"kernel_ms\": %.3f, \"load_ms\": %.3f, "
+				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
+				"\"table_bytes\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
+				(unsigned long long)tableBytes);
+			std::fclose(f);
+		}
+	};
+
+	// libtwopaco_hip.so, loaded when --gpu is given: ../lib beside the directory of the executable
+	class DeviceLibrary
+	{
+	public:
+		decltype(&tpc_ctx_create) ctxCreate;
+		decltype(&tpc_ctx_destroy) ctxDestroy;
+		decltype(&tpc_last_error) lastError;
+		decltype(&tpc_seq_upload) seqUpload;
+		decltype(&tpc_segments_build_host) segmentsBuildHost;
+		decltype(&tpc_segments_counts) segmentsCounts;
+		decltype(&tpc_segments_error) segmentsError;
+		decltype(&tpc_segments_fetch_names) segmentsFetchNames;
+		decltype(&tpc_segments_fetch_first) segmentsFetchFirst;
+		decltype(&tpc_kernel_ms) kernelMs;
+		tpc_ctx * ctx;
+
+		explicit DeviceLibrary(int device) : ctx(0), handle_(0)
+		{
+			char exe[4096];
+			const ssize_t n = ::readlink("/proc/self/exe", exe, sizeof(exe) - 1);
+			std::string dir = n > 0 ? std::string(exe, size_t(n)) : std::string();
+			dir = dir.find('/') == std::string::npos ? std::string(".") : dir.substr(0, dir.rfind('/'));
+			const std::string path = dir + "/../lib/libtwopaco_hip.so";
+			handle_ = ::dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+			if (!handle_)
+			{
+				const char * why = ::dlerror();
+				throw std::runtime_error("--gpu: cannot load " + path + (why ? std::string(": ") + why : std::string()));
+			}
+
+			Load(ctxCreate, "tpc_ctx_create");
+			Load(ctxDestroy, "tpc_ctx_destroy");
+			Load(lastError, "tpc_last_error");
+			Load(seqUpload, "tpc_seq_upload");
+			Load(segmentsBuildHost, "tpc_segments_build_host");
+			Load(segmentsCounts, "tpc_segments_counts");
+			Load(segmentsError, "tpc_segments_error");
+			Load(segmentsFetchNames, "tpc_segments_fetch_names");
+			Load(segmentsFetchFirst, "tpc_segments_fetch_first");
+			Load(kernelMs, "tpc_kernel_ms");
+			const int rc = ctxCreate(device, &ctx);
+			if (rc != 0 || !ctx)
+			{
+				ctx = 0;
+				throw std::runtime_error("--gpu: no HIP device " + std::to_string(device) + " (tpc_ctx_create returned " + std::to_string(rc) + "); there is no CPU fallback behind --gpu");
+			}
+		}
+
+		~DeviceLibrary()
+		{
+			if (ctx) ctxDestroy(ctx);
+		}
+
+		void Check(int rc, const char * what) const
+		{
+			if (rc != 0) throw std::runtime_error(std::string("--gpu: ") + what + " failed: " + lastError(ctx));
+		}
+
+	private:
+		DeviceLibrary(const DeviceLibrary &);
+		void operator = (const DeviceLibrary &);
+		template<class F> void Load(F & fn, const char * name)
+		{
+			fn = reinterpret_cast<F>(::dlsym(handle_, name));
+			if (!fn) throw std::runtime_error(std::string("--gpu: libtwopaco_hip.so lacks ") + name);
+		}
+
+		void * handle_;
+	};
+
+	// What ListSequences and SequenceCursor give the serial walk -- names, lengths, the letters as the parser upper-cases
+	// them -- read once, files in parallel; and per sequence the positions of the valid letters other than A C G T N, which
+	// the packed text holds as 'N' while the namer does not (SegmentNamer::Name: MakeUpChar of such a letter is -1).
+	struct LoadedSequences
+	{
+		std::vector<std::string> body;
+		std::vector<std::vector<uint64_t> > ambiguous;
+	};
+
+	template<class Fn> void RunParallel(size_t items, size_t threads, const Fn & fn)
+	{
+		std::atomic<size_t> cursor(0);
+		auto work = [&]() { for (size_t i = cursor++; i < items; i = cursor++) fn(i); };
+		std::vector<std::thread> pool;
+		for (size_t t = 1; t < std::min(threads, items); t++) pool.emplace_back(work);
+		work();
+		for (std::thread & th : pool) th.join();
+	}
+
+	void LoadSequences(const std::vector<std::string> & fasta, bool prefixed, size_t threads, InputSequences & seq, LoadedSequences & loaded)
+	{
+		struct PerFile
+		{
+			std::vector<std::string> name, body;
+			std::vector<std::vector<uint64_t> > ambiguous;
+			std::string error;
+		};
+
+		std::vector<PerFile> file(fasta.size());
+		RunParallel(fasta.size(), threads, [&](size_t f)
+		{
+			PerFile & out = file[f];
+			try
+			{
+				TwoPaCo::StreamFastaParser parser(fasta[f]);
+				while (parser.ReadRecord())
+				{
+					out.name.push_back(prefixed ? "s0_" + parser.GetCurrentHeader() : parser.GetCurrentHeader());  // "s0_": see ListSequences
+					std::string body;
+					std::vector<uint64_t> ambiguous;
+					for (char ch; parser.GetChar(ch);)
+					{
+						if (!DnaChar::IsDefinite(ch) && ch != 'N') ambiguous.push_back(body.size());
+						body.push_back(ch);
+					}
+
+					out.body.push_back(std::string());
+					out.body.back().swap(body);
+					out.ambiguous.push_back(std::vector<uint64_t>());
+					out.ambiguous.back().swap(ambiguous);
+				}
+			}
+			catch (std::runtime_error & e)
+			{
+				out.error = e.what();
+				if (out.error.empty()) out.error = "unreadable FASTA file";
+			}
+		});
+
+		for (size_t f = 0; f < fasta.size(); f++)
+		{
+			// the serial walk meets the records of a broken file before its error; what it reports is the first error in file order
+			if (!file[f].error.empty()) throw std::runtime_error(file[f].error);
+			for (size_t r = 0; r < file[f].name.size(); r++)
+			{
+				seq.name.push_back(file[f].name[r]);
+				seq.file[file[f].name[r]] = fasta[f];
+				seq.length.push_back(file[f].body[r].size());
+				loaded.body.push_back(std::string());
+				loaded.body.back().swap(file[f].body[r]);
+				loaded.ambiguous.push_back(std::vector<uint64_t>());
+				loaded.ambiguous.back().swap(file[f].ambiguous[r]);
+			}
+		}
+	}
+
+	const size_t SLOT_BYTES = 12;
+	uint32_t SlotPos(const std::vector<char> & bin, uint64_t slot)
+	{
+		uint32_t p;
+		std::memcpy(&p, &bin[slot * SLOT_BYTES], sizeof(p));
+		return p;
+	}
+
+	bool SlotIsSeparator(const std::vector<char> & bin, uint64_t slot)
+	{
+		int64_t id;
+		std::memcpy(&id, &bin[slot * SLOT_BYTES + 4], sizeof(id));
+		return SlotPos(bin, slot) == UINT32_MAX || id == INT64_MAX;  // JunctionPositionReader::NextJunctionPosition
+	}
+
+	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines); `makeSink` builds the
+	// format's sink over a chunk's buffer.
+	template<class MakeSink>
+	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, const MakeSink & makeSink)
+	{
+		// the stream's bytes
+		std::vector<char> bin;
+		{
+			std::ifstream in(binFile.c_str(), std::ios::binary);
+			if (!in) throw std::runtime_error("Can't read the input file");
+			in.seekg(0, std::ios::end);
+			const std::streamoff size = in.tellg();
+			in.seekg(0, std::ios::beg);
+			if (size > 0)
+			{
+				bin.resize(size_t(size));
+				in.read(&bin[0], size);
+				bin.resize(size_t(in.gcount()));
+			}
+		}
+
+		// the packed text and where the namer must not read 'N'
+		std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+		TwoPaCo::PackedText text;
+		TwoPaCo::PackFastaFiles(fasta, threads, text);
+		if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+		std::vector<uint64_t> ambiguous;
+		for (size_t r = 0; r < loaded.body.size(); r++)
+		{
+			if (text.recLength[r] != loaded.body[r].size()) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+			for (uint64_t at : loaded.ambiguous[r]) ambiguous.push_back(text.recStart[r] + at);
+		}
+
+		stats.packMs = MsSince(t0);
+
+		// the device stage
+		t0 = std::chrono::steady_clock::now();
+		lib.Check(lib.seqUpload(lib.ctx, text.bases.data(), text.nmask.data(), text.length), "tpc_seq_upload");
+		lib.Check(lib.segmentsBuildHost(lib.ctx, bin.data(), bin.size(), int(k), text.recStart.data(), text.recLength.data(), uint32_t(text.recStart.size()),
+			ambiguous.data(), ambiguous.size()), "tpc_segments_build_host");
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0}, errorSlot = 0;
+		int errorKind = 0;
+		lib.Check(lib.segmentsCounts(lib.ctx, counts), "tpc_segments_counts");
+		lib.Check(lib.segmentsError(lib.ctx, &errorSlot, &errorKind), "tpc_segments_error");
+		stats.path = "device";
+		stats.events = counts[0];
+		stats.segments = counts[1];
+		stats.nNamed = counts[2];
+		stats.tableBytes = counts[3];
+		stats.deviceBytes = counts[5];
+		stats.streamBytes = counts[4] * SLOT_BYTES;
+		stats.textBytes = ((text.length + 31) / 32) * 12;
+		stats.kernelMs = lib.kernelMs(lib.ctx, TPC_K_SEGMENTS);
+		if (errorKind != TPC_SEG_OK)
+		{
+			stats.deviceMs = MsSince(t0);
+			stats.Write();
+			// what the serial walk throws at this pair
+			throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
+		}
+
+		const uint64_t events = counts[0];
+		std::vector<int64_t> name(events);
+		std::vector<uint32_t> first((events + 31) / 32);
+		lib.Check(lib.segmentsFetchNames(lib.ctx, 0, events, name.data()), "tpc_segments_fetch_names");
+		lib.Check(lib.segmentsFetchFirst(lib.ctx, 0, first.size(), first.data()), "tpc_segments_fetch_first");
+		stats.deviceMs = MsSince(t0);
+
+		// where every event sits in the stream: the slot of its right record and its sequence
+		t0 = std::chrono::steady_clock::now();
+		const uint64_t slots = bin.size() / SLOT_BYTES;
+		std::vector<uint32_t> eventSlot, eventSequence;
+		eventSlot.reserve(events);
+		eventSequence.reserve(events);
+		{
+			uint32_t sequence = 0;
+			bool previousIsRecord = false;
+			for (uint64_t i = 0; i < slots; i++)
+			{
+				if (SlotIsSeparator(bin, i))
+				{
+					++sequence;
+					previousIsRecord = false;
+					continue;
+				}
+
+				if (previousIsRecord)
+				{
+					eventSlot.push_back(uint32_t(i));
+					eventSequence.push_back(sequence);
+				}
+
+				previousIsRecord = true;
+			}
+		}
+
+		if (eventSlot.size() != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
+		stats.indexMs = MsSince(t0);
+
+		// format: contiguous chunks of events, each into its own buffer, buffers to stdout in order
+		t0 = std::chrono::steady_clock::now();
+		out.Flush();
+		// about eight chunks per thread, of 16 .. 65536 events (a few MB of text at most): small inputs are cut as well
+		const uint64_t chunkEvents = std::max<uint64_t>(16, std::min<uint64_t>(uint64_t(1) << 16, events / (8 * threads) + 1));
+		const size_t chunks = size_t((events + chunkEvents - 1) / chunkEvents);
+		auto formatChunk = [&](size_t c, std::string & into)
+		{
+			Out chunkOut(false);
+			GfaSink * gfa = 0;
+			std::unique_ptr<SegmentSink> sink(makeSink(chunkOut, gfa));
+			const uint64_t e0 = uint64_t(c) * chunkEvents, e1 = std::min(events, e0 + chunkEvents);
+			for (uint64_t e = e0; e < e1; e++)
+			{
+				const uint32_t slot = eventSlot[e];
+				SegmentEvent ev;
+				ev.id = name[e];
+				ev.begin = SlotPos(bin, slot - 1);
+				ev.end = SlotPos(bin, slot);
+				ev.size = ev.end + k - ev.begin;
+				ev.first = (first[e >> 5] >> (e & 31)) & 1u;
+				ev.sequence = eventSequence[e];
+				if (e == e0 && gfa)
+				{
+					const bool continues = e > 0 && eventSlot[e - 1] + 1 == slot;  // the event before lies in the same sequence
+					if (continues) gfa->Resume(name[e - 1], uint64_t(SlotPos(bin, slot - 1)) + k - SlotPos(bin, slot - 2));
+					else gfa->Resume(0, 0);
+				}
+
+				sink->Segment(ev, loaded.body[ev.sequence], k);
+				if (gfa && (e + 1 == events || eventSlot[e + 1] != slot + 1))
+				{
+					// last event of its sequence: the path line is this worker's, whatever chunk the path began in
+					uint64_t begin = e;
+					while (begin > 0 && eventSlot[begin - 1] + 1 == eventSlot[begin]) --begin;
+					gfa->EndOfSequence(ev.sequence, &name[begin], size_t(e - begin + 1));
+				}
+			}
+
+			into.swap(chunkOut.Text());
+		};
+
+		if (threads <= 1 || chunks <= 1)
+		{
+			for (size_t c = 0; c < chunks; c++)
+			{
+				std::string textOfChunk;
+				formatChunk(c, textOfChunk);
+				std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
+			}
+		}
+		else
+		{
+			// threads - 1 workers format, this thread writes; a worker runs at most `window` chunks ahead of the writer
+			std::vector<std::string> done(chunks);
+			std::vector<char> ready(chunks, 0);
+			std::mutex lock;
+			std::condition_variable changed;
+			size_t written = 0;
+			const size_t window = 4 * threads;
+			std::atomic<size_t> cursor(0);
+			std::vector<std::thread> pool;
+			for (size_t t = 1; t < threads; t++)
+			{
+				pool.emplace_back([&]()
+				{
+					for (size_t c = cursor++; c < chunks; c = cursor++)
+					{
+						{
+							std::unique_lock<std::mutex> hold(lock);
+							changed.wait(hold, [&]() { return c < written + window; });
+						}
+
+						std::string textOfChunk;
+						formatChunk(c, textOfChunk);
+						{
+							std::unique_lock<std::mutex> hold(lock);
+							done[c].swap(textOfChunk);
+							ready[c] = 1;
+						}
+
+						changed.notify_all();
+					}
+				});
+			}
+
+			for (size_t c = 0; c < chunks; c++)
+			{
+				std::string textOfChunk;
+				{
+					std::unique_lock<std::mutex> hold(lock);
+					changed.wait(hold, [&]() { return ready[c] != 0; });
+					textOfChunk.swap(done[c]);
+				}
+
+				std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
+				{
+					std::unique_lock<std::mutex> hold(lock);
+					written = c + 1;
+				}
+
+				changed.notify_all();
+			}
+
+			for (std::thread & th : pool) th.join();
+		}
+
+		std::fflush(stdout);
+		stats.formatMs = MsSince(t0);
+	}
+
 	// ---------------------------------------------------------------------------------------- command line
 	struct ArgError
 	{
@@ -448,12 +886,15 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
 			"   -f <seq|group|dot|gfa1|gfa2|fasta>,  --format <seq|group|dot|gfa1|gfa2|fasta>\n     (required)  Output format\n\n"
 			"   --prefix\n     Add a prefix to segments in GFA (in case if you have genomes with identical FASTA headers)\n\n"
+			"   --gpu [<device>]\n     gfa1, gfa2, fasta: name and deduplicate the segments on HIP device <device> (default 0) and format the output with\n"
+			"     several threads; the output is the same.  An error when there is no device: no CPU fallback\n\n"
+			"   --threads <integer>\n     threads of --gpu (1..16, default 16)\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -465,8 +906,9 @@ int main(int argc, char * argv[])
 	{
 		std::string binFile, format;
 		std::vector<std::string> fasta;
-		bool prefix = false, haveK = false, haveFormat = false, haveFile = false;
-		size_t k = 25;
+		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false;
+		int device = 0;
+		size_t k = 25, threads = 16;
 		bool positionalOnly = false;
 		for (int i = 1; i < argc; i++)
 		{
@@ -487,6 +929,20 @@ int main(int argc, char * argv[])
 			else if (a == "-h" || a == "--help") { Usage(); return 0; }
 			else if (a == "--version") { std::printf("\n%s  version: 0.9.4\n\n", argv[0]); return 0; }
 			else if (a == "--prefix") prefix = true;
+			else if (a == "--gpu")
+			{
+				gpu = true;
+				const std::string next = i + 1 < argc ? argv[i + 1] : "";
+				if (!next.empty() && next.size() <= 4 && next.find_first_not_of("0123456789") == std::string::npos) device = std::atoi(argv[++i]);
+			}
+			else if (a == "--threads")
+			{
+				const std::string v = value("(--threads)");
+				char * end = 0;
+				const long long parsed = std::strtoll(v.c_str(), &end, 10);
+				if (end == v.c_str() || *end != 0 || parsed < 1) throw ArgError("Couldn't read argument value from string '" + v + "'", "(--threads)");
+				threads = size_t(std::min<long long>(parsed, 16));
+			}
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -513,8 +969,39 @@ int main(int argc, char * argv[])
 		const bool needsSequences = format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
+		DumpStats stats;
+		std::unique_ptr<DeviceLibrary> lib;
+		if (gpu && needsSequences) lib.reset(new DeviceLibrary(device));  // before the first byte of output: no device is an error
+		stats.threads = lib ? threads : 1;
 		Out out;
-		if (format == "seq") DumpSeq(binFile, out);
+		if (lib)
+		{
+			// the serial branch below, with the walk's serial part done on the device
+			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+			InputSequences seq;
+			LoadedSequences loaded;
+			if (format == "gfa1") out << "H\tVN:Z:1.0\n";
+			if (format == "gfa2") out << "H\tVN:Z:2.0\n";
+			LoadSequences(fasta, format == "fasta" ? true : prefix, threads, seq, loaded);
+			stats.loadMs = MsSince(t0);
+			if (format == "gfa1")
+			{
+				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file[name] << '\n';
+				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
+					[&seq](Out & o, GfaSink * & gfa) -> SegmentSink * { return gfa = new Gfa1Sink(o, seq); });
+			}
+			else if (format == "gfa2")
+			{
+				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
+					[&seq](Out & o, GfaSink * & gfa) -> SegmentSink * { return gfa = new Gfa2Sink(o, seq); });
+			}
+			else
+			{
+				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
+					[](Out & o, GfaSink * & gfa) -> SegmentSink * { gfa = 0; return new FastaSink(o); });
+			}
+		}
+		else if (format == "seq") DumpSeq(binFile, out);
 		else if (format == "group") DumpGroups(binFile, out);
 		else if (format == "dot") DumpDot(binFile, out);
 		else
@@ -542,6 +1029,8 @@ int main(int argc, char * argv[])
 				WalkSegments(binFile, fasta, k, sink);
 			}
 		}
+
+		stats.Write();
 	}
 	catch (ArgError & e)
 	{
