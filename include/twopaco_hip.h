@@ -427,12 +427,17 @@ int tpc_filter_copy_in(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, const uin
  *   name[e]   signed segment name, SegmentNamer::Name of twopaco_amd/host/junctiondump.cpp (graphdump.cpp:44-113)
  *   first[e]  bit e % 32 of word e / 32: e is the smallest event index with this |name| (exact: a direct-addressed table of
  *             32-bit event indices filled with atomicMin; 'N'-named events are always first)
+ *   begin[e], end[e]   the position fields of the event's left and right record (32 bits each)
+ *   seq_event_begin[s], s = 0 .. n_rec   the number of events whose sequence id (the count of separator slots before the event)
+ *             is < s: the events of sequence s are [seq_event_begin[s], seq_event_begin[s + 1]), entries behind the last
+ *             separator hold the event count.  Together with name[] and first[] this EVENT TABLE is all a formatter needs of
+ *             the stream (twopaco_amd/host/graphformat.h)
  * and the walk's first error in file order.  The text comes from tpc_seq_upload (tpc_set_params is not needed: a context used only
  * for this holds no filter and no partition buffers); rec_start / rec_len are those of EVERY input sequence, as for tpc_emit_stream;
  * amb_pos (n_amb entries, ascending, may be NULL when n_amb = 0) lists the global text positions that hold a valid letter other
  * than A C G T N: the packed text cannot tell them from 'N', the namer can (graphdump.cpp:75-92: such a letter after the left
  * junction of a forward segment gives the name -1, an 'N' there a fresh name).
- * Memory: the stream (12 B / slot), 8 B / slot of scan scratch, 13 B / event, and the table of 4 x (largest |name| + 1) bytes,
+ * Memory: the stream (12 B / slot), 8 B / slot of scan scratch, 21 B / event, 4 B / input sequence, and the table of 4 x (largest |name| + 1) bytes,
  * at most 32 x (largest |id| + 1).  A stream of 2^32 - 1 slots or more, or one whose buffers do not fit the free device memory,
  * is refused with an error text (never a fault).
  *   tpc_segments_build_host      from the stream's bytes in host memory (what graphdump reads from the file)
@@ -444,8 +449,12 @@ int tpc_filter_copy_in(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, const uin
  *                                sequence id is not 0), *kind = 0 none, 1 "The input is corrupted", 2 "A vertex id is too large,
  *                                cannot generate GFA" (|id| >= 2^31 in an event; inside one pair the corruption checks come first).
  *                                The table is built all the same: an event that fails its own checks gets the name 0, every
- *                                other entry is what the rule gives (sequence ids being the count of separators before a slot)
- *   tpc_segments_fetch_names / _first   name[e0 .. e0 + n) / words [word0, word0 + n_words) of first[] to the host */
+ *                                other entry is what the rule gives (sequence ids being the count of separators before a slot);
+ *                                begin[] / end[] of such an event are unspecified
+ *   tpc_segments_fetch_names / _first   name[e0 .. e0 + n) / words [word0, word0 + n_words) of first[] to the host
+ *   tpc_segments_fetch_events           begin[e0 .. e0 + n) and end[e0 .. e0 + n) to the host
+ *   tpc_segments_fetch_sequences        seq_event_begin[s0 .. s0 + n), s0 + n <= n_rec + 1, to the host
+ * A range outside the table is refused with an error text. */
 #define TPC_SEG_OK 0
 #define TPC_SEG_CORRUPTED 1
 #define TPC_SEG_ID_TOO_LARGE 2
@@ -457,6 +466,8 @@ int tpc_segments_counts(const tpc_ctx *ctx, uint64_t *counts /* [6] */);
 int tpc_segments_error(const tpc_ctx *ctx, uint64_t *slot, int *kind);
 int tpc_segments_fetch_names(tpc_ctx *ctx, uint64_t e0, uint64_t n, int64_t *name_host);
 int tpc_segments_fetch_first(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uint32_t *first_host);
+int tpc_segments_fetch_events(tpc_ctx *ctx, uint64_t e0, uint64_t n, uint32_t *begin_host, uint32_t *end_host);
+int tpc_segments_fetch_sequences(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint32_t *first_event_host);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

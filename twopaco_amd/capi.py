@@ -27,7 +27,8 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_junction_keys_export", "tpc_junction_keys_import", "tpc_warmup", "tpc_preload", "tpc_reserve", "tpc_shard_chunk", "tpc_emit_stream_partial", "tpc_emit_stream_part",
                "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
-               "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first"]
+               "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
+               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -146,6 +147,8 @@ def hip():
         L.tpc_segments_error.argtypes = [p, p, p]
         L.tpc_segments_fetch_names.argtypes = [p, u64, u64, p]
         L.tpc_segments_fetch_first.argtypes = [p, u64, u64, p]
+        L.tpc_segments_fetch_events.argtypes = [p, u64, u64, p, p]
+        L.tpc_segments_fetch_sequences.argtypes = [p, u64, u64, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
         L.tpc_get_stat.restype = i64
@@ -177,6 +180,10 @@ def host():
         L.tpch_create_enumerator_mgpu.restype = p
         L.tpch_create_enumerator_mgpu.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
                                                   ctypes.c_char_p, ci, u64, ci, ci, ci, ci, ci, ctypes.POINTER(p)]
+        L.tpch_create_enumerator_graph.restype = p
+        L.tpch_create_enumerator_graph.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
+                                                   ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.POINTER(p)]
+        L.tpch_graph_format.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, ctypes.c_char_p, ci, ci, u64, p, p, p, p, u64, p, ctypes.c_char_p]
         L.tpch_enumerator_free.argtypes = [p]
         L.tpch_vertices_count.restype = u64
         L.tpch_vertices_count.argtypes = [p]
@@ -203,6 +210,27 @@ def seed_table(q, bits, seed=None):
     if host().tpch_seed_table(0 if seed is None else seed, 0 if seed is None else 1, q, bits, t.ctypes.data) != 0:
         raise RuntimeError(host().tpch_last_error().decode())
     return t
+
+
+def graph_format(files, k, fmt, out_path, name, first, begin, end, seq_event_begin, prefix=False, threads=16):
+    """The text of the compacted graph (gfa1 / gfa2 / fasta) from an event table (include/twopaco_hip.h: the tpc_segments_*
+    group) and the FASTA files, written to out_path by host/graphformat.h -- no device involved.  name: int64 per event,
+    first: bool per event, begin / end: the positions of the event's two records, seq_event_begin: one entry per sequence
+    and one more (the events of sequence s are [seq_event_begin[s], seq_event_begin[s + 1]))."""
+    name = np.ascontiguousarray(name, dtype=np.int64)
+    begin = np.ascontiguousarray(begin, dtype=np.uint32)
+    end = np.ascontiguousarray(end, dtype=np.uint32)
+    seqs = np.ascontiguousarray(seq_event_begin, dtype=np.uint32)
+    if not (name.size == begin.size == end.size == len(first)) or seqs.size < 1:
+        raise ValueError("graph_format: one entry per event in name, first, begin, end; at least one in seq_event_begin")
+    bits = np.zeros((name.size + 31) // 32 * 32, dtype=np.uint8)
+    bits[:name.size] = np.asarray(first, dtype=bool)
+    words = np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)) if name.size else np.zeros(1, dtype=np.uint32)
+    arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
+    rc = host().tpch_graph_format(arr, len(files), k, fmt.encode(), 1 if prefix else 0, threads, name.size, name.ctypes.data, words.ctypes.data,
+                                  begin.ctypes.data, end.ctypes.data, seqs.size - 1, seqs.ctypes.data, os.fsencode(out_path))
+    if rc != 0:
+        raise RuntimeError(host().tpch_last_error().decode())
 
 
 class PackedText:
@@ -466,6 +494,20 @@ class Context:
         bits = np.unpackbits(words.view(np.uint8), bitorder="little")[e0 - 32 * w0:e0 - 32 * w0 + n].astype(bool)
         return name, bits
 
+    def segments_fetch_events(self, e0=0, n=None):
+        """(begin[e0 : e0 + n], end[e0 : e0 + n]) as uint32: the positions of every event's left and right record; n = None: to the last event."""
+        n = self.segments_counts()["events"] - e0 if n is None else n
+        begin, end = np.zeros(max(n, 0), dtype=np.uint32), np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_fetch_events(self._h, e0, n, begin.ctypes.data, end.ctypes.data))
+        return begin, end
+
+    def segments_fetch_sequences(self, s0, n):
+        """seq_event_begin[s0 : s0 + n] as uint32 (the table has one entry more than the build was given sequences): the events
+        of sequence s are [seq_event_begin[s], seq_event_begin[s + 1])."""
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_fetch_sequences(self._h, s0, n, out.ctypes.data))
+        return out
+
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))
 
@@ -656,10 +698,26 @@ class Enumerator:
     """TwoPaCo::CreateEnumerator through the C++ host layer (host/vertexenumerator.h)."""
 
     def __init__(self, files, k, filter_bits, q=5, rounds=1, threads=1, abundance=(1 << 64) - 1, tmpdir=".",
-                 out="de_bruijn.bin", seed=None, device=0, test_first=False, gpus=1, rccl=True, emulate_ranks=False, force_sharded=False):
+                 out=None, seed=None, device=0, test_first=False, gpus=1, rccl=True, emulate_ranks=False, force_sharded=False,
+                 graph=None, graph_out=None, graph_prefix=False, graph_threads=16):
+        """out: the junction stream's file, default de_bruijn.bin.  graph = gfa1 | gfa2 | fasta: `twopaco --graph` -- the
+        compacted graph's text goes to graph_out (default de_bruijn.<graph>) and the junction stream is written only when
+        `out` is given."""
         arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
         log = ctypes.c_void_p()
-        if gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
+        if graph is not None:
+            if gpus > 1 or force_sharded:
+                raise ValueError("graph: one GPU only (every rank of a sharded run holds its own piece of the junction stream)")
+            graph_out = "de_bruijn." + graph if graph_out is None else graph_out
+            self._h = host().tpch_create_enumerator_graph(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),
+                                                          b"" if out is None else out.encode(), 0 if seed is None else 1, 0 if seed is None else seed,
+                                                          device, 1 if test_first else 0, graph.encode(), os.fsencode(graph_out),
+                                                          1 if graph_prefix else 0, graph_threads, ctypes.byref(log))
+            out = ""
+        out = "de_bruijn.bin" if out is None else out
+        if graph is not None:
+            pass
+        elif gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
             self._h = host().tpch_create_enumerator_mgpu(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),
                                                          out.encode(), 0 if seed is None else 1, 0 if seed is None else seed, device,
                                                          gpus, 1 if rccl else 0, 1 if emulate_ranks else 0, 1 if force_sharded else 0, ctypes.byref(log))

@@ -332,7 +332,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = { c->tab, c->bases_alloc, c->nmask_alloc, c->filter, c->rmask, c->mask, c->marks, c->block_sums, c->table,
-                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg_name, c->seg_first };
+                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg_name, c->seg_first, c->seg_ev[0], c->seg_ev[1], c->seg_ev[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     stream_part_release(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);

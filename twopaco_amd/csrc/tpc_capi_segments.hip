@@ -9,8 +9,9 @@ int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k,
                    const uint64_t *amb_pos, uint64_t n_amb)
 {
     c->seg_valid = false;
-    for (void *p : { (void *)c->seg_name, (void *)c->seg_first }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)c->seg_name, (void *)c->seg_first, (void *)c->seg_ev[0], (void *)c->seg_ev[1], (void *)c->seg_ev[2] }) if (p) (void)hipFree(p);
     c->seg_name = nullptr; c->seg_first = nullptr;
+    c->seg_ev[0] = c->seg_ev[1] = c->seg_ev[2] = nullptr;
     if (k < 0) return fail(c, -1, "segment table: k must not be negative");
     if (!c->bases || !c->nmask || c->text_windowed) return fail(c, -1, "segment table: tpc_seq_upload the whole text first");
     if (n_rec && (!rec_start || !rec_len)) return fail(c, -1, "segment table: records required");
@@ -30,14 +31,14 @@ int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k,
     char text[TPC_SEG_ERR_TEXT] = "";
     if (rc == 0) {
         Timed t(c, TPC_K_SEGMENTS);
-        rc = tpc_launch_segments(c->stream, d_slots, n_slots, k, c->bases, c->nmask, d_rec, d_rec + n_rec, n_rec, d_amb, n_amb, &c->seg_name, &c->seg_first, &res, text);
+        rc = tpc_launch_segments(c->stream, d_slots, n_slots, k, c->bases, c->nmask, d_rec, d_rec + n_rec, n_rec, d_amb, n_amb, &c->seg_name, &c->seg_first, c->seg_ev, &res, text);
     }
     const hipError_t e = hipStreamSynchronize(c->stream);
     for (void *p : { (void *)d_rec, (void *)d_amb }) if (p) (void)hipFree(p);
     if (rc) return text[0] ? fail(c, rc, "%s", text) : fail(c, rc, "segment table failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
     HIPCHK(c, e);
     c->seg_events = res.events; c->seg_segments = res.segments; c->seg_named = res.named; c->seg_table_bytes = res.table_bytes;
-    c->seg_slots = n_slots; c->seg_peak_bytes = res.peak_bytes;
+    c->seg_slots = n_slots; c->seg_peak_bytes = res.peak_bytes; c->seg_n_rec = n_rec;
     c->seg_err_slot = res.err_slot; c->seg_err_kind = res.err_kind;
     c->seg_valid = true;
     return 0;
@@ -111,6 +112,26 @@ int tpc_segments_fetch_first(tpc_ctx *c, uint64_t word0, uint64_t n_words, uint3
     if (!c || !c->seg_valid || (n_words && !first_host) || word0 > words || n_words > words - word0) return fail(c, -1, "segment table: bad first-bit range");
     HIPCHK(c, hipSetDevice(c->device));
     if (n_words) HIPCHK(c, hipMemcpy(first_host, c->seg_first + word0, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tpc_segments_fetch_events(tpc_ctx *c, uint64_t e0, uint64_t n, uint32_t *begin_host, uint32_t *end_host)
+{
+    if (!c || !c->seg_valid || (n && (!begin_host || !end_host)) || e0 > c->seg_events || n > c->seg_events - e0) return fail(c, -1, "segment table: bad event range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n) {
+        HIPCHK(c, hipMemcpy(begin_host, c->seg_ev[0] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(end_host, c->seg_ev[1] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int tpc_segments_fetch_sequences(tpc_ctx *c, uint64_t s0, uint64_t n, uint32_t *first_event_host)
+{
+    const uint64_t entries = c ? (uint64_t)c->seg_n_rec + 1 : 0;
+    if (!c || !c->seg_valid || (n && !first_event_host) || s0 > entries || n > entries - s0) return fail(c, -1, "segment table: bad sequence range");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n) HIPCHK(c, hipMemcpy(first_event_host, c->seg_ev[2] + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -86,9 +86,11 @@ struct tpc_ctx {
     uint64_t *sp_rec = nullptr, *sp_vscan = nullptr, *sp_cnt = nullptr, *sp_lo = nullptr;
     uint32_t *sp_flags = nullptr;
     uint32_t sp_n_rec = 0;
-    // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed, of the last build
+    // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed and the event table, of the last build
     int64_t *seg_name = nullptr;
     uint32_t *seg_first = nullptr;
+    uint32_t *seg_ev[3] = {nullptr, nullptr, nullptr};  // the event table: begin[e], end[e], seq_event_begin[0 .. seg_n_rec]
+    uint32_t seg_n_rec = 0;
     uint64_t seg_events = 0, seg_segments = 0, seg_named = 0, seg_table_bytes = 0, seg_slots = 0, seg_peak_bytes = 0;
     uint64_t seg_err_slot = 0;
     int seg_err_kind = 0;

@@ -325,4 +325,4 @@ int tpc_warm_stream();
 struct TpcSegResult { uint64_t events, segments, named, table_bytes, peak_bytes, err_slot; int err_kind; };
 int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, int k, const uint64_t *bases, const uint32_t *nmask,
                         const uint64_t *d_rec_start, const uint64_t *d_rec_len, uint32_t n_rec, const uint64_t *d_amb, uint64_t n_amb,
-                        int64_t **name_out, uint32_t **first_out, TpcSegResult *res, char *err);
+                        int64_t **name_out, uint32_t **first_out, uint32_t **ev_out /* [3]: begin, end, seq_event_begin */, TpcSegResult *res, char *err);

@@ -17,8 +17,12 @@
 //                 An exclusive scan over the 'N' flags numbers the fresh names.
 //   k_seg_min     table[|name[e]|] = min(e) with atomicMin on 32-bit entries; 'N'-named events get 2^34 + their rank.
 //   k_seg_first   first[e] = 'N'-named or table[|name[e]|] == e, bit-packed by wave ballot; counts the bits.
-// Memory (B = bytes): stream 12 B / slot (the caller's), scans 8 B / slot, name 8 B + 'N' rank 4 B + first 1 bit per
-// event, table 4 B x (largest |name| + 1) <= 32 B x (largest |id| + 1), ids being below 2^31 (an event with a larger one is
+//   k_seg_events  one thread per slot, from the two scans alone (slot i closes an event when e_of steps behind it, is a separator
+//                 when seq_of does): begin[e] / end[e] = the position fields of the event's two records, and
+//                 seq_event_begin[s] = events before the s-th separator (the events of sequence s are [seq_event_begin[s],
+//                 seq_event_begin[s + 1])) -- the EVENT TABLE, what a formatter needs of the stream beside name[] and first[].
+// Memory (B = bytes): stream 12 B / slot (the caller's), scans 8 B / slot, name 8 B + begin 4 B + end 4 B + 'N' rank 4 B + first
+// 1 bit per event, seq_event_begin 4 B per input sequence, table 4 B x (largest |name| + 1) <= 32 B x (largest |id| + 1), ids being below 2^31 (an event with a larger one is
 // the walk's "A vertex id is too large": it gets the name 0 and does not size the table).  Streams of 2^32 - 1 slots or more are refused (32-bit event
 // indices), and so is a table that does not fit the free device memory: an error text, never a fault.
 #include "../../include/twopaco_hip.h"
@@ -159,6 +163,25 @@ __global__ void k_seg_first(const int64_t *__restrict__ name, uint64_t n_events,
     if (mine) atomicAdd(n_first, mine);
 }
 
+// The event table.  seq_of / e_of: the exclusive scans (n + 1 entries).  The events of one sequence are consecutive, so the
+// separator that ends sequence s gives seq_event_begin[s + 1]; entries behind the last separator hold the event count.
+__global__ void k_seg_events(const uint32_t *__restrict__ slots, uint64_t n, const uint32_t *__restrict__ seq_of, const uint32_t *__restrict__ e_of,
+                             uint32_t *__restrict__ begin, uint32_t *__restrict__ end, uint64_t n_events, uint32_t *__restrict__ seq_begin, uint32_t n_rec)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t n_sep = seq_of[n];
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n || i <= n_rec; i += stride) {
+        if (i <= n_rec && (i == 0 || i > n_sep)) seq_begin[i] = i == 0 ? 0u : (uint32_t)n_events;
+        if (i >= n) continue;
+        const uint32_t e = e_of[i], s = seq_of[i];
+        if (e_of[i + 1] != e && i > 0 && e < n_events) {  // slot i closes event e
+            begin[e] = slots[(i - 1) * 3];
+            end[e] = slots[i * 3];
+        }
+        if (seq_of[i + 1] != s && s < n_rec) seq_begin[s + 1] = e;  // the (s + 1)-th separator: e events lie before it
+    }
+}
+
 int seg_scan32(hipStream_t s, uint32_t *data, uint64_t n, void *&tmp, size_t &tmp_cap)
 {
     size_t need = 0;
@@ -184,16 +207,18 @@ bool seg_fits(size_t bytes)
 }  // namespace
 
 // slots: n_slots x 12 bytes on the device.  *name_out / *first_out: device arrays of res->events entries / (events + 63) / 64 * 2
-// words, the caller's to free; both null when the stream has no event.  0, or < 0 with a text in err (TPC_SEG_ERR_TEXT bytes).
+// words, the caller's to free; both null when the stream has no event.  ev_out[0] / ev_out[1]: begin[] / end[] (res->events
+// entries each, null without events), ev_out[2]: seq_event_begin[] (n_rec + 1 entries, never null); the caller's to free too.  0, or < 0 with a text in err (TPC_SEG_ERR_TEXT bytes).
 int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, int k, const uint64_t *bases, const uint32_t *nmask,
                         const uint64_t *d_rec_start, const uint64_t *d_rec_len, uint32_t n_rec, const uint64_t *d_amb, uint64_t n_amb,
-                        int64_t **name_out, uint32_t **first_out, TpcSegResult *res, char *err)
+                        int64_t **name_out, uint32_t **first_out, uint32_t **ev_out, TpcSegResult *res, char *err)
 {
     *name_out = nullptr; *first_out = nullptr;
+    ev_out[0] = ev_out[1] = ev_out[2] = nullptr;
     *res = TpcSegResult{};
     err[0] = 0;
     if (n_slots >= 0xFFFFFFFFull) { snprintf(err, TPC_SEG_ERR_TEXT, "segment table: %llu slots, event indices are 32 bits (fewer than 2^32 - 1 slots)", (unsigned long long)n_slots); return -20; }
-    uint32_t *seq_of = nullptr, *e_of = nullptr, *nflag = nullptr, *table = nullptr, *first = nullptr;
+    uint32_t *seq_of = nullptr, *e_of = nullptr, *nflag = nullptr, *table = nullptr, *first = nullptr, *begin = nullptr, *end = nullptr, *seq_begin = nullptr;
     int64_t *name = nullptr;
     unsigned long long *scal = nullptr;
     void *tmp = nullptr;
@@ -203,7 +228,7 @@ int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, 
     uint32_t n_events = 0, n_named = 0;
     auto done = [&](int code) {
         for (void *p : { (void *)seq_of, (void *)e_of, (void *)nflag, (void *)table, (void *)scal, tmp }) if (p) (void)hipFree(p);
-        if (code) { for (void *p : { (void *)name, (void *)first }) if (p) (void)hipFree(p); }
+        if (code) { for (void *p : { (void *)name, (void *)first, (void *)begin, (void *)end, (void *)seq_begin }) if (p) (void)hipFree(p); }
         return code;
     };
     const size_t scan_bytes = (size_t)(n_slots + 1) * sizeof(uint32_t);
@@ -215,14 +240,21 @@ int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, 
     if (hipMemcpyAsync(&n_events, e_of + n_slots, sizeof n_events, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(scal, h, sizeof h, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return done(-10);
     const uint64_t first_words = ((uint64_t)n_events + 63) / 64 * 2;
-    const size_t ev_bytes = (size_t)n_events * 8 + ((size_t)n_events + 1) * 4 + first_words * 4;
-    if (!seg_fits(ev_bytes)) { snprintf(err, TPC_SEG_ERR_TEXT, "segment table: %zu bytes for %u events do not fit the free device memory", ev_bytes, n_events); return done(-20); }
-    if (hipMalloc((void **)&nflag, ((size_t)n_events + 1) * 4) != hipSuccess) return done(-10);
-    if (n_events && (hipMalloc((void **)&name, (size_t)n_events * 8) != hipSuccess || hipMalloc((void **)&first, first_words * 4) != hipSuccess)) return done(-10);
+    const size_t ev_bytes = (size_t)n_events * 16 + ((size_t)n_events + 1) * 4 + first_words * 4 + ((size_t)n_rec + 1) * 4;
+    if (!seg_fits(ev_bytes)) {
+        snprintf(err, TPC_SEG_ERR_TEXT, "segment table: %zu bytes for %u events and %u sequences do not fit the free device memory", ev_bytes, n_events, n_rec);
+        return done(-20);
+    }
+    if (hipMalloc((void **)&nflag, ((size_t)n_events + 1) * 4) != hipSuccess || hipMalloc((void **)&seq_begin, ((size_t)n_rec + 1) * 4) != hipSuccess) return done(-10);
+    if (n_events && (hipMalloc((void **)&name, (size_t)n_events * 8) != hipSuccess || hipMalloc((void **)&first, first_words * 4) != hipSuccess ||
+                     hipMalloc((void **)&begin, (size_t)n_events * 4) != hipSuccess || hipMalloc((void **)&end, (size_t)n_events * 4) != hipSuccess)) return done(-10);
     if (hipMemsetAsync(nflag + n_events, 0, 4, s) != hipSuccess || (first && hipMemsetAsync(first, 0, first_words * 4, s) != hipSuccess)) return done(-10);
     if (n_slots)
         hipLaunchKernelGGL(k_seg_name, dim3(seg_grid(n_slots)), dim3(256), 0, s, slots, n_slots, k, seq_of, e_of, bases, nmask, d_rec_start, d_rec_len, n_rec,
                            d_amb, n_amb, name, nflag, (uint64_t)n_events, scal);
+    // before e_of is reused for the 'N' ranks below
+    hipLaunchKernelGGL(k_seg_events, dim3(seg_grid(std::max<uint64_t>(n_slots, (uint64_t)n_rec + 1))), dim3(256), 0, s, slots, n_slots, seq_of, e_of, begin, end,
+                       (uint64_t)n_events, seq_begin, n_rec);
     if (hipMemcpyAsync(h, scal, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return done(-10);
     res->events = n_events;
     res->err_slot = 0; res->err_kind = TPC_SEG_OK;
@@ -252,5 +284,6 @@ int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, 
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) res->peak_bytes = total_b - free_b;
     *name_out = name; *first_out = first;
+    ev_out[0] = begin; ev_out[1] = end; ev_out[2] = seq_begin;
     return done(0);
 }

@@ -8,8 +8,12 @@
 // RCCL between them; --no-rccl: device-to-device copies; --emulate-ranks: N ranks on one device, for testing),
 // --save-filter F / --load-filter F (checkpoint of the Bloom filter after each round's first-pass insert, the reference's
 // commented-out ReloadBloomFilter, vertexenumerator.h:29,113-121; a run that loads skips the insert), and with --test,
-// --seed makes the trials reproducible (the reference's are not, test.cpp:169).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// --seed makes the trials reproducible (the reference's are not, test.cpp:169);
+// --graph gfa1|gfa2|fasta [--graph-out F] [--graph-prefix] [--graph-threads N]: the compacted graph as text from this process,
+// byte for byte what `graphdump -f <format> [--prefix]` prints for the junction stream of the same command (graphformat.h; the
+// stream stays on the device and the junction file is written only when -o is given as well; one GPU).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -60,8 +64,12 @@ namespace
 			<< "               [-t <integer>] [-a <integer>] [--tmpdir <directory name>] [-o <file name>] [--test]" << std::endl
 			<< "               [--seed <integer>] [--device <integer>] [--test-first] [--gpus <power of two>] [--no-rccl]" << std::endl
 			<< "               [--save-filter <file>] [--load-filter <file>]" << std::endl
+			<< "               [--graph <gfa1|gfa2|fasta>] [--graph-out <file name>] [--graph-prefix] [--graph-threads <integer>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
-			<< "       -q: 1..64 hash functions (the reference takes any number; more than 16 run on slower closed-form kernels)" << std::endl;
+			<< "       -q: 1..64 hash functions (the reference takes any number; more than 16 run on slower closed-form kernels)" << std::endl
+			<< "       --graph: also write the compacted graph as graphdump -f <format> prints it, to --graph-out (default" << std::endl
+			<< "               de_bruijn.<format>); the junction file is then written only when -o is given.  --graph-prefix:" << std::endl
+			<< "               graphdump's --prefix.  --graph-threads: formatting threads (1..16, default 16).  One GPU only" << std::endl;
 	}
 }
 
@@ -102,7 +110,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -124,7 +132,7 @@ int main(int argc, char * argv[])
 			else if (Match(a, "t", "threads")) threads = Parse<unsigned int>(value("(--threads)"), "(--threads)");
 			else if (Match(a, "a", "abundance")) abundance = Parse<size_t>(value("(--abundance)"), "(--abundance)");
 			else if (Match(a, 0, "tmpdir")) tmpDirName = value("(--tmpdir)");
-			else if (Match(a, "o", "outfile")) outFileName = value("(--outfile)");
+			else if (Match(a, "o", "outfile")) { outFileName = value("(--outfile)"); outFileSet = true; }
 			else if (Match(a, 0, "test")) runTests = true;
 			else if (Match(a, 0, "seed")) { options.pinnedSeed = true; options.seed = Parse<uint64_t>(value("(--seed)"), "(--seed)"); optionsSet = true; }
 			else if (Match(a, 0, "device")) { options.device = int(Parse<unsigned int>(value("(--device)"), "(--device)")); optionsSet = true; }
@@ -134,6 +142,26 @@ int main(int argc, char * argv[])
 			else if (Match(a, 0, "emulate-ranks")) { options.emulateRanks = true; optionsSet = true; }
 			else if (Match(a, 0, "save-filter")) { options.saveFilter = value("(--save-filter)"); optionsSet = true; }
 			else if (Match(a, 0, "load-filter")) { options.loadFilter = value("(--load-filter)"); optionsSet = true; }
+			else if (Match(a, 0, "graph"))
+			{
+				options.graphFormat = value("(--graph)");
+				if (options.graphFormat != "gfa1" && options.graphFormat != "gfa2" && options.graphFormat != "fasta")
+				{
+					throw ArgError("Value '" + options.graphFormat + "' does not meet constraint: gfa1|gfa2|fasta", "(--graph)");
+				}
+
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "graph-out")) { options.graphFile = value("(--graph-out)"); graphOutSet = true; }
+			else if (Match(a, 0, "graph-prefix")) options.graphPrefix = true;
+			else if (Match(a, 0, "graph-threads"))
+			{
+				const std::string v = value("(--graph-threads)");
+				char * end = 0;
+				const long long parsed = std::strtoll(v.c_str(), &end, 10);
+				if (end == v.c_str() || *end != 0 || parsed < 1) throw ArgError("Couldn't read argument value from string '" + v + "'", "(--graph-threads)");
+				options.graphThreads = size_t(std::min<long long>(parsed, 16));
+			}
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -148,6 +176,17 @@ int main(int argc, char * argv[])
 		if (fileName.empty())
 		{
 			throw ArgError("Required argument missing: filenames", "(filenames)");
+		}
+
+		if (!options.graphFormat.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The graph is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--graph)");
+			if (!graphOutSet) options.graphFile = "de_bruijn." + options.graphFormat;
+			if (!outFileSet) outFileName.clear();  // the junction stream stays on the device
+		}
+		else if (graphOutSet || options.graphPrefix)
+		{
+			throw ArgError("This argument needs --graph <gfa1|gfa2|fasta>", graphOutSet ? "(--graph-out)" : "(--graph-prefix)");
 		}
 
 		if (runTests)

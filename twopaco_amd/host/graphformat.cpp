@@ -1,0 +1,368 @@
+// graphformat.cpp -- see graphformat.h.
+#include "graphformat.h"
+
+#include <algorithm>
+#include <cerrno>
+#include <condition_variable>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include "streamfastaparser.h"
+
+namespace TwoPaCo
+{
+	namespace GraphFormat
+	{
+		void LoadSequences(const std::vector<std::string> & fasta, bool prefixed, size_t threads, InputSequences & seq, LoadedSequences & loaded)
+		{
+			struct PerFile
+			{
+				std::vector<std::string> name, body;
+				std::vector<std::vector<uint64_t> > ambiguous;
+				std::string error;
+			};
+
+			std::vector<PerFile> file(fasta.size());
+			RunParallel(fasta.size(), threads, [&](size_t f)
+			{
+				PerFile & out = file[f];
+				try
+				{
+					TwoPaCo::StreamFastaParser parser(fasta[f]);
+					while (parser.ReadRecord())
+					{
+						// "s0_": the reference never advances its file counter, every prefix is "s0_" (graphdump.cpp:176-192)
+						out.name.push_back(prefixed ? "s0_" + parser.GetCurrentHeader() : parser.GetCurrentHeader());
+						std::string body;
+						std::vector<uint64_t> ambiguous;
+						for (char ch; parser.GetChar(ch);)
+						{
+							if (!DnaChar::IsDefinite(ch) && ch != 'N') ambiguous.push_back(body.size());
+							body.push_back(ch);
+						}
+
+						out.body.push_back(std::string());
+						out.body.back().swap(body);
+						out.ambiguous.push_back(std::vector<uint64_t>());
+						out.ambiguous.back().swap(ambiguous);
+					}
+				}
+				catch (std::runtime_error & e)
+				{
+					out.error = e.what();
+					if (out.error.empty()) out.error = "unreadable FASTA file";
+				}
+			});
+
+			for (size_t f = 0; f < fasta.size(); f++)
+			{
+				// the serial walk meets the records of a broken file before its error; what it reports is the first error in file order
+				if (!file[f].error.empty()) throw std::runtime_error(file[f].error);
+				for (size_t r = 0; r < file[f].name.size(); r++)
+				{
+					seq.name.push_back(file[f].name[r]);
+					seq.file[file[f].name[r]] = fasta[f];
+					seq.length.push_back(file[f].body[r].size());
+					loaded.body.push_back(std::string());
+					loaded.body.back().swap(file[f].body[r]);
+					loaded.ambiguous.push_back(std::vector<uint64_t>());
+					loaded.ambiguous.back().swap(file[f].ambiguous[r]);
+				}
+			}
+		}
+
+		bool IsGraphFormat(const std::string & format)
+		{
+			return format == "gfa1" || format == "gfa2" || format == "fasta";
+		}
+
+		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out)
+		{
+			if (format == "gfa1")
+			{
+				out << "H\tVN:Z:1.0\n";
+				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file.find(name)->second << '\n';
+			}
+
+			if (format == "gfa2") out << "H\tVN:Z:2.0\n";
+		}
+
+		namespace
+		{
+			// about eight chunks per thread, of 16 .. 65536 events (a few MB of text at most): small inputs are cut as well
+			uint64_t ChunkEvents(uint64_t events, size_t threads)
+			{
+				return std::max<uint64_t>(16, std::min<uint64_t>(uint64_t(1) << 16, events / (8 * threads) + 1));
+			}
+
+			SegmentSink * MakeSink(const std::string & format, Out & out, const InputSequences & seq, GfaSink * & gfa)
+			{
+				gfa = 0;
+				if (format == "gfa1") return gfa = new Gfa1Sink(out, seq);
+				if (format == "gfa2") return gfa = new Gfa2Sink(out, seq);
+				return new FastaSink(out);
+			}
+
+			// the sequence that holds event e: the last s with seqEventBegin[s] <= e (sequences without events share their entry
+			// with the next one that has some)
+			size_t SequenceOf(const EventTable & t, uint64_t e)
+			{
+				const uint32_t * b = t.seqEventBegin;
+				return size_t(std::upper_bound(b, b + t.sequences + 1, e, [](uint64_t v, uint32_t x) { return v < uint64_t(x); }) - b) - 1;
+			}
+
+			void FormatChunk(const EventTable & t, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+				uint64_t e0, uint64_t e1, std::string & into)
+			{
+				Out chunkOut(false);
+				GfaSink * gfa = 0;
+				std::unique_ptr<SegmentSink> sink(MakeSink(format, chunkOut, seq, gfa));
+				size_t sequence = e0 < e1 ? SequenceOf(t, e0) : 0;
+				for (uint64_t e = e0; e < e1; e++)
+				{
+					while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+					SegmentEvent ev;
+					ev.id = t.name[e];
+					ev.begin = t.begin[e];
+					ev.end = t.end[e];
+					ev.size = ev.end + k - ev.begin;
+					ev.first = (t.first[e >> 5] >> (e & 31)) & 1u;
+					ev.sequence = sequence;
+					if (e == e0 && gfa)
+					{
+						// the event before lies in the same sequence: the link to it is this chunk's
+						if (e > t.seqEventBegin[sequence]) gfa->Resume(t.name[e - 1], uint64_t(t.end[e - 1]) + k - t.begin[e - 1]);
+						else gfa->Resume(0, 0);
+					}
+
+					sink->Segment(ev, loaded.body[sequence], k);
+					if (gfa && e + 1 == t.seqEventBegin[sequence + 1])
+					{
+						// last event of its sequence: the path line is this worker's, whatever chunk the path began in
+						const uint64_t begin = t.seqEventBegin[sequence];
+						gfa->EndOfSequence(sequence, t.name + begin, size_t(e - begin + 1));
+					}
+				}
+
+				into.swap(chunkOut.Text());
+			}
+
+			bool WriteAll(int fd, const char * data, size_t n, uint64_t offset)
+			{
+				for (size_t done = 0; done < n;)
+				{
+					const ssize_t w = ::pwrite(fd, data + done, n - done, off_t(offset + done));
+					if (w < 0 && errno == EINTR) continue;
+					if (w <= 0) return false;
+					done += size_t(w);
+				}
+
+				return true;
+			}
+		}
+
+		void CheckEventTable(const EventTable & t, const LoadedSequences & loaded, size_t k, size_t threads)
+		{
+			if (t.events >= UINT32_MAX) throw std::runtime_error("event table: event indices are 32 bits");
+			if (t.events && (!t.name || !t.first || !t.begin || !t.end)) throw std::runtime_error("event table: arrays required");
+			if (!t.seqEventBegin) throw std::runtime_error("event table: sequence ranges required");
+			if (t.sequences != loaded.body.size())
+			{
+				throw std::runtime_error("event table: made for " + std::to_string(t.sequences) + " sequences, the FASTA files hold " + std::to_string(loaded.body.size()));
+			}
+
+			if (t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			for (uint64_t s = 0; s < t.sequences; s++)
+			{
+				if (t.seqEventBegin[s] > t.seqEventBegin[s + 1]) throw std::runtime_error("event table: the sequences' event ranges must ascend");
+			}
+
+			const size_t parts = std::max<size_t>(1, std::min<size_t>(threads, size_t(t.events / 65536 + 1)));
+			std::vector<uint64_t> bad(parts, UINT64_MAX);
+			RunParallel(parts, parts, [&](size_t p)
+			{
+				const uint64_t e0 = t.events * p / parts, e1 = t.events * (p + 1) / parts;
+				size_t sequence = e0 < e1 ? SequenceOf(t, e0) : 0;
+				for (uint64_t e = e0; e < e1; e++)
+				{
+					while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+					if (t.end[e] <= t.begin[e] || uint64_t(t.end[e]) + k > loaded.body[sequence].size())
+					{
+						bad[p] = e;
+						break;
+					}
+				}
+			});
+
+			for (uint64_t e : bad)
+			{
+				if (e != UINT64_MAX) throw std::runtime_error("event table: event " + std::to_string(e) + " does not lie inside its sequence");
+			}
+		}
+
+		uint64_t FormatEvents(const EventTable & t, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+			size_t threads, int fd, uint64_t fileOffset)
+		{
+			threads = std::max<size_t>(1, threads);
+			const uint64_t events = t.events;
+			const uint64_t chunkEvents = ChunkEvents(events, threads);
+			const size_t chunks = size_t((events + chunkEvents - 1) / chunkEvents);
+			auto formatChunk = [&](size_t c, std::string & into)
+			{
+				const uint64_t e0 = uint64_t(c) * chunkEvents;
+				FormatChunk(t, seq, loaded, k, format, e0, std::min(events, e0 + chunkEvents), into);
+			};
+
+			uint64_t total = 0;
+			if (threads <= 1 || chunks <= 1)
+			{
+				for (size_t c = 0; c < chunks; c++)
+				{
+					std::string textOfChunk;
+					formatChunk(c, textOfChunk);
+					if (fd < 0) std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
+					else if (!WriteAll(fd, textOfChunk.data(), textOfChunk.size(), fileOffset + total)) throw std::runtime_error("Can't write to the graph file");
+					total += textOfChunk.size();
+				}
+			}
+			else if (fd >= 0)
+			{
+				// Every worker writes its own chunk.  Chunks are taken in order, so the sizes of the chunks before c are known as
+				// soon as the workers holding them have formatted theirs: a worker waits only for chunks that are already running.
+				// The space is preallocated in doubling steps ahead of the frontier (the size of the text is not known before
+				// it is formatted); the caller truncates the file to what was written.
+				std::vector<uint64_t> offset(chunks + 1, 0);
+				std::mutex lock;
+				std::condition_variable changed;
+				size_t known = 0;            // offset[0 .. known] are final
+				uint64_t allocated = 0;
+				bool failed = false;
+				std::atomic<size_t> cursor(0);
+				auto work = [&]()
+				{
+					for (size_t c = cursor++; c < chunks; c = cursor++)
+					{
+						std::string textOfChunk;
+						formatChunk(c, textOfChunk);
+						uint64_t at = 0;
+						{
+							std::unique_lock<std::mutex> hold(lock);
+							changed.wait(hold, [&]() { return known >= c; });
+							at = offset[c];
+							offset[c + 1] = at + textOfChunk.size();
+							known = c + 1;
+							if (offset[c + 1] > allocated)
+							{
+								const uint64_t upTo = std::max<uint64_t>(offset[c + 1] + (uint64_t(8) << 20), 2 * allocated);
+								(void)::posix_fallocate(fd, off_t(fileOffset + allocated), off_t(upTo - allocated));  // a file system without it: the writes extend the file
+								allocated = upTo;
+							}
+						}
+
+						changed.notify_all();
+						if (!WriteAll(fd, textOfChunk.data(), textOfChunk.size(), fileOffset + at))
+						{
+							std::unique_lock<std::mutex> hold(lock);
+							failed = true;
+						}
+					}
+				};
+
+				std::vector<std::thread> pool;
+				for (size_t w = 1; w < std::min(threads, chunks); w++) pool.emplace_back(work);
+				work();
+				for (std::thread & th : pool) th.join();
+				if (failed) throw std::runtime_error("Can't write to the graph file");
+				total = offset[chunks];
+			}
+			else
+			{
+				// threads - 1 workers format, this thread writes; a worker runs at most `window` chunks ahead of the writer
+				std::vector<std::string> done(chunks);
+				std::vector<char> ready(chunks, 0);
+				std::mutex lock;
+				std::condition_variable changed;
+				size_t written = 0;
+				const size_t window = 4 * threads;
+				std::atomic<size_t> cursor(0);
+				std::vector<std::thread> pool;
+				for (size_t w = 1; w < threads; w++)
+				{
+					pool.emplace_back([&]()
+					{
+						for (size_t c = cursor++; c < chunks; c = cursor++)
+						{
+							{
+								std::unique_lock<std::mutex> hold(lock);
+								changed.wait(hold, [&]() { return c < written + window; });
+							}
+
+							std::string textOfChunk;
+							formatChunk(c, textOfChunk);
+							{
+								std::unique_lock<std::mutex> hold(lock);
+								done[c].swap(textOfChunk);
+								ready[c] = 1;
+							}
+
+							changed.notify_all();
+						}
+					});
+				}
+
+				for (size_t c = 0; c < chunks; c++)
+				{
+					std::string textOfChunk;
+					{
+						std::unique_lock<std::mutex> hold(lock);
+						changed.wait(hold, [&]() { return ready[c] != 0; });
+						textOfChunk.swap(done[c]);
+					}
+
+					std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
+					total += textOfChunk.size();
+					{
+						std::unique_lock<std::mutex> hold(lock);
+						written = c + 1;
+					}
+
+					changed.notify_all();
+				}
+
+				for (std::thread & th : pool) th.join();
+			}
+
+			if (fd < 0) std::fflush(stdout);
+			return total;
+		}
+
+		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+			size_t threads, const std::string & outPath)
+		{
+			int fd = ::open(outPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+			if (fd < 0) throw std::runtime_error("Can't create the graph file " + outPath);
+			try
+			{
+				Out head(false);
+				HeaderLines(format, seq, head);
+				if (!WriteAll(fd, head.Text().data(), head.Text().size(), 0)) throw std::runtime_error("Can't write to the graph file");
+				const uint64_t size = head.Text().size() + FormatEvents(table, seq, loaded, k, format, threads, fd, head.Text().size());
+				if (::ftruncate(fd, off_t(size)) != 0) throw std::runtime_error("Can't write to the graph file");
+				const int closing = fd;
+				fd = -1;
+				if (::close(closing) != 0) throw std::runtime_error("Can't write to the graph file");
+			}
+			catch (...)
+			{
+				if (fd >= 0) ::close(fd);
+				::unlink(outPath.c_str());
+				throw;
+			}
+		}
+	}
+}

@@ -1,0 +1,289 @@
+// graphformat.h -- the text of the compacted graph (gfa1 / gfa2 / fasta, reference src/graphdump/graphdump.cpp:379-585), shared
+// by `graphdump` (junctiondump.cpp) and `twopaco --graph` (vertexenumerator.cpp).  Two layers:
+//   * the sinks: one call per segment occurrence (an EVENT: two consecutive junction records of one sequence) and one per end
+//     of sequence, exactly what the serial walk of junctiondump.cpp feeds them;
+//   * the parallel formatter: given the EVENT TABLE of a stream (include/twopaco_hip.h, the tpc_segments_* group: name[],
+//     first[], begin[], end[] per event in file order and seq_event_begin[] per sequence) every output line depends only on
+//     its own event and the one before it, so workers format contiguous chunks of events.  The table and the letters of the
+//     input sequences are all it reads: it never sees the stream's bytes.
+// No device dependency: the table may come from the device library or from anywhere else (libtwopaco_host.so:
+// tpch_graph_format), and graphdump links this unit without linking the device library.
+#ifndef _GRAPH_FORMAT_H_
+#define _GRAPH_FORMAT_H_
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstdio>
+#include <map>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "dnachar.h"
+
+namespace TwoPaCo
+{
+	namespace GraphFormat
+	{
+		// ---------------------------------------------------------------------------------------- output
+		class Out
+		{
+		public:
+			// toStdout = false: the text only collects in Text() (a chunk of the parallel formatter, the head of a graph file)
+			explicit Out(bool toStdout = true) : toStdout_(toStdout) {}
+			~Out() { if (toStdout_) Flush(); }
+			std::string & Text() { return buf_; }
+			Out & operator << (const std::string & s) { buf_ += s; return Check(); }
+			Out & operator << (const char * s) { buf_ += s; return Check(); }
+			Out & operator << (char c) { buf_ += c; return Check(); }
+			Out & operator << (int64_t v) { buf_ += std::to_string(static_cast<long long>(v)); return Check(); }
+			Out & operator << (uint64_t v) { buf_ += std::to_string(static_cast<unsigned long long>(v)); return Check(); }
+			Out & operator << (uint32_t v) { buf_ += std::to_string(v); return Check(); }
+			void Flush()
+			{
+				if (!toStdout_) return;
+				if (!buf_.empty()) std::fwrite(buf_.data(), 1, buf_.size(), stdout);
+				buf_.clear();
+				std::fflush(stdout);
+			}
+
+		private:
+			Out & Check()
+			{
+				if (toStdout_ && buf_.size() > (1u << 20))
+				{
+					std::fwrite(buf_.data(), 1, buf_.size(), stdout);
+					buf_.clear();
+				}
+
+				return *this;
+			}
+
+			bool toStdout_;
+			std::string buf_;
+		};
+
+		inline int64_t Magnitude(int64_t x) { return x < 0 ? -x : x; }
+		inline char Strand(int64_t x) { return x >= 0 ? '+' : '-'; }
+
+		// ---------------------------------------------------------------------------------------- input sequences
+		struct InputSequences
+		{
+			std::vector<std::string> name;
+			std::vector<uint64_t> length;
+			std::map<std::string, std::string> file;
+		};
+
+		// What the serial walk reads record by record -- names, lengths, the letters as the parser upper-cases them -- read
+		// once, files in parallel; and per sequence the positions of the valid letters other than A C G T N, which the packed
+		// text holds as 'N' while the namer does not (SegmentNamer::Name: MakeUpChar of such a letter is -1).
+		struct LoadedSequences
+		{
+			std::vector<std::string> body;
+			std::vector<std::vector<uint64_t> > ambiguous;
+		};
+
+		template<class Fn> void RunParallel(size_t items, size_t threads, const Fn & fn)
+		{
+			std::atomic<size_t> cursor(0);
+			auto work = [&]() { for (size_t i = cursor++; i < items; i = cursor++) fn(i); };
+			std::vector<std::thread> pool;
+			for (size_t t = 1; t < std::min(threads, items); t++) pool.emplace_back(work);
+			work();
+			for (std::thread & th : pool) th.join();
+		}
+
+		// throws std::runtime_error with the parser's text (the first error in file order)
+		void LoadSequences(const std::vector<std::string> & fasta, bool prefixed, size_t threads, InputSequences & seq, LoadedSequences & loaded);
+
+		// ---------------------------------------------------------------------------------------- sinks
+		struct SegmentEvent
+		{
+			int64_t id;            // signed name
+			uint64_t size;
+			bool first;            // first sight of |id|
+			uint64_t begin, end;   // junction positions in the sequence
+			size_t sequence;
+		};
+
+		class SegmentSink
+		{
+		public:
+			virtual ~SegmentSink() {}
+			virtual void Segment(const SegmentEvent & e, const std::string & chr, size_t k) = 0;
+			virtual void EndOfSequence(size_t sequence) = 0;
+		};
+
+		inline std::string SegmentBody(const SegmentEvent & e, const std::string & chr, size_t k)
+		{
+			const std::string body = chr.substr(e.begin, e.end + k - e.begin);
+			return e.id > 0 ? body : DnaChar::ReverseCompliment(body);
+		}
+
+		class GfaSink : public SegmentSink
+		{
+		public:
+			GfaSink(Out & out, const InputSequences & seq) : out_(out), seq_(seq), prevId_(0), prevSize_(0) {}
+
+			void Segment(const SegmentEvent & e, const std::string & chr, size_t k)
+			{
+				if (e.first) SegmentLine(e, SegmentBody(e, chr, k));
+				Occurrence(e, k);
+				if (prevId_ != 0) Link(prevId_, prevSize_, e.id, e.size, k);
+				prevId_ = e.id;
+				prevSize_ = e.size;
+				path_.push_back(e.id);
+			}
+
+			void EndOfSequence(size_t sequence)
+			{
+				if (!path_.empty()) Path(seq_.name[sequence]);
+				path_.clear();
+				prevId_ = 0;
+			}
+
+			// The parallel formatter enters a sequence in the middle (Resume: the event before the chunk's first one, 0 when that
+			// begins its sequence) and hands the whole path to the worker that holds the sequence's last event.
+			void Resume(int64_t prevId, uint64_t prevSize)
+			{
+				path_.clear();
+				prevId_ = prevId;
+				prevSize_ = prevSize;
+			}
+
+			void EndOfSequence(size_t sequence, const int64_t * name, size_t count)
+			{
+				path_.assign(name, name + count);
+				EndOfSequence(sequence);
+			}
+
+		protected:
+			virtual void SegmentLine(const SegmentEvent & e, const std::string & body) = 0;
+			virtual void Occurrence(const SegmentEvent & e, size_t k) = 0;
+			virtual void Link(int64_t a, uint64_t aSize, int64_t b, uint64_t bSize, size_t k) = 0;
+			virtual void Path(const std::string & name) = 0;
+			Out & out_;
+			const InputSequences & seq_;
+			std::vector<int64_t> path_;
+
+		private:
+			int64_t prevId_;
+			uint64_t prevSize_;
+		};
+
+		class Gfa1Sink : public GfaSink
+		{
+		public:
+			Gfa1Sink(Out & out, const InputSequences & seq) : GfaSink(out, seq) {}
+
+		protected:
+			void SegmentLine(const SegmentEvent & e, const std::string & body) { out_ << "S\t" << Magnitude(e.id) << '\t' << body << '\n'; }
+
+			void Occurrence(const SegmentEvent & e, size_t)
+			{
+				out_ << "C\t" << Magnitude(e.id) << '\t' << Strand(e.id) << '\t' << seq_.name[e.sequence] << "\t+\t" << e.end << '\n';
+			}
+
+			void Link(int64_t a, uint64_t, int64_t b, uint64_t, size_t k)
+			{
+				out_ << "L\t" << Magnitude(a) << '\t' << Strand(a) << '\t' << Magnitude(b) << '\t' << Strand(b) << '\t' << uint64_t(k) << "M\n";
+			}
+
+			void Path(const std::string & name)
+			{
+				out_ << "P\t" << name << '\t';
+				for (size_t i = 0; i < path_.size(); i++) out_ << Magnitude(path_[i]) << Strand(path_[i]) << (i + 1 < path_.size() ? "," : "\t*\n");
+			}
+		};
+
+		class Gfa2Sink : public GfaSink
+		{
+		public:
+			Gfa2Sink(Out & out, const InputSequences & seq) : GfaSink(out, seq) {}
+
+		protected:
+			static std::string At(uint64_t pos, uint64_t length) { return pos == length ? std::to_string(pos) + "$" : std::to_string(pos); }
+
+			void SegmentLine(const SegmentEvent & e, const std::string & body) { out_ << "S\t" << Magnitude(e.id) << '\t' << e.size << '\t' << body << '\n'; }
+
+			void Occurrence(const SegmentEvent & e, size_t k)
+			{
+				const uint64_t total = seq_.length[e.sequence];
+				out_ << "F\t" << Magnitude(e.id) << '\t' << seq_.name[e.sequence] << Strand(e.id) << "\t0\t" << e.size << "$\t" << At(e.begin, total) << '\t'
+					<< At(e.end + k, total) << '\t' << uint64_t(k) << "M\n";
+			}
+
+			void Link(int64_t a, uint64_t aSize, int64_t b, uint64_t bSize, size_t k)
+			{
+				const uint64_t a0 = a > 0 ? aSize - k : 0, a1 = a > 0 ? aSize : k;   // the overlapping k-mer on each segment
+				const uint64_t b0 = b > 0 ? 0 : bSize - k, b1 = b > 0 ? k : bSize;
+				out_ << "E\t" << Magnitude(a) << Strand(a) << '\t' << Magnitude(b) << Strand(b) << '\t' << At(a0, aSize) << '\t' << At(a1, aSize) << '\t'
+					<< At(b0, bSize) << '\t' << At(b1, bSize) << '\t' << uint64_t(k) << "M\n";
+			}
+
+			void Path(const std::string & name)
+			{
+				out_ << "O\t" << name << "p\t";
+				for (size_t i = 0; i < path_.size(); i++) out_ << Magnitude(path_[i]) << Strand(path_[i]) << (i + 1 < path_.size() ? " " : "\n");
+			}
+		};
+
+		class FastaSink : public SegmentSink
+		{
+		public:
+			explicit FastaSink(Out & out) : out_(out) {}
+
+			void Segment(const SegmentEvent & e, const std::string & chr, size_t k)
+			{
+				if (!e.first) return;
+				out_ << '>' << Magnitude(e.id) << '\n';
+				const std::string body = SegmentBody(e, chr, k);
+				for (size_t i = 0; i < body.size(); i += 80) out_ << body.substr(i, 80) << '\n';
+			}
+
+			void EndOfSequence(size_t) {}
+
+		private:
+			Out & out_;
+		};
+
+		// ---------------------------------------------------------------------------------------- the parallel formatter
+		// The event table of a stream, as include/twopaco_hip.h defines it (arrays of the caller, host memory).
+		struct EventTable
+		{
+			uint64_t events;
+			const int64_t * name;            // [events]
+			const uint32_t * first;          // [(events + 31) / 32] bit e % 32 of word e / 32
+			const uint32_t * begin;          // [events]
+			const uint32_t * end;            // [events]
+			uint64_t sequences;
+			const uint32_t * seqEventBegin;  // [sequences + 1]
+			EventTable() : events(0), name(0), first(0), begin(0), end(0), sequences(0), seqEventBegin(0) {}
+		};
+
+		bool IsGraphFormat(const std::string & format);  // gfa1, gfa2, fasta
+
+		// The lines in front of the first segment, as graphdump prints them: "H\tVN:Z:..." and, for gfa1, one S line per input
+		// sequence whose UR:Z: tag is the file's name as it was given.
+		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out);
+
+		// Everything the formatter indexes with is checked here (the table may come from anywhere): the sequences' event ranges
+		// ascend from 0 to the event count, there are as many sequences as the FASTA files hold, every event lies inside its
+		// sequence.  Throws std::runtime_error.
+		void CheckEventTable(const EventTable & table, const LoadedSequences & loaded, size_t k, size_t threads);
+
+		// The text of all events, formatted by `threads` workers in contiguous chunks.  fd < 0: to stdout, in order, written by
+		// the calling thread.  Otherwise to the regular file open on fd, starting at fileOffset: every worker writes its own
+		// chunk with pwrite at the sum of the earlier chunks' sizes, into space preallocated with posix_fallocate; returns the
+		// bytes written (the caller truncates the file to fileOffset + that).  The table must have passed CheckEventTable.
+		uint64_t FormatEvents(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+			size_t threads, int fd, uint64_t fileOffset);
+
+		// Header lines and events into the file outPath (created or truncated; removed again when anything fails).
+		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+			size_t threads, const std::string & outPath);
+	}
+}
+
+#endif

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "graphformat.h"
 #include "seed.h"
 #include "streamfastaparser.h"
 #include "textpack.h"
@@ -128,6 +129,69 @@ extern "C"
 			if (log) *log = Dup(ss.str());
 			return 0;
 		}
+	}
+
+	// the same as tpch_create_enumerator with --graph (EnumeratorOptions::graphFormat ...): graphFormat gfa1 | gfa2 | fasta into
+	// graphFile; outFile may be empty, then the junction stream is not written
+	void * tpch_create_enumerator_graph(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
+		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
+		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, char ** log)
+	{
+		std::stringstream ss;
+		try
+		{
+			std::vector<std::string> names(files, files + nfiles);
+			TwoPaCo::EnumeratorOptions opt;
+			opt.pinnedSeed = pinned != 0;
+			opt.seed = seed;
+			opt.device = device;
+			opt.insertTestFirst = testFirst != 0;
+			opt.graphFormat = graphFormat ? graphFormat : "";
+			opt.graphFile = graphFile ? graphFile : "";
+			opt.graphPrefix = graphPrefix != 0;
+			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
+			if (opt.graphFormat.empty()) throw std::runtime_error("The graph format must be one of gfa1, gfa2, fasta");
+			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
+			if (log) *log = Dup(ss.str());
+			return e.release();
+		}
+		catch (std::exception & e)
+		{
+			g_error = e.what();
+			if (log) *log = Dup(ss.str());
+			return 0;
+		}
+	}
+
+	// The text of the compacted graph from an EVENT TABLE (include/twopaco_hip.h: name / first bits / begin / end per event,
+	// seq_event_begin[0 .. n_seq] per sequence) and the FASTA files, into out_path: graphformat.h without any device.  format
+	// gfa1 | gfa2 | fasta, prefix = graphdump's --prefix.  0, or nonzero with tpch_last_error.
+	int tpch_graph_format(const char ** files, int nfiles, uint64_t k, const char * format, int prefix, int threads, uint64_t n_events,
+		const int64_t * name, const uint32_t * first_words, const uint32_t * begin, const uint32_t * end, uint64_t n_seq,
+		const uint32_t * seq_event_begin, const char * out_path)
+	{
+		try
+		{
+			namespace GF = TwoPaCo::GraphFormat;
+			const std::string fmt = format ? format : "";
+			if (!GF::IsGraphFormat(fmt)) throw std::runtime_error("The graph format must be one of gfa1, gfa2, fasta");
+			if (!out_path || !*out_path) throw std::runtime_error("The graph needs an output file name");
+			if (nfiles < 0 || (nfiles && !files)) throw std::runtime_error("FASTA file names required");
+			const size_t workers = size_t(threads < 1 ? 1 : (threads > 16 ? 16 : threads));
+			std::vector<std::string> names(files, files + nfiles);
+			GF::InputSequences seq;
+			GF::LoadedSequences loaded;
+			GF::LoadSequences(names, fmt == "fasta" ? true : prefix != 0, workers, seq, loaded);
+			GF::EventTable table;
+			table.events = n_events;
+			table.name = name; table.first = first_words; table.begin = begin; table.end = end;
+			table.sequences = n_seq;
+			table.seqEventBegin = seq_event_begin;
+			GF::CheckEventTable(table, loaded, size_t(k), workers);
+			GF::WriteGraphFile(table, seq, loaded, size_t(k), fmt, workers, out_path);
+			return 0;
+		}
+		catch (std::exception & e) { g_error = e.what(); return -1; }
 	}
 
 	void tpch_enumerator_free(void * h) { delete static_cast<TwoPaCo::VertexEnumerator*>(h); }

@@ -20,7 +20,9 @@
 // fresh names of 'N' segments, first sight -- is computed on the device (csrc/tpc_segments.hip through the tpc_segments_*
 // group of include/twopaco_hip.h, loaded with dlopen: the binary has no link-time dependency on the device library), after
 // which every output line depends only on its own event and the one before it, and `--threads` workers format contiguous
-// chunks of events that go to stdout in order.  No device or no library with --gpu is an error: there is no fallback.
+// chunks of events that go to stdout in order (graphformat.h, shared with `twopaco --graph`; its input is the event table the
+// device leaves -- name, first sight, the two positions of every event, the events of every sequence -- fetched with
+// tpc_segments_fetch_*).  No device or no library with --gpu is an error: there is no fallback.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -43,6 +45,7 @@
 
 #include "../../include/twopaco_hip.h"
 #include "dnachar.h"
+#include "graphformat.h"
 #include "junctionapi.h"
 #include "streamfastaparser.h"
 #include "textpack.h"
@@ -52,45 +55,7 @@ namespace
 	using TwoPaCo::DnaChar;
 	using TwoPaCo::JunctionPosition;
 
-	// ---------------------------------------------------------------------------------------- output
-	class Out
-	{
-	public:
-		// toStdout = false: the text only collects in Text() (a chunk of the parallel formatter)
-		explicit Out(bool toStdout = true) : toStdout_(toStdout) {}
-		~Out() { if (toStdout_) Flush(); }
-		std::string & Text() { return buf_; }
-		Out & operator << (const std::string & s) { buf_ += s; return Check(); }
-		Out & operator << (const char * s) { buf_ += s; return Check(); }
-		Out & operator << (char c) { buf_ += c; return Check(); }
-		Out & operator << (int64_t v) { buf_ += std::to_string(static_cast<long long>(v)); return Check(); }
-		Out & operator << (uint64_t v) { buf_ += std::to_string(static_cast<unsigned long long>(v)); return Check(); }
-		Out & operator << (uint32_t v) { buf_ += std::to_string(v); return Check(); }
-		void Flush()
-		{
-			if (!buf_.empty()) std::fwrite(buf_.data(), 1, buf_.size(), stdout);
-			buf_.clear();
-			std::fflush(stdout);
-		}
-
-	private:
-		Out & Check()
-		{
-			if (toStdout_ && buf_.size() > (1u << 20))
-			{
-				std::fwrite(buf_.data(), 1, buf_.size(), stdout);
-				buf_.clear();
-			}
-
-			return *this;
-		}
-
-		bool toStdout_;
-		std::string buf_;
-	};
-
-	int64_t Magnitude(int64_t x) { return x < 0 ? -x : x; }
-	char Strand(int64_t x) { return x >= 0 ? '+' : '-'; }
+	using namespace TwoPaCo::GraphFormat;  // Out, the sinks, LoadSequences, the parallel formatter (graphformat.h)
 
 	// ---------------------------------------------------------------------------------------- seq / group / dot
 	void DumpSeq(const std::string & binFile, Out & out)
@@ -203,13 +168,6 @@ namespace
 		int64_t nextUnique_;
 	};
 
-	struct InputSequences
-	{
-		std::vector<std::string> name;
-		std::vector<uint64_t> length;
-		std::map<std::string, std::string> file;
-	};
-
 	void ListSequences(const std::vector<std::string> & fasta, bool prefixed, InputSequences & seq)
 	{
 		size_t index = 0;  // the reference never advances this counter: every prefix is "s0_" (graphdump.cpp:176-192)
@@ -264,23 +222,6 @@ namespace
 		std::vector<std::string> fasta_;
 		size_t file_;
 		TwoPaCo::StreamFastaParser * parser_;
-	};
-
-	struct SegmentEvent
-	{
-		int64_t id;            // signed name
-		uint64_t size;
-		bool first;            // first sight of |id|
-		uint64_t begin, end;   // junction positions in the sequence
-		size_t sequence;
-	};
-
-	class SegmentSink
-	{
-	public:
-		virtual ~SegmentSink() {}
-		virtual void Segment(const SegmentEvent & e, const std::string & chr, size_t k) = 0;
-		virtual void EndOfSequence(size_t sequence) = 0;
 	};
 
 	// The walk shared by gfa1 / gfa2 / fasta (reference graphdump.cpp:398-480).  Consecutive records of the same
@@ -340,140 +281,6 @@ namespace
 		sink.EndOfSequence(sequence);
 	}
 
-	std::string SegmentBody(const SegmentEvent & e, const std::string & chr, size_t k)
-	{
-		const std::string body = chr.substr(e.begin, e.end + k - e.begin);
-		return e.id > 0 ? body : DnaChar::ReverseCompliment(body);
-	}
-
-	// ---------------------------------------------------------------------------------------- GFA
-	class GfaSink : public SegmentSink
-	{
-	public:
-		GfaSink(Out & out, const InputSequences & seq) : out_(out), seq_(seq), prevId_(0), prevSize_(0) {}
-
-		void Segment(const SegmentEvent & e, const std::string & chr, size_t k)
-		{
-			if (e.first) SegmentLine(e, SegmentBody(e, chr, k));
-			Occurrence(e, k);
-			if (prevId_ != 0) Link(prevId_, prevSize_, e.id, e.size, k);
-			prevId_ = e.id;
-			prevSize_ = e.size;
-			path_.push_back(e.id);
-		}
-
-		void EndOfSequence(size_t sequence)
-		{
-			if (!path_.empty()) Path(seq_.name[sequence]);
-			path_.clear();
-			prevId_ = 0;
-		}
-
-		// The parallel formatter enters a sequence in the middle (Resume: the event before the chunk's first one, 0 when that
-		// begins its sequence) and hands the whole path to the worker that holds the sequence's last event.
-		void Resume(int64_t prevId, uint64_t prevSize)
-		{
-			path_.clear();
-			prevId_ = prevId;
-			prevSize_ = prevSize;
-		}
-
-		void EndOfSequence(size_t sequence, const int64_t * name, size_t count)
-		{
-			path_.assign(name, name + count);
-			EndOfSequence(sequence);
-		}
-
-	protected:
-		virtual void SegmentLine(const SegmentEvent & e, const std::string & body) = 0;
-		virtual void Occurrence(const SegmentEvent & e, size_t k) = 0;
-		virtual void Link(int64_t a, uint64_t aSize, int64_t b, uint64_t bSize, size_t k) = 0;
-		virtual void Path(const std::string & name) = 0;
-		Out & out_;
-		const InputSequences & seq_;
-		std::vector<int64_t> path_;
-
-	private:
-		int64_t prevId_;
-		uint64_t prevSize_;
-	};
-
-	class Gfa1Sink : public GfaSink
-	{
-	public:
-		Gfa1Sink(Out & out, const InputSequences & seq) : GfaSink(out, seq) {}
-
-	protected:
-		void SegmentLine(const SegmentEvent & e, const std::string & body) { out_ << "S\t" << Magnitude(e.id) << '\t' << body << '\n'; }
-
-		void Occurrence(const SegmentEvent & e, size_t)
-		{
-			out_ << "C\t" << Magnitude(e.id) << '\t' << Strand(e.id) << '\t' << seq_.name[e.sequence] << "\t+\t" << e.end << '\n';
-		}
-
-		void Link(int64_t a, uint64_t, int64_t b, uint64_t, size_t k)
-		{
-			out_ << "L\t" << Magnitude(a) << '\t' << Strand(a) << '\t' << Magnitude(b) << '\t' << Strand(b) << '\t' << uint64_t(k) << "M\n";
-		}
-
-		void Path(const std::string & name)
-		{
-			out_ << "P\t" << name << '\t';
-			for (size_t i = 0; i < path_.size(); i++) out_ << Magnitude(path_[i]) << Strand(path_[i]) << (i + 1 < path_.size() ? "," : "\t*\n");
-		}
-	};
-
-	class Gfa2Sink : public GfaSink
-	{
-	public:
-		Gfa2Sink(Out & out, const InputSequences & seq) : GfaSink(out, seq) {}
-
-	protected:
-		static std::string At(uint64_t pos, uint64_t length) { return pos == length ? std::to_string(pos) + "$" : std::to_string(pos); }
-
-		void SegmentLine(const SegmentEvent & e, const std::string & body) { out_ << "S\t" << Magnitude(e.id) << '\t' << e.size << '\t' << body << '\n'; }
-
-		void Occurrence(const SegmentEvent & e, size_t k)
-		{
-			const uint64_t total = seq_.length[e.sequence];
-			out_ << "F\t" << Magnitude(e.id) << '\t' << seq_.name[e.sequence] << Strand(e.id) << "\t0\t" << e.size << "$\t" << At(e.begin, total) << '\t'
-				<< At(e.end + k, total) << '\t' << uint64_t(k) << "M\n";
-		}
-
-		void Link(int64_t a, uint64_t aSize, int64_t b, uint64_t bSize, size_t k)
-		{
-			const uint64_t a0 = a > 0 ? aSize - k : 0, a1 = a > 0 ? aSize : k;   // the overlapping k-mer on each segment
-			const uint64_t b0 = b > 0 ? 0 : bSize - k, b1 = b > 0 ? k : bSize;
-			out_ << "E\t" << Magnitude(a) << Strand(a) << '\t' << Magnitude(b) << Strand(b) << '\t' << At(a0, aSize) << '\t' << At(a1, aSize) << '\t'
-				<< At(b0, bSize) << '\t' << At(b1, bSize) << '\t' << uint64_t(k) << "M\n";
-		}
-
-		void Path(const std::string & name)
-		{
-			out_ << "O\t" << name << "p\t";
-			for (size_t i = 0; i < path_.size(); i++) out_ << Magnitude(path_[i]) << Strand(path_[i]) << (i + 1 < path_.size() ? " " : "\n");
-		}
-	};
-
-	class FastaSink : public SegmentSink
-	{
-	public:
-		explicit FastaSink(Out & out) : out_(out) {}
-
-		void Segment(const SegmentEvent & e, const std::string & chr, size_t k)
-		{
-			if (!e.first) return;
-			out_ << '>' << Magnitude(e.id) << '\n';
-			const std::string body = SegmentBody(e, chr, k);
-			for (size_t i = 0; i < body.size(); i += 80) out_ << body.substr(i, 80) << '\n';
-		}
-
-		void EndOfSequence(size_t) {}
-
-	private:
-		Out & out_;
-	};
-
 	// ---------------------------------------------------------------------------------------- --gpu
 	double MsSince(const std::chrono::steady_clock::time_point & t0)
 	{
@@ -518,6 +325,8 @@ namespace
 		decltype(&tpc_segments_error) segmentsError;
 		decltype(&tpc_segments_fetch_names) segmentsFetchNames;
 		decltype(&tpc_segments_fetch_first) segmentsFetchFirst;
+		decltype(&tpc_segments_fetch_events) segmentsFetchEvents;
+		decltype(&tpc_segments_fetch_sequences) segmentsFetchSequences;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -544,6 +353,8 @@ namespace
 			Load(segmentsError, "tpc_segments_error");
 			Load(segmentsFetchNames, "tpc_segments_fetch_names");
 			Load(segmentsFetchFirst, "tpc_segments_fetch_first");
+			Load(segmentsFetchEvents, "tpc_segments_fetch_events");
+			Load(segmentsFetchSequences, "tpc_segments_fetch_sequences");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -575,103 +386,13 @@ namespace
 		void * handle_;
 	};
 
-	// What ListSequences and SequenceCursor give the serial walk -- names, lengths, the letters as the parser upper-cases
-	// them -- read once, files in parallel; and per sequence the positions of the valid letters other than A C G T N, which
-	// the packed text holds as 'N' while the namer does not (SegmentNamer::Name: MakeUpChar of such a letter is -1).
-	struct LoadedSequences
-	{
-		std::vector<std::string> body;
-		std::vector<std::vector<uint64_t> > ambiguous;
-	};
-
-	template<class Fn> void RunParallel(size_t items, size_t threads, const Fn & fn)
-	{
-		std::atomic<size_t> cursor(0);
-		auto work = [&]() { for (size_t i = cursor++; i < items; i = cursor++) fn(i); };
-		std::vector<std::thread> pool;
-		for (size_t t = 1; t < std::min(threads, items); t++) pool.emplace_back(work);
-		work();
-		for (std::thread & th : pool) th.join();
-	}
-
-	void LoadSequences(const std::vector<std::string> & fasta, bool prefixed, size_t threads, InputSequences & seq, LoadedSequences & loaded)
-	{
-		struct PerFile
-		{
-			std::vector<std::string> name, body;
-			std::vector<std::vector<uint64_t> > ambiguous;
-			std::string error;
-		};
-
-		std::vector<PerFile> file(fasta.size());
-		RunParallel(fasta.size(), threads, [&](size_t f)
-		{
-			PerFile & out = file[f];
-			try
-			{
-				TwoPaCo::StreamFastaParser parser(fasta[f]);
-				while (parser.ReadRecord())
-				{
-					out.name.push_back(prefixed ? "s0_" + parser.GetCurrentHeader() : parser.GetCurrentHeader());  // "s0_": see ListSequences
-					std::string body;
-					std::vector<uint64_t> ambiguous;
-					for (char ch; parser.GetChar(ch);)
-					{
-						if (!DnaChar::IsDefinite(ch) && ch != 'N') ambiguous.push_back(body.size());
-						body.push_back(ch);
-					}
-
-					out.body.push_back(std::string());
-					out.body.back().swap(body);
-					out.ambiguous.push_back(std::vector<uint64_t>());
-					out.ambiguous.back().swap(ambiguous);
-				}
-			}
-			catch (std::runtime_error & e)
-			{
-				out.error = e.what();
-				if (out.error.empty()) out.error = "unreadable FASTA file";
-			}
-		});
-
-		for (size_t f = 0; f < fasta.size(); f++)
-		{
-			// the serial walk meets the records of a broken file before its error; what it reports is the first error in file order
-			if (!file[f].error.empty()) throw std::runtime_error(file[f].error);
-			for (size_t r = 0; r < file[f].name.size(); r++)
-			{
-				seq.name.push_back(file[f].name[r]);
-				seq.file[file[f].name[r]] = fasta[f];
-				seq.length.push_back(file[f].body[r].size());
-				loaded.body.push_back(std::string());
-				loaded.body.back().swap(file[f].body[r]);
-				loaded.ambiguous.push_back(std::vector<uint64_t>());
-				loaded.ambiguous.back().swap(file[f].ambiguous[r]);
-			}
-		}
-	}
-
-	const size_t SLOT_BYTES = 12;
-	uint32_t SlotPos(const std::vector<char> & bin, uint64_t slot)
-	{
-		uint32_t p;
-		std::memcpy(&p, &bin[slot * SLOT_BYTES], sizeof(p));
-		return p;
-	}
-
-	bool SlotIsSeparator(const std::vector<char> & bin, uint64_t slot)
-	{
-		int64_t id;
-		std::memcpy(&id, &bin[slot * SLOT_BYTES + 4], sizeof(id));
-		return SlotPos(bin, slot) == UINT32_MAX || id == INT64_MAX;  // JunctionPositionReader::NextJunctionPosition
-	}
-
-	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines); `makeSink` builds the
-	// format's sink over a chunk's buffer.
-	template<class MakeSink>
+	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The device builds the
+	// event table of the stream (name, first sight, the two positions of every event, the events of every sequence); the
+	// formatter of graphformat.h reads the table and the letters, never the stream's bytes.
 	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, const MakeSink & makeSink)
+		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats)
 	{
+		const size_t SLOT_BYTES = 12;
 		// the stream's bytes
 		std::vector<char> bin;
 		{
@@ -707,6 +428,7 @@ namespace
 		lib.Check(lib.seqUpload(lib.ctx, text.bases.data(), text.nmask.data(), text.length), "tpc_seq_upload");
 		lib.Check(lib.segmentsBuildHost(lib.ctx, bin.data(), bin.size(), int(k), text.recStart.data(), text.recLength.data(), uint32_t(text.recStart.size()),
 			ambiguous.data(), ambiguous.size()), "tpc_segments_build_host");
+		std::vector<char>().swap(bin);
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0}, errorSlot = 0;
 		int errorKind = 0;
 		lib.Check(lib.segmentsCounts(lib.ctx, counts), "tpc_segments_counts");
@@ -735,145 +457,26 @@ namespace
 		lib.Check(lib.segmentsFetchFirst(lib.ctx, 0, first.size(), first.data()), "tpc_segments_fetch_first");
 		stats.deviceMs = MsSince(t0);
 
-		// where every event sits in the stream: the slot of its right record and its sequence
+		// where every event sits in the stream: its two positions and the events of every sequence, as the device's scans left them
 		t0 = std::chrono::steady_clock::now();
-		const uint64_t slots = bin.size() / SLOT_BYTES;
-		std::vector<uint32_t> eventSlot, eventSequence;
-		eventSlot.reserve(events);
-		eventSequence.reserve(events);
-		{
-			uint32_t sequence = 0;
-			bool previousIsRecord = false;
-			for (uint64_t i = 0; i < slots; i++)
-			{
-				if (SlotIsSeparator(bin, i))
-				{
-					++sequence;
-					previousIsRecord = false;
-					continue;
-				}
-
-				if (previousIsRecord)
-				{
-					eventSlot.push_back(uint32_t(i));
-					eventSequence.push_back(sequence);
-				}
-
-				previousIsRecord = true;
-			}
-		}
-
-		if (eventSlot.size() != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
+		std::vector<uint32_t> begin(events), end(events), seqEventBegin(text.recStart.size() + 1);
+		lib.Check(lib.segmentsFetchEvents(lib.ctx, 0, events, begin.data(), end.data()), "tpc_segments_fetch_events");
+		lib.Check(lib.segmentsFetchSequences(lib.ctx, 0, seqEventBegin.size(), seqEventBegin.data()), "tpc_segments_fetch_sequences");
+		EventTable table;
+		table.events = events;
+		table.name = name.data();
+		table.first = first.data();
+		table.begin = begin.data();
+		table.end = end.data();
+		table.sequences = text.recStart.size();
+		table.seqEventBegin = seqEventBegin.data();
+		if (seqEventBegin[table.sequences] != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
 		stats.indexMs = MsSince(t0);
 
 		// format: contiguous chunks of events, each into its own buffer, buffers to stdout in order
 		t0 = std::chrono::steady_clock::now();
 		out.Flush();
-		// about eight chunks per thread, of 16 .. 65536 events (a few MB of text at most): small inputs are cut as well
-		const uint64_t chunkEvents = std::max<uint64_t>(16, std::min<uint64_t>(uint64_t(1) << 16, events / (8 * threads) + 1));
-		const size_t chunks = size_t((events + chunkEvents - 1) / chunkEvents);
-		auto formatChunk = [&](size_t c, std::string & into)
-		{
-			Out chunkOut(false);
-			GfaSink * gfa = 0;
-			std::unique_ptr<SegmentSink> sink(makeSink(chunkOut, gfa));
-			const uint64_t e0 = uint64_t(c) * chunkEvents, e1 = std::min(events, e0 + chunkEvents);
-			for (uint64_t e = e0; e < e1; e++)
-			{
-				const uint32_t slot = eventSlot[e];
-				SegmentEvent ev;
-				ev.id = name[e];
-				ev.begin = SlotPos(bin, slot - 1);
-				ev.end = SlotPos(bin, slot);
-				ev.size = ev.end + k - ev.begin;
-				ev.first = (first[e >> 5] >> (e & 31)) & 1u;
-				ev.sequence = eventSequence[e];
-				if (e == e0 && gfa)
-				{
-					const bool continues = e > 0 && eventSlot[e - 1] + 1 == slot;  // the event before lies in the same sequence
-					if (continues) gfa->Resume(name[e - 1], uint64_t(SlotPos(bin, slot - 1)) + k - SlotPos(bin, slot - 2));
-					else gfa->Resume(0, 0);
-				}
-
-				sink->Segment(ev, loaded.body[ev.sequence], k);
-				if (gfa && (e + 1 == events || eventSlot[e + 1] != slot + 1))
-				{
-					// last event of its sequence: the path line is this worker's, whatever chunk the path began in
-					uint64_t begin = e;
-					while (begin > 0 && eventSlot[begin - 1] + 1 == eventSlot[begin]) --begin;
-					gfa->EndOfSequence(ev.sequence, &name[begin], size_t(e - begin + 1));
-				}
-			}
-
-			into.swap(chunkOut.Text());
-		};
-
-		if (threads <= 1 || chunks <= 1)
-		{
-			for (size_t c = 0; c < chunks; c++)
-			{
-				std::string textOfChunk;
-				formatChunk(c, textOfChunk);
-				std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
-			}
-		}
-		else
-		{
-			// threads - 1 workers format, this thread writes; a worker runs at most `window` chunks ahead of the writer
-			std::vector<std::string> done(chunks);
-			std::vector<char> ready(chunks, 0);
-			std::mutex lock;
-			std::condition_variable changed;
-			size_t written = 0;
-			const size_t window = 4 * threads;
-			std::atomic<size_t> cursor(0);
-			std::vector<std::thread> pool;
-			for (size_t t = 1; t < threads; t++)
-			{
-				pool.emplace_back([&]()
-				{
-					for (size_t c = cursor++; c < chunks; c = cursor++)
-					{
-						{
-							std::unique_lock<std::mutex> hold(lock);
-							changed.wait(hold, [&]() { return c < written + window; });
-						}
-
-						std::string textOfChunk;
-						formatChunk(c, textOfChunk);
-						{
-							std::unique_lock<std::mutex> hold(lock);
-							done[c].swap(textOfChunk);
-							ready[c] = 1;
-						}
-
-						changed.notify_all();
-					}
-				});
-			}
-
-			for (size_t c = 0; c < chunks; c++)
-			{
-				std::string textOfChunk;
-				{
-					std::unique_lock<std::mutex> hold(lock);
-					changed.wait(hold, [&]() { return ready[c] != 0; });
-					textOfChunk.swap(done[c]);
-				}
-
-				std::fwrite(textOfChunk.data(), 1, textOfChunk.size(), stdout);
-				{
-					std::unique_lock<std::mutex> hold(lock);
-					written = c + 1;
-				}
-
-				changed.notify_all();
-			}
-
-			for (std::thread & th : pool) th.join();
-		}
-
-		std::fflush(stdout);
+		FormatEvents(table, seq, loaded, k, format, threads, -1, 0);
 		stats.formatMs = MsSince(t0);
 	}
 
@@ -893,7 +496,8 @@ namespace
 			"   -f <seq|group|dot|gfa1|gfa2|fasta>,  --format <seq|group|dot|gfa1|gfa2|fasta>\n     (required)  Output format\n\n"
 			"   --prefix\n     Add a prefix to segments in GFA (in case if you have genomes with identical FASTA headers)\n\n"
 			"   --gpu [<device>]\n     gfa1, gfa2, fasta: name and deduplicate the segments on HIP device <device> (default 0) and format the output with\n"
-			"     several threads; the output is the same.  An error when there is no device: no CPU fallback\n\n"
+			"     several threads; the output is the same.  An error when there is no device: no CPU fallback.\n"
+			"     (twopaco --graph <gfa1|gfa2|fasta> writes the same text from the process that enumerates the junctions.)\n\n"
 			"   --threads <integer>\n     threads of --gpu (1..16, default 16)\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
@@ -987,19 +591,9 @@ int main(int argc, char * argv[])
 			if (format == "gfa1")
 			{
 				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file[name] << '\n';
-				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
-					[&seq](Out & o, GfaSink * & gfa) -> SegmentSink * { return gfa = new Gfa1Sink(o, seq); });
 			}
-			else if (format == "gfa2")
-			{
-				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
-					[&seq](Out & o, GfaSink * & gfa) -> SegmentSink * { return gfa = new Gfa2Sink(o, seq); });
-			}
-			else
-			{
-				DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, out, stats,
-					[](Out & o, GfaSink * & gfa) -> SegmentSink * { gfa = 0; return new FastaSink(o); });
-			}
+
+			DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, format, seq, loaded, out, stats);
 		}
 		else if (format == "seq") DumpSeq(binFile, out);
 		else if (format == "group") DumpGroups(binFile, out);

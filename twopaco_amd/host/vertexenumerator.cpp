@@ -16,6 +16,7 @@
 #include <stdexcept>
 
 #include "../../include/twopaco_hip.h"
+#include "graphformat.h"
 #include "multigpu.h"
 #include "streamfastaparser.h"
 #include "textpack.h"
@@ -265,6 +266,12 @@ namespace TwoPaCo
 					throw std::runtime_error("The number of GPUs must be a power of two (the Bloom filter is cut by bit address)");
 				}
 
+				const bool graph = !options.graphFormat.empty();
+				if (graph && !GraphFormat::IsGraphFormat(options.graphFormat)) throw std::runtime_error("The graph format must be one of gfa1, gfa2, fasta");
+				if (graph && options.graphFile.empty()) throw std::runtime_error("The graph needs an output file name");
+				if (graph && sharded) throw std::runtime_error("The graph is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				const size_t graphThreads = std::max<size_t>(1, std::min<size_t>(16, options.graphThreads));
+
 				const size_t capacity = (vertexLength + 4 + 31) / 32;  // CalculateNeededCapacity
 				if (capacity >= 20)
 				{
@@ -390,6 +397,31 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("parse + pack FASTA");
+				// --graph: the letters of the segment bodies, the sequence names and the positions of the letters the packed text
+				// cannot tell from 'N' -- the parse graphdump makes -- are read beside the device work, joined before the segment table
+				GraphFormat::InputSequences graphSeq;
+				GraphFormat::LoadedSequences graphLoaded;
+				std::string graphLoadError;
+				std::thread graphLoad;
+				struct ThreadJoiner graphLoadJoiner{graphLoad};
+				if (graph)
+				{
+					graphLoad = std::thread([&]()
+					{
+						try
+						{
+							PhaseTimer loadTimer;
+							GraphFormat::LoadSequences(fileName, options.graphFormat == "fasta" ? true : options.graphPrefix, graphThreads, graphSeq, graphLoaded);
+							loadTimer.Lap("  graph thread: sequences for the segment bodies");
+						}
+						catch (std::exception & e)
+						{
+							graphLoadError = e.what();
+							if (graphLoadError.empty()) graphLoadError = "unreadable FASTA file";
+						}
+					});
+				}
+
 				const uint64_t textChecksum = (options.loadFilter.empty() && options.saveFilter.empty()) ? 0 : TextChecksum(text);
 				textFingerprint_[0] = text.length; textFingerprint_[1] = text.recLength.size(); textFingerprint_[2] = textChecksum;
 				setup.join();
@@ -786,6 +818,7 @@ namespace TwoPaCo
 					std::cerr << "[timing] device memory in use after the rounds: " << double(tpc_get_stat(ctx_, "device_total_bytes") - tpc_get_stat(ctx_, "device_free_bytes")) / 1e9
 						<< " GB" << std::endl;
 				}
+				if (!graph || !outFileName.empty())  // with --graph the stream leaves the device only when a file was asked for
 				{
 					const int fd = ::open(outFileName.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
 					if (fd < 0)
@@ -869,12 +902,64 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
+				if (graph) WriteGraph(nothing, text, vertexLength, graphThreads, options, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
 			}
 
 		private:
+			// --graph: the segment table from the stream tpc_emit_stream left on the device, fetched as the event table, formatted
+			// into options.graphFile.  What the walk of graphdump would throw is thrown here, before the file is created.
+			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, std::thread & load,
+				const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
+			{
+				if (load.joinable()) load.join();
+				if (!loadError.empty()) throw std::runtime_error(loadError);
+				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
+				std::vector<uint64_t> ambiguous;
+				for (size_t r = 0; r < loaded.body.size(); r++)
+				{
+					if (text.recLength[r] != loaded.body[r].size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
+					for (uint64_t at : loaded.ambiguous[r]) ambiguous.push_back(text.recStart[r] + at);
+				}
+
+				const size_t sequences = text.recStart.size();
+				uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+				std::vector<int64_t> name;
+				std::vector<uint32_t> first, begin, end, seqEventBegin(sequences + 1, 0);
+				if (!nothing)  // (nothing dispatched: an empty stream, no event, and no text on the device)
+				{
+					Check(tpc_segments_build_resident(ctx_, int(k), text.recStart.data(), text.recLength.data(), uint32_t(sequences), ambiguous.data(), ambiguous.size()), "segments_build");
+					uint64_t errorSlot = 0;
+					int errorKind = 0;
+					Check(tpc_segments_counts(ctx_, counts), "segments_counts");
+					Check(tpc_segments_error(ctx_, &errorSlot, &errorKind), "segments_error");
+					timer.Lap("segment table");
+					if (errorKind != TPC_SEG_OK)
+					{
+						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
+					}
+
+					const uint64_t events = counts[0];
+					name.resize(events); first.resize((events + 31) / 32); begin.resize(events); end.resize(events);
+					Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
+					Check(tpc_segments_fetch_first(ctx_, 0, first.size(), first.data()), "segments_fetch_first");
+					Check(tpc_segments_fetch_events(ctx_, 0, events, begin.data(), end.data()), "segments_fetch_events");
+					Check(tpc_segments_fetch_sequences(ctx_, 0, seqEventBegin.size(), seqEventBegin.data()), "segments_fetch_sequences");
+					timer.Lap("segment table fetch");
+				}
+
+				GraphFormat::EventTable table;
+				table.events = counts[0];
+				table.name = name.data(); table.first = first.data(); table.begin = begin.data(); table.end = end.data();
+				table.sequences = sequences;
+				table.seqEventBegin = seqEventBegin.data();
+				GraphFormat::CheckEventTable(table, loaded, k, threads);
+				GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
+				timer.Lap("graph formatting + writing");
+			}
+
 			void SaveFilter(const std::string & name, size_t k, size_t bits, size_t q, size_t round, size_t rounds, uint64_t low, uint64_t high, const std::vector<uint64_t> & table,
 				tpc_ctx * ctx = 0, uint32_t shard = 0, uint32_t shards = 1)
 			{

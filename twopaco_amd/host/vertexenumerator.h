@@ -60,7 +60,16 @@ namespace TwoPaCo
 		// file (pinnedSeed / seed are ignored) and k, filter size, hash functions and the round's range must match.  Single GPU.
 		std::string saveFilter;
 		std::string loadFilter;
-		EnumeratorOptions() : pinnedSeed(false), seed(0), device(0), insertTestFirst(false), gpus(1), rccl(true), emulateRanks(false), forceSharded(false) {}
+		// The compacted graph as text, from the same process (graphformat.h): graphFormat = gfa1 | gfa2 | fasta (empty: off) is
+		// written to graphFile, byte for byte what `graphdump -f <format> [--prefix]` prints for the junction stream of this
+		// run.  The stream stays on the device, where the segment table is built from it (tpc_segments_build_resident); it
+		// is written to outFileName only when that name is not empty.  One GPU.
+		std::string graphFormat;
+		std::string graphFile;
+		bool graphPrefix;     // graphdump's --prefix
+		size_t graphThreads;  // formatting threads, 1..16
+		EnumeratorOptions() : pinnedSeed(false), seed(0), device(0), insertTestFirst(false), gpus(1), rccl(true), emulateRanks(false), forceSharded(false),
+			graphPrefix(false), graphThreads(16) {}
 	};
 
 	std::unique_ptr<VertexEnumerator> CreateEnumerator(const std::vector<std::string> & fileName,
