@@ -56,7 +56,9 @@ enum {
     TPC_K_LOOKUP = 13,      /* the k_apply_lookup launch of TPC_K_FUSED alone (the one kernel insert and query share: its time is split by bytes) */
     TPC_K_COMBINE = 14,     /* tpc_combine_export / tpc_combine_merge: k_slice_combine                                        */
     TPC_K_SEGMENTS = 15,    /* tpc_segments_build_*: names and first-sight bits of the compacted graph's segments, graphdump.cpp:44-113, 398-480 */
-    TPC_K_COUNT = 16
+    TPC_K_SEGTEXT = 16,     /* tpc_segments_text_*: the graph text rendered from the event table (host/graphformat.h's sinks); summed over the
+                               kernels since the last tpc_segments_text_plan (the plan's own included)                                    */
+    TPC_K_COUNT = 17
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -469,6 +471,35 @@ int tpc_segments_fetch_first(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uin
 int tpc_segments_fetch_events(tpc_ctx *ctx, uint64_t e0, uint64_t n, uint32_t *begin_host, uint32_t *end_host);
 int tpc_segments_fetch_sequences(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint32_t *first_event_host);
 
+/* The TEXT of the compacted graph, rendered on the device from the event table of the last build and the letters of
+ * tpc_seq_upload (csrc/tpc_segtext.hip): byte for byte what the sinks of twopaco_amd/host/graphformat.h (Gfa1Sink, Gfa2Sink,
+ * FastaSink fed by FormatChunk) write for the table, in file order.  The header lines (HeaderLines) are the caller's.
+ *   tpc_segments_text_plan   sizes and offsets of every event's lines (a size pass and two 64-bit exclusive scans); *total_bytes =
+ *                            the size of the whole text.  Needs a built table whose tpc_segments_error kind is TPC_SEG_OK and the
+ *                            text of tpc_seq_upload still resident; refused otherwise, and for a format outside 1..3.
+ *                            seq_names / seq_name_off: the names of the n_rec input sequences as one byte blob, name s =
+ *                            [seq_name_off[s], seq_name_off[s + 1]) (the caller adds the "s0_" prefix when asked; the kernels only
+ *                            copy).  amb_letter[i]: the letter at amb_pos[i] of the build, as the parser upper-cases it (R, Y, K, ...;
+ *                            may be NULL when the build had n_amb = 0): a forward body prints it, a reversed one prints 'N'.
+ *                            Adds 16 B per event, which count toward counts[5] of tpc_segments_counts; a new build or a new
+ *                            plan drops the old plan.
+ *   tpc_segments_text_fetch  renders the byte window [byte0, byte0 + n_bytes) of the text and copies it to dst_host.  A window may
+ *                            begin or end anywhere (inside a number, a body, a path line); a range outside [0, total) is refused.
+ *   tpc_segments_text_write  the whole text to the file descriptor fd: two device windows and two pinned host buffers of
+ *                            window_bytes (0 = the library's choice), window i + 1 rendered while window i is copied and a helper
+ *                            thread writes it -- with pwrite at file_offset + the bytes so far on a regular file, with write, in
+ *                            order, otherwise (a pipe; file_offset is then ignored).  Short writes and EINTR are handled; an I/O
+ *                            error ends the call with its text.  *written = bytes written (the caller truncates a file to
+ *                            file_offset + *written).
+ * Nothing here faults when device memory is short: the call is refused with an error text. */
+#define TPC_TEXT_GFA1 1
+#define TPC_TEXT_GFA2 2
+#define TPC_TEXT_FASTA 3
+int tpc_segments_text_plan(tpc_ctx *ctx, int format, const char *seq_names, const uint64_t *seq_name_off /* [n_rec + 1] */,
+                           const uint8_t *amb_letter /* [n_amb], may be NULL when n_amb = 0 */, uint64_t *total_bytes);
+int tpc_segments_text_fetch(tpc_ctx *ctx, uint64_t byte0, uint64_t n_bytes, void *dst_host);
+int tpc_segments_text_write(tpc_ctx *ctx, int fd, uint64_t file_offset, uint64_t window_bytes /* 0 = library's choice */, uint64_t *written);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -514,6 +545,8 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * only "seen twice"; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
  * tpc_pass2_filter consumed (what tpc_pass1_query reports; the sharded first pass has no single call that does);
  * "device_free_bytes" / "device_total_bytes" = hipMemGetInfo of the context's device, now;
+ * of the last tpc_segments_text_write: "text_write_us" = microseconds its helper thread spent inside write / pwrite, "text_wait_us" =
+ * microseconds the calling thread waited for a window's render and copy to finish, "text_window_bytes" = the window size used;
  * which kernels the last first pass ran (after a "+10" path: those of the partitioned pass the direct kernel completed):
  * "insert_hash_kernel" = 0 none (the direct rolling kernel), 1 the instruction-lean hash with its seed table in LDS, 2 the same
  * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);

@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -28,7 +28,7 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
                "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
-               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences"]
+               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -149,6 +149,9 @@ def hip():
         L.tpc_segments_fetch_first.argtypes = [p, u64, u64, p]
         L.tpc_segments_fetch_events.argtypes = [p, u64, u64, p, p]
         L.tpc_segments_fetch_sequences.argtypes = [p, u64, u64, p]
+        L.tpc_segments_text_plan.argtypes = [p, ci, p, p, p, p]
+        L.tpc_segments_text_fetch.argtypes = [p, u64, u64, p]
+        L.tpc_segments_text_write.argtypes = [p, ci, u64, u64, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
         L.tpc_get_stat.restype = i64
@@ -210,6 +213,9 @@ def seed_table(q, bits, seed=None):
     if host().tpch_seed_table(0 if seed is None else seed, 0 if seed is None else 1, q, bits, t.ctypes.data) != 0:
         raise RuntimeError(host().tpch_last_error().decode())
     return t
+
+
+TEXT_FORMATS = {"gfa1": 1, "gfa2": 2, "fasta": 3}  # TPC_TEXT_* of include/twopaco_hip.h
 
 
 def graph_format(files, k, fmt, out_path, name, first, begin, end, seq_event_begin, prefix=False, threads=16):
@@ -507,6 +513,34 @@ class Context:
         out = np.zeros(max(n, 0), dtype=np.uint32)
         self._ck(hip().tpc_segments_fetch_sequences(self._h, s0, n, out.ctypes.data))
         return out
+
+    def segments_text_plan(self, fmt, seq_names, amb_letters=b""):
+        """Sizes and offsets of the graph text (csrc/tpc_segtext.hip) of the last segments_build, whose error must be None.
+        fmt: "gfa1" / "gfa2" / "fasta" (or the C-ABI's 1 / 2 / 3); seq_names: the name of every input sequence as it is to be
+        printed (str or bytes); amb_letters: the letter at every ambiguous position of the build, in its order.  Returns the
+        size of the whole text in bytes."""
+        code = TEXT_FORMATS.get(fmt, fmt)
+        names = [n.encode() if isinstance(n, str) else bytes(n) for n in seq_names]
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(names) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(n) for n in names], dtype=np.uint64) if names else 0
+        letters = amb_letters.encode() if isinstance(amb_letters, str) else bytes(amb_letters)
+        let = np.frombuffer(letters + b"\0", dtype=np.uint8)
+        total = ctypes.c_uint64(0)
+        self._ck(hip().tpc_segments_text_plan(self._h, int(code), blob.ctypes.data, off.ctypes.data, let.ctypes.data if letters else None, ctypes.byref(total)))
+        return total.value
+
+    def segments_text_fetch(self, byte0, n):
+        """Bytes [byte0, byte0 + n) of the text of the last segments_text_plan, rendered on the device."""
+        buf = np.zeros(max(n, 1), dtype=np.uint8)
+        self._ck(hip().tpc_segments_text_fetch(self._h, byte0, n, buf.ctypes.data))
+        return buf[:n].tobytes()
+
+    def segments_text_write(self, fd, file_offset=0, window_bytes=0):
+        """The whole text to the file descriptor fd (a regular file: at file_offset; a pipe: in order).  Returns the bytes written."""
+        written = ctypes.c_uint64(0)
+        self._ck(hip().tpc_segments_text_write(self._h, fd, file_offset, window_bytes, ctypes.byref(written)))
+        return written.value
 
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))

@@ -332,7 +332,8 @@ void tpc_ctx_destroy(tpc_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = { c->tab, c->bases_alloc, c->nmask_alloc, c->filter, c->rmask, c->mask, c->marks, c->block_sums, c->table,
-                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg_name, c->seg_first, c->seg_ev[0], c->seg_ev[1], c->seg_ev[2] };
+                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg_name, c->seg_first, c->seg_ev[0], c->seg_ev[1], c->seg_ev[2],
+                     c->seg_rec, c->seg_amb, c->text_plan.off, c->text_plan.piece, c->text_names, c->text_win };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     stream_part_release(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
@@ -430,6 +431,9 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "text_word_end")) return (int64_t)c->text_w1;
     if (!strcmp(name, "periodic_any_query")) return c->periodic_valid && c->periodic_any_q ? 1 : 0;   // what the detection-only launch of ensure_periodic answered:
     if (!strcmp(name, "periodic_any_insert")) return c->periodic_valid && c->periodic_any_i ? 1 : 0;  // some position copies its verdict / drops its insert
+    if (!strcmp(name, "text_write_us")) return c->text_write_us;
+    if (!strcmp(name, "text_wait_us")) return c->text_wait_us;
+    if (!strcmp(name, "text_window_bytes")) return c->text_window_bytes;
     if (!strcmp(name, "device_free_bytes") || !strcmp(name, "device_total_bytes")) {  // hipMemGetInfo of the context's device, now
         size_t free_b = 0, total_b = 0;
         if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return -1; }
@@ -538,6 +542,7 @@ int tpc_seq_upload(tpc_ctx *c, const uint64_t *bases, const uint32_t *nmask, uin
     c->text_windowed = windowed; c->text_w0 = w0; c->text_w1 = w1;
     c->pending_apply = false;
     c->n_text = n_text; c->n_words = (n_text >> 5) + 1; c->n_words_alloc = alloc; c->n_tiles = tiles;
+    c->text_uploads++;  // a graph text planned over the previous text is void (tpc_capi_segments.hip)
     c->n_keys = 0; c->finalized = false; c->rounds_done = 0; c->mask_dirty = false; c->marks_valid = false; c->rmask_sums_valid = false;
     return 0;
 }
@@ -1115,6 +1120,7 @@ int tpc_hash_dump(tpc_ctx *c, uint64_t g0, uint64_t n, uint64_t *out_host)
 
 double tpc_kernel_ms(const tpc_ctx *c, int which)
 {
+    if (c && which == TPC_K_SEGTEXT) return c->text_valid ? c->text_ms : -1.0;  // a sum over many launches (tpc_capi_segments.hip)
     if (!c || which < 0 || which >= TPC_K_COUNT || !c->ev_used[which]) return -1.0;
     if (hipEventSynchronize(c->ev1[which]) != hipSuccess) return -1.0;
     float ms = 0;

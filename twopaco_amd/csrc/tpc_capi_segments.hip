@@ -1,16 +1,36 @@
 // tpc_capi_segments.hip -- C-ABI of the segment table (tpc_segments_*): the worker it replaces is graphdump's serial walk,
 // reference src/graphdump/graphdump.cpp:44-113 (segment naming) and :398-480 (the loop over the junction records).
-// Kernels and their memory bound: tpc_segments.hip.
+// Kernels and their memory bound: tpc_segments.hip.  The text of the graph from that table (tpc_segments_text_*): tpc_segtext.hip.
 #include "tpc_ctx.h"
 
+#include <cerrno>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <sys/stat.h>
+#include <unistd.h>
+
 namespace {
+
+void text_plan_drop(tpc_ctx *c)
+{
+    for (void *p : { (void *)c->text_plan.off, (void *)c->text_plan.piece, c->text_names, (void *)c->text_win }) if (p) (void)hipFree(p);
+    c->text_plan = TpcTextPlan{};
+    c->text_names = nullptr;
+    c->text_win = nullptr; c->text_win_cap = 0;
+    c->text_valid = false;
+    c->text_total = 0;
+    c->text_ms = 0;
+}
 
 int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k, const uint64_t *rec_start, const uint64_t *rec_len, uint32_t n_rec,
                    const uint64_t *amb_pos, uint64_t n_amb)
 {
     c->seg_valid = false;
-    for (void *p : { (void *)c->seg_name, (void *)c->seg_first, (void *)c->seg_ev[0], (void *)c->seg_ev[1], (void *)c->seg_ev[2] }) if (p) (void)hipFree(p);
+    text_plan_drop(c);
+    for (void *p : { (void *)c->seg_name, (void *)c->seg_first, (void *)c->seg_ev[0], (void *)c->seg_ev[1], (void *)c->seg_ev[2], (void *)c->seg_rec, (void *)c->seg_amb }) if (p) (void)hipFree(p);
     c->seg_name = nullptr; c->seg_first = nullptr;
+    c->seg_rec = c->seg_amb = nullptr;
     c->seg_ev[0] = c->seg_ev[1] = c->seg_ev[2] = nullptr;
     if (k < 0) return fail(c, -1, "segment table: k must not be negative");
     if (!c->bases || !c->nmask || c->text_windowed) return fail(c, -1, "segment table: tpc_seq_upload the whole text first");
@@ -34,15 +54,30 @@ int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k,
         rc = tpc_launch_segments(c->stream, d_slots, n_slots, k, c->bases, c->nmask, d_rec, d_rec + n_rec, n_rec, d_amb, n_amb, &c->seg_name, &c->seg_first, c->seg_ev, &res, text);
     }
     const hipError_t e = hipStreamSynchronize(c->stream);
-    for (void *p : { (void *)d_rec, (void *)d_amb }) if (p) (void)hipFree(p);
+    if (rc || e != hipSuccess) { for (void *p : { (void *)d_rec, (void *)d_amb }) if (p) (void)hipFree(p); }
+    else { c->seg_rec = d_rec; c->seg_amb = d_amb; }  // the graph text reads them (tpc_segments_text_plan)
     if (rc) return text[0] ? fail(c, rc, "%s", text) : fail(c, rc, "segment table failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
     HIPCHK(c, e);
     c->seg_events = res.events; c->seg_segments = res.segments; c->seg_named = res.named; c->seg_table_bytes = res.table_bytes;
     c->seg_slots = n_slots; c->seg_peak_bytes = res.peak_bytes; c->seg_n_rec = n_rec;
     c->seg_err_slot = res.err_slot; c->seg_err_kind = res.err_kind;
+    c->seg_n_amb = n_amb; c->seg_k = k;
+    c->seg_text_bases = c->bases; c->seg_text_n = c->n_text; c->seg_text_uploads = c->text_uploads;
     c->seg_valid = true;
     return 0;
 }
+
+// one render, timed into the sum behind TPC_K_SEGTEXT (the caller has synchronised ev1 before it reads the sum)
+struct TextTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok() { return (e0 || hipEventCreate(&e0) == hipSuccess) && (e1 || hipEventCreate(&e1) == hipSuccess); }
+    void add(tpc_ctx *c) { float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->text_ms += ms; }
+    ~TextTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+size_t text_tiles(uint64_t n) { return (size_t)((n + TPC_TEXT_TILE - 1) / TPC_TEXT_TILE * TPC_TEXT_TILE); }
+
+bool text_ready(tpc_ctx *c) { return c && c->seg_valid && c->text_valid && c->bases == c->seg_text_bases && c->n_text == c->seg_text_n && c->text_uploads == c->seg_text_uploads && !c->text_windowed; }
 
 }  // namespace
 
@@ -132,6 +167,235 @@ int tpc_segments_fetch_sequences(tpc_ctx *c, uint64_t s0, uint64_t n, uint32_t *
     if (!c || !c->seg_valid || (n && !first_event_host) || s0 > entries || n > entries - s0) return fail(c, -1, "segment table: bad sequence range");
     HIPCHK(c, hipSetDevice(c->device));
     if (n) HIPCHK(c, hipMemcpy(first_event_host, c->seg_ev[2] + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tpc_segments_text_plan(tpc_ctx *c, int format, const char *seq_names, const uint64_t *seq_name_off, const uint8_t *amb_letter, uint64_t *total_bytes)
+{
+    if (!c) return -1;
+    if (!total_bytes) return fail(c, -1, "graph text: total_bytes required");
+    *total_bytes = 0;
+    text_plan_drop(c);
+    if (!c->seg_valid) return fail(c, -1, "graph text: build the segment table first (tpc_segments_build_host / _resident)");
+    if (c->seg_err_kind != TPC_SEG_OK)
+        return fail(c, -1, "graph text: the segment table holds the walk's error %d at slot %llu, there is no text to render", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
+    if (format != TPC_TEXT_GFA1 && format != TPC_TEXT_GFA2 && format != TPC_TEXT_FASTA) return fail(c, -1, "graph text: format %d is none of gfa1 (1), gfa2 (2), fasta (3)", format);
+    if (!c->bases || !c->nmask || c->text_windowed || c->bases != c->seg_text_bases || c->n_text != c->seg_text_n || c->text_uploads != c->seg_text_uploads)
+        return fail(c, -1, "graph text: the text of tpc_seq_upload the table was built over is no longer resident");
+    const uint32_t n_rec = c->seg_n_rec;
+    if (!seq_name_off || (seq_name_off[n_rec] && !seq_names)) return fail(c, -1, "graph text: sequence names required");
+    if (seq_name_off[0] != 0) return fail(c, -1, "graph text: the names' offsets must begin at 0");
+    for (uint32_t r = 0; r < n_rec; r++)
+        if (seq_name_off[r] > seq_name_off[r + 1]) return fail(c, -1, "graph text: the names' offsets must ascend");
+    if (c->seg_n_amb && !amb_letter) return fail(c, -1, "graph text: the letters of the %llu ambiguity positions are required", (unsigned long long)c->seg_n_amb);
+    HIPCHK(c, hipSetDevice(c->device));
+    // the table's own consistency: every event belongs to one of the n_rec sequences
+    uint32_t last = 0;
+    HIPCHK(c, hipMemcpy(&last, c->seg_ev[2] + n_rec, sizeof last, hipMemcpyDeviceToHost));
+    if (last != c->seg_events) return fail(c, -1, "graph text: the stream holds events of more sequences than the %u given", n_rec);
+    // names' blob | offsets | letters in one allocation
+    const uint64_t blob = seq_name_off[n_rec];
+    const size_t off_at = (size_t)((blob + 7) / 8 * 8), let_at = off_at + ((size_t)n_rec + 1) * 8, bytes = let_at + (size_t)c->seg_n_amb + 8;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    if (bytes + ((size_t)64 << 20) > free_b) return fail(c, -20, "graph text: %zu bytes of sequence names and letters do not fit the free device memory", bytes);
+    HIPCHK(c, hipMalloc(&c->text_names, bytes));
+    uint8_t *base = (uint8_t *)c->text_names;
+    if (blob) HIPCHK(c, hipMemcpyAsync(base, seq_names, blob, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(base + off_at, seq_name_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (c->seg_n_amb) HIPCHK(c, hipMemcpyAsync(base + let_at, amb_letter, c->seg_n_amb, hipMemcpyHostToDevice, c->stream));
+    TpcTextPlan &T = c->text_plan;
+    T.format = format; T.k = c->seg_k;
+    T.n_events = c->seg_events; T.n_rec = n_rec;
+    T.name = c->seg_name; T.first = c->seg_first; T.begin = c->seg_ev[0]; T.end = c->seg_ev[1]; T.seq_begin = c->seg_ev[2];
+    T.rec_start = c->seg_rec; T.rec_len = c->seg_rec + n_rec;
+    T.bases = c->bases; T.nmask = c->nmask;
+    T.amb = c->seg_amb; T.amb_letter = base + let_at; T.n_amb = c->seg_n_amb;
+    T.seq_names = (const char *)base; T.seq_name_off = (const uint64_t *)(base + off_at);
+    char text[TPC_SEG_ERR_TEXT] = "";
+    TextTimer timer;
+    if (!timer.ok()) { text_plan_drop(c); return fail(c, -10, "graph text: hipEventCreate failed"); }
+    (void)hipEventRecord(timer.e0, c->stream);
+    const int rc = tpc_launch_segtext_plan(c->stream, T, &c->text_total, text);
+    (void)hipEventRecord(timer.e1, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc || e != hipSuccess) {
+        text_plan_drop(c);
+        return text[0] ? fail(c, rc, "%s", text) : fail(c, rc ? rc : -10, "graph text: the size pass failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    }
+    c->text_ms = 0;
+    timer.add(c);
+    size_t fb = 0, tb = 0;
+    if (hipMemGetInfo(&fb, &tb) == hipSuccess) c->seg_peak_bytes = std::max<uint64_t>(c->seg_peak_bytes, tb - fb);
+    c->text_valid = true;
+    *total_bytes = c->text_total;
+    return 0;
+}
+
+int tpc_segments_text_fetch(tpc_ctx *c, uint64_t byte0, uint64_t n_bytes, void *dst_host)
+{
+    if (!c) return -1;
+    if (!text_ready(c)) return fail(c, -1, "graph text: tpc_segments_text_plan first");
+    if ((n_bytes && !dst_host) || byte0 > c->text_total || n_bytes > c->text_total - byte0)
+        return fail(c, -1, "graph text: bad byte range (%llu bytes at %llu of a text of %llu)", (unsigned long long)n_bytes, (unsigned long long)byte0, (unsigned long long)c->text_total);
+    if (!n_bytes) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint64_t window = std::min<uint64_t>(n_bytes, (uint64_t)256 << 20);
+    if (text_tiles(window) > c->text_win_cap) {  // the window buffer is kept between calls (many small windows: no allocation each)
+        if (c->text_win) (void)hipFree(c->text_win);
+        c->text_win = nullptr; c->text_win_cap = 0;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        if (text_tiles(window) + ((size_t)64 << 20) > free_b) return fail(c, -20, "graph text: a window of %zu bytes does not fit the free device memory", text_tiles(window));
+        HIPCHK(c, hipMalloc((void **)&c->text_win, text_tiles(window)));
+        c->text_win_cap = text_tiles(window);
+    }
+    uint8_t *d = c->text_win;
+    hipEvent_t e0 = c->ev0[TPC_K_SEGTEXT], e1 = c->ev1[TPC_K_SEGTEXT];
+    for (uint64_t done = 0; done < n_bytes; done += window) {
+        const uint64_t n = std::min(window, n_bytes - done);
+        (void)hipEventRecord(e0, c->stream);
+        tpc_launch_segtext_render(c->stream, c->text_plan, byte0 + done, n, d);
+        (void)hipEventRecord(e1, c->stream);
+        if (hipMemcpyAsync((uint8_t *)dst_host + done, d, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
+            hipGetLastError() != hipSuccess)
+            return fail(c, -10, "graph text: rendering a window failed: %s", hipGetErrorString(hipGetLastError()));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) c->text_ms += ms;
+    }
+    return 0;
+}
+
+int tpc_segments_text_write(tpc_ctx *c, int fd, uint64_t file_offset, uint64_t window_bytes, uint64_t *written)
+{
+    if (!c) return -1;
+    if (written) *written = 0;
+    if (!text_ready(c)) return fail(c, -1, "graph text: tpc_segments_text_plan first");
+    struct stat st;
+    if (fd < 0 || ::fstat(fd, &st) != 0) return fail(c, -1, "graph text: bad file descriptor %d", fd);
+    const bool regular = S_ISREG(st.st_mode);
+    const uint64_t total = c->text_total;
+    c->text_write_us = c->text_wait_us = c->text_window_bytes = 0;
+    if (!total) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto us_since = [](std::chrono::steady_clock::time_point t0) { return (int64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count(); };
+    uint64_t window = window_bytes ? window_bytes : (uint64_t)64 << 20;
+    window = text_tiles(std::max<uint64_t>(1, std::min<uint64_t>(std::min(window, total), (uint64_t)1 << 30)));
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    // the library's choice shrinks to what is free; a size the caller asked for is taken as it is or refused
+    while (!window_bytes && window > ((uint64_t)1 << 20) && 2 * window + ((size_t)64 << 20) > free_b) window = text_tiles(window / 2);
+    if (2 * window + ((size_t)64 << 20) > free_b) return fail(c, -20, "graph text: two windows of %llu bytes do not fit the free device memory", (unsigned long long)window);
+
+    uint8_t *dev[2] = {nullptr, nullptr};
+    void *pin[2] = {nullptr, nullptr};
+    hipStream_t copy = nullptr;
+    hipEvent_t rendered[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
+    TextTimer timer[2];
+    std::string why;
+    bool hip_ok = hipStreamCreate(&copy) == hipSuccess && timer[0].ok() && timer[1].ok();
+    for (int i = 0; i < 2 && hip_ok; i++)
+        hip_ok = hipMalloc((void **)&dev[i], window) == hipSuccess && hipHostMalloc(&pin[i], window, hipHostMallocDefault) == hipSuccess &&
+                 hipEventCreateWithFlags(&rendered[i], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&copied[i], hipEventDisableTiming) == hipSuccess;
+
+    // the helper thread: windows in order, one at a time; busy[b] = buffer b is handed over and not written yet
+    std::mutex lock;
+    std::condition_variable changed;
+    struct Job { int buf; uint64_t at, n; };
+    std::vector<Job> queue;
+    size_t taken = 0;
+    bool busy[2] = {false, false}, closing = false;
+    std::string io_error;
+    uint64_t wrote = 0;
+    int64_t write_us = 0;
+    c->text_window_bytes = (int64_t)window;
+    std::thread writer([&]() {
+        for (;;) {
+            Job j;
+            {
+                std::unique_lock<std::mutex> hold(lock);
+                changed.wait(hold, [&]() { return taken < queue.size() || closing; });
+                if (taken == queue.size()) return;
+                j = queue[taken++];
+                if (!io_error.empty()) {  // after an error nothing more is written: the buffers are only given back
+                    busy[j.buf] = false;
+                    hold.unlock();
+                    changed.notify_all();
+                    continue;
+                }
+            }
+            std::string err;
+            const char *p = (const char *)pin[j.buf];
+            const auto t0 = std::chrono::steady_clock::now();
+            for (uint64_t done = 0; done < j.n && err.empty();) {
+                const ssize_t w = regular ? ::pwrite(fd, p + done, j.n - done, (off_t)(file_offset + j.at + done)) : ::write(fd, p + done, j.n - done);
+                if (w < 0 && errno == EINTR) continue;
+                if (w < 0) err = std::string("graph text: writing failed: ") + strerror(errno);
+                else if (w == 0) err = "graph text: writing failed: no byte was taken";
+                else done += (uint64_t)w;
+            }
+            {
+                std::unique_lock<std::mutex> hold(lock);
+                write_us += us_since(t0);
+                if (err.empty()) wrote += j.n; else if (io_error.empty()) io_error = err;
+                busy[j.buf] = false;
+            }
+            changed.notify_all();
+        }
+    });
+
+    const uint64_t windows = (total + window - 1) / window;
+    auto issue = [&](uint64_t i) {  // render window i on the context's stream, copy it on the other
+        const int b = (int)(i & 1);
+        const uint64_t at = i * window, n = std::min(window, total - at);
+        {
+            std::unique_lock<std::mutex> hold(lock);  // the pinned buffer must have been written out (window i - 2)
+            changed.wait(hold, [&]() { return !busy[b]; });
+            if (!io_error.empty()) return false;
+        }
+        // (the device buffer is free: window i - 2's copy was synchronised before it was handed to the writer)
+        if (hipEventRecord(timer[b].e0, c->stream) != hipSuccess) return false;
+        tpc_launch_segtext_render(c->stream, c->text_plan, at, n, dev[b]);
+        if (hipEventRecord(timer[b].e1, c->stream) != hipSuccess || hipEventRecord(rendered[b], c->stream) != hipSuccess ||
+            hipStreamWaitEvent(copy, rendered[b], 0) != hipSuccess || hipMemcpyAsync(pin[b], dev[b], n, hipMemcpyDeviceToHost, copy) != hipSuccess ||
+            hipEventRecord(copied[b], copy) != hipSuccess) return false;
+        return true;
+    };
+    if (hip_ok) hip_ok = issue(0);
+    for (uint64_t i = 0; hip_ok && i < windows; i++) {
+        const int b = (int)(i & 1);
+        if (i + 1 < windows && !issue(i + 1)) { hip_ok = false; break; }  // window i + 1 renders while window i copies
+        const auto t0 = std::chrono::steady_clock::now();
+        if (hipEventSynchronize(copied[b]) != hipSuccess) { hip_ok = false; break; }
+        c->text_wait_us += us_since(t0);
+        timer[b].add(c);
+        {
+            std::unique_lock<std::mutex> hold(lock);
+            if (!io_error.empty()) break;
+            busy[b] = true;
+            queue.push_back(Job{b, i * window, std::min(window, total - i * window)});
+        }
+        changed.notify_all();
+    }
+    {
+        std::unique_lock<std::mutex> hold(lock);
+        closing = true;
+    }
+    changed.notify_all();
+    writer.join();
+    c->text_write_us = write_us;
+    const hipError_t last = hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    if (copy) { (void)hipStreamSynchronize(copy); (void)hipStreamDestroy(copy); }
+    for (int i = 0; i < 2; i++) {
+        if (dev[i]) (void)hipFree(dev[i]);
+        if (pin[i]) (void)hipHostFree(pin[i]);
+        if (rendered[i]) (void)hipEventDestroy(rendered[i]);
+        if (copied[i]) (void)hipEventDestroy(copied[i]);
+    }
+    if (written) *written = wrote;
+    if (!io_error.empty()) return fail(c, -30, "%s", io_error.c_str());
+    if (!hip_ok || wrote != total) return fail(c, -10, "graph text: rendering or copying a window failed: %s", hipGetErrorString(last));
     return 0;
 }
 

@@ -3,7 +3,7 @@
 //   tpc_capi_pass2.hip    second pass, junction keys, ids, junction stream (tpc_pass2_*, tpc_junction*, tpc_emit*)
 //   tpc_capi_shard.hip    the filter cut by address over ranks (tpc_shard_*), mask unions
 //   tpc_capi_combine.hip  the filter replicated through set-bit lists (tpc_combine_*)
-//   tpc_capi_segments.hip the segment table of the compacted graph (tpc_segments_*)
+//   tpc_capi_segments.hip the segment table of the compacted graph and its text (tpc_segments_*)
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
 #include "../../include/twopaco_hip.h"
@@ -35,6 +35,7 @@ struct tpc_ctx {
     uint64_t *bases = nullptr;
     uint32_t *nmask = nullptr;
     uint64_t n_text = 0, n_words = 0, n_words_alloc = 0, n_tiles = 0;
+    uint64_t text_uploads = 0;  // tpc_seq_upload calls so far
     // periodic-window masks of the text (tpc_internal.h:TpcLaunch): [8][n_words_alloc] = per_qs, the six bit planes of the copy distance, per_i (at 7 * n_words_alloc); built at the first
     // partitioned pass after an upload / a change of k (ensure_periodic), option "periodic_skip" (default on)
     uint32_t *periodic = nullptr;
@@ -95,6 +96,20 @@ struct tpc_ctx {
     uint64_t seg_err_slot = 0;
     int seg_err_kind = 0;
     bool seg_valid = false;
+    // ... kept for the graph text (tpc_segments_text_*, tpc_segtext.hip): the build's sequence records and ambiguity positions, the
+    // text they index, and the plan of the last tpc_segments_text_plan
+    uint64_t *seg_rec = nullptr, *seg_amb = nullptr;   // device: rec_start[n_rec] then rec_len[n_rec]; amb_pos[n_amb]
+    uint64_t seg_n_amb = 0, seg_text_n = 0, seg_text_uploads = 0;
+    const void *seg_text_bases = nullptr;
+    int seg_k = 0;
+    TpcTextPlan text_plan;
+    void *text_names = nullptr;       // device: the names' blob, then (8-aligned) its offsets, then amb_letter
+    uint8_t *text_win = nullptr;      // device: the window buffer of tpc_segments_text_fetch, whole tiles
+    size_t text_win_cap = 0;
+    bool text_valid = false;
+    uint64_t text_total = 0;
+    double text_ms = 0;               // TPC_K_SEGTEXT: kernels since the last plan
+    int64_t text_write_us = 0, text_wait_us = 0, text_window_bytes = 0;  // of the last tpc_segments_text_write (tpc_get_stat)
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors

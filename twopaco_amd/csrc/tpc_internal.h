@@ -326,3 +326,24 @@ struct TpcSegResult { uint64_t events, segments, named, table_bytes, peak_bytes,
 int tpc_launch_segments(hipStream_t s, const uint32_t *slots, uint64_t n_slots, int k, const uint64_t *bases, const uint32_t *nmask,
                         const uint64_t *d_rec_start, const uint64_t *d_rec_len, uint32_t n_rec, const uint64_t *d_amb, uint64_t n_amb,
                         int64_t **name_out, uint32_t **first_out, uint32_t **ev_out /* [3]: begin, end, seq_event_begin */, TpcSegResult *res, char *err);
+// tpc_segtext.hip: the graph text (gfa1 / gfa2 / fasta) rendered from the event table.  Everything is a device pointer.
+struct TpcTextPlan {
+    int format = 0, k = 0;           // TPC_TEXT_*
+    uint64_t n_events = 0;
+    uint32_t n_rec = 0;
+    const int64_t *name = nullptr;
+    const uint32_t *first = nullptr, *begin = nullptr, *end = nullptr, *seq_begin = nullptr;
+    const uint64_t *rec_start = nullptr, *rec_len = nullptr;
+    const uint64_t *bases = nullptr;
+    const uint32_t *nmask = nullptr;
+    const uint64_t *amb = nullptr;
+    const uint8_t *amb_letter = nullptr;
+    uint64_t n_amb = 0;
+    const char *seq_names = nullptr;      // one blob
+    const uint64_t *seq_name_off = nullptr;  // [n_rec + 1]
+    uint64_t *off = nullptr;    // [n_events + 1] byte offset of every event's lines in the whole text; the last entry is the total
+    uint64_t *piece = nullptr;  // [n_events + 1] offset of every event's piece among all path pieces
+};
+#define TPC_TEXT_TILE 8192  // bytes of text one workgroup renders; window buffers are whole tiles
+int tpc_launch_segtext_plan(hipStream_t s, TpcTextPlan &plan, uint64_t *total_bytes, char *err);  // allocates plan.off / plan.piece (the caller frees)
+void tpc_launch_segtext_render(hipStream_t s, const TpcTextPlan &plan, uint64_t byte0, uint64_t n_bytes, uint8_t *out /* n_bytes rounded up to whole tiles */);

@@ -9,9 +9,10 @@
 // --save-filter F / --load-filter F (checkpoint of the Bloom filter after each round's first-pass insert, the reference's
 // commented-out ReloadBloomFilter, vertexenumerator.h:29,113-121; a run that loads skips the insert), and with --test,
 // --seed makes the trials reproducible (the reference's are not, test.cpp:169);
-// --graph gfa1|gfa2|fasta [--graph-out F] [--graph-prefix] [--graph-threads N]: the compacted graph as text from this process,
+// --graph gfa1|gfa2|fasta [--graph-out F] [--graph-prefix] [--graph-threads N] [--graph-text host|device]: the compacted graph as text from this process,
 // byte for byte what `graphdump -f <format> [--prefix]` prints for the junction stream of the same command (graphformat.h; the
-// stream stays on the device and the junction file is written only when -o is given as well; one GPU).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// stream stays on the device and the junction file is written only when -o is given as well; one GPU; --graph-text device renders
+// the text on the device too, csrc/tpc_segtext.hip, instead of fetching the event table and formatting it here).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -65,11 +66,14 @@ namespace
 			<< "               [--seed <integer>] [--device <integer>] [--test-first] [--gpus <power of two>] [--no-rccl]" << std::endl
 			<< "               [--save-filter <file>] [--load-filter <file>]" << std::endl
 			<< "               [--graph <gfa1|gfa2|fasta>] [--graph-out <file name>] [--graph-prefix] [--graph-threads <integer>]" << std::endl
+			<< "               [--graph-text <host|device>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -q: 1..64 hash functions (the reference takes any number; more than 16 run on slower closed-form kernels)" << std::endl
 			<< "       --graph: also write the compacted graph as graphdump -f <format> prints it, to --graph-out (default" << std::endl
 			<< "               de_bruijn.<format>); the junction file is then written only when -o is given.  --graph-prefix:" << std::endl
-			<< "               graphdump's --prefix.  --graph-threads: formatting threads (1..16, default 16).  One GPU only" << std::endl;
+			<< "               graphdump's --prefix.  --graph-threads: formatting threads (1..16, default 16).  One GPU only." << std::endl
+			<< "               --graph-text: host (default) formats the text with the threads above; device renders the same bytes" << std::endl
+			<< "               on the GPU, the host only writes them (--graph-threads is then unused)" << std::endl;
 	}
 }
 
@@ -110,7 +114,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -162,6 +166,13 @@ int main(int argc, char * argv[])
 				if (end == v.c_str() || *end != 0 || parsed < 1) throw ArgError("Couldn't read argument value from string '" + v + "'", "(--graph-threads)");
 				options.graphThreads = size_t(std::min<long long>(parsed, 16));
 			}
+			else if (Match(a, 0, "graph-text"))
+			{
+				const std::string v = value("(--graph-text)");
+				if (v != "host" && v != "device") throw ArgError("Value '" + v + "' does not meet constraint: host|device", "(--graph-text)");
+				options.graphTextOnDevice = v == "device";
+				graphTextSet = true;
+			}
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -184,9 +195,9 @@ int main(int argc, char * argv[])
 			if (!graphOutSet) options.graphFile = "de_bruijn." + options.graphFormat;
 			if (!outFileSet) outFileName.clear();  // the junction stream stays on the device
 		}
-		else if (graphOutSet || options.graphPrefix)
+		else if (graphOutSet || options.graphPrefix || graphTextSet)
 		{
-			throw ArgError("This argument needs --graph <gfa1|gfa2|fasta>", graphOutSet ? "(--graph-out)" : "(--graph-prefix)");
+			throw ArgError("This argument needs --graph <gfa1|gfa2|fasta>", graphOutSet ? "(--graph-out)" : options.graphPrefix ? "(--graph-prefix)" : "(--graph-text)");
 		}
 
 		if (runTests)

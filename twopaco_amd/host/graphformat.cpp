@@ -341,8 +341,8 @@ namespace TwoPaCo
 			return total;
 		}
 
-		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
-			size_t threads, const std::string & outPath)
+		void WriteGraphFileWith(const std::string & format, const InputSequences & seq, const std::string & outPath,
+			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events)
 		{
 			int fd = ::open(outPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
 			if (fd < 0) throw std::runtime_error("Can't create the graph file " + outPath);
@@ -351,7 +351,7 @@ namespace TwoPaCo
 				Out head(false);
 				HeaderLines(format, seq, head);
 				if (!WriteAll(fd, head.Text().data(), head.Text().size(), 0)) throw std::runtime_error("Can't write to the graph file");
-				const uint64_t size = head.Text().size() + FormatEvents(table, seq, loaded, k, format, threads, fd, head.Text().size());
+				const uint64_t size = head.Text().size() + events(fd, head.Text().size());
 				if (::ftruncate(fd, off_t(size)) != 0) throw std::runtime_error("Can't write to the graph file");
 				const int closing = fd;
 				fd = -1;
@@ -363,6 +363,15 @@ namespace TwoPaCo
 				::unlink(outPath.c_str());
 				throw;
 			}
+		}
+
+		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
+			size_t threads, const std::string & outPath)
+		{
+			WriteGraphFileWith(format, seq, outPath, [&](int fd, uint64_t fileOffset)
+			{
+				return FormatEvents(table, seq, loaded, k, format, threads, fd, fileOffset);
+			});
 		}
 	}
 }

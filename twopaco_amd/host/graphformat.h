@@ -15,6 +15,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -279,6 +280,38 @@ namespace TwoPaCo
 		// bytes written (the caller truncates the file to fileOffset + that).  The table must have passed CheckEventTable.
 		uint64_t FormatEvents(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, int fd, uint64_t fileOffset);
+
+		// The file outPath (created or truncated; removed again when anything fails): the header lines, then what `events` writes
+		// from the offset it is given on (it returns its bytes); the file is truncated to the sum.
+		void WriteGraphFileWith(const std::string & format, const InputSequences & seq, const std::string & outPath,
+			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events);
+
+		// What the device formatter (include/twopaco_hip.h: tpc_segments_text_plan) takes beside the event table: the names as they
+		// are printed, as one blob with offsets, and the letter at every ambiguous position in the order of the positions.
+		struct DeviceTextInput
+		{
+			std::string names;
+			std::vector<uint64_t> nameOffset;   // [sequences + 1]
+			std::vector<uint8_t> ambiguousLetter;
+		};
+
+		inline void MakeDeviceTextInput(const InputSequences & seq, const LoadedSequences & loaded, DeviceTextInput & out)
+		{
+			out.nameOffset.assign(1, 0);
+			for (const std::string & name : seq.name)
+			{
+				out.names += name;
+				out.nameOffset.push_back(out.names.size());
+			}
+
+			for (size_t r = 0; r < loaded.body.size(); r++)
+			{
+				for (uint64_t at : loaded.ambiguous[r]) out.ambiguousLetter.push_back(uint8_t(loaded.body[r][at]));
+			}
+		}
+
+		// TPC_TEXT_GFA1 / _GFA2 / _FASTA of include/twopaco_hip.h
+		inline int DeviceTextFormat(const std::string & format) { return format == "gfa1" ? 1 : format == "gfa2" ? 2 : format == "fasta" ? 3 : 0; }
 
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails).
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

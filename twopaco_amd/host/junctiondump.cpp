@@ -2,7 +2,7 @@
 //
 // Downstream consumer of the junction stream, kept flag- and byte-compatible with the reference's
 // graphdump (reference src/graphdump/graphdump.cpp) so that pipelines built on it are unchanged:
-//   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>]
+//   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>] [--text host|device]
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -23,6 +23,10 @@
 // chunks of events that go to stdout in order (graphformat.h, shared with `twopaco --graph`; its input is the event table the
 // device leaves -- name, first sight, the two positions of every event, the events of every sequence -- fetched with
 // tpc_segments_fetch_*).  No device or no library with --gpu is an error: there is no fallback.
+// --text device (with --gpu; the default is host): the text itself is rendered on the device from the table that is already
+// there (csrc/tpc_segtext.hip: tpc_segments_text_plan / _text_write) and this process only writes it -- the table is not
+// fetched and --threads formats nothing.  The bytes are the same.  The table is complete before the first byte is printed, so
+// a stream the walk refuses prints its error and nothing else (the host paths have printed the header lines by then).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -289,12 +293,12 @@ namespace
 
 	struct DumpStats
 	{
-		std::string path;
+		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
-		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs;
+		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs;
 		size_t threads;
-		DumpStats() : path("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), threads(1) {}
+		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -305,9 +309,9 @@ namespace
 			if (!f) return;
 			std::fprintf(f, "{\"path\": \"%s\", \"events\": %llu, \"segments\": %llu, \"n_named\": %llu, \"device_ms\": %.3f, \"kernel_ms\": %.3f, \"load_ms\": %.3f, "
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
-				"\"table_bytes\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
-				(unsigned long long)tableBytes);
+				(unsigned long long)tableBytes, text.c_str(), textKernelMs);
 			std::fclose(f);
 		}
 	};
@@ -327,6 +331,8 @@ namespace
 		decltype(&tpc_segments_fetch_first) segmentsFetchFirst;
 		decltype(&tpc_segments_fetch_events) segmentsFetchEvents;
 		decltype(&tpc_segments_fetch_sequences) segmentsFetchSequences;
+		decltype(&tpc_segments_text_plan) segmentsTextPlan;
+		decltype(&tpc_segments_text_write) segmentsTextWrite;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -355,6 +361,8 @@ namespace
 			Load(segmentsFetchFirst, "tpc_segments_fetch_first");
 			Load(segmentsFetchEvents, "tpc_segments_fetch_events");
 			Load(segmentsFetchSequences, "tpc_segments_fetch_sequences");
+			Load(segmentsTextPlan, "tpc_segments_text_plan");
+			Load(segmentsTextWrite, "tpc_segments_text_write");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -390,7 +398,7 @@ namespace
 	// event table of the stream (name, first sight, the two positions of every event, the events of every sequence); the
 	// formatter of graphformat.h reads the table and the letters, never the stream's bytes.
 	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats)
+		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, bool textOnDevice)
 	{
 		const size_t SLOT_BYTES = 12;
 		// the stream's bytes
@@ -450,6 +458,33 @@ namespace
 			throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 		}
 
+		if (textOnDevice)
+		{
+			// the text from the table where it is: nothing is fetched but the bytes to print
+			TwoPaCo::GraphFormat::DeviceTextInput input;
+			TwoPaCo::GraphFormat::MakeDeviceTextInput(seq, loaded, input);
+			uint64_t total = 0, written = 0;
+			lib.Check(lib.segmentsTextPlan(lib.ctx, TwoPaCo::GraphFormat::DeviceTextFormat(format), input.names.data(), input.nameOffset.data(),
+				input.ambiguousLetter.empty() ? 0 : input.ambiguousLetter.data(), &total), "tpc_segments_text_plan");
+			uint64_t after[6] = {0, 0, 0, 0, 0, 0};
+			lib.Check(lib.segmentsCounts(lib.ctx, after), "tpc_segments_counts");
+			stats.deviceBytes = after[5];
+			stats.deviceMs = MsSince(t0);
+			t0 = std::chrono::steady_clock::now();
+			std::fwrite(out.Text().data(), 1, out.Text().size(), stdout);  // the header lines, held back until here
+			out.Text().clear();
+			std::fflush(stdout);
+			// a regular file is written at its offset (pwrite), anything else in order
+			const off_t at = ::lseek(STDOUT_FILENO, 0, SEEK_CUR);
+			lib.Check(lib.segmentsTextWrite(lib.ctx, STDOUT_FILENO, at >= 0 ? uint64_t(at) : 0, 0, &written), "tpc_segments_text_write");
+			if (written != total) throw std::runtime_error("--gpu: the text was not written in full");
+			if (at >= 0) (void)::lseek(STDOUT_FILENO, at + off_t(written), SEEK_SET);
+			stats.formatMs = MsSince(t0);
+			stats.textKernelMs = lib.kernelMs(lib.ctx, TPC_K_SEGTEXT);
+			if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] graph text on device: %.3f ms\n", stats.formatMs);
+			return;
+		}
+
 		const uint64_t events = counts[0];
 		std::vector<int64_t> name(events);
 		std::vector<uint32_t> first((events + 31) / 32);
@@ -489,7 +524,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -499,6 +534,8 @@ namespace
 			"     several threads; the output is the same.  An error when there is no device: no CPU fallback.\n"
 			"     (twopaco --graph <gfa1|gfa2|fasta> writes the same text from the process that enumerates the junctions.)\n\n"
 			"   --threads <integer>\n     threads of --gpu (1..16, default 16)\n\n"
+			"   --text <host|device>\n     with --gpu: host (default) formats the text with the threads above, device renders the same bytes on the\n"
+			"     GPU and this process only writes them\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -510,7 +547,7 @@ int main(int argc, char * argv[])
 	{
 		std::string binFile, format;
 		std::vector<std::string> fasta;
-		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false;
+		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
 		bool positionalOnly = false;
@@ -547,6 +584,12 @@ int main(int argc, char * argv[])
 				if (end == v.c_str() || *end != 0 || parsed < 1) throw ArgError("Couldn't read argument value from string '" + v + "'", "(--threads)");
 				threads = size_t(std::min<long long>(parsed, 16));
 			}
+			else if (a == "--text")
+			{
+				const std::string v = value("(--text)");
+				if (v != "host" && v != "device") throw ArgError("Value '" + v + "' does not meet constraint: host|device", "Argument: (--text)");
+				textOnDevice = v == "device";
+			}
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -570,6 +613,7 @@ int main(int argc, char * argv[])
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
 		if (!haveFormat) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
+		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
 		const bool needsSequences = format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
@@ -577,7 +621,9 @@ int main(int argc, char * argv[])
 		std::unique_ptr<DeviceLibrary> lib;
 		if (gpu && needsSequences) lib.reset(new DeviceLibrary(device));  // before the first byte of output: no device is an error
 		stats.threads = lib ? threads : 1;
-		Out out;
+		const bool deviceText = lib && textOnDevice;
+		stats.text = deviceText ? "device" : "host";
+		Out out(!deviceText);  // --text device: the header lines wait until the table is known to be good
 		if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device
@@ -593,7 +639,7 @@ int main(int argc, char * argv[])
 				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file[name] << '\n';
 			}
 
-			DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, format, seq, loaded, out, stats);
+			DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, format, seq, loaded, out, stats, deviceText);
 		}
 		else if (format == "seq") DumpSeq(binFile, out);
 		else if (format == "group") DumpGroups(binFile, out);

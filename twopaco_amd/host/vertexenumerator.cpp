@@ -941,6 +941,12 @@ namespace TwoPaCo
 						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 					}
 
+					if (options.graphTextOnDevice)
+					{
+						WriteGraphOnDevice(options, seq, loaded, timer);
+						return;
+					}
+
 					const uint64_t events = counts[0];
 					name.resize(events); first.resize((events + 31) / 32); begin.resize(events); end.resize(events);
 					Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
@@ -958,6 +964,34 @@ namespace TwoPaCo
 				GraphFormat::CheckEventTable(table, loaded, k, threads);
 				GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
 				timer.Lap("graph formatting + writing");
+			}
+
+			// --graph-text device: the table stays where it was built.  The header lines are written here, the events' text is
+			// rendered window by window on the device and written behind them; nothing is fetched but the text itself.  The plan
+			// (and with it every refusal for want of device memory) comes before the file is created.
+			void WriteGraphOnDevice(const EnumeratorOptions & options, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
+			{
+				GraphFormat::DeviceTextInput input;
+				GraphFormat::MakeDeviceTextInput(seq, loaded, input);
+				uint64_t total = 0;
+				Check(tpc_segments_text_plan(ctx_, GraphFormat::DeviceTextFormat(options.graphFormat), input.names.data(), input.nameOffset.data(),
+					input.ambiguousLetter.empty() ? 0 : input.ambiguousLetter.data(), &total), "segments_text_plan");
+				GraphFormat::WriteGraphFileWith(options.graphFormat, seq, options.graphFile, [&](int fd, uint64_t fileOffset)
+				{
+					uint64_t written = 0;
+					Check(tpc_segments_text_write(ctx_, fd, fileOffset, 0, &written), "segments_text_write");
+					if (written != total) throw std::runtime_error("Can't write to the graph file");
+					return written;
+				});
+
+				timer.Lap("graph text on device");
+				if (std::getenv("TWOPACO_TIMING"))
+				{
+					// inside the phase above: the kernels, the helper thread's time in pwrite, this thread's waits for render + copy
+					std::cerr << "[timing]   text_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_SEGTEXT) << " ms" << std::endl;
+					std::cerr << "[timing]   text file write (helper thread): " << double(tpc_get_stat(ctx_, "text_write_us")) / 1e3 << " ms" << std::endl;
+					std::cerr << "[timing]   text render + copy waits: " << double(tpc_get_stat(ctx_, "text_wait_us")) / 1e3 << " ms" << std::endl;
+				}
 			}
 
 			void SaveFilter(const std::string & name, size_t k, size_t bits, size_t q, size_t round, size_t rounds, uint64_t low, uint64_t high, const std::vector<uint64_t> & table,

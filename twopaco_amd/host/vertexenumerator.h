@@ -67,9 +67,12 @@ namespace TwoPaCo
 		std::string graphFormat;
 		std::string graphFile;
 		bool graphPrefix;     // graphdump's --prefix
-		size_t graphThreads;  // formatting threads, 1..16
+		size_t graphThreads;  // formatting threads, 1..16 (unused by graphTextOnDevice)
+		// false: the event table is fetched and the text formatted by graphThreads host threads.  true: the text is rendered on
+		// the device and only written here (tpc_segments_text_plan / _text_write); the same bytes
+		bool graphTextOnDevice;
 		EnumeratorOptions() : pinnedSeed(false), seed(0), device(0), insertTestFirst(false), gpus(1), rccl(true), emulateRanks(false), forceSharded(false),
-			graphPrefix(false), graphThreads(16) {}
+			graphPrefix(false), graphThreads(16), graphTextOnDevice(false) {}
 	};
 
 	std::unique_ptr<VertexEnumerator> CreateEnumerator(const std::vector<std::string> & fileName,
