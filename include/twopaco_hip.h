@@ -58,7 +58,8 @@ enum {
     TPC_K_SEGMENTS = 15,    /* tpc_segments_build_*: names and first-sight bits of the compacted graph's segments, graphdump.cpp:44-113, 398-480 */
     TPC_K_SEGTEXT = 16,     /* tpc_segments_text_*: the graph text rendered from the event table (host/graphformat.h's sinks); summed over the
                                kernels since the last tpc_segments_text_plan (the plan's own included)                                    */
-    TPC_K_COUNT = 17
+    TPC_K_SKETCH = 17,      /* tpc_distinct_sketch: HyperLogLog registers of the distinct canonical (k+1)-mers (no counterpart in the reference) */
+    TPC_K_COUNT = 18
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -93,6 +94,21 @@ int tpc_seq_upload(tpc_ctx *ctx, const uint64_t *bases, const uint32_t *nmask, u
 /* Start a new enumeration over the uploaded text: forgets the junction keys, masks and round
  * state of the previous run (the reference builds a fresh VertexEnumerator per run, VE.h:122). */
 int tpc_run_begin(tpc_ctx *ctx);
+
+/* HyperLogLog registers (p = 14: 16384 one-byte registers) of the distinct canonical (k+1)-mers of the uploaded text: the edges
+ * tpc_pass1_insert puts into the filter, i.e. the one quantity the right filter size depends on (host/filterplan.h turns the
+ * registers into a count and the count into L and rounds; `twopaco -f auto`).  The reference has no counterpart: its README
+ * leaves the filter size to a rule of thumb.  Needs tpc_seq_upload only -- no tpc_set_params, L being what the caller is about
+ * to decide -- and works after tpc_set_params and after a run as well; it changes nothing a pass reads.  Every call starts from
+ * zeroed registers.  With n = k + 1 and h[0..3] = the first four outputs of splitmix64 started at state 0x5457504143 (state +=
+ * 0x9E3779B97F4A7C15, then the finaliser tpc_mix64 of csrc/tpc_device.h), every window w = T[g .. g + n) that holds no 'N'
+ * (separators included) contributes
+ *     F = XOR over t of rotl64(h[w_t], (n - 1 - t) mod 64)        R = XOR over t of rotl64(h[3 - w_t], t mod 64)  (F of the reverse complement)
+ *     x = mix64(min(F, R));  idx = x >> 50;  v = x << 14;  rank = 51 if v == 0, else clz64(v) + 1;  reg[idx] = max(reg[idx], rank)
+ * Windows with an 'N' contribute nothing (the at most two A/T dummy edges the insert adds beside an 'N' run are not counted).
+ * *n_windows (may be NULL) = the number of contributing windows.  A text shorter than n gives all-zero registers and 0.  max is
+ * order independent: the result is bit-exact.  k + 1 must fit a tile's halo (k <= 670); a larger k is refused with an error text. */
+int tpc_distinct_sketch(tpc_ctx *ctx, int k, uint8_t *registers_host /* [16384] */, uint64_t *n_windows /* may be NULL */);
 
 /* ConcurrentBitVector(2^L) construction = zero fill (concurrentbitvector.cpp:11-24, VE.h:257). */
 int tpc_filter_reset(tpc_ctx *ctx);
@@ -530,6 +546,8 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *   test_sched_cap     tests only, process-wide: rounds per segment of the split kernels' round schedule (0 = what fits in LDS)
  *   test_fail_mallocs  tests only, process-wide: the next N second-pass / output allocations fail at their first attempt, as if
  *                      the device were full (they then give the partition buffers back and try again, see "pbuf_releases")
+ *   test_sketch_grid   tests only, process-wide: workgroups of tpc_distinct_sketch's kernel (0 = a few per CU), so that a small text
+ *                      makes every workgroup stride over several tiles
  *   test_force_anyq    tests only, process-wide: 1 = the closed-form first-pass kernels that serve q = 17..64
  *                      (csrc/tpc_pass1_anyq.hip) for every q, so that they can be checked on the goldens with q <= 16
  *   part_budget_bytes  partition buffers per tile batch (0 = automatic: 40 GiB, or 60 % of the free device

@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -28,7 +28,7 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
                "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
-               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write"]
+               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write", "tpc_distinct_sketch"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -152,6 +152,7 @@ def hip():
         L.tpc_segments_text_plan.argtypes = [p, ci, p, p, p, p]
         L.tpc_segments_text_fetch.argtypes = [p, u64, u64, p]
         L.tpc_segments_text_write.argtypes = [p, ci, u64, u64, p]
+        L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
         L.tpc_get_stat.restype = i64
@@ -186,6 +187,12 @@ def host():
         L.tpch_create_enumerator_graph.restype = p
         L.tpch_create_enumerator_graph.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
                                                    ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.POINTER(p)]
+        L.tpch_create_enumerator_auto.restype = p
+        L.tpch_create_enumerator_auto.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, ctypes.c_char_p, ctypes.c_char_p, ci, u64, ci,
+                                                  ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(p)]
+        L.tpch_hll_estimate.restype = ctypes.c_double
+        L.tpch_hll_estimate.argtypes = [p, u64]
+        L.tpch_filter_plan.argtypes = [u64, ci, u64, u64, ci, p, p]
         L.tpch_graph_format.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, ctypes.c_char_p, ci, ci, u64, p, p, p, p, u64, p, ctypes.c_char_p]
         L.tpch_enumerator_free.argtypes = [p]
         L.tpch_vertices_count.restype = u64
@@ -213,6 +220,25 @@ def seed_table(q, bits, seed=None):
     if host().tpch_seed_table(0 if seed is None else seed, 0 if seed is None else 1, q, bits, t.ctypes.data) != 0:
         raise RuntimeError(host().tpch_last_error().decode())
     return t
+
+
+HLL_REGISTERS = 16384  # p = 14 (include/twopaco_hip.h: tpc_distinct_sketch)
+
+
+def hll_estimate(registers):
+    """The distinct count behind HyperLogLog registers (host/filterplan.h); no device."""
+    r = np.ascontiguousarray(registers, dtype=np.uint8)
+    return float(host().tpch_hll_estimate(r.ctypes.data, r.size))
+
+
+def filter_plan(n_distinct, q, text_length, filter_bytes_cap, rounds=0):
+    """`-f auto`'s plan (host/filterplan.h; no device): dict with L, rounds, clipped, L_fp, L_mem and false_marks (predicted false
+    marks per position).  rounds = 0: the plan chooses them."""
+    out = (ctypes.c_int * 5)()
+    fm = ctypes.c_double(0)
+    if host().tpch_filter_plan(int(n_distinct), int(q), int(text_length), int(filter_bytes_cap), int(rounds), out, ctypes.byref(fm)) != 0:
+        raise RuntimeError(host().tpch_last_error().decode())
+    return {"L": out[0], "rounds": out[1], "clipped": bool(out[2]), "L_fp": out[3], "L_mem": out[4], "false_marks": fm.value}
 
 
 TEXT_FORMATS = {"gfa1": 1, "gfa2": 2, "fasta": 3}  # TPC_TEXT_* of include/twopaco_hip.h
@@ -337,6 +363,14 @@ class Context:
 
     def run_begin(self):
         self._ck(hip().tpc_run_begin(self._h))
+
+    def distinct_sketch(self, k):
+        """(registers uint8[16384], contributing windows): the HyperLogLog sketch of the distinct canonical (k+1)-mers of the
+        uploaded text (csrc/tpc_sketch.hip).  Needs seq_upload only."""
+        reg = np.zeros(HLL_REGISTERS, dtype=np.uint8)
+        n = ctypes.c_uint64(0)
+        self._ck(hip().tpc_distinct_sketch(self._h, int(k), reg.ctypes.data, ctypes.byref(n)))
+        return reg, n.value
 
     def filter_reset(self):
         self._ck(hip().tpc_filter_reset(self._h))
@@ -739,7 +773,17 @@ class Enumerator:
         `out` is given."""
         arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
         log = ctypes.c_void_p()
-        if graph is not None:
+        if filter_bits == "auto":  # EnumeratorOptions::autoFilterSize (`twopaco -f auto`); rounds = 0: the plan chooses them too
+            if gpus > 1 or force_sharded or test_first:
+                raise ValueError("filter_bits='auto': one GPU, plain insert")
+            if graph is not None:
+                graph_out = "de_bruijn." + graph if graph_out is None else graph_out
+            elif out is None:
+                out = "de_bruijn.bin"
+            self._h = host().tpch_create_enumerator_auto(arr, len(files), k, q, rounds, threads, abundance, tmpdir.encode(), b"" if out is None else out.encode(),
+                                                         0 if seed is None else 1, 0 if seed is None else seed, device, None if graph is None else graph.encode(),
+                                                         None if graph is None else os.fsencode(graph_out), ctypes.byref(log))
+        elif graph is not None:
             if gpus > 1 or force_sharded:
                 raise ValueError("graph: one GPU only (every rank of a sharded run holds its own piece of the junction stream)")
             graph_out = "de_bruijn." + graph if graph_out is None else graph_out
@@ -749,7 +793,7 @@ class Enumerator:
                                                           1 if graph_prefix else 0, graph_threads, ctypes.byref(log))
             out = ""
         out = "de_bruijn.bin" if out is None else out
-        if graph is not None:
+        if graph is not None or filter_bits == "auto":
             pass
         elif gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
             self._h = host().tpch_create_enumerator_mgpu(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),

@@ -4,6 +4,7 @@
 //   tpc_capi_shard.hip    the filter cut by address over ranks (tpc_shard_*), mask unions
 //   tpc_capi_combine.hip  the filter replicated through set-bit lists (tpc_combine_*)
 //   tpc_capi_segments.hip the segment table of the compacted graph and its text (tpc_segments_*)
+//   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
 #include "../../include/twopaco_hip.h"

@@ -320,6 +320,7 @@ int tpc_warm_partition();
 int tpc_warm_qpartition();
 int tpc_warm_pass2();
 int tpc_warm_stream();
+extern int tpc_test_sketch_grid;     // tpc_sketch.hip: option "test_sketch_grid" (tests: workgroups of the sketch kernel, so that a small text strides over its tiles; process-wide)
 // tpc_segments.hip
 #define TPC_SEG_ERR_TEXT 256
 struct TpcSegResult { uint64_t events, segments, named, table_bytes, peak_bytes, err_slot; int err_kind; };

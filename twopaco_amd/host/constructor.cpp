@@ -1,6 +1,7 @@
 // constructor.cpp -- the `twopaco` command line, flag-compatible with the reference CLI
 // (reference src/graphconstructor/constructor.cpp:53-218): -k/--kvalue (odd, default 25),
-// -f/--filtersize xor --filtermemory (GB; bits = log2(GB*8e9) truncated, :158), -q/--hashfnumber
+// -f/--filtersize xor --filtermemory (GB; bits = log2(GB*8e9) truncated, :158; `-f auto`, not in the reference: the size from a
+// sketch of the input's distinct edges, filterplan.h), -q/--hashfnumber
 // (5), -r/--rounds (1), -t/--threads (1), -a/--abundance (UINT64_MAX), --tmpdir ("."),
 // -o/--outfile ("de_bruijn.bin"), --test, and the FASTA file names.  Extra flags that do not
 // exist in the reference: --seed S (pin the hash tables, see seed.h), --device N,
@@ -61,13 +62,15 @@ namespace
 
 	void Usage()
 	{
-		std::cout << "USAGE: twopaco {-f <integer>|--filtermemory <float>} [-k <oddc>] [-q <integer>] [-r <integer>]" << std::endl
+		std::cout << "USAGE: twopaco {-f <integer|auto>|--filtermemory <float>} [-k <oddc>] [-q <integer>] [-r <integer>]" << std::endl
 			<< "               [-t <integer>] [-a <integer>] [--tmpdir <directory name>] [-o <file name>] [--test]" << std::endl
 			<< "               [--seed <integer>] [--device <integer>] [--test-first] [--gpus <power of two>] [--no-rccl]" << std::endl
 			<< "               [--save-filter <file>] [--load-filter <file>]" << std::endl
 			<< "               [--graph <gfa1|gfa2|fasta>] [--graph-out <file name>] [--graph-prefix] [--graph-threads <integer>]" << std::endl
 			<< "               [--graph-text <host|device>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
+			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
+			<< "               (one GPU; not with --load-filter or --test)" << std::endl
 			<< "       -q: 1..64 hash functions (the reference takes any number; more than 16 run on slower closed-form kernels)" << std::endl
 			<< "       --graph: also write the compacted graph as graphdump -f <format> prints it, to --graph-out (default" << std::endl
 			<< "               de_bruijn.<format>); the junction file is then written only when -o is given.  --graph-prefix:" << std::endl
@@ -108,7 +111,7 @@ int main(int argc, char * argv[])
 	{
 		unsigned int kvalue = 25, hashFunctions = 5, rounds = 1, threads = 1;
 		size_t abundance = UINT64_MAX;
-		bool filterSizeSet = false, filterMemorySet = false, runTests = false;
+		bool filterSizeSet = false, filterMemorySet = false, runTests = false, roundsSet = false;
 		unsigned int filterSize = 32;
 		double filterMemory = 4;
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
@@ -129,10 +132,15 @@ int main(int argc, char * argv[])
 				kvalue = Parse<unsigned int>(value("(--kvalue)"), "(--kvalue)");
 				if (kvalue % 2 != 1) throw ArgError("Value '" + std::to_string(kvalue) + "' does not meet constraint: value of K must be odd", "(--kvalue)");
 			}
-			else if (Match(a, "f", "filtersize")) { filterSize = Parse<unsigned int>(value("(--filtersize)"), "(--filtersize)"); filterSizeSet = true; }
+			else if (Match(a, "f", "filtersize"))
+			{
+				const std::string v = value("(--filtersize)");
+				if (v == "auto") options.autoFilterSize = true; else filterSize = Parse<unsigned int>(v, "(--filtersize)");
+				filterSizeSet = true;
+			}
 			else if (Match(a, 0, "filtermemory")) { filterMemory = std::atof(value("(--filtermemory)").c_str()); filterMemorySet = true; }
 			else if (Match(a, "q", "hashfnumber")) hashFunctions = Parse<unsigned int>(value("(--hashfnumber)"), "(--hashfnumber)");
-			else if (Match(a, "r", "rounds")) rounds = Parse<unsigned int>(value("(--rounds)"), "(--rounds)");
+			else if (Match(a, "r", "rounds")) { rounds = Parse<unsigned int>(value("(--rounds)"), "(--rounds)"); roundsSet = true; }
 			else if (Match(a, "t", "threads")) threads = Parse<unsigned int>(value("(--threads)"), "(--threads)");
 			else if (Match(a, "a", "abundance")) abundance = Parse<size_t>(value("(--abundance)"), "(--abundance)");
 			else if (Match(a, 0, "tmpdir")) tmpDirName = value("(--tmpdir)");
@@ -187,6 +195,15 @@ int main(int argc, char * argv[])
 		if (fileName.empty())
 		{
 			throw ArgError("Required argument missing: filenames", "(filenames)");
+		}
+
+		if (options.autoFilterSize)
+		{
+			if (options.gpus > 1) throw ArgError("The filter size is chosen on one GPU only (every rank holds a chunk of the text, and their sketches are not merged): not with --gpus above 1", "(--filtersize)");
+			if (!options.loadFilter.empty()) throw ArgError("A Bloom filter checkpoint fixes the filter size: not with --load-filter", "(--filtersize)");
+			if (runTests) throw ArgError("The self-test draws its own filter sizes: not with --test", "(--filtersize)");
+			options.autoRounds = !roundsSet;
+			optionsSet = true;
 		}
 
 		if (!options.graphFormat.empty())

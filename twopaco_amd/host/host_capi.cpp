@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "filterplan.h"
 #include "graphformat.h"
 #include "seed.h"
 #include "streamfastaparser.h"
@@ -38,6 +39,18 @@ extern "C"
 			return 0;
 		}
 		catch (std::exception & e) { g_error = e.what(); return -1; }
+	}
+
+	// ---- `-f auto` (filterplan.h): the count behind 16384 HyperLogLog registers (tpc_distinct_sketch), and the filter size and
+	// rounds for a count.  No device.  out[5] = L, rounds, clipped, L_fp, L_mem; *falseMarks = predicted false marks per position.
+	double tpch_hll_estimate(const uint8_t * registers, uint64_t m) { return TwoPaCo::HllEstimate(registers, size_t(m)); }
+	int tpch_filter_plan(uint64_t distinctEdges, int q, uint64_t textLength, uint64_t filterBytesCap, int userRounds, int * out, double * falseMarks)
+	{
+		if (q < 1 || userRounds < 0 || !out) { g_error = "tpch_filter_plan: bad arguments"; return -1; }
+		const TwoPaCo::FilterPlan plan = TwoPaCo::PlanFilter(distinctEdges, unsigned(q), textLength, filterBytesCap, unsigned(userRounds));
+		out[0] = int(plan.filterBits); out[1] = int(plan.rounds); out[2] = plan.clipped ? 1 : 0; out[3] = int(plan.bitsForTarget); out[4] = int(plan.bitsForMemory);
+		if (falseMarks) *falseMarks = plan.falseMarks;
+		return 0;
 	}
 
 	// ---- packed text handle -------------------------------------------------------------
@@ -90,6 +103,36 @@ extern "C"
 			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
 			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, ss, opt);
+			if (log) *log = Dup(ss.str());
+			return e.release();
+		}
+		catch (std::exception & e)
+		{
+			g_error = e.what();
+			if (log) *log = Dup(ss.str());
+			return 0;
+		}
+	}
+
+	// the same with EnumeratorOptions::autoFilterSize (`-f auto`): the filter size comes from the device's sketch of the distinct
+	// edges; rounds = 0 lets the plan choose them too.  graphFormat may be NULL or empty (no graph)
+	void * tpch_create_enumerator_auto(const char ** files, int nfiles, uint64_t k, uint64_t q, uint64_t rounds,
+		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
+		const char * graphFormat, const char * graphFile, char ** log)
+	{
+		std::stringstream ss;
+		try
+		{
+			std::vector<std::string> names(files, files + nfiles);
+			TwoPaCo::EnumeratorOptions opt;
+			opt.pinnedSeed = pinned != 0;
+			opt.seed = seed;
+			opt.device = device;
+			opt.autoFilterSize = true;
+			opt.autoRounds = rounds == 0;
+			opt.graphFormat = graphFormat ? graphFormat : "";
+			opt.graphFile = graphFile ? graphFile : "";
+			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, 0, q, rounds == 0 ? 1 : rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
 			if (log) *log = Dup(ss.str());
 			return e.release();
 		}

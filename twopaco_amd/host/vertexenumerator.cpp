@@ -16,6 +16,7 @@
 #include <stdexcept>
 
 #include "../../include/twopaco_hip.h"
+#include "filterplan.h"
 #include "graphformat.h"
 #include "multigpu.h"
 #include "streamfastaparser.h"
@@ -190,6 +191,74 @@ namespace TwoPaCo
 				std::ostream & logStream,
 				const EnumeratorOptions & options)
 			{
+				// -f auto (EnumeratorOptions::autoFilterSize): the filter size is the one thing that cannot be prepared beside the parser,
+				// so this comes first -- context, parse, upload, the device's sketch of the distinct edges (tpc_distinct_sketch needs the
+				// text alone), the plan (filterplan.h) -- and everything below runs as if the size had been given, on the context and the
+				// text that are already there: the hash tables (they depend on L), tpc_set_params and tpc_reserve follow the upload.
+				PackedText text;
+				bool textPacked = false, textUploaded = false;
+				if (options.autoFilterSize)
+				{
+					if (options.gpus > 1 || options.forceSharded) throw std::runtime_error("The filter size is chosen on one GPU only: every rank of a sharded run holds a chunk of the text, and their sketches are not merged");
+					if (!options.loadFilter.empty()) throw std::runtime_error("A Bloom filter checkpoint fixes the filter size: it cannot be chosen");
+					if (!options.autoRounds && rounds < 1) throw std::runtime_error("The number of rounds must be positive");
+					if ((vertexLength + 4 + 31) / 32 >= 20)
+					{
+						throw std::runtime_error("The value of K is too big. Please refer to documentaion how to increase the max supported value of K.");
+					}
+
+					PhaseTimer autoTimer;
+					std::string contextError;
+					std::thread context([&]()
+					{
+						if (tpc_ctx_create(options.device, &ctx_) != 0) contextError = "Can't create a GPU context (no MI355X visible?)";
+					});
+					try
+					{
+						PackFastaFiles(fileName, threads, text);
+					}
+					catch (...)
+					{
+						context.join();
+						throw;
+					}
+
+					context.join();
+					if (!contextError.empty()) throw std::runtime_error(contextError);
+					textPacked = true;
+					autoTimer.Lap("auto: context + parse + pack FASTA");
+					bool dispatched = false;
+					for (uint64_t len : text.recLength) dispatched = dispatched || len >= vertexLength;
+					double estimate = 0;
+					if (dispatched)
+					{
+						Check(tpc_seq_upload(ctx_, text.bases.data(), text.nmask.data(), text.length), "seq_upload");
+						textUploaded = true;
+						autoTimer.Lap("auto: upload");
+						std::vector<uint8_t> registers(HLL_REGISTERS);
+						Check(tpc_distinct_sketch(ctx_, int(vertexLength), registers.data(), 0), "distinct_sketch");
+						estimate = HllEstimate(registers.data(), registers.size());
+						if (autoTimer.on) std::cerr << "[timing] edge sketch: " << tpc_kernel_ms(ctx_, TPC_K_SKETCH) << " ms" << std::endl;
+						autoTimer.Lap("auto: sketch call (kernel, registers to the host, estimate)");
+					}
+
+					// half of what the device has free now: room for the partition buffers (they batch down to what is left); admits f = 40 here
+					uint64_t cap = uint64_t(std::max<int64_t>(0, tpc_get_stat(ctx_, "device_free_bytes"))) / 2;
+					if (const char * capEnv = std::getenv("TWOPACO_FILTER_CAP_BYTES")) cap = std::strtoull(capEnv, 0, 0);
+					const FilterPlan plan = PlanFilter(uint64_t(estimate + 0.5), unsigned(hashFunctions), text.length, cap, options.autoRounds ? 0u : unsigned(rounds));
+					filterSize = plan.filterBits;
+					rounds = plan.rounds;
+					logStream << "Distinct edges (estimate) = " << uint64_t(estimate + 0.5) << std::endl;
+					logStream << "Filter size (auto) = " << filterSize << std::endl;
+					if (options.autoRounds) logStream << "Rounds (auto) = " << rounds << std::endl;
+					logStream << "Predicted false marks per position = " << plan.falseMarks << std::endl;
+					if (plan.clipped)
+					{
+						logStream << "Warning: the filter is clipped by memory at " << filterSize << " bits of address and " << rounds
+							<< " rounds do not make up for it: expect more false candidate marks than the target of " << FILTER_PLAN_TARGET << " per position" << std::endl;
+					}
+				}
+
 				if (filterSize < 2 || filterSize > 62)
 				{
 					throw std::runtime_error("Unsupported filter size");
@@ -332,7 +401,7 @@ namespace TwoPaCo
 					try
 					{
 						PhaseTimer setupTimer;
-						if (tpc_ctx_create(options.device, &ctx_) != 0)
+						if (!ctx_ && tpc_ctx_create(options.device, &ctx_) != 0)  // (-f auto made it already)
 						{
 							throw std::runtime_error("Can't create a GPU context (no MI355X visible?)");
 						}
@@ -384,10 +453,9 @@ namespace TwoPaCo
 					}
 				});
 
-				PackedText text;
 				try
 				{
-					PackFastaFiles(fileName, threads, text);
+					if (!textPacked) PackFastaFiles(fileName, threads, text);
 				}
 				catch (...)
 				{
@@ -446,7 +514,7 @@ namespace TwoPaCo
 				// empty task stream, prints zero counters and leaves an empty output file.  Same here, without device work.
 				const bool nothing = dispStart.empty();
 				{
-					const int rcUpload = nothing ? 0 : tpc_seq_upload(ctx_, text.bases.data(), text.nmask.data(), text.length);
+					const int rcUpload = nothing || textUploaded ? 0 : tpc_seq_upload(ctx_, text.bases.data(), text.nmask.data(), text.length);
 					if (warm.joinable()) warm.join();  // (letting the rounds start while the last objects load measured the same)
 					Check(rcUpload, "seq_upload");
 				}

@@ -71,8 +71,16 @@ namespace TwoPaCo
 		// false: the event table is fetched and the text formatted by graphThreads host threads.  true: the text is rendered on
 		// the device and only written here (tpc_segments_text_plan / _text_write); the same bytes
 		bool graphTextOnDevice;
+		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
+		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
+		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
+		// filter allocated.  autoRounds: the plan may choose the rounds too (the `rounds` argument is ignored); otherwise the
+		// caller's rounds enter the plan.  One GPU, no loadFilter.  The log gains "Distinct edges (estimate) = ", "Filter size
+		// (auto) = ", "Rounds (auto) = " (autoRounds only) and "Predicted false marks per position = " before "Threads = ".
+		bool autoFilterSize;
+		bool autoRounds;
 		EnumeratorOptions() : pinnedSeed(false), seed(0), device(0), insertTestFirst(false), gpus(1), rccl(true), emulateRanks(false), forceSharded(false),
-			graphPrefix(false), graphThreads(16), graphTextOnDevice(false) {}
+			graphPrefix(false), graphThreads(16), graphTextOnDevice(false), autoFilterSize(false), autoRounds(false) {}
 	};
 
 	std::unique_ptr<VertexEnumerator> CreateEnumerator(const std::vector<std::string> & fileName,
