@@ -59,7 +59,8 @@ enum {
     TPC_K_SEGTEXT = 16,     /* tpc_segments_text_*: the graph text rendered from the event table (host/graphformat.h's sinks); summed over the
                                kernels since the last tpc_segments_text_plan (the plan's own included)                                    */
     TPC_K_SKETCH = 17,      /* tpc_distinct_sketch: HyperLogLog registers of the distinct canonical (k+1)-mers (no counterpart in the reference) */
-    TPC_K_COUNT = 18
+    TPC_K_COLORS = 18,      /* tpc_segments_colors_build: rows, counts and presence bits of the segment colour table (no counterpart in the reference) */
+    TPC_K_COUNT = 19
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -515,6 +516,37 @@ int tpc_segments_text_plan(tpc_ctx *ctx, int format, const char *seq_names, cons
                            const uint8_t *amb_letter /* [n_amb], may be NULL when n_amb = 0 */, uint64_t *total_bytes);
 int tpc_segments_text_fetch(tpc_ctx *ctx, uint64_t byte0, uint64_t n_bytes, void *dst_host);
 int tpc_segments_text_write(tpc_ctx *ctx, int fd, uint64_t file_offset, uint64_t window_bytes /* 0 = library's choice */, uint64_t *written);
+
+/* The SEGMENT COLOUR TABLE (csrc/tpc_colors.hip): for every segment of the compacted graph, which colours hold it and how often.
+ * No counterpart in the reference; its gfa1 defines the table (an S line with a body is a row, a C line one occurrence of a row in
+ * a sequence), and ComputeColors of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The
+ * caller maps every input sequence to a colour, color_of_seq[s] in [0, n_colors) for s < n_rec of the build (one colour per file,
+ * per sequence, or any other map).  One ROW per segment, that is per event whose first bit is set, in event order -- the order of
+ * the body-carrying S lines of gfa1; every 'N'-named event (names >= 2^34) is a row of its own.  For row r with first event e0:
+ *   first_event[r]  e0 (name = |name[e0]| and length = end[e0] - begin[e0] + k come from the fetches of the group above)
+ *   occurrences[r]  events e with |name[e]| == |name[e0]|
+ *   forward[r]      those of them with name[e] > 0
+ *   presence[r]     W = ceil(n_colors / 32) words, bit c % 32 of word c / 32 set iff such an event lies in a sequence of colour c
+ *   n_colors[r]     popcount of presence[r]
+ * and the histogram: segments[n] rows with n_colors == n and bases[n] the 64-bit sum of their lengths, n = 0 .. n_colors (bin 0
+ * stays empty).  Separate from the build and opt-in: a context that never calls it holds none of this, and tpc_segments_counts
+ * reports what it reported before.
+ *   tpc_segments_colors_build           over the table of the last tpc_segments_build_*.  Refused with an error text: no table, a
+ *                                       table whose tpc_segments_error kind is not TPC_SEG_OK, n_colors == 0 or above 2^31, a colour >= n_colors,
+ *                                       buffers beyond the free device memory.  Memory: 16 B + 4 W B per row and 16 B per histogram
+ *                                       bin, kept until the next segment build or colour build; during the call also the first-sight
+ *                                       table again (counts[3]), 4 B / event and 4 B / sequence.  Kernel time: TPC_K_COLORS.
+ *   tpc_segments_colors_info            info[0] rows, [1] colours, [2] W
+ *   tpc_segments_colors_fetch_rows      first_event / occurrences / forward / n_colors of rows [r0, r0 + n) to the host
+ *   tpc_segments_colors_fetch_presence  the n x W presence words of rows [r0, r0 + n), row-major
+ *   tpc_segments_colors_fetch_hist      segments[0 .. n_colors] and bases[0 .. n_colors]
+ * A range outside the table is refused with an error text. */
+int tpc_segments_colors_build(tpc_ctx *ctx, const uint32_t *color_of_seq /* [n_rec] */, uint32_t n_colors);
+int tpc_segments_colors_info(tpc_ctx *ctx, uint64_t *info /* [3] */);
+int tpc_segments_colors_fetch_rows(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *first_event_host, uint32_t *occurrences_host, uint32_t *forward_host,
+                                   uint32_t *n_colors_host);
+int tpc_segments_colors_fetch_presence(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *words_host /* [n x W] */);
+int tpc_segments_colors_fetch_hist(tpc_ctx *ctx, uint64_t *segments_host /* [n_colors + 1] */, uint64_t *bases_host /* [n_colors + 1] */);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

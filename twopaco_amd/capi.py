@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -28,7 +28,8 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_shard_plan_both", "tpc_shard_hash_begin", "tpc_shard_hash_end", "tpc_shard_apply_inplace", "tpc_shard_survivors_home", "tpc_shard_verify_send", "tpc_shard_finish", "tpc_shard_verify_local", "tpc_shard_periodic_copy", "tpc_periodic_download",
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
                "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
-               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write", "tpc_distinct_sketch"]
+               "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write", "tpc_distinct_sketch",
+               "tpc_segments_colors_build", "tpc_segments_colors_info", "tpc_segments_colors_fetch_rows", "tpc_segments_colors_fetch_presence", "tpc_segments_colors_fetch_hist"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -152,6 +153,11 @@ def hip():
         L.tpc_segments_text_plan.argtypes = [p, ci, p, p, p, p]
         L.tpc_segments_text_fetch.argtypes = [p, u64, u64, p]
         L.tpc_segments_text_write.argtypes = [p, ci, u64, u64, p]
+        L.tpc_segments_colors_build.argtypes = [p, p, u32]
+        L.tpc_segments_colors_info.argtypes = [p, p]
+        L.tpc_segments_colors_fetch_rows.argtypes = [p, u64, u64, p, p, p, p]
+        L.tpc_segments_colors_fetch_presence.argtypes = [p, u64, u64, p]
+        L.tpc_segments_colors_fetch_hist.argtypes = [p, p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -187,6 +193,10 @@ def host():
         L.tpch_create_enumerator_graph.restype = p
         L.tpch_create_enumerator_graph.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
                                                    ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.POINTER(p)]
+        L.tpch_create_enumerator_colors.restype = p
+        L.tpch_create_enumerator_colors.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
+                                                    ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.c_char_p, ctypes.c_char_p,
+                                                    ctypes.POINTER(p)]
         L.tpch_create_enumerator_auto.restype = p
         L.tpch_create_enumerator_auto.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, ctypes.c_char_p, ctypes.c_char_p, ci, u64, ci,
                                                   ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(p)]
@@ -576,6 +586,41 @@ class Context:
         self._ck(hip().tpc_segments_text_write(self._h, fd, file_offset, window_bytes, ctypes.byref(written)))
         return written.value
 
+    def segments_colors_build(self, color_of_seq, n_colors):
+        """The segment colour table (csrc/tpc_colors.hip) over the table of the last segments_build, whose error must be None:
+        color_of_seq[s] in [0, n_colors) for every sequence of that build.  Returns segments_colors_info()."""
+        col = np.ascontiguousarray(color_of_seq, dtype=np.uint32)
+        self._ck(hip().tpc_segments_colors_build(self._h, col.ctypes.data if col.size else None, n_colors))
+        return self.segments_colors_info()
+
+    def segments_colors_info(self):
+        """dict: rows (segments), colors, words (uint32 of presence per row)."""
+        c = np.zeros(3, dtype=np.uint64)
+        self._ck(hip().tpc_segments_colors_info(self._h, c.ctypes.data))
+        return dict(zip(("rows", "colors", "words"), (int(x) for x in c)))
+
+    def segments_colors_fetch_rows(self, r0=0, n=None):
+        """(first_event, occurrences, forward, n_colors) of rows [r0, r0 + n) as uint32; n = None: to the last row."""
+        n = self.segments_colors_info()["rows"] - r0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(4)]
+        self._ck(hip().tpc_segments_colors_fetch_rows(self._h, r0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_colors_fetch_presence(self, r0=0, n=None):
+        """The presence words of rows [r0, r0 + n) as uint32 [n, words]: bit c % 32 of word c // 32 is colour c."""
+        info = self.segments_colors_info()
+        n = info["rows"] - r0 if n is None else n
+        out = np.zeros((max(n, 0), info["words"]), dtype=np.uint32)
+        self._ck(hip().tpc_segments_colors_fetch_presence(self._h, r0, n, out.ctypes.data))
+        return out
+
+    def segments_colors_fetch_hist(self):
+        """(segments, bases) as uint64 [colors + 1]: rows with that many colours and the sum of their lengths."""
+        bins = self.segments_colors_info()["colors"] + 1
+        seg, bases = np.zeros(bins, dtype=np.uint64), np.zeros(bins, dtype=np.uint64)
+        self._ck(hip().tpc_segments_colors_fetch_hist(self._h, seg.ctypes.data, bases.ctypes.data))
+        return seg, bases
+
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))
 
@@ -767,13 +812,27 @@ class Enumerator:
 
     def __init__(self, files, k, filter_bits, q=5, rounds=1, threads=1, abundance=(1 << 64) - 1, tmpdir=".",
                  out=None, seed=None, device=0, test_first=False, gpus=1, rccl=True, emulate_ranks=False, force_sharded=False,
-                 graph=None, graph_out=None, graph_prefix=False, graph_threads=16):
+                 graph=None, graph_out=None, graph_prefix=False, graph_threads=16, colors=None, colors_out=None):
         """out: the junction stream's file, default de_bruijn.bin.  graph = gfa1 | gfa2 | fasta: `twopaco --graph` -- the
         compacted graph's text goes to graph_out (default de_bruijn.<graph>) and the junction stream is written only when
-        `out` is given."""
+        `out` is given.  colors = file | sequence: `twopaco --colors` -- the segment colour table goes to colors_out (default
+        de_bruijn.colors.tsv); combines with graph and out."""
         arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
         log = ctypes.c_void_p()
-        if filter_bits == "auto":  # EnumeratorOptions::autoFilterSize (`twopaco -f auto`); rounds = 0: the plan chooses them too
+        if colors is not None:
+            if filter_bits == "auto" or gpus > 1 or force_sharded:
+                raise ValueError("colors: one GPU and a given filter size")
+            if graph is not None:
+                graph_out = "de_bruijn." + graph if graph_out is None else graph_out
+            elif out is None:
+                out = "de_bruijn.bin"
+            colors_out = "de_bruijn.colors.tsv" if colors_out is None else colors_out
+            self._h = host().tpch_create_enumerator_colors(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),
+                                                           b"" if out is None else out.encode(), 0 if seed is None else 1, 0 if seed is None else seed,
+                                                           device, 1 if test_first else 0, None if graph is None else graph.encode(),
+                                                           None if graph is None else os.fsencode(graph_out), 1 if graph_prefix else 0, graph_threads,
+                                                           colors.encode(), os.fsencode(colors_out), ctypes.byref(log))
+        elif filter_bits == "auto":  # EnumeratorOptions::autoFilterSize (`twopaco -f auto`); rounds = 0: the plan chooses them too
             if gpus > 1 or force_sharded or test_first:
                 raise ValueError("filter_bits='auto': one GPU, plain insert")
             if graph is not None:
@@ -793,7 +852,7 @@ class Enumerator:
                                                           1 if graph_prefix else 0, graph_threads, ctypes.byref(log))
             out = ""
         out = "de_bruijn.bin" if out is None else out
-        if graph is not None or filter_bits == "auto":
+        if graph is not None or filter_bits == "auto" or colors is not None:
             pass
         elif gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
             self._h = host().tpch_create_enumerator_mgpu(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),

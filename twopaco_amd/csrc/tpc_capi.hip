@@ -336,6 +336,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
                      c->seg_rec, c->seg_amb, c->text_plan.off, c->text_plan.piece, c->text_names, c->text_win };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     stream_part_release(c);
+    colors_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);

@@ -4,6 +4,7 @@
 //   tpc_capi_shard.hip    the filter cut by address over ranks (tpc_shard_*), mask unions
 //   tpc_capi_combine.hip  the filter replicated through set-bit lists (tpc_combine_*)
 //   tpc_capi_segments.hip the segment table of the compacted graph and its text (tpc_segments_*)
+//   tpc_colors.hip        the segment colour table (tpc_segments_colors_*), kernels and entry points
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -111,6 +112,13 @@ struct tpc_ctx {
     uint64_t text_total = 0;
     double text_ms = 0;               // TPC_K_SEGTEXT: kernels since the last plan
     int64_t text_write_us = 0, text_wait_us = 0, text_window_bytes = 0;  // of the last tpc_segments_text_write (tpc_get_stat)
+    // segment colour table (tpc_segments_colors_*, tpc_colors.hip) of the last tpc_segments_colors_build; a new segment build drops it
+    uint32_t *col_rows = nullptr;            // device, [4][col_n_rows]: first event, occurrences, forward, n_colors
+    uint32_t *col_presence = nullptr;        // device, [col_n_rows][col_words]
+    unsigned long long *col_hist = nullptr;  // device, [2][col_n_colors + 1]: segments, bases
+    uint64_t col_n_rows = 0;
+    uint32_t col_n_colors = 0, col_words = 0;
+    bool col_valid = false;
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors
@@ -222,6 +230,7 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
+void colors_drop(tpc_ctx *c);           // tpc_colors.hip
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -13,7 +13,11 @@
 // --graph gfa1|gfa2|fasta [--graph-out F] [--graph-prefix] [--graph-threads N] [--graph-text host|device]: the compacted graph as text from this process,
 // byte for byte what `graphdump -f <format> [--prefix]` prints for the junction stream of the same command (graphformat.h; the
 // stream stays on the device and the junction file is written only when -o is given as well; one GPU; --graph-text device renders
-// the text on the device too, csrc/tpc_segtext.hip, instead of fetching the event table and formatting it here).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// the text on the device too, csrc/tpc_segtext.hip, instead of fetching the event table and formatting it here);
+// --colors file|sequence [--colors-out F]: the segment colour table of the same graph -- which input files, or sequences, hold
+// each segment, how often, on which strand -- as TSV, byte for byte what `graphdump --colors` writes for the junction stream of
+// the same command (csrc/tpc_colors.hip groups the events on the device; combines with --graph and -o, the segment table is
+// built once; one GPU).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -68,6 +72,7 @@ namespace
 			<< "               [--save-filter <file>] [--load-filter <file>]" << std::endl
 			<< "               [--graph <gfa1|gfa2|fasta>] [--graph-out <file name>] [--graph-prefix] [--graph-threads <integer>]" << std::endl
 			<< "               [--graph-text <host|device>]" << std::endl
+			<< "               [--colors <file|sequence>] [--colors-out <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -76,7 +81,11 @@ namespace
 			<< "               de_bruijn.<format>); the junction file is then written only when -o is given.  --graph-prefix:" << std::endl
 			<< "               graphdump's --prefix.  --graph-threads: formatting threads (1..16, default 16).  One GPU only." << std::endl
 			<< "               --graph-text: host (default) formats the text with the threads above; device renders the same bytes" << std::endl
-			<< "               on the GPU, the host only writes them (--graph-threads is then unused)" << std::endl;
+			<< "               on the GPU, the host only writes them (--graph-threads is then unused)" << std::endl
+			<< "       --colors: also write the segment colour table of the graph as TSV to --colors-out (default de_bruijn.colors.tsv):" << std::endl
+			<< "               per segment its length, occurrences, forward occurrences, number of colours and presence bits, a colour" << std::endl
+			<< "               being the c-th input file or the c-th sequence; then the histogram of segments by number of colours." << std::endl
+			<< "               Combines with --graph and -o.  One GPU only." << std::endl;
 	}
 }
 
@@ -117,7 +126,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -181,6 +190,17 @@ int main(int argc, char * argv[])
 				options.graphTextOnDevice = v == "device";
 				graphTextSet = true;
 			}
+			else if (Match(a, 0, "colors"))
+			{
+				options.colorsBy = value("(--colors)");
+				if (options.colorsBy != "file" && options.colorsBy != "sequence")
+				{
+					throw ArgError("Value '" + options.colorsBy + "' does not meet constraint: file|sequence", "(--colors)");
+				}
+
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "colors-out")) { options.colorsFile = value("(--colors-out)"); colorsOutSet = true; }
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -215,6 +235,16 @@ int main(int argc, char * argv[])
 		else if (graphOutSet || options.graphPrefix || graphTextSet)
 		{
 			throw ArgError("This argument needs --graph <gfa1|gfa2|fasta>", graphOutSet ? "(--graph-out)" : options.graphPrefix ? "(--graph-prefix)" : "(--graph-text)");
+		}
+
+		if (!options.colorsBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The colour table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--colors)");
+			if (!colorsOutSet) options.colorsFile = "de_bruijn.colors.tsv";
+		}
+		else if (colorsOutSet)
+		{
+			throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
 		}
 
 		if (runTests)

@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <unordered_map>
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -67,6 +68,7 @@ namespace TwoPaCo
 				{
 					seq.name.push_back(file[f].name[r]);
 					seq.file[file[f].name[r]] = fasta[f];
+					seq.fileIndex.push_back(uint32_t(f));
 					seq.length.push_back(file[f].body[r].size());
 					loaded.body.push_back(std::string());
 					loaded.body.back().swap(file[f].body[r]);
@@ -362,6 +364,130 @@ namespace TwoPaCo
 				if (fd >= 0) ::close(fd);
 				::unlink(outPath.c_str());
 				throw;
+			}
+		}
+
+		void MakeColorMap(const InputSequences & seq, const std::vector<std::string> & fasta, bool bySequence, ColorMap & out)
+		{
+			if (seq.fileIndex.size() != seq.name.size()) throw std::runtime_error("colour table: the file of every sequence is required");
+			out.bySequence = bySequence;
+			out.colorOfSequence.clear();
+			out.label.clear();
+			for (size_t s = 0; s < seq.name.size(); s++)
+			{
+				out.colorOfSequence.push_back(bySequence ? uint32_t(s) : seq.fileIndex[s]);
+				if (bySequence) out.label.push_back(std::to_string(s + 1) + "\t" + fasta[seq.fileIndex[s]]);
+			}
+
+			if (!bySequence) out.label = fasta;
+		}
+
+		void ComputeColors(const EventTable & t, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t colors, ColorTable & out)
+		{
+			if (colors == 0) throw std::runtime_error("colour table: at least one colour is required");
+			if (colorOfSequence.size() != t.sequences) throw std::runtime_error("colour table: the colour of every sequence is required");
+			for (uint32_t c : colorOfSequence)
+			{
+				if (c >= colors) throw std::runtime_error("colour table: a sequence has the colour " + std::to_string(c) + ", there are " + std::to_string(colors) + " colours");
+			}
+
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			out = ColorTable();
+			out.colors = colors;
+			const size_t words = out.Words();
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			size_t sequence = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+				const int64_t name = Magnitude(t.name[e]);
+				uint32_t row = 0;
+				std::unordered_map<int64_t, uint32_t>::const_iterator seen = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				if (seen == rowOf.end())
+				{
+					row = uint32_t(out.firstEvent.size());
+					if (name < FRESH) rowOf[name] = row;
+					out.firstEvent.push_back(uint32_t(e));
+					out.occurrences.push_back(0);
+					out.forward.push_back(0);
+					out.presence.resize(out.presence.size() + words, 0);
+				}
+				else row = seen->second;
+
+				const uint32_t c = colorOfSequence[sequence];
+				out.occurrences[row] += 1;
+				if (t.name[e] > 0) out.forward[row] += 1;
+				out.presence[size_t(row) * words + (c >> 5)] |= uint32_t(1) << (c & 31);
+			}
+
+			out.histSegments.assign(colors + 1, 0);
+			out.histBases.assign(colors + 1, 0);
+			for (size_t r = 0; r < out.Rows(); r++)
+			{
+				uint32_t n = 0;
+				for (size_t w = 0; w < words; w++) n += uint32_t(__builtin_popcount(out.presence[r * words + w]));
+				out.nColors.push_back(n);
+				const uint32_t e0 = out.firstEvent[r];
+				out.histSegments[n] += 1;
+				out.histBases[n] += uint64_t(t.end[e0]) - t.begin[e0] + k;
+			}
+		}
+
+		void WriteColors(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, const std::string & path)
+		{
+			const size_t rows = colors.Rows(), words = colors.Words();
+			if (colors.occurrences.size() != rows || colors.forward.size() != rows || colors.nColors.size() != rows || colors.presence.size() != rows * words ||
+				colors.histSegments.size() != colors.colors + 1 || colors.histBases.size() != colors.colors + 1 || map.label.size() != colors.colors)
+			{
+				throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			}
+
+			for (uint32_t e0 : colors.firstEvent)
+			{
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+			}
+
+			std::FILE * f = path.empty() ? stdout : std::fopen(path.c_str(), "wb");
+			if (!f) throw std::runtime_error("Can't create the colour table " + path);
+			std::string buf;
+			bool good = true;
+			auto flush = [&]() { good = good && std::fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); };
+			buf += "#twopaco-colors\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(colors.colors) +
+				"\tsegments=" + std::to_string(rows) + "\tevents=" + std::to_string(t.events) + "\n";
+			for (uint64_t c = 0; c < colors.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+			const size_t digits = size_t((colors.colors + 3) / 4);
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t e0 = colors.firstEvent[r];
+				buf += std::to_string(static_cast<long long>(Magnitude(t.name[e0])));
+				buf += '\t';
+				buf += std::to_string(static_cast<unsigned long long>(uint64_t(t.end[e0]) - t.begin[e0] + k));
+				buf += '\t';
+				buf += std::to_string(colors.occurrences[r]);
+				buf += '\t';
+				buf += std::to_string(colors.forward[r]);
+				buf += '\t';
+				buf += std::to_string(colors.nColors[r]);
+				buf += '\t';
+				const uint32_t * p = &colors.presence[r * words];
+				for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(p[j >> 3] >> (4 * (j & 7))) & 15u];
+				buf += '\n';
+				if (buf.size() > (size_t(1) << 20)) flush();
+			}
+
+			for (uint64_t n = 1; n <= colors.colors; n++)
+			{
+				if (colors.histSegments[n]) buf += "#hist\t" + std::to_string(n) + "\t" + std::to_string(colors.histSegments[n]) + "\t" + std::to_string(colors.histBases[n]) + "\n";
+			}
+
+			flush();
+			good = good && std::fflush(f) == 0;
+			if (f != stdout) good = (std::fclose(f) == 0) && good;
+			if (!good)
+			{
+				if (f != stdout) ::unlink(path.c_str());
+				throw std::runtime_error("Can't write the colour table");
 			}
 		}
 

@@ -74,6 +74,7 @@ namespace TwoPaCo
 			std::vector<std::string> name;
 			std::vector<uint64_t> length;
 			std::map<std::string, std::string> file;
+			std::vector<uint32_t> fileIndex;   // per sequence: the index of its file among the files given (the colour table's by=file)
 		};
 
 		// What the serial walk reads record by record -- names, lengths, the letters as the parser upper-cases them -- read
@@ -312,6 +313,42 @@ namespace TwoPaCo
 
 		// TPC_TEXT_GFA1 / _GFA2 / _FASTA of include/twopaco_hip.h
 		inline int DeviceTextFormat(const std::string & format) { return format == "gfa1" ? 1 : format == "gfa2" ? 2 : format == "fasta" ? 3 : 0; }
+
+		// ---------------------------------------------------------------------------------------- the segment colour table
+		// Which colours hold each segment, how often, on which strand (include/twopaco_hip.h, the tpc_segments_colors_* group, defines
+		// rows, columns and the histogram).  The arrays come from ComputeColors below -- the serial statement of the table -- or from
+		// the device (csrc/tpc_colors.hip); WriteColors prints either as the same bytes.
+		struct ColorTable
+		{
+			uint64_t colors;
+			std::vector<uint32_t> firstEvent, occurrences, forward, nColors;   // [rows]
+			std::vector<uint32_t> presence;                                    // [rows][Words()], bit c % 32 of word c / 32
+			std::vector<uint64_t> histSegments, histBases;                     // [colors + 1]
+			ColorTable() : colors(0) {}
+			size_t Rows() const { return firstEvent.size(); }
+			size_t Words() const { return size_t((colors + 31) / 32); }
+		};
+
+		// The colour of every sequence and the label of every colour: one colour per file (label: the file name as given) or one
+		// per sequence (label: the 1-based sequence number, a tab, its file name).
+		struct ColorMap
+		{
+			bool bySequence;
+			std::vector<uint32_t> colorOfSequence;
+			std::vector<std::string> label;
+			ColorMap() : bySequence(false) {}
+		};
+
+		void MakeColorMap(const InputSequences & seq, const std::vector<std::string> & fasta, bool bySequence, ColorMap & out);
+
+		// One pass over the events with a hash map from |name| to its row.  The table must be one whose walk did not fail; every
+		// event's sequence needs a colour below `colors` (std::runtime_error otherwise).
+		void ComputeColors(const EventTable & table, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t colors, ColorTable & out);
+
+		// The TSV text: "#twopaco-colors" header, one "#color" line per colour, one line per row (name, length, occurrences, forward,
+		// n_colors, presence as ceil(colors / 4) hex digits, digit j from the left = colours 4j .. 4j + 3, colour 4j + b = 1 << b),
+		// "#hist" lines of the non-empty bins.  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteColors(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const std::string & path);
 
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails).
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

@@ -27,6 +27,12 @@
 // there (csrc/tpc_segtext.hip: tpc_segments_text_plan / _text_write) and this process only writes it -- the table is not
 // fetched and --threads formats nothing.  The bytes are the same.  The table is complete before the first byte is printed, so
 // a stream the walk refuses prints its error and nothing else (the host paths have printed the header lines by then).
+// --colors file|sequence [--colors-out <path>] (an addition; instead of -f): the segment colour table -- for every segment of the
+// graph (the body-carrying S lines of gfa1, in their order) its length, its occurrences (the C lines), how many of them are
+// forward, and which colours hold it, a colour being an input file or an input sequence; then the histogram of segments by
+// their number of colours -- as TSV (graphformat.h: WriteColors).  Without --gpu the serial walk collects the event table and
+// ComputeColors groups it; with --gpu the device does both (csrc/tpc_colors.hip); the bytes are the same.  A stream the walk
+// refuses prints the walk's error and nothing else, and creates no file.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -175,14 +181,16 @@ namespace
 	void ListSequences(const std::vector<std::string> & fasta, bool prefixed, InputSequences & seq)
 	{
 		size_t index = 0;  // the reference never advances this counter: every prefix is "s0_" (graphdump.cpp:176-192)
-		for (const std::string & f : fasta)
+		for (size_t fileNumber = 0; fileNumber < fasta.size(); fileNumber++)
 		{
+			const std::string & f = fasta[fileNumber];
 			TwoPaCo::StreamFastaParser parser(f);
 			while (parser.ReadRecord())
 			{
 				const std::string id = prefixed ? "s" + std::to_string(index) + "_" + parser.GetCurrentHeader() : parser.GetCurrentHeader();
 				seq.name.push_back(id);
 				seq.file[id] = f;
+				seq.fileIndex.push_back(uint32_t(fileNumber));
 				uint64_t n = 0;
 				for (char ch; parser.GetChar(ch);) ++n;
 				seq.length.push_back(n);
@@ -285,6 +293,63 @@ namespace
 		sink.EndOfSequence(sequence);
 	}
 
+	// ---------------------------------------------------------------------------------------- --colors, serial
+	// The event table of the stream, collected from the serial walk: what the device leaves after tpc_segments_build_*.
+	class EventCollector : public SegmentSink
+	{
+	public:
+		std::vector<int64_t> name;
+		std::vector<uint32_t> first, begin, end, sequenceOf;
+
+		void Segment(const SegmentEvent & e, const std::string &, size_t)
+		{
+			if ((name.size() & 31) == 0) first.push_back(0);
+			if (e.first) first.back() |= uint32_t(1) << (name.size() & 31);
+			name.push_back(e.id);
+			begin.push_back(uint32_t(e.begin));
+			end.push_back(uint32_t(e.end));
+			sequenceOf.push_back(uint32_t(e.sequence));
+		}
+
+		void EndOfSequence(size_t) {}
+
+		// seqEventBegin must outlive the table
+		void Table(size_t sequences, std::vector<uint32_t> & seqEventBegin, EventTable & table) const
+		{
+			seqEventBegin.assign(sequences + 1, 0);
+			for (uint32_t s : sequenceOf)
+			{
+				if (s >= sequences) throw std::runtime_error("The input is corrupted");
+				seqEventBegin[s + 1] += 1;
+			}
+
+			for (size_t s = 0; s < sequences; s++) seqEventBegin[s + 1] += seqEventBegin[s];
+			table.events = name.size();
+			table.name = name.data();
+			table.first = first.data();
+			table.begin = begin.data();
+			table.end = end.data();
+			table.sequences = sequences;
+			table.seqEventBegin = seqEventBegin.data();
+		}
+	};
+
+	void DumpColors(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath)
+	{
+		InputSequences seq;
+		ListSequences(fasta, prefix, seq);
+		EventCollector events;
+		WalkSegments(binFile, fasta, k, events);
+		std::vector<uint32_t> seqEventBegin;
+		EventTable table;
+		events.Table(seq.name.size(), seqEventBegin, table);
+		ColorMap map;
+		MakeColorMap(seq, fasta, bySequence, map);
+		ColorTable colors;
+		ComputeColors(table, k, map.colorOfSequence, map.label.size(), colors);
+		WriteColors(table, k, map, colors, outPath);
+	}
+
 	// ---------------------------------------------------------------------------------------- --gpu
 	double MsSince(const std::chrono::steady_clock::time_point & t0)
 	{
@@ -295,10 +360,10 @@ namespace
 	{
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
-		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs;
+		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), threads(1) {}
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -309,9 +374,9 @@ namespace
 			if (!f) return;
 			std::fprintf(f, "{\"path\": \"%s\", \"events\": %llu, \"segments\": %llu, \"n_named\": %llu, \"device_ms\": %.3f, \"kernel_ms\": %.3f, \"load_ms\": %.3f, "
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
-				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
-				(unsigned long long)tableBytes, text.c_str(), textKernelMs);
+				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs);
 			std::fclose(f);
 		}
 	};
@@ -333,6 +398,10 @@ namespace
 		decltype(&tpc_segments_fetch_sequences) segmentsFetchSequences;
 		decltype(&tpc_segments_text_plan) segmentsTextPlan;
 		decltype(&tpc_segments_text_write) segmentsTextWrite;
+		decltype(&tpc_segments_colors_build) segmentsColorsBuild;
+		decltype(&tpc_segments_colors_fetch_rows) segmentsColorsFetchRows;
+		decltype(&tpc_segments_colors_fetch_presence) segmentsColorsFetchPresence;
+		decltype(&tpc_segments_colors_fetch_hist) segmentsColorsFetchHist;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -363,6 +432,10 @@ namespace
 			Load(segmentsFetchSequences, "tpc_segments_fetch_sequences");
 			Load(segmentsTextPlan, "tpc_segments_text_plan");
 			Load(segmentsTextWrite, "tpc_segments_text_write");
+			Load(segmentsColorsBuild, "tpc_segments_colors_build");
+			Load(segmentsColorsFetchRows, "tpc_segments_colors_fetch_rows");
+			Load(segmentsColorsFetchPresence, "tpc_segments_colors_fetch_presence");
+			Load(segmentsColorsFetchHist, "tpc_segments_colors_fetch_hist");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -394,11 +467,11 @@ namespace
 		void * handle_;
 	};
 
-	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The device builds the
-	// event table of the stream (name, first sight, the two positions of every event, the events of every sequence); the
-	// formatter of graphformat.h reads the table and the letters, never the stream's bytes.
-	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, bool textOnDevice)
+	// The front half of every device path: the stream's bytes and the packed text go up, the device builds the event table of
+	// the stream (name, first sight, the two positions of every event, the events of every sequence).  counts: tpc_segments_counts;
+	// sequences: how many the text holds; t0: when the device stage began.  Throws what the serial walk throws at a stream it refuses.
+	void BuildTableOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const LoadedSequences & loaded, DumpStats & stats, uint64_t * counts, size_t & sequences, std::chrono::steady_clock::time_point & t0)
 	{
 		const size_t SLOT_BYTES = 12;
 		// the stream's bytes
@@ -418,7 +491,7 @@ namespace
 		}
 
 		// the packed text and where the namer must not read 'N'
-		std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+		t0 = std::chrono::steady_clock::now();
 		TwoPaCo::PackedText text;
 		TwoPaCo::PackFastaFiles(fasta, threads, text);
 		if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
@@ -437,8 +510,9 @@ namespace
 		lib.Check(lib.segmentsBuildHost(lib.ctx, bin.data(), bin.size(), int(k), text.recStart.data(), text.recLength.data(), uint32_t(text.recStart.size()),
 			ambiguous.data(), ambiguous.size()), "tpc_segments_build_host");
 		std::vector<char>().swap(bin);
-		uint64_t counts[6] = {0, 0, 0, 0, 0, 0}, errorSlot = 0;
+		uint64_t errorSlot = 0;
 		int errorKind = 0;
+		sequences = text.recStart.size();
 		lib.Check(lib.segmentsCounts(lib.ctx, counts), "tpc_segments_counts");
 		lib.Check(lib.segmentsError(lib.ctx, &errorSlot, &errorKind), "tpc_segments_error");
 		stats.path = "device";
@@ -457,7 +531,87 @@ namespace
 			// what the serial walk throws at this pair
 			throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 		}
+	}
 
+	// The event table of the last build, fetched: `held` owns the arrays the table points to.
+	struct FetchedTable
+	{
+		std::vector<int64_t> name;
+		std::vector<uint32_t> first, begin, end, seqEventBegin;
+		EventTable table;
+	};
+
+	// returns the milliseconds of the second half: the positions and the sequences' ranges (DumpStats::indexMs)
+	double FetchTable(DeviceLibrary & lib, uint64_t events, size_t sequences, FetchedTable & held)
+	{
+		held.name.resize(events);
+		held.first.resize((events + 31) / 32);
+		held.begin.resize(events);
+		held.end.resize(events);
+		held.seqEventBegin.resize(sequences + 1);
+		lib.Check(lib.segmentsFetchNames(lib.ctx, 0, events, held.name.data()), "tpc_segments_fetch_names");
+		lib.Check(lib.segmentsFetchFirst(lib.ctx, 0, held.first.size(), held.first.data()), "tpc_segments_fetch_first");
+		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsFetchEvents(lib.ctx, 0, events, held.begin.data(), held.end.data()), "tpc_segments_fetch_events");
+		lib.Check(lib.segmentsFetchSequences(lib.ctx, 0, held.seqEventBegin.size(), held.seqEventBegin.data()), "tpc_segments_fetch_sequences");
+		held.table.events = events;
+		held.table.name = held.name.data();
+		held.table.first = held.first.data();
+		held.table.begin = held.begin.data();
+		held.table.end = held.end.data();
+		held.table.sequences = sequences;
+		held.table.seqEventBegin = held.seqEventBegin.data();
+		if (held.seqEventBegin[sequences] != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
+		return MsSince(t0);
+	}
+
+	// --colors with --gpu: the table stays on the device, where the colour stage groups its events by segment (csrc/tpc_colors.hip);
+	// what is fetched is the rows, their presence words, the histogram, and the event table for the names and lengths.
+	void DumpColorsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats)
+	{
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+		size_t sequences = 0;
+		std::chrono::steady_clock::time_point t0;
+		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
+		ColorMap map;
+		MakeColorMap(seq, fasta, bySequence, map);
+		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
+		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
+		ColorTable colors;
+		colors.colors = map.label.size();
+		const uint64_t rows = counts[1];
+		colors.firstEvent.resize(rows);
+		colors.occurrences.resize(rows);
+		colors.forward.resize(rows);
+		colors.nColors.resize(rows);
+		colors.presence.resize(rows * colors.Words());
+		colors.histSegments.resize(colors.colors + 1);
+		colors.histBases.resize(colors.colors + 1);
+		lib.Check(lib.segmentsColorsFetchRows(lib.ctx, 0, rows, colors.firstEvent.data(), colors.occurrences.data(), colors.forward.data(), colors.nColors.data()), "tpc_segments_colors_fetch_rows");
+		lib.Check(lib.segmentsColorsFetchPresence(lib.ctx, 0, rows, colors.presence.data()), "tpc_segments_colors_fetch_presence");
+		lib.Check(lib.segmentsColorsFetchHist(lib.ctx, colors.histSegments.data(), colors.histBases.data()), "tpc_segments_colors_fetch_hist");
+		stats.colorsMs = MsSince(c0);
+		FetchedTable held;
+		FetchTable(lib, counts[0], sequences, held);
+		stats.deviceMs = MsSince(t0);
+		t0 = std::chrono::steady_clock::now();
+		WriteColors(held.table, k, map, colors, outPath);
+		stats.formatMs = MsSince(t0);
+		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] colour table on device: %.3f ms (kernels %.3f ms)\n", stats.colorsMs, stats.colorsKernelMs);
+	}
+
+	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The formatter of
+	// graphformat.h reads the table and the letters, never the stream's bytes.
+	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, bool textOnDevice)
+	{
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+		size_t sequences = 0;
+		std::chrono::steady_clock::time_point t0;
+		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		if (textOnDevice)
 		{
 			// the text from the table where it is: nothing is fetched but the bytes to print
@@ -485,28 +639,12 @@ namespace
 			return;
 		}
 
-		const uint64_t events = counts[0];
-		std::vector<int64_t> name(events);
-		std::vector<uint32_t> first((events + 31) / 32);
-		lib.Check(lib.segmentsFetchNames(lib.ctx, 0, events, name.data()), "tpc_segments_fetch_names");
-		lib.Check(lib.segmentsFetchFirst(lib.ctx, 0, first.size(), first.data()), "tpc_segments_fetch_first");
-		stats.deviceMs = MsSince(t0);
-
-		// where every event sits in the stream: its two positions and the events of every sequence, as the device's scans left them
-		t0 = std::chrono::steady_clock::now();
-		std::vector<uint32_t> begin(events), end(events), seqEventBegin(text.recStart.size() + 1);
-		lib.Check(lib.segmentsFetchEvents(lib.ctx, 0, events, begin.data(), end.data()), "tpc_segments_fetch_events");
-		lib.Check(lib.segmentsFetchSequences(lib.ctx, 0, seqEventBegin.size(), seqEventBegin.data()), "tpc_segments_fetch_sequences");
-		EventTable table;
-		table.events = events;
-		table.name = name.data();
-		table.first = first.data();
-		table.begin = begin.data();
-		table.end = end.data();
-		table.sequences = text.recStart.size();
-		table.seqEventBegin = seqEventBegin.data();
-		if (seqEventBegin[table.sequences] != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
-		stats.indexMs = MsSince(t0);
+		// name and first sight, then where every event sits in the stream: its two positions and the events of every sequence, as
+		// the device's scans left them
+		FetchedTable held;
+		stats.indexMs = FetchTable(lib, counts[0], sequences, held);
+		const EventTable & table = held.table;
+		stats.deviceMs = MsSince(t0) - stats.indexMs;
 
 		// format: contiguous chunks of events, each into its own buffer, buffers to stdout in order
 		t0 = std::chrono::steady_clock::now();
@@ -524,7 +662,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -536,6 +674,11 @@ namespace
 			"   --threads <integer>\n     threads of --gpu (1..16, default 16)\n\n"
 			"   --text <host|device>\n     with --gpu: host (default) formats the text with the threads above, device renders the same bytes on the\n"
 			"     GPU and this process only writes them\n\n"
+			"   --colors <file|sequence>\n     instead of -f: the segment colour table as TSV -- per segment of the graph its length, occurrences, forward\n"
+			"     occurrences, number of colours and presence bits, a colour being an input file or an input sequence, then the\n"
+			"     histogram of segments by number of colours.  Needs -k and -s.  With --gpu the table is grouped on the device.\n"
+			"     Not with --text; --prefix is accepted and changes nothing (sequence names are not printed).\n\n"
+			"   --colors-out <file name>\n     with --colors: write the table there instead of to the standard output\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -545,8 +688,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format;
+		std::string binFile, format, colorsBy, colorsOut;
 		std::vector<std::string> fasta;
+		bool colorsOutSet = false, textSet = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -589,7 +733,14 @@ int main(int argc, char * argv[])
 				const std::string v = value("(--text)");
 				if (v != "host" && v != "device") throw ArgError("Value '" + v + "' does not meet constraint: host|device", "Argument: (--text)");
 				textOnDevice = v == "device";
+				textSet = true;
 			}
+			else if (a == "--colors")
+			{
+				colorsBy = value("(--colors)");
+				if (colorsBy != "file" && colorsBy != "sequence") throw ArgError("Value '" + colorsBy + "' does not meet constraint: file|sequence", "Argument: (--colors)");
+			}
+			else if (a == "--colors-out") { colorsOut = value("(--colors-out)"); colorsOutSet = true; }
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -610,11 +761,15 @@ int main(int argc, char * argv[])
 			else throw ArgError("Couldn't find match for argument", "(" + a + ")");
 		}
 
+		const bool colors = !colorsBy.empty();
+		if (colors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--colors)");
+		if (colors && textSet) throw ArgError("The colour table is formatted by the host: not with --colors", "(--text)");
+		if (colorsOutSet && !colors) throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -624,7 +779,17 @@ int main(int argc, char * argv[])
 		const bool deviceText = lib && textOnDevice;
 		stats.text = deviceText ? "device" : "host";
 		Out out(!deviceText);  // --text device: the header lines wait until the table is known to be good
-		if (lib)
+		if (colors && lib)
+		{
+			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+			InputSequences seq;
+			LoadedSequences loaded;
+			LoadSequences(fasta, prefix, threads, seq, loaded);
+			stats.loadMs = MsSince(t0);
+			DumpColorsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, colorsBy == "sequence", colorsOut, stats);
+		}
+		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut);
+		else if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -340,6 +340,10 @@ namespace TwoPaCo
 				if (graph && options.graphFile.empty()) throw std::runtime_error("The graph needs an output file name");
 				if (graph && sharded) throw std::runtime_error("The graph is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				const size_t graphThreads = std::max<size_t>(1, std::min<size_t>(16, options.graphThreads));
+				const bool colors = !options.colorsBy.empty();
+				if (colors && options.colorsBy != "file" && options.colorsBy != "sequence") throw std::runtime_error("The colours must be one of file, sequence");
+				if (colors && options.colorsFile.empty()) throw std::runtime_error("The colour table needs an output file name");
+				if (colors && sharded) throw std::runtime_error("The colour table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 
 				const size_t capacity = (vertexLength + 4 + 31) / 32;  // CalculateNeededCapacity
 				if (capacity >= 20)
@@ -472,14 +476,14 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph)
+				if (graph || colors)
 				{
 					graphLoad = std::thread([&]()
 					{
 						try
 						{
 							PhaseTimer loadTimer;
-							GraphFormat::LoadSequences(fileName, options.graphFormat == "fasta" ? true : options.graphPrefix, graphThreads, graphSeq, graphLoaded);
+							GraphFormat::LoadSequences(fileName, options.graphFormat == "fasta" ? true : (graph && options.graphPrefix), graphThreads, graphSeq, graphLoaded);
 							loadTimer.Lap("  graph thread: sequences for the segment bodies");
 						}
 						catch (std::exception & e)
@@ -970,7 +974,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph) WriteGraph(nothing, text, vertexLength, graphThreads, options, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -979,9 +983,11 @@ namespace TwoPaCo
 		private:
 			// --graph: the segment table from the stream tpc_emit_stream left on the device, fetched as the event table, formatted
 			// into options.graphFile.  What the walk of graphdump would throw is thrown here, before the file is created.
-			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, std::thread & load,
-				const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
+			// --colors: the same table, built once for both, grouped by segment on the device and written to options.colorsFile.
+			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
+				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
+				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty();
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1009,29 +1015,113 @@ namespace TwoPaCo
 						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 					}
 
-					if (options.graphTextOnDevice)
+					// With both, everything of the colour table that can fail on the device comes first and its file is written last:
+					// a graph step that throws leaves no colour file behind (the graph file removes itself).
+					DeviceColors deviceColors;
+					if (colors && !(graph && options.graphTextOnDevice)) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+					if (colors) ColorsFromDevice(options, fileName, seq, counts, name, begin, end, seqEventBegin, deviceColors, timer);
+					if (graph && options.graphTextOnDevice) WriteGraphOnDevice(options, seq, loaded, timer);
+					else if (graph)
 					{
-						WriteGraphOnDevice(options, seq, loaded, timer);
-						return;
+						if (!colors) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+						WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, options, seq, loaded, k, threads, timer);
 					}
 
-					const uint64_t events = counts[0];
-					name.resize(events); first.resize((events + 31) / 32); begin.resize(events); end.resize(events);
-					Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
-					Check(tpc_segments_fetch_first(ctx_, 0, first.size(), first.data()), "segments_fetch_first");
-					Check(tpc_segments_fetch_events(ctx_, 0, events, begin.data(), end.data()), "segments_fetch_events");
-					Check(tpc_segments_fetch_sequences(ctx_, 0, seqEventBegin.size(), seqEventBegin.data()), "segments_fetch_sequences");
-					timer.Lap("segment table fetch");
+					if (colors)
+					{
+						GraphFormat::WriteColors(deviceColors.events, k, deviceColors.map, deviceColors.table, options.colorsFile);
+						timer.Lap("colour table writing");
+					}
+
+					return;
+				}
+				else if (colors)
+				{
+					// nothing dispatched: no event, the header and the colours alone
+					GraphFormat::EventTable empty;
+					empty.sequences = sequences;
+					empty.seqEventBegin = seqEventBegin.data();
+					GraphFormat::ColorMap map;
+					GraphFormat::MakeColorMap(seq, fileName, options.colorsBy == "sequence", map);
+					GraphFormat::ColorTable table;
+					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
+					GraphFormat::WriteColors(empty, k, map, table, options.colorsFile);
+					timer.Lap("colour table writing");
 				}
 
+				if (graph) WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, options, seq, loaded, k, threads, timer);
+			}
+
+			void WriteGraphFromTable(uint64_t events, const std::vector<int64_t> & name, const std::vector<uint32_t> & first, const std::vector<uint32_t> & begin,
+				const std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin, const EnumeratorOptions & options, const GraphFormat::InputSequences & seq,
+				const GraphFormat::LoadedSequences & loaded, size_t k, size_t threads, PhaseTimer & timer)
+			{
 				GraphFormat::EventTable table;
-				table.events = counts[0];
+				table.events = events;
 				table.name = name.data(); table.first = first.data(); table.begin = begin.data(); table.end = end.data();
-				table.sequences = sequences;
+				table.sequences = seqEventBegin.size() - 1;
 				table.seqEventBegin = seqEventBegin.data();
 				GraphFormat::CheckEventTable(table, loaded, k, threads);
 				GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
 				timer.Lap("graph formatting + writing");
+			}
+
+			// what --colors fetched from the device, until its file is written
+			struct DeviceColors
+			{
+				GraphFormat::ColorMap map;
+				GraphFormat::ColorTable table;
+				GraphFormat::EventTable events;
+			};
+
+			void FetchEventTable(uint64_t events, std::vector<int64_t> & name, std::vector<uint32_t> & first, std::vector<uint32_t> & begin, std::vector<uint32_t> & end,
+				std::vector<uint32_t> & seqEventBegin, PhaseTimer & timer)
+			{
+				name.resize(events); first.resize((events + 31) / 32); begin.resize(events); end.resize(events);
+				Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
+				Check(tpc_segments_fetch_first(ctx_, 0, first.size(), first.data()), "segments_fetch_first");
+				Check(tpc_segments_fetch_events(ctx_, 0, events, begin.data(), end.data()), "segments_fetch_events");
+				Check(tpc_segments_fetch_sequences(ctx_, 0, seqEventBegin.size(), seqEventBegin.data()), "segments_fetch_sequences");
+				timer.Lap("segment table fetch");
+			}
+
+			// --colors: the events of the table on the device grouped by segment there (csrc/tpc_colors.hip); fetched are the rows,
+			// their presence words and the histogram.  The names and lengths of the rows come from the fetched event table (`out`
+			// points into name / begin / end / seqEventBegin).  The file is the caller's to write.
+			void ColorsFromDevice(const EnumeratorOptions & options, const std::vector<std::string> & fileName, const GraphFormat::InputSequences & seq,
+				const uint64_t * counts, std::vector<int64_t> & name, std::vector<uint32_t> & begin, std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin,
+				DeviceColors & out, PhaseTimer & timer)
+			{
+				GraphFormat::ColorMap & map = out.map;
+				GraphFormat::ColorTable & table = out.table;
+				GraphFormat::EventTable & events = out.events;
+				const bool keptTable = !name.empty() || counts[0] == 0;
+				if (!keptTable)
+				{
+					// (--graph-text device fetches no table: the names and positions alone are fetched here)
+					name.resize(counts[0]); begin.resize(counts[0]); end.resize(counts[0]);
+					Check(tpc_segments_fetch_names(ctx_, 0, counts[0], name.data()), "segments_fetch_names");
+					Check(tpc_segments_fetch_events(ctx_, 0, counts[0], begin.data(), end.data()), "segments_fetch_events");
+				}
+
+				GraphFormat::MakeColorMap(seq, fileName, options.colorsBy == "sequence", map);
+				if (map.colorOfSequence.size() + 1 != seqEventBegin.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
+				Check(tpc_segments_colors_build(ctx_, map.colorOfSequence.data(), uint32_t(map.label.size())), "segments_colors_build");
+				timer.Lap("segment colours");
+				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   colors_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_COLORS) << " ms" << std::endl;
+				table.colors = map.label.size();
+				const uint64_t rows = counts[1];
+				table.firstEvent.resize(rows); table.occurrences.resize(rows); table.forward.resize(rows); table.nColors.resize(rows);
+				table.presence.resize(rows * table.Words());
+				table.histSegments.resize(table.colors + 1); table.histBases.resize(table.colors + 1);
+				Check(tpc_segments_colors_fetch_rows(ctx_, 0, rows, table.firstEvent.data(), table.occurrences.data(), table.forward.data(), table.nColors.data()), "segments_colors_fetch_rows");
+				Check(tpc_segments_colors_fetch_presence(ctx_, 0, rows, table.presence.data()), "segments_colors_fetch_presence");
+				Check(tpc_segments_colors_fetch_hist(ctx_, table.histSegments.data(), table.histBases.data()), "segments_colors_fetch_hist");
+				timer.Lap("segment colours fetch");
+				events.events = counts[0];
+				events.name = name.data(); events.begin = begin.data(); events.end = end.data();
+				events.sequences = seqEventBegin.size() - 1;
+				events.seqEventBegin = seqEventBegin.data();
 			}
 
 			// --graph-text device: the table stays where it was built.  The header lines are written here, the events' text is

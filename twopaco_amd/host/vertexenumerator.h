@@ -71,6 +71,12 @@ namespace TwoPaCo
 		// false: the event table is fetched and the text formatted by graphThreads host threads.  true: the text is rendered on
 		// the device and only written here (tpc_segments_text_plan / _text_write); the same bytes
 		bool graphTextOnDevice;
+		// The segment colour table (graphformat.h: WriteColors; `graphdump --colors` writes the same bytes for the junction stream
+		// of this run): colorsBy = file | sequence (empty: off) -- colour c is the c-th input file or the c-th sequence -- into
+		// colorsFile.  The events are grouped by segment on the device (tpc_segments_colors_build) over the segment table --graph
+		// uses, built once for both.  One GPU.
+		std::string colorsBy;
+		std::string colorsFile;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
