@@ -60,7 +60,8 @@ enum {
                                kernels since the last tpc_segments_text_plan (the plan's own included)                                    */
     TPC_K_SKETCH = 17,      /* tpc_distinct_sketch: HyperLogLog registers of the distinct canonical (k+1)-mers (no counterpart in the reference) */
     TPC_K_COLORS = 18,      /* tpc_segments_colors_build: rows, counts and presence bits of the segment colour table (no counterpart in the reference) */
-    TPC_K_COUNT = 19
+    TPC_K_LINKS = 19,       /* tpc_segments_links_build: the device hash set of the distinct links, their counts and first bits (no counterpart in the reference) */
+    TPC_K_COUNT = 20
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -548,6 +549,38 @@ int tpc_segments_colors_fetch_rows(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32
 int tpc_segments_colors_fetch_presence(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *words_host /* [n x W] */);
 int tpc_segments_colors_fetch_hist(tpc_ctx *ctx, uint64_t *segments_host /* [n_colors + 1] */, uint64_t *bases_host /* [n_colors + 1] */);
 
+/* The LINK TABLE of the compacted graph (csrc/tpc_links.hip): every distinct link between two segments once.  No counterpart in the
+ * reference, whose gfa1 prints one L line per occurrence; ComputeLinks of twopaco_amd/host/graphformat.h is the serial statement the
+ * kernels are tested against.  The definition, over the event table of the last tpc_segments_build_*:
+ *   LINK OCCURRENCE  every event e that is not the first event of its sequence closes an occurrence (name[e - 1], name[e]) -- exactly
+ *                    where GfaSink::Segment calls Link, that is one L line of gfa1.
+ *   LINK CLASS       occurrences (a, b) and (c, d) are the same link when (c, d) == (a, b) or (c, d) == (-b, -a): the same bidirected
+ *                    edge, walked on the other strand.
+ *   ROWS             one per class, in the order of the classes' first occurrences in event order.  For row r:
+ *     first_event[r]   the event e of the first occurrence; the row is SPELLED as that occurrence, from = name[e - 1], to = name[e]
+ *     count[r]         the occurrences of the class
+ *     same[r]          those of them spelled exactly as the row (the rest are spelled (-to, -from))
+ *   FIRST BITS       link_first: one bit per event, laid out as first[] is (bit e % 32 of word e / 32), set when e closes the first
+ *                    occurrence of its class.
+ *   'N'-named segments (names >= 2^34) are segments like any other: a link that touches one is simply unique.  A class that is its
+ *   own reverse (a+ a-) cannot occur with odd k; it is one class all the same, with same == count.
+ * Separate from the build and opt-in: a context that never calls it holds none of this, and tpc_segments_counts reports what it
+ * reported before.  It is independent of the colour table: both may be built over one segment table, in either order.
+ *   tpc_segments_links_build        over the table of the last tpc_segments_build_*: a device hash set of the classes (open addressing,
+ *                                   the smallest power of two >= 2 x occurrences slots, at least 1024, 20 B each during the call).
+ *                                   Refused with an error text: no table, a table whose tpc_segments_error kind is not TPC_SEG_OK,
+ *                                   more than 2^31 segments, buffers beyond the free device memory, a set that fills up (only with
+ *                                   the option test_links_slots_log2); the context stays usable.  Kept until the next segment build
+ *                                   or link build: 12 B per row and one bit per event.  Kernel time: TPC_K_LINKS.
+ *   tpc_segments_links_info         info[0] rows, [1] occurrences, [2] slots, [3] the stage's device bytes at their peak
+ *   tpc_segments_links_fetch_rows   first_event / count / same of rows [r0, r0 + n) to the host
+ *   tpc_segments_links_fetch_first  words [word0, word0 + n_words) of link_first, (events + 31) / 32 words in all
+ * A range outside the table is refused with an error text. */
+int tpc_segments_links_build(tpc_ctx *ctx);
+int tpc_segments_links_info(tpc_ctx *ctx, uint64_t *info /* [4] */);
+int tpc_segments_links_fetch_rows(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *first_event_host, uint32_t *count_host, uint32_t *same_host);
+int tpc_segments_links_fetch_first(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uint32_t *bits_host);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -582,6 +615,8 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      makes every workgroup stride over several tiles
  *   test_force_anyq    tests only, process-wide: 1 = the closed-form first-pass kernels that serve q = 17..64
  *                      (csrc/tpc_pass1_anyq.hip) for every q, so that they can be checked on the goldens with q <= 16
+ *   test_links_slots_log2  tests only: the next tpc_segments_links_build takes 2^n slots for its link set instead of sizing it by
+ *                      the occurrences (0 = by the occurrences), so that long probe chains and a full set can be reached
  *   part_budget_bytes  partition buffers per tile batch (0 = automatic: 40 GiB, or 60 % of the free device
  *                      memory when that is more; any number of batches, not only powers of two); part_min_tiles  smallest batch */
 /*   replicate_filter   1 (before tpc_shard_config / tpc_set_params): a sharded context keeps the whole filter; tpc_pass1_insert / tpc_pass1_query

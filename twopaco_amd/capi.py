@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -29,7 +29,8 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_pass1_query_begin", "tpc_combine_info", "tpc_combine_export", "tpc_combine_merge", "tpc_combine_import", "tpc_combine_choose", "tpc_filter_copy_out", "tpc_filter_copy_in",
                "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
                "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write", "tpc_distinct_sketch",
-               "tpc_segments_colors_build", "tpc_segments_colors_info", "tpc_segments_colors_fetch_rows", "tpc_segments_colors_fetch_presence", "tpc_segments_colors_fetch_hist"]
+               "tpc_segments_colors_build", "tpc_segments_colors_info", "tpc_segments_colors_fetch_rows", "tpc_segments_colors_fetch_presence", "tpc_segments_colors_fetch_hist",
+               "tpc_segments_links_build", "tpc_segments_links_info", "tpc_segments_links_fetch_rows", "tpc_segments_links_fetch_first"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -158,6 +159,10 @@ def hip():
         L.tpc_segments_colors_fetch_rows.argtypes = [p, u64, u64, p, p, p, p]
         L.tpc_segments_colors_fetch_presence.argtypes = [p, u64, u64, p]
         L.tpc_segments_colors_fetch_hist.argtypes = [p, p, p]
+        L.tpc_segments_links_build.argtypes = [p]
+        L.tpc_segments_links_info.argtypes = [p, p]
+        L.tpc_segments_links_fetch_rows.argtypes = [p, u64, u64, p, p, p]
+        L.tpc_segments_links_fetch_first.argtypes = [p, u64, u64, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -197,6 +202,10 @@ def host():
         L.tpch_create_enumerator_colors.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
                                                     ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.c_char_p, ctypes.c_char_p,
                                                     ctypes.POINTER(p)]
+        L.tpch_create_enumerator_links.restype = p
+        L.tpch_create_enumerator_links.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
+                                                   ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.c_char_p, ctypes.c_char_p,
+                                                   ctypes.c_char_p, ci, ctypes.POINTER(p)]
         L.tpch_create_enumerator_auto.restype = p
         L.tpch_create_enumerator_auto.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, ctypes.c_char_p, ctypes.c_char_p, ci, u64, ci,
                                                   ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(p)]
@@ -621,6 +630,33 @@ class Context:
         self._ck(hip().tpc_segments_colors_fetch_hist(self._h, seg.ctypes.data, bases.ctypes.data))
         return seg, bases
 
+    def segments_links_build(self):
+        """The link table (csrc/tpc_links.hip) over the table of the last segments_build, whose error must be None.  Returns
+        segments_links_info()."""
+        self._ck(hip().tpc_segments_links_build(self._h))
+        return self.segments_links_info()
+
+    def segments_links_info(self):
+        """dict: rows (distinct links), occurrences, slots (of the device hash set), peak_bytes (device memory of the stage)."""
+        c = np.zeros(4, dtype=np.uint64)
+        self._ck(hip().tpc_segments_links_info(self._h, c.ctypes.data))
+        return dict(zip(("rows", "occurrences", "slots", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_links_fetch_rows(self, r0=0, n=None):
+        """(first_event, count, same) of rows [r0, r0 + n) as uint32; n = None: to the last row."""
+        n = self.segments_links_info()["rows"] - r0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(3)]
+        self._ck(hip().tpc_segments_links_fetch_rows(self._h, r0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_links_fetch_first(self, word0=0, n_words=None):
+        """Words [word0, word0 + n_words) of the link_first bits as uint32 (bit e % 32 of word e // 32); None: to the last word."""
+        if n_words is None:
+            n_words = (self.segments_counts()["events"] + 31) // 32 - word0
+        out = np.zeros(max(n_words, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_links_fetch_first(self._h, word0, n_words, out.ctypes.data))
+        return out
+
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))
 
@@ -812,14 +848,32 @@ class Enumerator:
 
     def __init__(self, files, k, filter_bits, q=5, rounds=1, threads=1, abundance=(1 << 64) - 1, tmpdir=".",
                  out=None, seed=None, device=0, test_first=False, gpus=1, rccl=True, emulate_ranks=False, force_sharded=False,
-                 graph=None, graph_out=None, graph_prefix=False, graph_threads=16, colors=None, colors_out=None):
+                 graph=None, graph_out=None, graph_prefix=False, graph_threads=16, colors=None, colors_out=None,
+                 links=False, links_out=None, graph_compact=False):
         """out: the junction stream's file, default de_bruijn.bin.  graph = gfa1 | gfa2 | fasta: `twopaco --graph` -- the
         compacted graph's text goes to graph_out (default de_bruijn.<graph>) and the junction stream is written only when
         `out` is given.  colors = file | sequence: `twopaco --colors` -- the segment colour table goes to colors_out (default
-        de_bruijn.colors.tsv); combines with graph and out."""
+        de_bruijn.colors.tsv); combines with graph and out.  links: `twopaco --links` -- the link table goes to links_out (default
+        de_bruijn.links.tsv); graph_compact: `--graph-compact`, with graph = gfa1.  Both combine with graph, colors and out."""
         arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
         log = ctypes.c_void_p()
-        if colors is not None:
+        if links or graph_compact:
+            if filter_bits == "auto" or gpus > 1 or force_sharded:
+                raise ValueError("links / graph_compact: one GPU and a given filter size")
+            if graph is not None:
+                graph_out = "de_bruijn." + graph if graph_out is None else graph_out
+            elif out is None:
+                out = "de_bruijn.bin"
+            links_out = ("de_bruijn.links.tsv" if links_out is None else links_out) if links else None
+            if colors is not None:
+                colors_out = "de_bruijn.colors.tsv" if colors_out is None else colors_out
+            self._h = host().tpch_create_enumerator_links(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),
+                                                          b"" if out is None else out.encode(), 0 if seed is None else 1, 0 if seed is None else seed,
+                                                          device, 1 if test_first else 0, None if graph is None else graph.encode(),
+                                                          None if graph is None else os.fsencode(graph_out), 1 if graph_prefix else 0, graph_threads,
+                                                          None if colors is None else colors.encode(), None if colors is None else os.fsencode(colors_out),
+                                                          None if links_out is None else os.fsencode(links_out), 1 if graph_compact else 0, ctypes.byref(log))
+        elif colors is not None:
             if filter_bits == "auto" or gpus > 1 or force_sharded:
                 raise ValueError("colors: one GPU and a given filter size")
             if graph is not None:
@@ -852,7 +906,7 @@ class Enumerator:
                                                           1 if graph_prefix else 0, graph_threads, ctypes.byref(log))
             out = ""
         out = "de_bruijn.bin" if out is None else out
-        if graph is not None or filter_bits == "auto" or colors is not None:
+        if graph is not None or filter_bits == "auto" or colors is not None or links or graph_compact:
             pass
         elif gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
             self._h = host().tpch_create_enumerator_mgpu(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),

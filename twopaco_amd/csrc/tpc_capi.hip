@@ -337,6 +337,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
     for (void *p : ptrs) if (p) (void)hipFree(p);
     stream_part_release(c);
     colors_drop(c);
+    links_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);
@@ -375,6 +376,7 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "replicate_filter")) { c->opt_replicate = value != 0; return 0; }  // before tpc_shard_config / tpc_set_params
     if (!strcmp(name, "test_force_anyq")) { tpc_test_force_anyq = value != 0; return 0; }  // process-wide, tests only
     if (!strcmp(name, "test_sketch_grid")) { tpc_test_sketch_grid = value > 0 ? (int)value : 0; return 0; }  // process-wide, tests only
+    if (!strcmp(name, "test_links_slots_log2")) { c->opt_links_slots_log2 = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 64)); return 0; }  // tests only: slots of the next tpc_segments_links_build
     if (!strcmp(name, "test_fail_mallocs")) { tpc_test_fail_mallocs.store(value > 0 ? (int)value : 0); return 0; }  // process-wide, tests only
     return fail(c, -1, "unknown option %s", name);
 }

@@ -6,7 +6,7 @@
 //
 // Input: the event table the last tpc_segments_build_* left in the context (name[e], first[] bits, begin / end,
 // seq_event_begin[]; tpc_segments.hip).  What that table lacks is the ROW of every event, the index of its segment among the
-// first bits in event order.  The build's first-sight table is gone by then, so it is made again:
+// first bits in event order.  The build's first-sight table is gone by then, so it is made again (tpc_segrows.h, shared with tpc_links.hip):
 //   k_col_flags    rank[e] = first bit of e; one exclusive scan makes it the row of every first event (the total is the row count)
 //   k_col_min      table[|name[e]|] = min(e), as k_seg_min of tpc_segments.hip ('N'-named events, names >= 2^34, are their own row)
 //   k_col_scatter  one thread per event: row = rank[table[|name|]], colour = color_of_seq[sequence of e] (the sequence by binary
@@ -23,35 +23,14 @@
 // 4 B / event of ranks, 4 B / sequence of colours.  None of it exists in a context that never asks for colours, and
 // tpc_segments_counts reports what it reported before.  What does not fit the free device memory is refused with an error text.
 #include "tpc_ctx.h"
+#include "tpc_segrows.h"
 
 #include <rocprim/rocprim.hpp>
 
 namespace {
 
-constexpr int64_t COL_FRESH = (int64_t)1 << 34;  // first fresh name (tpc_segments.hip: SEG_FRESH)
 constexpr uint32_t COL_MAX_COLORS = 1u << 31;     // the most colours of one build
 constexpr uint32_t COL_LDS_BINS = 2048;          // histogram bins a block keeps in LDS: 2 x 8 B x 2048 = 32 KiB
-
-__device__ __forceinline__ uint64_t col_mag(int64_t x) { return x < 0 ? 0ull - (uint64_t)x : (uint64_t)x; }
-
-// n_events + 1 entries: the scan's last element is the row count
-__global__ void k_col_flags(const uint32_t *__restrict__ first, uint64_t n_events, uint32_t *__restrict__ rank)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= n_events; e += stride)
-        rank[e] = e < n_events ? (first[e >> 5] >> (e & 31)) & 1u : 0u;
-}
-
-__global__ void k_col_min(const int64_t *__restrict__ name, uint64_t n_events, uint32_t *__restrict__ table, uint64_t n_table)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_events; e += stride) {
-        const int64_t nm = name[e];
-        if (nm >= COL_FRESH) continue;
-        const uint64_t m = col_mag(nm);
-        if (m < n_table) atomicMin(&table[m], (uint32_t)e);
-    }
-}
 
 // rows: [0, S) first event, [S, 2S) occurrences, [2S, 3S) forward.  A whole wave runs every iteration (the stride is a multiple of
 // 64), lanes past the last event take part in the shuffles and ballots and nothing else.
@@ -122,8 +101,6 @@ __global__ void k_col_rows(uint32_t *__restrict__ rows, uint64_t n_rows, const u
         for (uint32_t i = threadIdx.x; i < 2 * bins; i += blockDim.x) if (s_bins[i]) atomicAdd(&hist[i], s_bins[i]);
     }
 }
-
-unsigned col_grid(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 8192)); }
 
 }  // namespace
 

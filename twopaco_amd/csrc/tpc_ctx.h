@@ -5,6 +5,7 @@
 //   tpc_capi_combine.hip  the filter replicated through set-bit lists (tpc_combine_*)
 //   tpc_capi_segments.hip the segment table of the compacted graph and its text (tpc_segments_*)
 //   tpc_colors.hip        the segment colour table (tpc_segments_colors_*), kernels and entry points
+//   tpc_links.hip         the link table of the compacted graph (tpc_segments_links_*), kernels and entry points
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -119,6 +120,12 @@ struct tpc_ctx {
     uint64_t col_n_rows = 0;
     uint32_t col_n_colors = 0, col_words = 0;
     bool col_valid = false;
+    // link table (tpc_segments_links_*, tpc_links.hip) of the last tpc_segments_links_build; a new segment build drops it
+    uint32_t *lnk_rows = nullptr;            // device, [3][lnk_n_rows]: first event, count, same
+    uint32_t *lnk_first = nullptr;           // device, [(seg_events + 31) / 32]: link_first bits
+    uint64_t lnk_n_rows = 0, lnk_occurrences = 0, lnk_slots = 0, lnk_peak_bytes = 0;
+    bool lnk_valid = false;
+    int opt_links_slots_log2 = 0;            // option test_links_slots_log2 (tests only): slots of the link set, 0 = by the occurrences
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors
@@ -231,6 +238,7 @@ bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
 void colors_drop(tpc_ctx *c);           // tpc_colors.hip
+void links_drop(tpc_ctx *c);            // tpc_links.hip
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

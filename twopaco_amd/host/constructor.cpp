@@ -17,7 +17,10 @@
 // --colors file|sequence [--colors-out F]: the segment colour table of the same graph -- which input files, or sequences, hold
 // each segment, how often, on which strand -- as TSV, byte for byte what `graphdump --colors` writes for the junction stream of
 // the same command (csrc/tpc_colors.hip groups the events on the device; combines with --graph and -o, the segment table is
-// built once; one GPU).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// built once; one GPU);
+// --links [--links-out F]: the link table of the same graph -- every distinct link once with its occurrences -- as TSV, byte for
+// byte what `graphdump --links` writes (csrc/tpc_links.hip finds the links on the device; combines with --graph, --colors and -o);
+// --graph-compact: with --graph gfa1 the text `graphdump -f gfa1 --compact` prints, every link once.  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -73,6 +76,7 @@ namespace
 			<< "               [--graph <gfa1|gfa2|fasta>] [--graph-out <file name>] [--graph-prefix] [--graph-threads <integer>]" << std::endl
 			<< "               [--graph-text <host|device>]" << std::endl
 			<< "               [--colors <file|sequence>] [--colors-out <file name>]" << std::endl
+			<< "               [--links] [--links-out <file name>] [--graph-compact]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -85,7 +89,12 @@ namespace
 			<< "       --colors: also write the segment colour table of the graph as TSV to --colors-out (default de_bruijn.colors.tsv):" << std::endl
 			<< "               per segment its length, occurrences, forward occurrences, number of colours and presence bits, a colour" << std::endl
 			<< "               being the c-th input file or the c-th sequence; then the histogram of segments by number of colours." << std::endl
-			<< "               Combines with --graph and -o.  One GPU only." << std::endl;
+			<< "               Combines with --graph and -o.  One GPU only." << std::endl
+			<< "       --links: also write the link table of the graph as TSV to --links-out (default de_bruijn.links.tsv): every distinct" << std::endl
+			<< "               link between two segments once, as spelled where it is first met, its occurrences and how many of them" << std::endl
+			<< "               are spelled that way (a b and -b -a are one link).  Combines with --graph, --colors and -o.  One GPU only." << std::endl
+			<< "       --graph-compact: with --graph gfa1, the compact text: no per-sequence S lines, no C lines, every link once (what" << std::endl
+			<< "               graphdump -f gfa1 --compact prints).  Not with --graph-text device.  One GPU only." << std::endl;
 	}
 }
 
@@ -126,7 +135,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -201,6 +210,9 @@ int main(int argc, char * argv[])
 				optionsSet = true;
 			}
 			else if (Match(a, 0, "colors-out")) { options.colorsFile = value("(--colors-out)"); colorsOutSet = true; }
+			else if (Match(a, 0, "links")) { links = true; optionsSet = true; }
+			else if (Match(a, 0, "links-out")) { options.linksFile = value("(--links-out)"); linksOutSet = true; }
+			else if (Match(a, 0, "graph-compact")) { options.graphCompact = true; optionsSet = true; }
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -226,6 +238,13 @@ int main(int argc, char * argv[])
 			optionsSet = true;
 		}
 
+		if (options.graphCompact)
+		{
+			if (options.graphFormat != "gfa1") throw ArgError("The compact graph is gfa1 with every link once: it needs --graph gfa1", "(--graph-compact)");
+			if (options.graphTextOnDevice) throw ArgError("The compact graph is formatted by the host: not with --graph-text device", "(--graph-compact)");
+			if (options.gpus > 1) throw ArgError("The compact graph is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--graph-compact)");
+		}
+
 		if (!options.graphFormat.empty())
 		{
 			if (options.gpus > 1) throw ArgError("The graph is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--graph)");
@@ -245,6 +264,17 @@ int main(int argc, char * argv[])
 		else if (colorsOutSet)
 		{
 			throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
+		}
+
+		if (links)
+		{
+			if (options.gpus > 1) throw ArgError("The link table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--links)");
+			if (!linksOutSet) options.linksFile = "de_bruijn.links.tsv";
+			if (options.linksFile.empty()) throw ArgError("The link table needs a file name", "(--links-out)");
+		}
+		else if (linksOutSet)
+		{
+			throw ArgError("This argument needs --links", "(--links-out)");
 		}
 
 		if (runTests)

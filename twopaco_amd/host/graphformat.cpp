@@ -83,12 +83,12 @@ namespace TwoPaCo
 			return format == "gfa1" || format == "gfa2" || format == "fasta";
 		}
 
-		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out)
+		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out, bool compact)
 		{
 			if (format == "gfa1")
 			{
 				out << "H\tVN:Z:1.0\n";
-				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file.find(name)->second << '\n';
+				if (!compact) for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file.find(name)->second << '\n';
 			}
 
 			if (format == "gfa2") out << "H\tVN:Z:2.0\n";
@@ -102,9 +102,11 @@ namespace TwoPaCo
 				return std::max<uint64_t>(16, std::min<uint64_t>(uint64_t(1) << 16, events / (8 * threads) + 1));
 			}
 
-			SegmentSink * MakeSink(const std::string & format, Out & out, const InputSequences & seq, GfaSink * & gfa)
+			SegmentSink * MakeSink(const std::string & format, Out & out, const InputSequences & seq, GfaSink * & gfa, CompactGfa1Sink * & compact, bool wantCompact)
 			{
 				gfa = 0;
+				compact = 0;
+				if (format == "gfa1" && wantCompact) return gfa = compact = new CompactGfa1Sink(out, seq);
 				if (format == "gfa1") return gfa = new Gfa1Sink(out, seq);
 				if (format == "gfa2") return gfa = new Gfa2Sink(out, seq);
 				return new FastaSink(out);
@@ -123,7 +125,8 @@ namespace TwoPaCo
 			{
 				Out chunkOut(false);
 				GfaSink * gfa = 0;
-				std::unique_ptr<SegmentSink> sink(MakeSink(format, chunkOut, seq, gfa));
+				CompactGfa1Sink * compact = 0;
+				std::unique_ptr<SegmentSink> sink(MakeSink(format, chunkOut, seq, gfa, compact, t.linkFirst != 0));
 				size_t sequence = e0 < e1 ? SequenceOf(t, e0) : 0;
 				for (uint64_t e = e0; e < e1; e++)
 				{
@@ -142,6 +145,7 @@ namespace TwoPaCo
 						else gfa->Resume(0, 0);
 					}
 
+					if (compact) compact->NextLink((t.linkFirst[e >> 5] >> (e & 31)) & 1u);
 					sink->Segment(ev, loaded.body[sequence], k);
 					if (gfa && e + 1 == t.seqEventBegin[sequence + 1])
 					{
@@ -344,14 +348,14 @@ namespace TwoPaCo
 		}
 
 		void WriteGraphFileWith(const std::string & format, const InputSequences & seq, const std::string & outPath,
-			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events)
+			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events, bool compact)
 		{
 			int fd = ::open(outPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
 			if (fd < 0) throw std::runtime_error("Can't create the graph file " + outPath);
 			try
 			{
 				Out head(false);
-				HeaderLines(format, seq, head);
+				HeaderLines(format, seq, head, compact);
 				if (!WriteAll(fd, head.Text().data(), head.Text().size(), 0)) throw std::runtime_error("Can't write to the graph file");
 				const uint64_t size = head.Text().size() + events(fd, head.Text().size());
 				if (::ftruncate(fd, off_t(size)) != 0) throw std::runtime_error("Can't write to the graph file");
@@ -491,13 +495,111 @@ namespace TwoPaCo
 			}
 		}
 
+		namespace
+		{
+			struct LinkClass
+			{
+				int64_t from, to;
+				bool operator == (const LinkClass & o) const { return from == o.from && to == o.to; }
+			};
+
+			struct LinkClassHash
+			{
+				size_t operator () (const LinkClass & c) const
+				{
+					uint64_t x = uint64_t(c.from) * 0x9e3779b97f4a7c15ull ^ (uint64_t(c.to) + 0x7f4a7c15ull);
+					x ^= x >> 31; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 29;
+					return size_t(x);
+				}
+			};
+		}
+
+		void ComputeLinks(const EventTable & t, LinkTable & out)
+		{
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			out = LinkTable();
+			out.linkFirst.assign(size_t((t.events + 31) / 32), 0);
+			std::unordered_map<LinkClass, uint32_t, LinkClassHash> rowOf;
+			size_t sequence = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+				if (e == t.seqEventBegin[sequence]) continue;   // the first event of its sequence closes no link
+				const LinkClass spelled = {t.name[e - 1], t.name[e]}, reversed = {-t.name[e], -t.name[e - 1]};
+				const bool keep = spelled.from < reversed.from || (spelled.from == reversed.from && spelled.to <= reversed.to);
+				const LinkClass key = keep ? spelled : reversed;
+				out.occurrences += 1;
+				std::unordered_map<LinkClass, uint32_t, LinkClassHash>::const_iterator seen = rowOf.find(key);
+				uint32_t row = 0;
+				if (seen == rowOf.end())
+				{
+					row = uint32_t(out.firstEvent.size());
+					rowOf[key] = row;
+					out.firstEvent.push_back(uint32_t(e));
+					out.count.push_back(0);
+					out.same.push_back(0);
+					out.linkFirst[e >> 5] |= uint32_t(1) << (e & 31);
+				}
+				else row = seen->second;
+
+				const uint32_t e0 = out.firstEvent[row];
+				out.count[row] += 1;
+				if (t.name[e0 - 1] == spelled.from && t.name[e0] == spelled.to) out.same[row] += 1;
+			}
+		}
+
+		void WriteLinks(const EventTable & t, size_t k, uint64_t segments, const LinkTable & links, const std::string & path)
+		{
+			const size_t rows = links.Rows();
+			if (links.count.size() != rows || links.same.size() != rows) throw std::runtime_error("link table: the arrays do not agree about the rows");
+			for (uint32_t e0 : links.firstEvent)
+			{
+				if (e0 == 0 || e0 >= t.events) throw std::runtime_error("link table: a row's first event lies outside the event table");
+			}
+
+			std::FILE * f = path.empty() ? stdout : std::fopen(path.c_str(), "wb");
+			if (!f) throw std::runtime_error("Can't create the link table " + path);
+			std::string buf;
+			bool good = true;
+			auto flush = [&]() { good = good && std::fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); };
+			buf += "#twopaco-links\t1\tk=" + std::to_string(k) + "\tsegments=" + std::to_string(segments) + "\tlinks=" + std::to_string(rows) + "\toccurrences=" +
+				std::to_string(links.occurrences) + "\n";
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t e0 = links.firstEvent[r];
+				const int64_t from = t.name[e0 - 1], to = t.name[e0];
+				buf += std::to_string(static_cast<long long>(Magnitude(from)));
+				buf += '\t';
+				buf += Strand(from);
+				buf += '\t';
+				buf += std::to_string(static_cast<long long>(Magnitude(to)));
+				buf += '\t';
+				buf += Strand(to);
+				buf += '\t';
+				buf += std::to_string(links.count[r]);
+				buf += '\t';
+				buf += std::to_string(links.same[r]);
+				buf += '\n';
+				if (buf.size() > (size_t(1) << 20)) flush();
+			}
+
+			flush();
+			good = good && std::fflush(f) == 0;
+			if (f != stdout) good = (std::fclose(f) == 0) && good;
+			if (!good)
+			{
+				if (f != stdout) ::unlink(path.c_str());
+				throw std::runtime_error("Can't write the link table");
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{
 			WriteGraphFileWith(format, seq, outPath, [&](int fd, uint64_t fileOffset)
 			{
 				return FormatEvents(table, seq, loaded, k, format, threads, fd, fileOffset);
-			});
+			}, format == "gfa1" && table.linkFirst != 0);
 		}
 	}
 }

@@ -199,6 +199,28 @@ namespace TwoPaCo
 			}
 		};
 
+		// The COMPACT gfa1: the gfa1 text without its C lines and with every link once -- the L line of an event is printed only
+		// when the event closes the first occurrence of its link (the link_first bits of include/twopaco_hip.h's link table; the
+		// caller announces the bit of an event with NextLink before it hands the event to Segment).  S lines with a body and P
+		// lines are what Gfa1Sink prints.
+		class CompactGfa1Sink : public Gfa1Sink
+		{
+		public:
+			CompactGfa1Sink(Out & out, const InputSequences & seq) : Gfa1Sink(out, seq), printLink_(false) {}
+			void NextLink(bool first) { printLink_ = first; }
+
+		protected:
+			void Occurrence(const SegmentEvent &, size_t) {}
+
+			void Link(int64_t a, uint64_t aSize, int64_t b, uint64_t bSize, size_t k)
+			{
+				if (printLink_) Gfa1Sink::Link(a, aSize, b, bSize, k);
+			}
+
+		private:
+			bool printLink_;
+		};
+
 		class Gfa2Sink : public GfaSink
 		{
 		public:
@@ -261,14 +283,16 @@ namespace TwoPaCo
 			const uint32_t * end;            // [events]
 			uint64_t sequences;
 			const uint32_t * seqEventBegin;  // [sequences + 1]
-			EventTable() : events(0), name(0), first(0), begin(0), end(0), sequences(0), seqEventBegin(0) {}
+			const uint32_t * linkFirst;      // optional, laid out as first: the link table's first bits.  Given, gfa1 is formatted COMPACT
+			EventTable() : events(0), name(0), first(0), begin(0), end(0), sequences(0), seqEventBegin(0), linkFirst(0) {}
 		};
 
 		bool IsGraphFormat(const std::string & format);  // gfa1, gfa2, fasta
 
 		// The lines in front of the first segment, as graphdump prints them: "H\tVN:Z:..." and, for gfa1, one S line per input
 		// sequence whose UR:Z: tag is the file's name as it was given.
-		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out);
+		// compact (gfa1 only): the H line alone.
+		void HeaderLines(const std::string & format, const InputSequences & seq, Out & out, bool compact = false);
 
 		// Everything the formatter indexes with is checked here (the table may come from anywhere): the sequences' event ranges
 		// ascend from 0 to the event count, there are as many sequences as the FASTA files hold, every event lies inside its
@@ -285,7 +309,7 @@ namespace TwoPaCo
 		// The file outPath (created or truncated; removed again when anything fails): the header lines, then what `events` writes
 		// from the offset it is given on (it returns its bytes); the file is truncated to the sum.
 		void WriteGraphFileWith(const std::string & format, const InputSequences & seq, const std::string & outPath,
-			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events);
+			const std::function<uint64_t(int fd, uint64_t fileOffset)> & events, bool compact = false);
 
 		// What the device formatter (include/twopaco_hip.h: tpc_segments_text_plan) takes beside the event table: the names as they
 		// are printed, as one blob with offsets, and the letter at every ambiguous position in the order of the positions.
@@ -350,7 +374,30 @@ namespace TwoPaCo
 		// "#hist" lines of the non-empty bins.  To stdout (path empty) or into the file `path` (removed again when writing fails).
 		void WriteColors(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const std::string & path);
 
-		// Header lines and events into the file outPath (created or truncated; removed again when anything fails).
+		// ---------------------------------------------------------------------------------------- the link table
+		// Every distinct link of the graph once (include/twopaco_hip.h, the tpc_segments_links_* group, defines occurrence, class,
+		// rows and first bits).  The arrays come from ComputeLinks below -- the serial statement -- or from the device
+		// (csrc/tpc_links.hip); WriteLinks prints either as the same bytes.
+		struct LinkTable
+		{
+			uint64_t occurrences;
+			std::vector<uint32_t> firstEvent, count, same;   // [rows]
+			std::vector<uint32_t> linkFirst;                 // [(events + 31) / 32]
+			LinkTable() : occurrences(0) {}
+			size_t Rows() const { return firstEvent.size(); }
+		};
+
+		// One pass over the events with a hash map from the class -- the smaller of (a, b) and (-b, -a) -- to its row.  The table
+		// must be one whose walk did not fail.
+		void ComputeLinks(const EventTable & table, LinkTable & out);
+
+		// The TSV text: "#twopaco-links\t1\tk=<k>\tsegments=<S>\tlinks=<N>\toccurrences=<M>", then one line per row as it is spelled:
+		// |from|, its strand, |to|, its strand, count, same.  To stdout (path empty) or into the file `path` (removed again when
+		// writing fails).
+		void WriteLinks(const EventTable & table, size_t k, uint64_t segments, const LinkTable & links, const std::string & path);
+
+		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
+		// the table carries linkFirst.
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath);
 	}

@@ -3,6 +3,7 @@
 // Downstream consumer of the junction stream, kept flag- and byte-compatible with the reference's
 // graphdump (reference src/graphdump/graphdump.cpp) so that pipelines built on it are unchanged:
 //   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>] [--text host|device]
+//             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]   (the last two instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -33,6 +34,15 @@
 // their number of colours -- as TSV (graphformat.h: WriteColors).  Without --gpu the serial walk collects the event table and
 // ComputeColors groups it; with --gpu the device does both (csrc/tpc_colors.hip); the bytes are the same.  A stream the walk
 // refuses prints the walk's error and nothing else, and creates no file.
+// --links [--links-out <path>] (an addition; instead of -f): the link table -- every distinct link between two segments once, as it
+// is spelled where the walk first meets it, with the number of its occurrences (the L lines of gfa1) and how many of them are
+// spelled that way; (a, b) and (-b, -a) are one link -- as TSV (graphformat.h: WriteLinks; include/twopaco_hip.h defines the table).
+// Without --gpu the serial walk collects the event table and ComputeLinks groups it; with --gpu the device does both
+// (csrc/tpc_links.hip); the bytes are the same.
+// -f gfa1 --compact (an addition): the gfa1 text without the per-sequence S header lines, without the C lines, and with every link
+// once (the L line of its first occurrence); the H line, the S lines with a body and the P lines are byte for byte those of gfa1.
+// Serial or with --gpu, the same bytes.  The whole table is known before the first byte is printed: a stream the walk refuses
+// prints the walk's error and nothing else.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -350,6 +360,52 @@ namespace
 		WriteColors(table, k, map, colors, outPath);
 	}
 
+	// ---------------------------------------------------------------------------------------- --links and --compact, serial
+	struct SerialTable
+	{
+		InputSequences seq;
+		LoadedSequences loaded;
+		EventCollector events;
+		std::vector<uint32_t> seqEventBegin;
+		EventTable table;
+		LinkTable links;
+	};
+
+	// the walk's event table and its links; nothing is printed before both are complete
+	void WalkLinks(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bodies, SerialTable & out)
+	{
+		if (bodies) LoadSequences(fasta, prefix, 1, out.seq, out.loaded);
+		else ListSequences(fasta, prefix, out.seq);
+		WalkSegments(binFile, fasta, k, out.events);
+		out.events.Table(out.seq.name.size(), out.seqEventBegin, out.table);
+		ComputeLinks(out.table, out.links);
+	}
+
+	uint64_t CountFirstBits(const EventTable & table)
+	{
+		uint64_t n = 0;
+		for (uint64_t w = 0; w < (table.events + 31) / 32; w++) n += uint64_t(__builtin_popcount(table.first[w]));
+		return n;
+	}
+
+	void DumpLinks(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, const std::string & outPath)
+	{
+		SerialTable t;
+		WalkLinks(binFile, fasta, k, prefix, false, t);
+		WriteLinks(t.table, k, CountFirstBits(t.table), t.links, outPath);
+	}
+
+	void DumpCompact(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix)
+	{
+		SerialTable t;
+		WalkLinks(binFile, fasta, k, prefix, true, t);
+		t.table.linkFirst = t.links.linkFirst.data();
+		Out head(false);
+		HeaderLines("gfa1", t.seq, head, true);
+		std::fwrite(head.Text().data(), 1, head.Text().size(), stdout);
+		FormatEvents(t.table, t.seq, t.loaded, k, "gfa1", 1, -1, 0);
+	}
+
 	// ---------------------------------------------------------------------------------------- --gpu
 	double MsSince(const std::chrono::steady_clock::time_point & t0)
 	{
@@ -360,10 +416,11 @@ namespace
 	{
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
-		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs;
+		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
+		uint64_t links, linkOccurrences;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), threads(1) {}
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -374,9 +431,11 @@ namespace
 			if (!f) return;
 			std::fprintf(f, "{\"path\": \"%s\", \"events\": %llu, \"segments\": %llu, \"n_named\": %llu, \"device_ms\": %.3f, \"kernel_ms\": %.3f, \"load_ms\": %.3f, "
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
-				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f, "
+				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
-				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs);
+				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
+				(unsigned long long)linkOccurrences);
 			std::fclose(f);
 		}
 	};
@@ -402,6 +461,10 @@ namespace
 		decltype(&tpc_segments_colors_fetch_rows) segmentsColorsFetchRows;
 		decltype(&tpc_segments_colors_fetch_presence) segmentsColorsFetchPresence;
 		decltype(&tpc_segments_colors_fetch_hist) segmentsColorsFetchHist;
+		decltype(&tpc_segments_links_build) segmentsLinksBuild;
+		decltype(&tpc_segments_links_info) segmentsLinksInfo;
+		decltype(&tpc_segments_links_fetch_rows) segmentsLinksFetchRows;
+		decltype(&tpc_segments_links_fetch_first) segmentsLinksFetchFirst;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -436,6 +499,10 @@ namespace
 			Load(segmentsColorsFetchRows, "tpc_segments_colors_fetch_rows");
 			Load(segmentsColorsFetchPresence, "tpc_segments_colors_fetch_presence");
 			Load(segmentsColorsFetchHist, "tpc_segments_colors_fetch_hist");
+			Load(segmentsLinksBuild, "tpc_segments_links_build");
+			Load(segmentsLinksInfo, "tpc_segments_links_info");
+			Load(segmentsLinksFetchRows, "tpc_segments_links_fetch_rows");
+			Load(segmentsLinksFetchFirst, "tpc_segments_links_fetch_first");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -603,10 +670,57 @@ namespace
 		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] colour table on device: %.3f ms (kernels %.3f ms)\n", stats.colorsMs, stats.colorsKernelMs);
 	}
 
+	// The link table of the table on the device (csrc/tpc_links.hip), fetched: rows when wanted, and the first bits.
+	void LinksOnDevice(DeviceLibrary & lib, uint64_t events, bool rows, LinkTable & links, DumpStats & stats)
+	{
+		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsLinksBuild(lib.ctx), "tpc_segments_links_build");
+		stats.linksKernelMs = lib.kernelMs(lib.ctx, TPC_K_LINKS);
+		uint64_t info[4] = {0, 0, 0, 0};
+		lib.Check(lib.segmentsLinksInfo(lib.ctx, info), "tpc_segments_links_info");
+		stats.links = info[0];
+		stats.linkOccurrences = info[1];
+		links.occurrences = info[1];
+		if (rows)
+		{
+			links.firstEvent.resize(info[0]);
+			links.count.resize(info[0]);
+			links.same.resize(info[0]);
+			lib.Check(lib.segmentsLinksFetchRows(lib.ctx, 0, info[0], links.firstEvent.data(), links.count.data(), links.same.data()), "tpc_segments_links_fetch_rows");
+		}
+		else
+		{
+			links.linkFirst.resize((events + 31) / 32);
+			lib.Check(lib.segmentsLinksFetchFirst(lib.ctx, 0, links.linkFirst.size(), links.linkFirst.data()), "tpc_segments_links_fetch_first");
+		}
+
+		stats.linksMs = MsSince(t0);
+		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] link table on device: %.3f ms (kernels %.3f ms)\n", stats.linksMs, stats.linksKernelMs);
+	}
+
+	// --links with --gpu: the table stays on the device, where the link stage finds the distinct links (csrc/tpc_links.hip); what
+	// is fetched is the rows, and the event table for the names.
+	void DumpLinksOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const LoadedSequences & loaded, const std::string & outPath, DumpStats & stats)
+	{
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+		size_t sequences = 0;
+		std::chrono::steady_clock::time_point t0;
+		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
+		LinkTable links;
+		LinksOnDevice(lib, counts[0], true, links, stats);
+		FetchedTable held;
+		FetchTable(lib, counts[0], sequences, held);
+		stats.deviceMs = MsSince(t0);
+		t0 = std::chrono::steady_clock::now();
+		WriteLinks(held.table, k, counts[1], links, outPath);
+		stats.formatMs = MsSince(t0);
+	}
+
 	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The formatter of
 	// graphformat.h reads the table and the letters, never the stream's bytes.
 	void DumpSegmentsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, bool textOnDevice)
+		const std::string & format, const InputSequences & seq, const LoadedSequences & loaded, Out & out, DumpStats & stats, bool textOnDevice, bool compact)
 	{
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 		size_t sequences = 0;
@@ -643,12 +757,26 @@ namespace
 		// the device's scans left them
 		FetchedTable held;
 		stats.indexMs = FetchTable(lib, counts[0], sequences, held);
-		const EventTable & table = held.table;
+		EventTable & table = held.table;
+		LinkTable links;
+		if (compact)
+		{
+			LinksOnDevice(lib, counts[0], false, links, stats);
+			table.linkFirst = links.linkFirst.data();
+		}
+
 		stats.deviceMs = MsSince(t0) - stats.indexMs;
 
 		// format: contiguous chunks of events, each into its own buffer, buffers to stdout in order
 		t0 = std::chrono::steady_clock::now();
 		out.Flush();
+		if (!out.Text().empty())
+		{
+			// (--compact holds its header line back until the table is known to be good)
+			std::fwrite(out.Text().data(), 1, out.Text().size(), stdout);
+			out.Text().clear();
+		}
+
 		FormatEvents(table, seq, loaded, k, format, threads, -1, 0);
 		stats.formatMs = MsSince(t0);
 	}
@@ -662,7 +790,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -679,6 +807,13 @@ namespace
 			"     histogram of segments by number of colours.  Needs -k and -s.  With --gpu the table is grouped on the device.\n"
 			"     Not with --text; --prefix is accepted and changes nothing (sequence names are not printed).\n\n"
 			"   --colors-out <file name>\n     with --colors: write the table there instead of to the standard output\n\n"
+			"   --links\n     instead of -f: the link table as TSV -- every distinct link between two segments once, as spelled where it is\n"
+			"     first met (segment, strand, segment, strand), its occurrences (the L lines of gfa1) and how many of them are spelled\n"
+			"     that way; a b and -b -a are one link.  Needs -k and -s.  With --gpu the links are found on the device.\n"
+			"     Not with --colors or --text.\n\n"
+			"   --links-out <file name>\n     with --links: write the table there instead of to the standard output\n\n"
+			"   --compact\n     with -f gfa1: no per-sequence S header lines, no C lines, and every link once (the L line of its first\n"
+			"     occurrence); everything else as gfa1.  Serial or with --gpu; not with --text device.\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -688,9 +823,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut;
+		std::string binFile, format, colorsBy, colorsOut, linksOut;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false;
+		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -741,6 +876,9 @@ int main(int argc, char * argv[])
 				if (colorsBy != "file" && colorsBy != "sequence") throw ArgError("Value '" + colorsBy + "' does not meet constraint: file|sequence", "Argument: (--colors)");
 			}
 			else if (a == "--colors-out") { colorsOut = value("(--colors-out)"); colorsOutSet = true; }
+			else if (a == "--links") links = true;
+			else if (a == "--links-out") { linksOut = value("(--links-out)"); linksOutSet = true; }
+			else if (a == "--compact") compact = true;
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -765,11 +903,17 @@ int main(int argc, char * argv[])
 		if (colors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--colors)");
 		if (colors && textSet) throw ArgError("The colour table is formatted by the host: not with --colors", "(--text)");
 		if (colorsOutSet && !colors) throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
+		if (links && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--links)");
+		if (links && colors) throw ArgError("The link table and the colour table are written one at a time: not with --colors", "(--links)");
+		if (links && textSet) throw ArgError("The link table is formatted by the host: not with --links", "(--text)");
+		if (linksOutSet && !links) throw ArgError("This argument needs --links", "(--links-out)");
+		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
+		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -778,7 +922,7 @@ int main(int argc, char * argv[])
 		stats.threads = lib ? threads : 1;
 		const bool deviceText = lib && textOnDevice;
 		stats.text = deviceText ? "device" : "host";
-		Out out(!deviceText);  // --text device: the header lines wait until the table is known to be good
+		Out out(!deviceText && !compact);  // --text device, --compact: the header lines wait until the table is known to be good
 		if (colors && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -789,6 +933,16 @@ int main(int argc, char * argv[])
 			DumpColorsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, colorsBy == "sequence", colorsOut, stats);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut);
+		else if (links && lib)
+		{
+			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+			InputSequences seq;
+			LoadedSequences loaded;
+			LoadSequences(fasta, prefix, threads, seq, loaded);
+			stats.loadMs = MsSince(t0);
+			DumpLinksOnDevice(*lib, binFile, fasta, k, threads, loaded, linksOut, stats);
+		}
+		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);
 		else if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device
@@ -799,16 +953,17 @@ int main(int argc, char * argv[])
 			if (format == "gfa2") out << "H\tVN:Z:2.0\n";
 			LoadSequences(fasta, format == "fasta" ? true : prefix, threads, seq, loaded);
 			stats.loadMs = MsSince(t0);
-			if (format == "gfa1")
+			if (format == "gfa1" && !compact)
 			{
 				for (const std::string & name : seq.name) out << "S\t" << name << "\t*\tUR:Z:" << seq.file[name] << '\n';
 			}
 
-			DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, format, seq, loaded, out, stats, deviceText);
+			DumpSegmentsOnDevice(*lib, binFile, fasta, k, threads, format, seq, loaded, out, stats, deviceText, compact);
 		}
 		else if (format == "seq") DumpSeq(binFile, out);
 		else if (format == "group") DumpGroups(binFile, out);
 		else if (format == "dot") DumpDot(binFile, out);
+		else if (compact) DumpCompact(binFile, fasta, k, prefix);
 		else
 		{
 			InputSequences seq;

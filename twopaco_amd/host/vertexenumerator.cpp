@@ -344,6 +344,10 @@ namespace TwoPaCo
 				if (colors && options.colorsBy != "file" && options.colorsBy != "sequence") throw std::runtime_error("The colours must be one of file, sequence");
 				if (colors && options.colorsFile.empty()) throw std::runtime_error("The colour table needs an output file name");
 				if (colors && sharded) throw std::runtime_error("The colour table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				const bool links = !options.linksFile.empty();
+				if (links && sharded) throw std::runtime_error("The link table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
+				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
 				const size_t capacity = (vertexLength + 4 + 31) / 32;  // CalculateNeededCapacity
 				if (capacity >= 20)
@@ -476,7 +480,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors)
+				if (graph || colors || links)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -974,7 +978,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -987,7 +991,7 @@ namespace TwoPaCo
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
-				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty();
+				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1010,6 +1014,7 @@ namespace TwoPaCo
 					Check(tpc_segments_counts(ctx_, counts), "segments_counts");
 					Check(tpc_segments_error(ctx_, &errorSlot, &errorKind), "segments_error");
 					timer.Lap("segment table");
+					if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   segments_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_SEGMENTS) << " ms" << std::endl;
 					if (errorKind != TPC_SEG_OK)
 					{
 						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
@@ -1020,17 +1025,37 @@ namespace TwoPaCo
 					DeviceColors deviceColors;
 					if (colors && !(graph && options.graphTextOnDevice)) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
 					if (colors) ColorsFromDevice(options, fileName, seq, counts, name, begin, end, seqEventBegin, deviceColors, timer);
+					// the link table likewise: found on the device before the graph is written (the compact graph needs its first
+					// bits), its file written after it
+					GraphFormat::LinkTable deviceLinks;
+					bool fetched = colors && !(graph && options.graphTextOnDevice);
+					if ((links || compact) && !fetched && !(graph && options.graphTextOnDevice))
+					{
+						FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+						fetched = true;
+					}
+
+					if (links || compact) LinksFromDevice(counts[0], links, compact, name, deviceLinks, timer);
 					if (graph && options.graphTextOnDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph)
 					{
-						if (!colors) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
-						WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, options, seq, loaded, k, threads, timer);
+						if (!fetched) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+						WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, compact ? deviceLinks.linkFirst.data() : 0, options, seq, loaded, k, threads, timer);
 					}
 
 					if (colors)
 					{
 						GraphFormat::WriteColors(deviceColors.events, k, deviceColors.map, deviceColors.table, options.colorsFile);
 						timer.Lap("colour table writing");
+					}
+
+					if (links)
+					{
+						GraphFormat::EventTable events;
+						events.events = counts[0];
+						events.name = name.data();
+						GraphFormat::WriteLinks(events, k, counts[1], deviceLinks, options.linksFile);
+						timer.Lap("link table writing");
 					}
 
 					return;
@@ -1049,18 +1074,62 @@ namespace TwoPaCo
 					timer.Lap("colour table writing");
 				}
 
-				if (graph) WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, options, seq, loaded, k, threads, timer);
+				const std::vector<uint32_t> noBits(1, 0);
+				if (graph) WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, compact ? noBits.data() : 0, options, seq, loaded, k, threads, timer);
+				if (links)
+				{
+					// nothing dispatched: no event, the header alone
+					GraphFormat::EventTable empty;
+					empty.sequences = sequences;
+					empty.seqEventBegin = seqEventBegin.data();
+					GraphFormat::LinkTable table;
+					GraphFormat::ComputeLinks(empty, table);
+					GraphFormat::WriteLinks(empty, k, 0, table, options.linksFile);
+					timer.Lap("link table writing");
+				}
+			}
+
+			// --links / the compact graph: the distinct links of the table on the device found there (csrc/tpc_links.hip); fetched are
+			// the rows (for the link file) and the first bits (for the compact text).  The rows' names come from name[], fetched
+			// here when nothing else fetched it (--graph-text device keeps the table on the device).
+			void LinksFromDevice(uint64_t events, bool rows, bool bits, std::vector<int64_t> & name, GraphFormat::LinkTable & out, PhaseTimer & timer)
+			{
+				Check(tpc_segments_links_build(ctx_), "segments_links_build");
+				timer.Lap("segment links");
+				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   links_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_LINKS) << " ms" << std::endl;
+				uint64_t info[4] = {0, 0, 0, 0};
+				Check(tpc_segments_links_info(ctx_, info), "segments_links_info");
+				out.occurrences = info[1];
+				if (rows)
+				{
+					out.firstEvent.resize(info[0]); out.count.resize(info[0]); out.same.resize(info[0]);
+					Check(tpc_segments_links_fetch_rows(ctx_, 0, info[0], out.firstEvent.data(), out.count.data(), out.same.data()), "segments_links_fetch_rows");
+					if (name.empty() && events)
+					{
+						name.resize(events);
+						Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
+					}
+				}
+
+				if (bits)
+				{
+					out.linkFirst.assign(std::max<size_t>(1, size_t((events + 31) / 32)), 0);
+					Check(tpc_segments_links_fetch_first(ctx_, 0, (events + 31) / 32, out.linkFirst.data()), "segments_links_fetch_first");
+				}
+
+				timer.Lap("segment links fetch");
 			}
 
 			void WriteGraphFromTable(uint64_t events, const std::vector<int64_t> & name, const std::vector<uint32_t> & first, const std::vector<uint32_t> & begin,
-				const std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin, const EnumeratorOptions & options, const GraphFormat::InputSequences & seq,
-				const GraphFormat::LoadedSequences & loaded, size_t k, size_t threads, PhaseTimer & timer)
+				const std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin, const uint32_t * linkFirst, const EnumeratorOptions & options,
+				const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, size_t k, size_t threads, PhaseTimer & timer)
 			{
 				GraphFormat::EventTable table;
 				table.events = events;
 				table.name = name.data(); table.first = first.data(); table.begin = begin.data(); table.end = end.data();
 				table.sequences = seqEventBegin.size() - 1;
 				table.seqEventBegin = seqEventBegin.data();
+				table.linkFirst = linkFirst;   // given: the compact gfa1
 				GraphFormat::CheckEventTable(table, loaded, k, threads);
 				GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
 				timer.Lap("graph formatting + writing");

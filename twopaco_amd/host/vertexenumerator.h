@@ -77,6 +77,12 @@ namespace TwoPaCo
 		// uses, built once for both.  One GPU.
 		std::string colorsBy;
 		std::string colorsFile;
+		// The link table (graphformat.h: WriteLinks; `graphdump --links` writes the same bytes for the junction stream of this run):
+		// linksFile (empty: off).  The distinct links are found on the device (tpc_segments_links_build) over the same segment
+		// table.  graphCompact (graphFormat gfa1, host text only): the graph file is the compact gfa1 of `graphdump -f gfa1
+		// --compact` -- no per-sequence S lines, no C lines, every link once -- from the same link stage.  One GPU.
+		std::string linksFile;
+		bool graphCompact;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
@@ -86,7 +92,7 @@ namespace TwoPaCo
 		bool autoFilterSize;
 		bool autoRounds;
 		EnumeratorOptions() : pinnedSeed(false), seed(0), device(0), insertTestFirst(false), gpus(1), rccl(true), emulateRanks(false), forceSharded(false),
-			graphPrefix(false), graphThreads(16), graphTextOnDevice(false), autoFilterSize(false), autoRounds(false) {}
+			graphPrefix(false), graphThreads(16), graphTextOnDevice(false), graphCompact(false), autoFilterSize(false), autoRounds(false) {}
 	};
 
 	std::unique_ptr<VertexEnumerator> CreateEnumerator(const std::vector<std::string> & fileName,
