@@ -61,7 +61,8 @@ enum {
     TPC_K_SKETCH = 17,      /* tpc_distinct_sketch: HyperLogLog registers of the distinct canonical (k+1)-mers (no counterpart in the reference) */
     TPC_K_COLORS = 18,      /* tpc_segments_colors_build: rows, counts and presence bits of the segment colour table (no counterpart in the reference) */
     TPC_K_LINKS = 19,       /* tpc_segments_links_build: the device hash set of the distinct links, their counts and first bits (no counterpart in the reference) */
-    TPC_K_COUNT = 20
+    TPC_K_BUBBLES = 20,     /* tpc_segments_bubbles_build: arcs, degrees, the simple bubbles and the degree histogram (no counterpart in the reference) */
+    TPC_K_COUNT = 21
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -580,6 +581,53 @@ int tpc_segments_links_build(tpc_ctx *ctx);
 int tpc_segments_links_info(tpc_ctx *ctx, uint64_t *info /* [4] */);
 int tpc_segments_links_fetch_rows(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *first_event_host, uint32_t *count_host, uint32_t *same_host);
 int tpc_segments_links_fetch_first(tpc_ctx *ctx, uint64_t word0, uint64_t n_words, uint32_t *bits_host);
+
+/* The SIMPLE BUBBLES of the compacted graph (csrc/tpc_bubbles.hip): where the genomes differ.  Two segments leave one side of a
+ * segment, touch nothing else, and meet again at one side of another segment: a substitution, a short insertion or a short deletion
+ * between genomes; the colour rows of the two arms say which genomes carry which allele.  No counterpart in the reference;
+ * ComputeBubbles of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The definition, over the
+ * link table of the last tpc_segments_links_build:
+ *   ROW              a segment, in the order of gfa1's S lines with a body: the rows of the colour table.
+ *   SIDE             an oriented segment, code = row * 2 + (1 when the strand is '-'), in 32 bits; rev(code) = code ^ 1.  2^31 segments
+ *                    or more are refused: the code of all ones is kept for "no side" (the lo of a side of degree 0).
+ *   ARCS             a link row spelled (from, to) gives the arc from -> to and the arc rev(to) -> rev(from).  When the two are one arc
+ *                    (a+ a-, its own reverse) it counts ONCE.  A self-loop a+ a+ gives two different arcs, a+ -> a+ and a- -> a-.
+ *   OUT SET, DEGREE  out(u): the heads of the arcs that leave side u.  The link table holds every class once, so no arc arrives twice.
+ *                    deg(u) = |out(u)|.  The in-neighbours of v are the rev of out(rev(v)).
+ *   SIMPLE BUBBLE at side s, when all of these hold:
+ *                      out(s) = {a, b}, two members;
+ *                      deg(rev(a)) == 1 and deg(rev(b)) == 1: s is the only way in to each arm;
+ *                      deg(a) == 1, deg(b) == 1 and out(a) == out(b) == {t};
+ *                      deg(rev(t)) == 2;
+ *                      the rows of s, a, b, t are four different rows (no hairpin, no inversion read as a bubble, no arm that is a
+ *                      self-loop).
+ *   CANONICAL ORIENTATION  every bubble is found twice, at s and at rev(t) with the arms rev(a), rev(b) and the sink rev(s).  It is
+ *                    reported ONCE, in the orientation whose source code is the smaller.
+ *   ARM ORDER        arm_a is the arm with the smaller code in the reported orientation.
+ *   ROW ORDER        bubble rows ascend by source code; a side is the source of at most one bubble, so the order is total.
+ *   NOT BUBBLES      three or more alleles at one place (deg(s) >= 3), nested bubbles and longer superbubbles are not simple bubbles
+ *                    and are not reported: that is the definition.
+ *   SIDE ARRAYS      deg[u], lo[u] = the smallest and hi[u] = the largest member of out(u), for every side u; with deg[u] == 0 lo is all
+ *                    ones and hi is 0.  The definition reads only sides of degree 1 (lo is the neighbour) and 2 (lo, hi are the two).
+ *   HISTOGRAM        hist[d] = the sides of degree d for d = 0 .. 4, hist[5] = those of degree 5 or more; hist[0] are the dead ends.
+ * Separate from the build and opt-in: a context that never calls it holds none of this; tpc_segments_counts, the colour outputs and the
+ * link outputs are what they were, in any order of the three builds.
+ *   tpc_segments_bubbles_build       over the link table of the last tpc_segments_links_build.  Refused with an error text: no segment
+ *                                    table, a table whose tpc_segments_error kind is not TPC_SEG_OK, no link table, 2^31 segments
+ *                                    or more, buffers beyond the free device memory; the context stays usable.  Kept until the next
+ *                                    segment, link or bubble build: 16 B per bubble, 12 B per side and 48 B of histogram.  TPC_K_BUBBLES
+ *                                    times the stage on the stream from its first kernel to its last, the host's one wait for the
+ *                                    bubble count and the allocation of the rows included, as TPC_K_LINKS times the link stage.
+ *   tpc_segments_bubbles_info        info[0] bubbles, [1] sides (2 x segments), [2] arcs, [3] the stage's device bytes at their peak
+ *   tpc_segments_bubbles_fetch_rows  source / arm_a / arm_b / sink (side codes) of bubbles [b0, b0 + n) to the host
+ *   tpc_segments_bubbles_fetch_sides deg / lo / hi of sides [c0, c0 + n) to the host
+ *   tpc_segments_bubbles_fetch_hist  the six bins
+ * A range outside a table is refused with an error text. */
+int tpc_segments_bubbles_build(tpc_ctx *ctx);
+int tpc_segments_bubbles_info(tpc_ctx *ctx, uint64_t *info /* [4]: bubbles, sides, arcs, peak device bytes */);
+int tpc_segments_bubbles_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *source, uint32_t *arm_a, uint32_t *arm_b, uint32_t *sink);
+int tpc_segments_bubbles_fetch_sides(tpc_ctx *ctx, uint64_t c0, uint64_t n, uint32_t *deg, uint32_t *lo, uint32_t *hi);
+int tpc_segments_bubbles_fetch_hist(tpc_ctx *ctx, uint64_t *hist /* [6] */);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

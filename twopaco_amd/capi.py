@@ -10,7 +10,7 @@ from .build import lib_dir
 
 INVALID_VERTEX = (1 << 63) - 1
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
-           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19}
+           "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -30,7 +30,8 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_build_host", "tpc_segments_build_resident", "tpc_segments_counts", "tpc_segments_error", "tpc_segments_fetch_names", "tpc_segments_fetch_first",
                "tpc_segments_fetch_events", "tpc_segments_fetch_sequences", "tpc_segments_text_plan", "tpc_segments_text_fetch", "tpc_segments_text_write", "tpc_distinct_sketch",
                "tpc_segments_colors_build", "tpc_segments_colors_info", "tpc_segments_colors_fetch_rows", "tpc_segments_colors_fetch_presence", "tpc_segments_colors_fetch_hist",
-               "tpc_segments_links_build", "tpc_segments_links_info", "tpc_segments_links_fetch_rows", "tpc_segments_links_fetch_first"]
+               "tpc_segments_links_build", "tpc_segments_links_info", "tpc_segments_links_fetch_rows", "tpc_segments_links_fetch_first",
+               "tpc_segments_bubbles_build", "tpc_segments_bubbles_info", "tpc_segments_bubbles_fetch_rows", "tpc_segments_bubbles_fetch_sides", "tpc_segments_bubbles_fetch_hist"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -163,6 +164,11 @@ def hip():
         L.tpc_segments_links_info.argtypes = [p, p]
         L.tpc_segments_links_fetch_rows.argtypes = [p, u64, u64, p, p, p]
         L.tpc_segments_links_fetch_first.argtypes = [p, u64, u64, p]
+        L.tpc_segments_bubbles_build.argtypes = [p]
+        L.tpc_segments_bubbles_info.argtypes = [p, p]
+        L.tpc_segments_bubbles_fetch_rows.argtypes = [p, u64, u64, p, p, p, p]
+        L.tpc_segments_bubbles_fetch_sides.argtypes = [p, u64, u64, p, p, p]
+        L.tpc_segments_bubbles_fetch_hist.argtypes = [p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -655,6 +661,38 @@ class Context:
             n_words = (self.segments_counts()["events"] + 31) // 32 - word0
         out = np.zeros(max(n_words, 0), dtype=np.uint32)
         self._ck(hip().tpc_segments_links_fetch_first(self._h, word0, n_words, out.ctypes.data))
+        return out
+
+    def segments_bubbles_build(self):
+        """The simple bubbles (csrc/tpc_bubbles.hip) over the link table of the last segments_links_build.  Returns
+        segments_bubbles_info()."""
+        self._ck(hip().tpc_segments_bubbles_build(self._h))
+        return self.segments_bubbles_info()
+
+    def segments_bubbles_info(self):
+        """dict: bubbles, sides (2 x segments), arcs, peak_bytes (device memory of the stage)."""
+        c = np.zeros(4, dtype=np.uint64)
+        self._ck(hip().tpc_segments_bubbles_info(self._h, c.ctypes.data))
+        return dict(zip(("bubbles", "sides", "arcs", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_bubbles_fetch_rows(self, b0=0, n=None):
+        """(source, arm_a, arm_b, sink) of bubbles [b0, b0 + n) as uint32 side codes (row * 2 + 1 for '-'); n = None: to the last."""
+        n = self.segments_bubbles_info()["bubbles"] - b0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(4)]
+        self._ck(hip().tpc_segments_bubbles_fetch_rows(self._h, b0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_bubbles_fetch_sides(self, c0=0, n=None):
+        """(deg, lo, hi) of sides [c0, c0 + n) as uint32; n = None: to the last side."""
+        n = self.segments_bubbles_info()["sides"] - c0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(3)]
+        self._ck(hip().tpc_segments_bubbles_fetch_sides(self._h, c0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_bubbles_fetch_hist(self):
+        """uint64 [6]: the sides of degree 0, 1, 2, 3, 4 and 5 or more."""
+        out = np.zeros(6, dtype=np.uint64)
+        self._ck(hip().tpc_segments_bubbles_fetch_hist(self._h, out.ctypes.data))
         return out
 
     def filter_words(self):

@@ -6,6 +6,7 @@
 //   tpc_capi_segments.hip the segment table of the compacted graph and its text (tpc_segments_*)
 //   tpc_colors.hip        the segment colour table (tpc_segments_colors_*), kernels and entry points
 //   tpc_links.hip         the link table of the compacted graph (tpc_segments_links_*), kernels and entry points
+//   tpc_bubbles.hip       the simple bubbles of the compacted graph (tpc_segments_bubbles_*), kernels and entry points
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -126,6 +127,12 @@ struct tpc_ctx {
     uint64_t lnk_n_rows = 0, lnk_occurrences = 0, lnk_slots = 0, lnk_peak_bytes = 0;
     bool lnk_valid = false;
     int opt_links_slots_log2 = 0;            // option test_links_slots_log2 (tests only): slots of the link set, 0 = by the occurrences
+    // simple bubbles (tpc_segments_bubbles_*, tpc_bubbles.hip) of the last tpc_segments_bubbles_build; a new segment or link build drops them
+    uint32_t *bub_rows = nullptr;            // device, [4][bub_n_rows]: source, arm_a, arm_b, sink
+    uint32_t *bub_sides = nullptr;           // device, [3][bub_n_sides]: degree, smallest and largest neighbour
+    unsigned long long *bub_hist = nullptr;  // device, [6]: sides of degree 0, 1, 2, 3, 4, 5 or more
+    uint64_t bub_n_rows = 0, bub_n_sides = 0, bub_arcs = 0, bub_peak_bytes = 0;
+    bool bub_valid = false;
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors
@@ -239,6 +246,7 @@ int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
 void colors_drop(tpc_ctx *c);           // tpc_colors.hip
 void links_drop(tpc_ctx *c);            // tpc_links.hip
+void bubbles_drop(tpc_ctx *c);          // tpc_bubbles.hip
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -40,17 +40,6 @@ __device__ __forceinline__ uint64_t link_hash(uint64_t x)
     return x;
 }
 
-// row << 1 | strand of event e, 0xFFFFFFFF when the table does not know its segment (cannot happen after a good build)
-__device__ __forceinline__ uint32_t link_side(const int64_t *__restrict__ name, uint64_t e, uint64_t n_events, const uint32_t *__restrict__ table, uint64_t n_table,
-                                              const uint32_t *__restrict__ rank, uint64_t n_rows)
-{
-    const int64_t nm = name[e];
-    const uint64_t m = col_mag(nm);
-    const uint32_t e0 = (nm >= COL_FRESH || m >= n_table) ? (uint32_t)e : table[m];
-    const uint32_t row = e0 < n_events ? rank[e0] : 0xFFFFFFFFu;
-    return row < n_rows ? (row << 1) | (nm < 0 ? 1u : 0u) : 0xFFFFFFFFu;
-}
-
 // the spelling of the occurrence event e closes, LINK_EMPTY when e begins its sequence (or a side is unknown: *bad is set)
 __device__ __forceinline__ unsigned long long link_spelling(const int64_t *__restrict__ name, uint64_t e, uint64_t n_events, const uint32_t *__restrict__ table,
                                                             uint64_t n_table, const uint32_t *__restrict__ rank, uint64_t n_rows,
@@ -168,6 +157,7 @@ int tpc_segments_links_build(tpc_ctx *c)
 {
     if (!c) return -1;
     links_drop(c);
+    bubbles_drop(c);   // they were found over the link table that goes
     if (!c->seg_valid) return fail(c, -1, "segment links: build the segment table first (tpc_segments_build_host / _resident)");
     if (c->seg_err_kind != TPC_SEG_OK)
         return fail(c, -1, "segment links: the segment table holds the walk's error %d at slot %llu, there are no segments to link", c->seg_err_kind, (unsigned long long)c->seg_err_slot);

@@ -20,7 +20,11 @@
 // built once; one GPU);
 // --links [--links-out F]: the link table of the same graph -- every distinct link once with its occurrences -- as TSV, byte for
 // byte what `graphdump --links` writes (csrc/tpc_links.hip finds the links on the device; combines with --graph, --colors and -o);
-// --graph-compact: with --graph gfa1 the text `graphdump -f gfa1 --compact` prints, every link once.  Errors go to stderr as "\nError: <what>\n", exit code 1
+// --graph-compact: with --graph gfa1 the text `graphdump -f gfa1 --compact` prints, every link once;
+// --bubbles file|sequence [--bubbles-out F]: the simple bubbles of the same graph -- where two segments leave one side of a segment,
+// touch nothing else and meet again -- with the colours of the two arms, as TSV, byte for byte what `graphdump --bubbles` writes
+// (csrc/tpc_bubbles.hip finds them on the device over the link table; combines with --graph, --graph-compact, --colors, --links
+// and -o from one segment, colour and link build; --colors must name the same colours).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -77,6 +81,7 @@ namespace
 			<< "               [--graph-text <host|device>]" << std::endl
 			<< "               [--colors <file|sequence>] [--colors-out <file name>]" << std::endl
 			<< "               [--links] [--links-out <file name>] [--graph-compact]" << std::endl
+			<< "               [--bubbles <file|sequence>] [--bubbles-out <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -94,7 +99,13 @@ namespace
 			<< "               link between two segments once, as spelled where it is first met, its occurrences and how many of them" << std::endl
 			<< "               are spelled that way (a b and -b -a are one link).  Combines with --graph, --colors and -o.  One GPU only." << std::endl
 			<< "       --graph-compact: with --graph gfa1, the compact text: no per-sequence S lines, no C lines, every link once (what" << std::endl
-			<< "               graphdump -f gfa1 --compact prints).  Not with --graph-text device.  One GPU only." << std::endl;
+			<< "               graphdump -f gfa1 --compact prints).  Not with --graph-text device.  One GPU only." << std::endl
+			<< "       --bubbles: also write the simple bubbles of the graph as TSV to --bubbles-out (default de_bruijn.bubbles.tsv): where" << std::endl
+			<< "               two segments leave one side of a segment, touch nothing else and meet again at one side of another -- a" << std::endl
+			<< "               substitution or a short insertion or deletion between genomes.  Per bubble its source, arms and sink, the arms'" << std::endl
+			<< "               lengths, occurrences and colours (by file or by sequence, as --colors) and the colours that hold both arms." << std::endl
+			<< "               Simple bubbles only: three alleles at one place, nested bubbles and superbubbles are not reported." << std::endl
+			<< "               Combines with --graph, --graph-compact, --colors (the same colours), --links and -o.  One GPU only." << std::endl;
 	}
 }
 
@@ -135,7 +146,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -213,6 +224,13 @@ int main(int argc, char * argv[])
 			else if (Match(a, 0, "links")) { links = true; optionsSet = true; }
 			else if (Match(a, 0, "links-out")) { options.linksFile = value("(--links-out)"); linksOutSet = true; }
 			else if (Match(a, 0, "graph-compact")) { options.graphCompact = true; optionsSet = true; }
+			else if (Match(a, 0, "bubbles"))
+			{
+				options.bubblesBy = value("(--bubbles)");
+				if (options.bubblesBy != "file" && options.bubblesBy != "sequence") throw ArgError("Value '" + options.bubblesBy + "' does not meet constraint: file|sequence", "(--bubbles)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "bubbles-out")) { options.bubblesFile = value("(--bubbles-out)"); bubblesOutSet = true; }
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -275,6 +293,18 @@ int main(int argc, char * argv[])
 		else if (linksOutSet)
 		{
 			throw ArgError("This argument needs --links", "(--links-out)");
+		}
+
+		if (!options.bubblesBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The bubble table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--bubbles)");
+			if (!options.colorsBy.empty() && options.colorsBy != options.bubblesBy) throw ArgError("The bubble table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --bubbles " + options.bubblesBy, "(--bubbles)");
+			if (!bubblesOutSet) options.bubblesFile = "de_bruijn.bubbles.tsv";
+			if (options.bubblesFile.empty()) throw ArgError("The bubble table needs a file name", "(--bubbles-out)");
+		}
+		else if (bubblesOutSet)
+		{
+			throw ArgError("This argument needs --bubbles <file|sequence>", "(--bubbles-out)");
 		}
 
 		if (runTests)

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <unordered_map>
 
@@ -590,6 +591,158 @@ namespace TwoPaCo
 			{
 				if (f != stdout) ::unlink(path.c_str());
 				throw std::runtime_error("Can't write the link table");
+			}
+		}
+
+		void ComputeBubbles(const EventTable & t, const LinkTable & links, BubbleTable & out)
+		{
+			out = BubbleTable();
+			// the row of every segment: the order of the first sights, as ComputeColors numbers them
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			std::vector<uint32_t> rowOfEvent(size_t(t.events), 0);
+			uint64_t rows = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator seen = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				if (seen == rowOf.end())
+				{
+					if (name < FRESH) rowOf[name] = uint32_t(rows);
+					rowOfEvent[e] = uint32_t(rows++);
+				}
+				else rowOfEvent[e] = seen->second;
+			}
+
+			if (rows > (uint64_t(1) << 31)) throw std::runtime_error("bubble table: " + std::to_string(rows) + " segments, a side holds at most 2147483648");
+			out.sides = 2 * rows;
+			auto side = [&](uint64_t e) { return uint32_t(rowOfEvent[e] << 1 | (t.name[e] < 0 ? 1u : 0u)); };
+			auto rev = [](uint32_t code) { return code ^ 1u; };
+			std::vector<std::set<uint32_t> > outSet(size_t(out.sides));
+			for (uint32_t e0 : links.firstEvent)
+			{
+				if (e0 == 0 || e0 >= t.events) throw std::runtime_error("link table: a row's first event lies outside the event table");
+				const uint32_t from = side(e0 - 1), to = side(e0);
+				outSet[from].insert(to);
+				outSet[rev(to)].insert(rev(from));   // the same arc once more when the link is its own reverse: a set holds it once
+			}
+
+			for (const std::set<uint32_t> & heads : outSet)
+			{
+				out.arcs += heads.size();
+				out.hist[std::min<size_t>(heads.size(), 5)] += 1;
+			}
+
+			auto deg = [&](uint32_t u) { return outSet[u].size(); };
+			for (uint64_t code = 0; code < out.sides; code++)
+			{
+				const uint32_t s = uint32_t(code);
+				if (deg(s) != 2) continue;
+				const uint32_t a = *outSet[s].begin(), b = *outSet[s].rbegin();   // a < b: the arm order
+				if (deg(rev(a)) != 1 || deg(rev(b)) != 1) continue;
+				if (deg(a) != 1 || deg(b) != 1 || outSet[a] != outSet[b]) continue;
+				const uint32_t sink = *outSet[a].begin();
+				if (deg(rev(sink)) != 2) continue;
+				const std::set<uint32_t> four = {s >> 1, a >> 1, b >> 1, sink >> 1};
+				if (four.size() != 4) continue;
+				if (!(s < rev(sink))) continue;   // found at rev(sink) as well: reported where the source code is the smaller
+				out.source.push_back(s);
+				out.armA.push_back(a);
+				out.armB.push_back(b);
+				out.sink.push_back(sink);
+			}
+		}
+
+		void WriteBubbles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const BubbleTable & bubbles,
+			const std::string & path)
+		{
+			const size_t rows = colors.Rows(), words = colors.Words(), n = bubbles.Rows();
+			if (colors.occurrences.size() != rows || colors.nColors.size() != rows || colors.presence.size() != rows * words || map.label.size() != colors.colors)
+			{
+				throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			}
+
+			if (bubbles.armA.size() != n || bubbles.armB.size() != n || bubbles.sink.size() != n) throw std::runtime_error("bubble table: the arrays do not agree about the rows");
+			if (bubbles.sides != 2 * uint64_t(rows)) throw std::runtime_error("bubble table: its sides are not those of the colour table's rows");
+			for (uint32_t e0 : colors.firstEvent)
+			{
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+			}
+
+			for (const std::vector<uint32_t> * codes : {&bubbles.source, &bubbles.armA, &bubbles.armB, &bubbles.sink})
+			{
+				for (uint32_t code : *codes)
+				{
+					if (code >= bubbles.sides) throw std::runtime_error("bubble table: a side lies outside the segments");
+				}
+			}
+
+			std::FILE * f = path.empty() ? stdout : std::fopen(path.c_str(), "wb");
+			if (!f) throw std::runtime_error("Can't create the bubble table " + path);
+			std::string buf;
+			bool good = true;
+			auto flush = [&]() { good = good && std::fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); };
+			buf += "#twopaco-bubbles\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(colors.colors) +
+				"\tsegments=" + std::to_string(rows) + "\tlinks=" + std::to_string(links) + "\tbubbles=" + std::to_string(n) + "\n";
+			for (uint64_t c = 0; c < colors.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+			for (size_t d = 0; d < 6; d++)
+			{
+				if (bubbles.hist[d]) buf += "#sides\t" + std::to_string(d) + (d == 5 ? "+" : "") + "\t" + std::to_string(bubbles.hist[d]) + "\n";
+			}
+
+			const size_t digits = size_t((colors.colors + 3) / 4);
+			auto side = [&](uint32_t code)
+			{
+				buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[code >> 1]])));
+				buf += '\t';
+				buf += (code & 1u) ? '-' : '+';
+				buf += '\t';
+			};
+
+			auto hex = [&](uint32_t row)
+			{
+				const uint32_t * p = &colors.presence[size_t(row) * words];
+				for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(p[j >> 3] >> (4 * (j & 7))) & 15u];
+			};
+
+			for (size_t r = 0; r < n; r++)
+			{
+				const uint32_t a = bubbles.armA[r] >> 1, b = bubbles.armB[r] >> 1;
+				side(bubbles.source[r]);
+				side(bubbles.armA[r]);
+				side(bubbles.armB[r]);
+				side(bubbles.sink[r]);
+				const uint32_t ea = colors.firstEvent[a], eb = colors.firstEvent[b];
+				buf += std::to_string(static_cast<unsigned long long>(uint64_t(t.end[ea]) - t.begin[ea] + k));
+				buf += '\t';
+				buf += std::to_string(static_cast<unsigned long long>(uint64_t(t.end[eb]) - t.begin[eb] + k));
+				buf += '\t';
+				buf += std::to_string(colors.occurrences[a]);
+				buf += '\t';
+				buf += std::to_string(colors.occurrences[b]);
+				buf += '\t';
+				buf += std::to_string(colors.nColors[a]);
+				buf += '\t';
+				buf += std::to_string(colors.nColors[b]);
+				buf += '\t';
+				hex(a);
+				buf += '\t';
+				hex(b);
+				buf += '\t';
+				uint32_t both = 0;
+				for (size_t w = 0; w < words; w++) both += uint32_t(__builtin_popcount(colors.presence[size_t(a) * words + w] & colors.presence[size_t(b) * words + w]));
+				buf += std::to_string(both);
+				buf += '\n';
+				if (buf.size() > (size_t(1) << 20)) flush();
+			}
+
+			flush();
+			good = good && std::fflush(f) == 0;
+			if (f != stdout) good = (std::fclose(f) == 0) && good;
+			if (!good)
+			{
+				if (f != stdout) ::unlink(path.c_str());
+				throw std::runtime_error("Can't write the bubble table");
 			}
 		}
 

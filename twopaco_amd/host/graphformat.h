@@ -396,6 +396,35 @@ namespace TwoPaCo
 		// writing fails).
 		void WriteLinks(const EventTable & table, size_t k, uint64_t segments, const LinkTable & links, const std::string & path);
 
+		// ---------------------------------------------------------------------------------------- the simple bubbles
+		// Where the genomes differ: two segments leave one side of a segment, touch nothing else and meet again at one side of
+		// another (include/twopaco_hip.h, the tpc_segments_bubbles_* group, defines side, arc, degree, bubble, canonical orientation
+		// and the orders; simple bubbles only -- three alleles at one place, nested bubbles and superbubbles are not reported).  The
+		// arrays come from ComputeBubbles below -- the serial statement -- or from the device (csrc/tpc_bubbles.hip); WriteBubbles
+		// prints either as the same bytes.  A side is row * 2 + (1 when the strand is '-'), the rows being the colour table's.
+		struct BubbleTable
+		{
+			uint64_t sides, arcs;
+			std::vector<uint32_t> source, armA, armB, sink;   // [bubbles], side codes
+			uint64_t hist[6];                                 // sides of degree 0, 1, 2, 3, 4, 5 or more
+			BubbleTable() : sides(0), arcs(0), hist{0, 0, 0, 0, 0, 0} {}
+			size_t Rows() const { return source.size(); }
+		};
+
+		// The definition stated with std:: containers: the row of every segment by a hash map from |name|, the arcs of every link
+		// row into one std::set of heads per side, then every side against the definition.  The table must be one whose walk did
+		// not fail, `links` its link rows.
+		void ComputeBubbles(const EventTable & table, const LinkTable & links, BubbleTable & out);
+
+		// The TSV text: "#twopaco-bubbles\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tlinks=<N>\tbubbles=<B>", the colour
+		// table's "#color" lines, "#sides\t<degree>\t<count>" for the bins 0, 1, 2, 3, 4, 5+ that hold sides (0: the dead ends), then
+		// one line per bubble: source, arm_a, arm_b, sink each as |name| and strand, then of the two arms the lengths, occurrences,
+		// numbers of colours and presence hex of their colour rows, and the number of colours that hold both arms.  `colors` is the
+		// colour table of the same event table (its rows are the sides' rows).  To stdout (path empty) or into the file `path`
+		// (removed again when writing fails).
+		void WriteBubbles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const BubbleTable & bubbles,
+			const std::string & path);
+
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
 		// the table carries linkFirst.
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

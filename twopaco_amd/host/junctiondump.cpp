@@ -3,7 +3,8 @@
 // Downstream consumer of the junction stream, kept flag- and byte-compatible with the reference's
 // graphdump (reference src/graphdump/graphdump.cpp) so that pipelines built on it are unchanged:
 //   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>] [--text host|device]
-//             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]   (the last two instead of -f)
+//             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]
+//             |  --bubbles file|sequence [--bubbles-out <path>]   (the last three instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -43,6 +44,11 @@
 // once (the L line of its first occurrence); the H line, the S lines with a body and the P lines are byte for byte those of gfa1.
 // Serial or with --gpu, the same bytes.  The whole table is known before the first byte is printed: a stream the walk refuses
 // prints the walk's error and nothing else.
+// --bubbles file|sequence [--bubbles-out <path>] (an addition; instead of -f): the simple bubbles of the graph -- where two segments
+// leave one side of a segment, touch nothing else and meet again at one side of another; include/twopaco_hip.h defines them -- as
+// TSV with the colour rows of the two arms (graphformat.h: WriteBubbles).  Without --gpu the serial walk, then ComputeColors,
+// ComputeLinks and ComputeBubbles; with --gpu the three device stages over one segment build (csrc/tpc_bubbles.hip); the bytes are
+// the same.  Every byte waits until the table is complete: a stream the walk refuses prints the walk's error and nothing else.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -406,6 +412,20 @@ namespace
 		FormatEvents(t.table, t.seq, t.loaded, k, "gfa1", 1, -1, 0);
 	}
 
+	// --bubbles, serial: the walk, then the three serial statements one after the other
+	void DumpBubbles(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath)
+	{
+		SerialTable t;
+		WalkLinks(binFile, fasta, k, prefix, false, t);
+		ColorMap map;
+		MakeColorMap(t.seq, fasta, bySequence, map);
+		ColorTable colors;
+		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
+		BubbleTable bubbles;
+		ComputeBubbles(t.table, t.links, bubbles);
+		WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, outPath);
+	}
+
 	// ---------------------------------------------------------------------------------------- --gpu
 	double MsSince(const std::chrono::steady_clock::time_point & t0)
 	{
@@ -417,10 +437,12 @@ namespace
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
-		uint64_t links, linkOccurrences;
+		uint64_t links, linkOccurrences, bubbles;
+		double bubblesKernelMs, bubblesMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), threads(1) {}
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), bubblesKernelMs(0), bubblesMs(0),
+			threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -432,10 +454,11 @@ namespace
 			std::fprintf(f, "{\"path\": \"%s\", \"events\": %llu, \"segments\": %llu, \"n_named\": %llu, \"device_ms\": %.3f, \"kernel_ms\": %.3f, \"load_ms\": %.3f, "
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
 				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f, "
-				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu, "
+				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
-				(unsigned long long)linkOccurrences);
+				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles);
 			std::fclose(f);
 		}
 	};
@@ -465,6 +488,10 @@ namespace
 		decltype(&tpc_segments_links_info) segmentsLinksInfo;
 		decltype(&tpc_segments_links_fetch_rows) segmentsLinksFetchRows;
 		decltype(&tpc_segments_links_fetch_first) segmentsLinksFetchFirst;
+		decltype(&tpc_segments_bubbles_build) segmentsBubblesBuild;
+		decltype(&tpc_segments_bubbles_info) segmentsBubblesInfo;
+		decltype(&tpc_segments_bubbles_fetch_rows) segmentsBubblesFetchRows;
+		decltype(&tpc_segments_bubbles_fetch_hist) segmentsBubblesFetchHist;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -503,6 +530,10 @@ namespace
 			Load(segmentsLinksInfo, "tpc_segments_links_info");
 			Load(segmentsLinksFetchRows, "tpc_segments_links_fetch_rows");
 			Load(segmentsLinksFetchFirst, "tpc_segments_links_fetch_first");
+			Load(segmentsBubblesBuild, "tpc_segments_bubbles_build");
+			Load(segmentsBubblesInfo, "tpc_segments_bubbles_info");
+			Load(segmentsBubblesFetchRows, "tpc_segments_bubbles_fetch_rows");
+			Load(segmentsBubblesFetchHist, "tpc_segments_bubbles_fetch_hist");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -632,6 +663,26 @@ namespace
 		return MsSince(t0);
 	}
 
+	// The colour table of the table on the device (csrc/tpc_colors.hip), fetched: rows, presence words and the histogram.
+	void ColorsOnDevice(DeviceLibrary & lib, const ColorMap & map, uint64_t rows, ColorTable & colors, DumpStats & stats)
+	{
+		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
+		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
+		colors.colors = map.label.size();
+		colors.firstEvent.resize(rows);
+		colors.occurrences.resize(rows);
+		colors.forward.resize(rows);
+		colors.nColors.resize(rows);
+		colors.presence.resize(rows * colors.Words());
+		colors.histSegments.resize(colors.colors + 1);
+		colors.histBases.resize(colors.colors + 1);
+		lib.Check(lib.segmentsColorsFetchRows(lib.ctx, 0, rows, colors.firstEvent.data(), colors.occurrences.data(), colors.forward.data(), colors.nColors.data()), "tpc_segments_colors_fetch_rows");
+		lib.Check(lib.segmentsColorsFetchPresence(lib.ctx, 0, rows, colors.presence.data()), "tpc_segments_colors_fetch_presence");
+		lib.Check(lib.segmentsColorsFetchHist(lib.ctx, colors.histSegments.data(), colors.histBases.data()), "tpc_segments_colors_fetch_hist");
+		stats.colorsMs = MsSince(c0);
+	}
+
 	// --colors with --gpu: the table stays on the device, where the colour stage groups its events by segment (csrc/tpc_colors.hip);
 	// what is fetched is the rows, their presence words, the histogram, and the event table for the names and lengths.
 	void DumpColorsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
@@ -644,23 +695,8 @@ namespace
 		ColorMap map;
 		MakeColorMap(seq, fasta, bySequence, map);
 		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
-		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
 		ColorTable colors;
-		colors.colors = map.label.size();
-		const uint64_t rows = counts[1];
-		colors.firstEvent.resize(rows);
-		colors.occurrences.resize(rows);
-		colors.forward.resize(rows);
-		colors.nColors.resize(rows);
-		colors.presence.resize(rows * colors.Words());
-		colors.histSegments.resize(colors.colors + 1);
-		colors.histBases.resize(colors.colors + 1);
-		lib.Check(lib.segmentsColorsFetchRows(lib.ctx, 0, rows, colors.firstEvent.data(), colors.occurrences.data(), colors.forward.data(), colors.nColors.data()), "tpc_segments_colors_fetch_rows");
-		lib.Check(lib.segmentsColorsFetchPresence(lib.ctx, 0, rows, colors.presence.data()), "tpc_segments_colors_fetch_presence");
-		lib.Check(lib.segmentsColorsFetchHist(lib.ctx, colors.histSegments.data(), colors.histBases.data()), "tpc_segments_colors_fetch_hist");
-		stats.colorsMs = MsSince(c0);
+		ColorsOnDevice(lib, map, counts[1], colors, stats);
 		FetchedTable held;
 		FetchTable(lib, counts[0], sequences, held);
 		stats.deviceMs = MsSince(t0);
@@ -714,6 +750,47 @@ namespace
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		WriteLinks(held.table, k, counts[1], links, outPath);
+		stats.formatMs = MsSince(t0);
+	}
+
+	// --bubbles with --gpu: one segment build, then the colour, link and bubble stages on the device (csrc/tpc_bubbles.hip reads the
+	// link rows where they lie); what is fetched is the bubble rows, the degree histogram, the colour rows and the event table.
+	void DumpBubblesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats)
+	{
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+		size_t sequences = 0;
+		std::chrono::steady_clock::time_point t0;
+		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
+		ColorMap map;
+		MakeColorMap(seq, fasta, bySequence, map);
+		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+		ColorTable colors;
+		ColorsOnDevice(lib, map, counts[1], colors, stats);
+		LinkTable links;
+		LinksOnDevice(lib, counts[0], true, links, stats);
+		const std::chrono::steady_clock::time_point b0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsBubblesBuild(lib.ctx), "tpc_segments_bubbles_build");
+		stats.bubblesKernelMs = lib.kernelMs(lib.ctx, TPC_K_BUBBLES);
+		uint64_t info[4] = {0, 0, 0, 0};
+		lib.Check(lib.segmentsBubblesInfo(lib.ctx, info), "tpc_segments_bubbles_info");
+		BubbleTable bubbles;
+		bubbles.sides = info[1];
+		bubbles.arcs = info[2];
+		bubbles.source.resize(info[0]);
+		bubbles.armA.resize(info[0]);
+		bubbles.armB.resize(info[0]);
+		bubbles.sink.resize(info[0]);
+		lib.Check(lib.segmentsBubblesFetchRows(lib.ctx, 0, info[0], bubbles.source.data(), bubbles.armA.data(), bubbles.armB.data(), bubbles.sink.data()), "tpc_segments_bubbles_fetch_rows");
+		lib.Check(lib.segmentsBubblesFetchHist(lib.ctx, bubbles.hist), "tpc_segments_bubbles_fetch_hist");
+		stats.bubbles = info[0];
+		stats.bubblesMs = MsSince(b0);
+		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] bubble table on device: %.3f ms (kernels %.3f ms)\n", stats.bubblesMs, stats.bubblesKernelMs);
+		FetchedTable held;
+		FetchTable(lib, counts[0], sequences, held);
+		stats.deviceMs = MsSince(t0);
+		t0 = std::chrono::steady_clock::now();
+		WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, outPath);
 		stats.formatMs = MsSince(t0);
 	}
 
@@ -790,7 +867,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -814,6 +891,14 @@ namespace
 			"   --links-out <file name>\n     with --links: write the table there instead of to the standard output\n\n"
 			"   --compact\n     with -f gfa1: no per-sequence S header lines, no C lines, and every link once (the L line of its first\n"
 			"     occurrence); everything else as gfa1.  Serial or with --gpu; not with --text device.\n\n"
+			"   --bubbles <file|sequence>\n     instead of -f: the simple bubbles of the graph as TSV -- the places where two segments (the arms) leave one side of\n"
+			"     a segment, touch nothing else and meet again at one side of another: a substitution or a short insertion or\n"
+			"     deletion between genomes.  Per bubble its source, two arms and sink (segment, strand), then of the arms the lengths,\n"
+			"     occurrences, numbers of colours and presence bits of --colors, and the number of colours that hold both arms;\n"
+			"     in front the colours and the number of sides (oriented segments) by degree, 0 being the dead ends.  Simple bubbles\n"
+			"     only: three alleles at one place, nested bubbles and superbubbles are not reported.  Needs -k and -s.  With --gpu\n"
+			"     the bubbles are found on the device.  Not with --colors, --links, --compact or --text.\n\n"
+			"   --bubbles-out <file name>\n     with --bubbles: write the table there instead of to the standard output\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -823,9 +908,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false;
+		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -879,6 +964,12 @@ int main(int argc, char * argv[])
 			else if (a == "--links") links = true;
 			else if (a == "--links-out") { linksOut = value("(--links-out)"); linksOutSet = true; }
 			else if (a == "--compact") compact = true;
+			else if (a == "--bubbles")
+			{
+				bubblesBy = value("(--bubbles)");
+				if (bubblesBy != "file" && bubblesBy != "sequence") throw ArgError("Value '" + bubblesBy + "' does not meet constraint: file|sequence", "Argument: (--bubbles)");
+			}
+			else if (a == "--bubbles-out") { bubblesOut = value("(--bubbles-out)"); bubblesOutSet = true; }
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -899,7 +990,13 @@ int main(int argc, char * argv[])
 			else throw ArgError("Couldn't find match for argument", "(" + a + ")");
 		}
 
-		const bool colors = !colorsBy.empty();
+		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty();
+		if (bubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--bubbles)");
+		if (bubbles && colors) throw ArgError("The bubble table and the colour table are written one at a time: not with --colors", "(--bubbles)");
+		if (bubbles && links) throw ArgError("The bubble table and the link table are written one at a time: not with --links", "(--bubbles)");
+		if (bubbles && compact) throw ArgError("The bubble table and the compact text are written one at a time: not with --compact", "(--bubbles)");
+		if (bubbles && textSet) throw ArgError("The bubble table is formatted by the host: not with --bubbles", "(--text)");
+		if (bubblesOutSet && !bubbles) throw ArgError("This argument needs --bubbles <file|sequence>", "(--bubbles-out)");
 		if (colors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--colors)");
 		if (colors && textSet) throw ArgError("The colour table is formatted by the host: not with --colors", "(--text)");
 		if (colorsOutSet && !colors) throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
@@ -910,10 +1007,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -943,6 +1040,16 @@ int main(int argc, char * argv[])
 			DumpLinksOnDevice(*lib, binFile, fasta, k, threads, loaded, linksOut, stats);
 		}
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);
+		else if (bubbles && lib)
+		{
+			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+			InputSequences seq;
+			LoadedSequences loaded;
+			LoadSequences(fasta, prefix, threads, seq, loaded);
+			stats.loadMs = MsSince(t0);
+			DumpBubblesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, bubblesBy == "sequence", bubblesOut, stats);
+		}
+		else if (bubbles) DumpBubbles(binFile, fasta, k, prefix, bubblesBy == "sequence", bubblesOut);
 		else if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device

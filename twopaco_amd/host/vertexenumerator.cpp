@@ -346,6 +346,10 @@ namespace TwoPaCo
 				if (colors && sharded) throw std::runtime_error("The colour table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				const bool links = !options.linksFile.empty();
 				if (links && sharded) throw std::runtime_error("The link table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				const bool bubbles = !options.bubblesFile.empty();
+				if (bubbles && options.bubblesBy != "file" && options.bubblesBy != "sequence") throw std::runtime_error("The bubble table's colours must be one of file, sequence");
+				if (bubbles && colors && options.bubblesBy != options.colorsBy) throw std::runtime_error("The bubble table and the colour table share one set of colours: both by file or both by sequence");
+				if (bubbles && sharded) throw std::runtime_error("The bubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -480,7 +484,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links)
+				if (graph || colors || links || bubbles)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -978,7 +982,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -988,10 +992,13 @@ namespace TwoPaCo
 			// --graph: the segment table from the stream tpc_emit_stream left on the device, fetched as the event table, formatted
 			// into options.graphFile.  What the walk of graphdump would throw is thrown here, before the file is created.
 			// --colors: the same table, built once for both, grouped by segment on the device and written to options.colorsFile.
+			// --bubbles: the colour rows and the link table of the same build, then the bubble stage (csrc/tpc_bubbles.hip) over the
+			// link rows where they lie; written to options.bubblesFile after the graph and the link file.
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
+				const bool bubbles = !options.bubblesFile.empty(), colorRows = colors || bubbles, bySequence = (colors ? options.colorsBy : options.bubblesBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1023,19 +1030,23 @@ namespace TwoPaCo
 					// With both, everything of the colour table that can fail on the device comes first and its file is written last:
 					// a graph step that throws leaves no colour file behind (the graph file removes itself).
 					DeviceColors deviceColors;
-					if (colors && !(graph && options.graphTextOnDevice)) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
-					if (colors) ColorsFromDevice(options, fileName, seq, counts, name, begin, end, seqEventBegin, deviceColors, timer);
+					if (colorRows && !(graph && options.graphTextOnDevice)) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+					if (colorRows) ColorsFromDevice(bySequence, fileName, seq, counts, name, begin, end, seqEventBegin, deviceColors, timer);
 					// the link table likewise: found on the device before the graph is written (the compact graph needs its first
 					// bits), its file written after it
 					GraphFormat::LinkTable deviceLinks;
-					bool fetched = colors && !(graph && options.graphTextOnDevice);
+					bool fetched = colorRows && !(graph && options.graphTextOnDevice);
 					if ((links || compact) && !fetched && !(graph && options.graphTextOnDevice))
 					{
 						FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
 						fetched = true;
 					}
 
-					if (links || compact) LinksFromDevice(counts[0], links, compact, name, deviceLinks, timer);
+					if (links || compact || bubbles) LinksFromDevice(counts[0], links, compact, name, deviceLinks, timer);
+					// the bubbles over the link rows on the device, before anything is written; their file comes last
+					GraphFormat::BubbleTable deviceBubbles;
+					uint64_t linkRows = 0;
+					if (bubbles) BubblesFromDevice(deviceBubbles, linkRows, timer);
 					if (graph && options.graphTextOnDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph)
 					{
@@ -1056,6 +1067,12 @@ namespace TwoPaCo
 						events.name = name.data();
 						GraphFormat::WriteLinks(events, k, counts[1], deviceLinks, options.linksFile);
 						timer.Lap("link table writing");
+					}
+
+					if (bubbles)
+					{
+						GraphFormat::WriteBubbles(deviceColors.events, k, deviceColors.map, deviceColors.table, linkRows, deviceBubbles, options.bubblesFile);
+						timer.Lap("bubble table writing");
 					}
 
 					return;
@@ -1087,6 +1104,43 @@ namespace TwoPaCo
 					GraphFormat::WriteLinks(empty, k, 0, table, options.linksFile);
 					timer.Lap("link table writing");
 				}
+
+				if (bubbles)
+				{
+					// nothing dispatched: no event, no side, the header and the colours alone
+					GraphFormat::EventTable empty;
+					empty.sequences = sequences;
+					empty.seqEventBegin = seqEventBegin.data();
+					GraphFormat::ColorMap map;
+					GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
+					GraphFormat::ColorTable table;
+					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
+					GraphFormat::LinkTable none;
+					GraphFormat::ComputeLinks(empty, none);
+					GraphFormat::BubbleTable found;
+					GraphFormat::ComputeBubbles(empty, none, found);
+					GraphFormat::WriteBubbles(empty, k, map, table, 0, found, options.bubblesFile);
+					timer.Lap("bubble table writing");
+				}
+			}
+
+			// --bubbles: the simple bubbles of the link table on the device found there (csrc/tpc_bubbles.hip); fetched are the bubble
+			// rows and the degree histogram.  The arms' names, lengths and colours come from what --colors fetches.
+			void BubblesFromDevice(GraphFormat::BubbleTable & out, uint64_t & linkRows, PhaseTimer & timer)
+			{
+				Check(tpc_segments_bubbles_build(ctx_), "segments_bubbles_build");
+				timer.Lap("segment bubbles");
+				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   bubbles_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_BUBBLES) << " ms" << std::endl;
+				uint64_t info[4] = {0, 0, 0, 0}, linkInfo[4] = {0, 0, 0, 0};
+				Check(tpc_segments_bubbles_info(ctx_, info), "segments_bubbles_info");
+				Check(tpc_segments_links_info(ctx_, linkInfo), "segments_links_info");
+				linkRows = linkInfo[0];
+				out.sides = info[1];
+				out.arcs = info[2];
+				out.source.resize(info[0]); out.armA.resize(info[0]); out.armB.resize(info[0]); out.sink.resize(info[0]);
+				Check(tpc_segments_bubbles_fetch_rows(ctx_, 0, info[0], out.source.data(), out.armA.data(), out.armB.data(), out.sink.data()), "segments_bubbles_fetch_rows");
+				Check(tpc_segments_bubbles_fetch_hist(ctx_, out.hist), "segments_bubbles_fetch_hist");
+				timer.Lap("segment bubbles fetch");
 			}
 
 			// --links / the compact graph: the distinct links of the table on the device found there (csrc/tpc_links.hip); fetched are
@@ -1157,7 +1211,7 @@ namespace TwoPaCo
 			// --colors: the events of the table on the device grouped by segment there (csrc/tpc_colors.hip); fetched are the rows,
 			// their presence words and the histogram.  The names and lengths of the rows come from the fetched event table (`out`
 			// points into name / begin / end / seqEventBegin).  The file is the caller's to write.
-			void ColorsFromDevice(const EnumeratorOptions & options, const std::vector<std::string> & fileName, const GraphFormat::InputSequences & seq,
+			void ColorsFromDevice(bool bySequence, const std::vector<std::string> & fileName, const GraphFormat::InputSequences & seq,
 				const uint64_t * counts, std::vector<int64_t> & name, std::vector<uint32_t> & begin, std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin,
 				DeviceColors & out, PhaseTimer & timer)
 			{
@@ -1173,7 +1227,7 @@ namespace TwoPaCo
 					Check(tpc_segments_fetch_events(ctx_, 0, counts[0], begin.data(), end.data()), "segments_fetch_events");
 				}
 
-				GraphFormat::MakeColorMap(seq, fileName, options.colorsBy == "sequence", map);
+				GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
 				if (map.colorOfSequence.size() + 1 != seqEventBegin.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
 				Check(tpc_segments_colors_build(ctx_, map.colorOfSequence.data(), uint32_t(map.label.size())), "segments_colors_build");
 				timer.Lap("segment colours");

@@ -83,6 +83,12 @@ namespace TwoPaCo
 		// --compact` -- no per-sequence S lines, no C lines, every link once -- from the same link stage.  One GPU.
 		std::string linksFile;
 		bool graphCompact;
+		// The simple bubbles of the graph (graphformat.h: WriteBubbles; `graphdump --bubbles` writes the same bytes for the junction
+		// stream of this run): bubblesFile (empty: off), bubblesBy = "file" | "sequence" the colours of the arms' presence columns --
+		// the same as colorsBy when both are given.  Found on the device (tpc_segments_bubbles_build) over the colour rows and the
+		// link table of the same segment table.  One GPU.
+		std::string bubblesBy;
+		std::string bubblesFile;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
