@@ -62,7 +62,8 @@ enum {
     TPC_K_COLORS = 18,      /* tpc_segments_colors_build: rows, counts and presence bits of the segment colour table (no counterpart in the reference) */
     TPC_K_LINKS = 19,       /* tpc_segments_links_build: the device hash set of the distinct links, their counts and first bits (no counterpart in the reference) */
     TPC_K_BUBBLES = 20,     /* tpc_segments_bubbles_build: arcs, degrees, the simple bubbles and the degree histogram (no counterpart in the reference) */
-    TPC_K_COUNT = 21
+    TPC_K_DISTANCES = 21,   /* tpc_segments_distances_build: bit columns, weight planes and the two colour x colour matrices (no counterpart in the reference) */
+    TPC_K_COUNT = 22
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -629,6 +630,38 @@ int tpc_segments_bubbles_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint3
 int tpc_segments_bubbles_fetch_sides(tpc_ctx *ctx, uint64_t c0, uint64_t n, uint32_t *deg, uint32_t *lo, uint32_t *hi);
 int tpc_segments_bubbles_fetch_hist(tpc_ctx *ctx, uint64_t *hist /* [6] */);
 
+/* The GENOME DISTANCE MATRICES (csrc/tpc_distances.hip): how much every colour shares with every other one.  No counterpart in the
+ * reference; ComputeDistances of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The
+ * definition, over the colour table of the last tpc_segments_colors_build (rows r < S, colours c < C):
+ *   ROW              whatever the colour table calls a row: a segment, in the order of gfa1's S lines with a body.  That includes the
+ *                    'N'-named rows (names >= 2^34, every one a row of its own) and the rows the reference names -1 for ambiguous
+ *                    letters; the stage counts them as the colour table holds them and claims nothing more about them.
+ *   WEIGHT           weight[r] = end[e0] - begin[e0] for the row's first event e0: the row's length minus k, the number of
+ *                    (k+1)-mers (EDGES) the segment spells.  Edges, not bases: neighbouring segments overlap by k bases, so summed
+ *                    lengths would count the junction k-mers twice, while every edge of the compacted graph lies in exactly one
+ *                    segment.  32 bits per row, 64 bits when summed.
+ *   segments[i][j]   the rows whose presence holds both colour i and colour j.
+ *   edges[i][j]      the sum of weight over those rows.
+ *   SHAPE            both C x C, uint64, symmetric, stored in full, row-major.  The diagonal holds a colour's own totals; a colour
+ *                    that no sequence has is a zero row and a zero column.
+ *   EXACT            integers and a commutative sum: the result does not depend on the schedule.  No floating point on the device;
+ *                    a reader gets the Jaccard similarity of two colours as edges[i][j] / (edges[i][i] + edges[j][j] - edges[i][j]).
+ * Separate from the builds and opt-in: a context that never calls it holds none of this; tpc_segments_counts, the colour outputs,
+ * the link outputs and the bubble outputs are what they were, in any order of the builds.
+ *   tpc_segments_distances_build  over the colour table of the last tpc_segments_colors_build.  Refused with an error text: no
+ *                                 segment table, a table whose tpc_segments_error kind is not TPC_SEG_OK, no colour table (a new
+ *                                 segment build drops it), more than 2^24 colours (16 B x C^2 must not wrap; no device holds it), matrices or bit columns beyond the free device memory; the context stays
+ *                                 usable.  Kept until the next segment, colour or distance build: 16 B x C^2.  During the call also
+ *                                 8 B x C x ceil(S / 64) of colour-major bit columns and 256 B x ceil(S / 64) of weight bit planes.
+ *                                 TPC_K_DISTANCES times the stage on the stream from its first kernel to its last.
+ *   tpc_segments_distances_info   info[0] colours, [1] rows, [2] weight bit planes used (the bit width of the largest weight),
+ *                                 [3] the stage's device bytes at their peak
+ *   tpc_segments_distances_fetch  rows [i0, i0 + n_rows) of both matrices to the host, n_rows x C values each
+ * A range outside the matrix is refused with an error text. */
+int tpc_segments_distances_build(tpc_ctx *ctx);
+int tpc_segments_distances_info(tpc_ctx *ctx, uint64_t *info /* [4]: colours, rows, planes used, peak device bytes */);
+int tpc_segments_distances_fetch(tpc_ctx *ctx, uint64_t i0, uint64_t n_rows, uint64_t *segments_host /* [n_rows x C] */, uint64_t *edges_host /* [n_rows x C] */);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -665,6 +698,9 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      (csrc/tpc_pass1_anyq.hip) for every q, so that they can be checked on the goldens with q <= 16
  *   test_links_slots_log2  tests only: the next tpc_segments_links_build takes 2^n slots for its link set instead of sizing it by
  *                      the occurrences (0 = by the occurrences), so that long probe chains and a full set can be reached
+ *   test_distances_chunk_words  tests only: the next tpc_segments_distances_build stages n column words (64 rows each) per chunk
+ *                      instead of its own 64 (0 = its own; more than 64 is refused), so that a table of a few hundred rows crosses
+ *                      chunk borders and ends in a partial chunk
  *   part_budget_bytes  partition buffers per tile batch (0 = automatic: 40 GiB, or 60 % of the free device
  *                      memory when that is more; any number of batches, not only powers of two); part_min_tiles  smallest batch */
 /*   replicate_filter   1 (before tpc_shard_config / tpc_set_params): a sharded context keeps the whole filter; tpc_pass1_insert / tpc_pass1_query
@@ -675,7 +711,7 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "insert_batches" / "query_batches" = tile batches; "filter2_retries" = exact-filter passes repeated
  * with the full-size table by the last exact filter (tpc_pass2_filter*), "aggregate_retries" those of the last tpc_pass2_aggregate_records;
  * "filter2_counted" = 1 when the last exact-filter launch (either call) counted occurrences (an abundance cut applies), 0 when it kept
- * only "seen twice"; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
+ * only "seen twice"; "text_words" = packed words of the text held (a window with option text_window); "fused_lookups" = queries that built the filter slices themselves (deferred apply); "query_overflow_entries" = entries the last batch of the last partitioned query handed to its overflow list (full rings or regions: address skew); "distances_tile" = colours on each side of the tile one workgroup of tpc_segments_distances_build's Gram kernel owns (a constant; the tests choose their colour counts around it); "pbuf_releases" = times a second-pass or output allocation did not fit beside the first pass' partition buffers, which were then freed (the next first pass allocates them again); "round_marks" = candidate marks of the round the last
  * tpc_pass2_filter consumed (what tpc_pass1_query reports; the sharded first pass has no single call that does);
  * "device_free_bytes" / "device_total_bytes" = hipMemGetInfo of the context's device, now;
  * of the last tpc_segments_text_write: "text_write_us" = microseconds its helper thread spent inside write / pwrite, "text_wait_us" =

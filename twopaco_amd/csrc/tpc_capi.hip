@@ -339,6 +339,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
     colors_drop(c);
     links_drop(c);
     bubbles_drop(c);
+    distances_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);
@@ -378,6 +379,7 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "test_force_anyq")) { tpc_test_force_anyq = value != 0; return 0; }  // process-wide, tests only
     if (!strcmp(name, "test_sketch_grid")) { tpc_test_sketch_grid = value > 0 ? (int)value : 0; return 0; }  // process-wide, tests only
     if (!strcmp(name, "test_links_slots_log2")) { c->opt_links_slots_log2 = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 64)); return 0; }  // tests only: slots of the next tpc_segments_links_build
+    if (!strcmp(name, "test_distances_chunk_words")) { c->opt_distances_chunk_words = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); return 0; }  // tests only: chunk length of the next tpc_segments_distances_build
     if (!strcmp(name, "test_fail_mallocs")) { tpc_test_fail_mallocs.store(value > 0 ? (int)value : 0); return 0; }  // process-wide, tests only
     return fail(c, -1, "unknown option %s", name);
 }
@@ -431,6 +433,7 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "insert_overflow_entries")) return c->stat_insert_overflow;
     if (!strcmp(name, "periodic_skip")) return c->periodic_valid ? 1 : 0;
     if (!strcmp(name, "pbuf_releases")) return c->stat_pbuf_releases;
+    if (!strcmp(name, "distances_tile")) return TPC_DISTANCES_TILE;
     if (!strcmp(name, "text_words")) return (int64_t)(c->text_w1 - c->text_w0);  // packed words of the text this context holds
     if (!strcmp(name, "text_word_begin")) return (int64_t)c->text_w0;  // ... words [begin, end) of the packed text (a windowed context: its tiles and their halo)
     if (!strcmp(name, "text_word_end")) return (int64_t)c->text_w1;

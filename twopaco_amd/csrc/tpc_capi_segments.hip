@@ -31,6 +31,7 @@ int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k,
     colors_drop(c);
     links_drop(c);
     bubbles_drop(c);
+    distances_drop(c);
     for (void *p : { (void *)c->seg_name, (void *)c->seg_first, (void *)c->seg_ev[0], (void *)c->seg_ev[1], (void *)c->seg_ev[2], (void *)c->seg_rec, (void *)c->seg_amb }) if (p) (void)hipFree(p);
     c->seg_name = nullptr; c->seg_first = nullptr;
     c->seg_rec = c->seg_amb = nullptr;

@@ -122,6 +122,7 @@ int tpc_segments_colors_build(tpc_ctx *c, const uint32_t *color_of_seq, uint32_t
 {
     if (!c) return -1;
     colors_drop(c);
+    distances_drop(c);   // they were summed over the colour table that goes
     if (!c->seg_valid) return fail(c, -1, "segment colours: build the segment table first (tpc_segments_build_host / _resident)");
     if (c->seg_err_kind != TPC_SEG_OK)
         return fail(c, -1, "segment colours: the segment table holds the walk's error %d at slot %llu, there are no segments to colour", c->seg_err_kind, (unsigned long long)c->seg_err_slot);

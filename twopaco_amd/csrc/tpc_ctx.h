@@ -7,6 +7,7 @@
 //   tpc_colors.hip        the segment colour table (tpc_segments_colors_*), kernels and entry points
 //   tpc_links.hip         the link table of the compacted graph (tpc_segments_links_*), kernels and entry points
 //   tpc_bubbles.hip       the simple bubbles of the compacted graph (tpc_segments_bubbles_*), kernels and entry points
+//   tpc_distances.hip     the genome distance matrices over the colour table (tpc_segments_distances_*), kernels and entry points
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -133,6 +134,12 @@ struct tpc_ctx {
     unsigned long long *bub_hist = nullptr;  // device, [6]: sides of degree 0, 1, 2, 3, 4, 5 or more
     uint64_t bub_n_rows = 0, bub_n_sides = 0, bub_arcs = 0, bub_peak_bytes = 0;
     bool bub_valid = false;
+    // genome distance matrices (tpc_segments_distances_*, tpc_distances.hip) of the last tpc_segments_distances_build; a new segment or
+    // colour build drops them
+    unsigned long long *dst_mat = nullptr;   // device, [2][dst_n_colors][dst_n_colors]: segments, edges
+    uint64_t dst_n_colors = 0, dst_n_rows = 0, dst_planes = 0, dst_peak_bytes = 0;
+    bool dst_valid = false;
+    int opt_distances_chunk_words = 0;       // option test_distances_chunk_words (tests only): column words a block stages at once, 0 = the kernel's own
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
     unsigned long long *route_scratch = nullptr;  // device, 128 words: tpc_shard_route's per-owner counts and cursors
@@ -247,12 +254,15 @@ void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
 void colors_drop(tpc_ctx *c);           // tpc_colors.hip
 void links_drop(tpc_ctx *c);            // tpc_links.hip
 void bubbles_drop(tpc_ctx *c);          // tpc_bubbles.hip
+void distances_drop(tpc_ctx *c);        // tpc_distances.hip
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \
         hipError_t e_ = (expr);                                                                 \
         if (e_ != hipSuccess) return tpch::fail(c, -10, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+constexpr int TPC_DISTANCES_TILE = 32;  // tpc_distances.hip: colours on each side of the tile one workgroup of its Gram kernel owns (tpc_get_stat "distances_tile")
 
 struct Timed {
     tpc_ctx *c;

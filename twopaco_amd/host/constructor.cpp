@@ -24,7 +24,12 @@
 // --bubbles file|sequence [--bubbles-out F]: the simple bubbles of the same graph -- where two segments leave one side of a segment,
 // touch nothing else and meet again -- with the colours of the two arms, as TSV, byte for byte what `graphdump --bubbles` writes
 // (csrc/tpc_bubbles.hip finds them on the device over the link table; combines with --graph, --graph-compact, --colors, --links
-// and -o from one segment, colour and link build; --colors must name the same colours).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// and -o from one segment, colour and link build; --colors must name the same colours);
+// --distances file|sequence [--distances-out F] [--distances-phylip F]: how much every colour shares with every other one -- the
+// segments and the edges ((k+1)-mers) two colours both hold -- as TSV of integers, byte for byte what `graphdump --distances` writes,
+// and asked for, the Jaccard distances over edges as a PHYLIP square matrix (csrc/tpc_distances.hip sums the matrices on the device
+// over the colour build; combines with everything above from one segment build and one colour build; --colors and --bubbles must
+// name the same colours; its file is written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -82,6 +87,7 @@ namespace
 			<< "               [--colors <file|sequence>] [--colors-out <file name>]" << std::endl
 			<< "               [--links] [--links-out <file name>] [--graph-compact]" << std::endl
 			<< "               [--bubbles <file|sequence>] [--bubbles-out <file name>]" << std::endl
+			<< "               [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -105,7 +111,12 @@ namespace
 			<< "               substitution or a short insertion or deletion between genomes.  Per bubble its source, arms and sink, the arms'" << std::endl
 			<< "               lengths, occurrences and colours (by file or by sequence, as --colors) and the colours that hold both arms." << std::endl
 			<< "               Simple bubbles only: three alleles at one place, nested bubbles and superbubbles are not reported." << std::endl
-			<< "               Combines with --graph, --graph-compact, --colors (the same colours), --links and -o.  One GPU only." << std::endl;
+			<< "               Combines with --graph, --graph-compact, --colors (the same colours), --links and -o.  One GPU only." << std::endl
+			<< "       --distances: also write how much every colour (file or sequence, as --colors) shares with every other one as TSV to" << std::endl
+			<< "               --distances-out (default de_bruijn.distances.tsv): per colour its own segments and edges ((k+1)-mers), then for" << std::endl
+			<< "               every pair i < j the segments and the edges both hold; integers only, Jaccard = e_ij / (e_ii + e_jj - e_ij)." << std::endl
+			<< "               --distances-phylip: also the Jaccard distances over edges as a relaxed PHYLIP square matrix." << std::endl
+			<< "               Combines with --graph, --graph-compact, --colors and --bubbles (the same colours), --links and -o.  One GPU only." << std::endl;
 	}
 }
 
@@ -146,7 +157,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -231,6 +242,14 @@ int main(int argc, char * argv[])
 				optionsSet = true;
 			}
 			else if (Match(a, 0, "bubbles-out")) { options.bubblesFile = value("(--bubbles-out)"); bubblesOutSet = true; }
+			else if (Match(a, 0, "distances"))
+			{
+				options.distancesBy = value("(--distances)");
+				if (options.distancesBy != "file" && options.distancesBy != "sequence") throw ArgError("Value '" + options.distancesBy + "' does not meet constraint: file|sequence", "(--distances)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "distances-out")) { options.distancesFile = value("(--distances-out)"); distancesOutSet = true; }
+			else if (Match(a, 0, "distances-phylip")) { options.distancesPhylipFile = value("(--distances-phylip)"); distancesPhylipSet = true; }
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -305,6 +324,20 @@ int main(int argc, char * argv[])
 		else if (bubblesOutSet)
 		{
 			throw ArgError("This argument needs --bubbles <file|sequence>", "(--bubbles-out)");
+		}
+
+		if (!options.distancesBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The distance table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--distances)");
+			if (!options.colorsBy.empty() && options.colorsBy != options.distancesBy) throw ArgError("The distance table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --distances " + options.distancesBy, "(--distances)");
+			if (!options.bubblesBy.empty() && options.bubblesBy != options.distancesBy) throw ArgError("The distance table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --distances " + options.distancesBy, "(--distances)");
+			if (!distancesOutSet) options.distancesFile = "de_bruijn.distances.tsv";
+			if (options.distancesFile.empty()) throw ArgError("The distance table needs a file name", "(--distances-out)");
+			if (distancesPhylipSet && options.distancesPhylipFile.empty()) throw ArgError("The PHYLIP matrix needs a file name", "(--distances-phylip)");
+		}
+		else if (distancesOutSet || distancesPhylipSet)
+		{
+			throw ArgError("This argument needs --distances <file|sequence>", distancesOutSet ? "(--distances-out)" : "(--distances-phylip)");
 		}
 
 		if (runTests)

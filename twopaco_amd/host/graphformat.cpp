@@ -746,6 +746,125 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeDistances(const EventTable & t, const ColorTable & colors, DistanceTable & out)
+		{
+			const size_t rows = colors.Rows(), words = colors.Words(), n = size_t(colors.colors);
+			if (colors.presence.size() != rows * words) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			out = DistanceTable();
+			out.colors = colors.colors;
+			out.segments.assign(n * n, 0);
+			out.edges.assign(n * n, 0);
+			std::vector<uint32_t> held;
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t e0 = colors.firstEvent[r];
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				const uint64_t weight = uint64_t(t.end[e0]) - t.begin[e0];
+				held.clear();
+				for (size_t c = 0; c < n; c++)
+				{
+					if ((colors.presence[r * words + (c >> 5)] >> (c & 31)) & 1u) held.push_back(uint32_t(c));
+				}
+
+				for (uint32_t i : held)
+				{
+					for (uint32_t j : held)
+					{
+						out.segments[size_t(i) * n + j] += 1;
+						out.edges[size_t(i) * n + j] += weight;
+					}
+				}
+			}
+		}
+
+		namespace
+		{
+			void CheckDistances(const ColorMap & map, const DistanceTable & d)
+			{
+				const size_t n = size_t(d.colors);
+				if (d.segments.size() != n * n || d.edges.size() != n * n || map.label.size() != n) throw std::runtime_error("distance table: the arrays do not agree about the colours");
+			}
+
+			void WriteWhole(const std::string & buf, const std::string & path, const char * what)
+			{
+				std::FILE * f = path.empty() ? stdout : std::fopen(path.c_str(), "wb");
+				if (!f) throw std::runtime_error(std::string("Can't create the ") + what + " " + path);
+				bool good = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+				good = good && std::fflush(f) == 0;
+				if (f != stdout) good = (std::fclose(f) == 0) && good;
+				if (!good)
+				{
+					if (f != stdout) ::unlink(path.c_str());
+					throw std::runtime_error(std::string("Can't write the ") + what);
+				}
+			}
+		}
+
+		void WriteDistances(size_t k, const ColorMap & map, uint64_t rows, const DistanceTable & d, const std::string & path)
+		{
+			CheckDistances(map, d);
+			const size_t n = size_t(d.colors);
+			std::string buf;
+			buf += "#twopaco-distances\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(d.colors) +
+				"\tsegments=" + std::to_string(rows) + "\n";
+			for (size_t c = 0; c < n; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+			for (size_t c = 0; c < n; c++) buf += "#self\t" + std::to_string(c) + "\t" + std::to_string(d.segments[c * n + c]) + "\t" + std::to_string(d.edges[c * n + c]) + "\n";
+			for (size_t i = 0; i < n; i++)
+			{
+				for (size_t j = i + 1; j < n; j++)
+				{
+					buf += std::to_string(i);
+					buf += '\t';
+					buf += std::to_string(j);
+					buf += '\t';
+					buf += std::to_string(d.segments[i * n + j]);
+					buf += '\t';
+					buf += std::to_string(d.edges[i * n + j]);
+					buf += '\n';
+				}
+			}
+
+			WriteWhole(buf, path, "distance table");
+		}
+
+		void WriteDistancesPhylip(const ColorMap & map, const DistanceTable & d, const std::string & path)
+		{
+			CheckDistances(map, d);
+			if (path.empty()) throw std::runtime_error("The PHYLIP matrix needs a file name");
+			const size_t n = size_t(d.colors);
+			std::string buf = std::to_string(n) + "\n";
+			char number[64];
+			for (size_t i = 0; i < n; i++)
+			{
+				for (char ch : map.label[i]) buf += static_cast<unsigned char>(ch) <= ' ' ? '_' : ch;
+				for (size_t j = 0; j < n; j++)
+				{
+					const uint64_t shared = d.edges[i * n + j], u = d.edges[i * n + i] + d.edges[j * n + j] - shared;
+					const double value = (i == j || u == 0) ? 0.0 : double(u - shared) / double(u);
+					std::snprintf(number, sizeof number, " %.6f", value);
+					buf += number;
+				}
+
+				buf += '\n';
+			}
+
+			WriteWhole(buf, path, "PHYLIP matrix");
+		}
+
+		void WriteDistanceFiles(size_t k, const ColorMap & map, uint64_t rows, const DistanceTable & d, const std::string & path, const std::string & phylipPath)
+		{
+			if (!phylipPath.empty()) WriteDistancesPhylip(map, d, phylipPath);
+			try
+			{
+				WriteDistances(k, map, rows, d, path);
+			}
+			catch (...)
+			{
+				if (!phylipPath.empty()) ::unlink(phylipPath.c_str());
+				throw;
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{

@@ -425,6 +425,37 @@ namespace TwoPaCo
 		void WriteBubbles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const BubbleTable & bubbles,
 			const std::string & path);
 
+		// ---------------------------------------------------------------------------------------- the genome distance matrices
+		// How much every colour shares with every other one (include/twopaco_hip.h, the tpc_segments_distances_* group, defines
+		// weight, rows and the two matrices; edges -- (k+1)-mers -- not bases, and whatever the colour table calls a row counts).
+		// The arrays come from ComputeDistances below -- the serial statement -- or from the device (csrc/tpc_distances.hip);
+		// WriteDistances and WriteDistancesPhylip print either as the same bytes.
+		struct DistanceTable
+		{
+			uint64_t colors;
+			std::vector<uint64_t> segments, edges;   // [colors][colors], row-major, symmetric, stored in full
+			DistanceTable() : colors(0) {}
+		};
+
+		// Two nested loops over the set bits of every row of the colour table; weight = end - begin of the row's first event.
+		void ComputeDistances(const EventTable & table, const ColorTable & colors, DistanceTable & out);
+
+		// The TSV text: "#twopaco-distances\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>", the colour table's "#color" lines,
+		// "#self\t<c>\t<segments[c][c]>\t<edges[c][c]>" per colour, then "<i>\t<j>\t<segments[i][j]>\t<edges[i][j]>" for every i < j, i
+		// ascending then j, the pairs that share nothing included.  Integers only: a reader gets the Jaccard similarity as
+		// e_ij / (e_ii + e_jj - e_ij).  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteDistances(size_t k, const ColorMap & map, uint64_t rows, const DistanceTable & distances, const std::string & path);
+
+		// The relaxed PHYLIP square matrix neighbour-joining tools read, into the file `path`: the line "C", then per colour its
+		// label with every byte <= ' ' replaced by '_' and C values, each preceded by one space and printed with %.6f:
+		// d = (u - e_ij) / u with u = e_ii + e_jj - e_ij, the Jaccard distance over edges; 0 when u == 0 and on the diagonal.  One
+		// correctly rounded division of two exactly represented integers.
+		void WriteDistancesPhylip(const ColorMap & map, const DistanceTable & distances, const std::string & path);
+
+		// Both files of the distance table, or neither: the PHYLIP matrix first when phylipPath is given, then the TSV (to stdout when
+		// path is empty); when the TSV cannot be written the PHYLIP file is removed again before the error is thrown.
+		void WriteDistanceFiles(size_t k, const ColorMap & map, uint64_t rows, const DistanceTable & distances, const std::string & path, const std::string & phylipPath);
+
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
 		// the table carries linkFirst.
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

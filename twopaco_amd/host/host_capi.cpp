@@ -277,6 +277,51 @@ extern "C"
 		}
 	}
 
+	// the same as tpch_create_enumerator_links with --distances (EnumeratorOptions::distancesBy, distancesFile, distancesPhylipFile):
+	// distancesBy file | sequence into distancesFile, phylipFile NULL or empty: no PHYLIP matrix; linksFile NULL or empty: no link
+	// table; colorsBy NULL or empty: no colour table; autoFilter != 0: `-f auto` (EnumeratorOptions::autoFilterSize, filterBits is
+	// ignored and rounds = 0 lets the plan choose them too, as tpch_create_enumerator_auto)
+	void * tpch_create_enumerator_distances(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
+		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
+		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile,
+		const char * linksFile, int graphCompact, const char * distancesBy, const char * distancesFile, const char * phylipFile, int autoFilter, char ** log)
+	{
+		std::stringstream ss;
+		try
+		{
+			std::vector<std::string> names(files, files + nfiles);
+			TwoPaCo::EnumeratorOptions opt;
+			opt.pinnedSeed = pinned != 0;
+			opt.seed = seed;
+			opt.device = device;
+			opt.insertTestFirst = testFirst != 0;
+			opt.graphFormat = graphFormat ? graphFormat : "";
+			opt.graphFile = graphFile ? graphFile : "";
+			opt.graphPrefix = graphPrefix != 0;
+			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
+			opt.colorsBy = colorsBy ? colorsBy : "";
+			opt.colorsFile = colorsFile ? colorsFile : "";
+			opt.linksFile = linksFile ? linksFile : "";
+			opt.graphCompact = graphCompact != 0;
+			opt.distancesBy = distancesBy ? distancesBy : "";
+			opt.distancesFile = distancesFile ? distancesFile : "";
+			opt.distancesPhylipFile = phylipFile ? phylipFile : "";
+			if (opt.distancesBy.empty() || opt.distancesFile.empty()) throw std::runtime_error("The distance table needs its colours, one of file, sequence, and a file name");
+			opt.autoFilterSize = autoFilter != 0;
+			opt.autoRounds = autoFilter != 0 && rounds == 0;
+			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, autoFilter ? 0 : filterBits, q, autoFilter && rounds == 0 ? 1 : rounds, threads, abundance, tmpDir,
+				outFile ? outFile : "", ss, opt);
+			if (log) *log = Dup(ss.str());
+			return e.release();
+		}
+		catch (std::exception & e)
+		{
+			g_error = e.what();
+			if (log) *log = Dup(ss.str());
+			return 0;
+		}
+	}
+
 	// The text of the compacted graph from an EVENT TABLE (include/twopaco_hip.h: name / first bits / begin / end per event,
 	// seq_event_begin[0 .. n_seq] per sequence) and the FASTA files, into out_path: graphformat.h without any device.  format
 	// gfa1 | gfa2 | fasta, prefix = graphdump's --prefix.  0, or nonzero with tpch_last_error.

@@ -4,7 +4,8 @@
 // graphdump (reference src/graphdump/graphdump.cpp) so that pipelines built on it are unchanged:
 //   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>] [--text host|device]
 //             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]
-//             |  --bubbles file|sequence [--bubbles-out <path>]   (the last three instead of -f)
+//             |  --bubbles file|sequence [--bubbles-out <path>]
+//             |  --distances file|sequence [--distances-out <path>] [--distances-phylip <path>]   (the last four instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -49,6 +50,11 @@
 // TSV with the colour rows of the two arms (graphformat.h: WriteBubbles).  Without --gpu the serial walk, then ComputeColors,
 // ComputeLinks and ComputeBubbles; with --gpu the three device stages over one segment build (csrc/tpc_bubbles.hip); the bytes are
 // the same.  Every byte waits until the table is complete: a stream the walk refuses prints the walk's error and nothing else.
+// --distances file|sequence [--distances-out <path>] [--distances-phylip <path>] (an addition; instead of -f): how much every colour
+// shares with every other one -- the segments and the edges ((k+1)-mers) two colours both hold; include/twopaco_hip.h defines them --
+// as TSV of integers (graphformat.h: WriteDistances) and, asked for, as a PHYLIP square matrix of Jaccard distances over edges.
+// Without --gpu the serial walk, then ComputeColors and ComputeDistances; with --gpu the colour stage and the distance stage over one
+// segment build (csrc/tpc_distances.hip); the bytes are the same.  A stream the walk refuses prints the walk's error and nothing else.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -350,7 +356,17 @@ namespace
 		}
 	};
 
-	void DumpColors(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath)
+	// --distances beside another table of the same colours: the file names of the distance table, written after that table from the
+	// same walk (or segment build) and the same colour table
+	struct DistancesWanted
+	{
+		bool on;
+		std::string out, phylip;
+		DistancesWanted() : on(false) {}
+	};
+
+	void DumpColors(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
+		const DistancesWanted & also = DistancesWanted())
 	{
 		InputSequences seq;
 		ListSequences(fasta, prefix, seq);
@@ -363,7 +379,10 @@ namespace
 		MakeColorMap(seq, fasta, bySequence, map);
 		ColorTable colors;
 		ComputeColors(table, k, map.colorOfSequence, map.label.size(), colors);
+		DistanceTable distances;
+		if (also.on) ComputeDistances(table, colors, distances);
 		WriteColors(table, k, map, colors, outPath);
+		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
 	}
 
 	// ---------------------------------------------------------------------------------------- --links and --compact, serial
@@ -413,7 +432,8 @@ namespace
 	}
 
 	// --bubbles, serial: the walk, then the three serial statements one after the other
-	void DumpBubbles(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath)
+	void DumpBubbles(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
+		const DistancesWanted & also = DistancesWanted())
 	{
 		SerialTable t;
 		WalkLinks(binFile, fasta, k, prefix, false, t);
@@ -423,7 +443,30 @@ namespace
 		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
 		BubbleTable bubbles;
 		ComputeBubbles(t.table, t.links, bubbles);
+		DistanceTable distances;
+		if (also.on) ComputeDistances(t.table, colors, distances);
 		WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, outPath);
+		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
+	}
+
+	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
+	void DumpDistances(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
+		const std::string & phylipPath)
+	{
+		InputSequences seq;
+		ListSequences(fasta, prefix, seq);
+		EventCollector events;
+		WalkSegments(binFile, fasta, k, events);
+		std::vector<uint32_t> seqEventBegin;
+		EventTable table;
+		events.Table(seq.name.size(), seqEventBegin, table);
+		ColorMap map;
+		MakeColorMap(seq, fasta, bySequence, map);
+		ColorTable colors;
+		ComputeColors(table, k, map.colorOfSequence, map.label.size(), colors);
+		DistanceTable distances;
+		ComputeDistances(table, colors, distances);
+		WriteDistanceFiles(k, map, colors.Rows(), distances, outPath, phylipPath);
 	}
 
 	// ---------------------------------------------------------------------------------------- --gpu
@@ -438,10 +481,10 @@ namespace
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
 		uint64_t links, linkOccurrences, bubbles;
-		double bubblesKernelMs, bubblesMs;
+		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), bubblesKernelMs(0), bubblesMs(0),
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
 			threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
@@ -455,10 +498,10 @@ namespace
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
 				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f, "
 				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu, "
-				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
-				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles);
+				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs);
 			std::fclose(f);
 		}
 	};
@@ -492,6 +535,9 @@ namespace
 		decltype(&tpc_segments_bubbles_info) segmentsBubblesInfo;
 		decltype(&tpc_segments_bubbles_fetch_rows) segmentsBubblesFetchRows;
 		decltype(&tpc_segments_bubbles_fetch_hist) segmentsBubblesFetchHist;
+		decltype(&tpc_segments_distances_build) segmentsDistancesBuild;
+		decltype(&tpc_segments_distances_info) segmentsDistancesInfo;
+		decltype(&tpc_segments_distances_fetch) segmentsDistancesFetch;
 		decltype(&tpc_kernel_ms) kernelMs;
 		tpc_ctx * ctx;
 
@@ -534,6 +580,9 @@ namespace
 			Load(segmentsBubblesInfo, "tpc_segments_bubbles_info");
 			Load(segmentsBubblesFetchRows, "tpc_segments_bubbles_fetch_rows");
 			Load(segmentsBubblesFetchHist, "tpc_segments_bubbles_fetch_hist");
+			Load(segmentsDistancesBuild, "tpc_segments_distances_build");
+			Load(segmentsDistancesInfo, "tpc_segments_distances_info");
+			Load(segmentsDistancesFetch, "tpc_segments_distances_fetch");
 			Load(kernelMs, "tpc_kernel_ms");
 			const int rc = ctxCreate(device, &ctx);
 			if (rc != 0 || !ctx)
@@ -683,10 +732,28 @@ namespace
 		stats.colorsMs = MsSince(c0);
 	}
 
+	// The distance matrices over the colour build in the context (csrc/tpc_distances.hip), fetched.
+	void DistancesOnDevice(DeviceLibrary & lib, const ColorMap & map, uint64_t rows, DistanceTable & distances, DumpStats & stats)
+	{
+		const std::chrono::steady_clock::time_point d0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsDistancesBuild(lib.ctx), "tpc_segments_distances_build");
+		stats.distancesKernelMs = lib.kernelMs(lib.ctx, TPC_K_DISTANCES);
+		uint64_t info[4] = {0, 0, 0, 0};
+		lib.Check(lib.segmentsDistancesInfo(lib.ctx, info), "tpc_segments_distances_info");
+		if (info[0] != map.label.size() || info[1] != rows) throw std::runtime_error("--gpu: the distance stage and the colour map disagree about the colours or the segments");
+		distances.colors = info[0];
+		distances.segments.resize(size_t(info[0] * info[0]));
+		distances.edges.resize(size_t(info[0] * info[0]));
+		lib.Check(lib.segmentsDistancesFetch(lib.ctx, 0, info[0], distances.segments.data(), distances.edges.data()), "tpc_segments_distances_fetch");
+		stats.distancesMs = MsSince(d0);
+		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] distance matrices on device: %.3f ms (kernels %.3f ms)\n", stats.distancesMs, stats.distancesKernelMs);
+	}
+
 	// --colors with --gpu: the table stays on the device, where the colour stage groups its events by segment (csrc/tpc_colors.hip);
 	// what is fetched is the rows, their presence words, the histogram, and the event table for the names and lengths.
 	void DumpColorsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats)
+		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats,
+		const DistancesWanted & also = DistancesWanted())
 	{
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 		size_t sequences = 0;
@@ -697,11 +764,14 @@ namespace
 		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
 		ColorTable colors;
 		ColorsOnDevice(lib, map, counts[1], colors, stats);
+		DistanceTable distances;
+		if (also.on) DistancesOnDevice(lib, map, counts[1], distances, stats);
 		FetchedTable held;
 		FetchTable(lib, counts[0], sequences, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		WriteColors(held.table, k, map, colors, outPath);
+		if (also.on) WriteDistanceFiles(k, map, counts[1], distances, also.out, also.phylip);
 		stats.formatMs = MsSince(t0);
 		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] colour table on device: %.3f ms (kernels %.3f ms)\n", stats.colorsMs, stats.colorsKernelMs);
 	}
@@ -756,7 +826,8 @@ namespace
 	// --bubbles with --gpu: one segment build, then the colour, link and bubble stages on the device (csrc/tpc_bubbles.hip reads the
 	// link rows where they lie); what is fetched is the bubble rows, the degree histogram, the colour rows and the event table.
 	void DumpBubblesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats)
+		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats,
+		const DistancesWanted & also = DistancesWanted())
 	{
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 		size_t sequences = 0;
@@ -767,6 +838,8 @@ namespace
 		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
 		ColorTable colors;
 		ColorsOnDevice(lib, map, counts[1], colors, stats);
+		DistanceTable distances;
+		if (also.on) DistancesOnDevice(lib, map, counts[1], distances, stats);
 		LinkTable links;
 		LinksOnDevice(lib, counts[0], true, links, stats);
 		const std::chrono::steady_clock::time_point b0 = std::chrono::steady_clock::now();
@@ -791,6 +864,31 @@ namespace
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, outPath);
+		if (also.on) WriteDistanceFiles(k, map, counts[1], distances, also.out, also.phylip);
+		stats.formatMs = MsSince(t0);
+	}
+
+	// --distances with --gpu: one segment build, the colour stage, then the distance stage over the presence bits where they lie
+	// (csrc/tpc_distances.hip); what is fetched is the two matrices.  Neither the colour rows nor the event table come back.
+	void DumpDistancesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, const std::string & phylipPath, DumpStats & stats)
+	{
+		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
+		size_t sequences = 0;
+		std::chrono::steady_clock::time_point t0;
+		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
+		ColorMap map;
+		MakeColorMap(seq, fasta, bySequence, map);
+		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
+		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
+		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
+		stats.colorsMs = MsSince(c0);
+		DistanceTable distances;
+		DistancesOnDevice(lib, map, counts[1], distances, stats);
+		stats.deviceMs = MsSince(t0);
+		t0 = std::chrono::steady_clock::now();
+		WriteDistanceFiles(k, map, counts[1], distances, outPath, phylipPath);
 		stats.formatMs = MsSince(t0);
 	}
 
@@ -867,7 +965,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -899,6 +997,13 @@ namespace
 			"     only: three alleles at one place, nested bubbles and superbubbles are not reported.  Needs -k and -s.  With --gpu\n"
 			"     the bubbles are found on the device.  Not with --colors, --links, --compact or --text.\n\n"
 			"   --bubbles-out <file name>\n     with --bubbles: write the table there instead of to the standard output\n\n"
+			"   --distances <file|sequence>\n     instead of -f: how much every colour (file or sequence, as --colors) shares with every other one, as TSV of\n"
+			"     integers: per colour its own segments and edges ((k+1)-mers), then for every pair i < j the segments and the edges\n"
+			"     both hold.  Edges, not bases: neighbouring segments overlap by k bases.  Jaccard = e_ij / (e_ii + e_jj - e_ij).\n"
+			"     Needs -k and -s.  With --gpu the matrices are summed on the device.  Goes with --colors or --bubbles of the\n"
+			"     same colours (one walk and one colour table for both; that table is written first, this one after it); not with --links, --compact or --text.\n\n"
+			"   --distances-out <file name>\n     with --distances: write the table there instead of to the standard output\n\n"
+			"   --distances-phylip <file name>\n     with --distances: also write the Jaccard distances over edges as a relaxed PHYLIP square matrix there\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -908,9 +1013,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false;
+		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -970,6 +1075,13 @@ int main(int argc, char * argv[])
 				if (bubblesBy != "file" && bubblesBy != "sequence") throw ArgError("Value '" + bubblesBy + "' does not meet constraint: file|sequence", "Argument: (--bubbles)");
 			}
 			else if (a == "--bubbles-out") { bubblesOut = value("(--bubbles-out)"); bubblesOutSet = true; }
+			else if (a == "--distances")
+			{
+				distancesBy = value("(--distances)");
+				if (distancesBy != "file" && distancesBy != "sequence") throw ArgError("Value '" + distancesBy + "' does not meet constraint: file|sequence", "Argument: (--distances)");
+			}
+			else if (a == "--distances-out") { distancesOut = value("(--distances-out)"); distancesOutSet = true; }
+			else if (a == "--distances-phylip") { distancesPhylip = value("(--distances-phylip)"); distancesPhylipSet = true; }
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -990,7 +1102,17 @@ int main(int argc, char * argv[])
 			else throw ArgError("Couldn't find match for argument", "(" + a + ")");
 		}
 
-		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty();
+		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty();
+		if (distances && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--distances)");
+		// one set of colours per run: the modes are compared before anything else is said about the combination
+		if (distances && colors && colorsBy != distancesBy) throw ArgError("The distance table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --distances " + distancesBy, "(--distances)");
+		if (distances && bubbles && bubblesBy != distancesBy) throw ArgError("The distance table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --distances " + distancesBy, "(--distances)");
+		if (distances && links) throw ArgError("The distance table and the link table are written one at a time: not with --links", "(--distances)");
+		if (distances && compact) throw ArgError("The distance table and the compact text are written one at a time: not with --compact", "(--distances)");
+		if (distances && textSet) throw ArgError("The distance table is formatted by the host: not with --distances", "(--text)");
+		if (distancesOutSet && !distances) throw ArgError("This argument needs --distances <file|sequence>", "(--distances-out)");
+		if (distancesPhylipSet && !distances) throw ArgError("This argument needs --distances <file|sequence>", "(--distances-phylip)");
+		if (distancesPhylipSet && distancesPhylip.empty()) throw ArgError("The PHYLIP matrix needs a file name", "(--distances-phylip)");
 		if (bubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--bubbles)");
 		if (bubbles && colors) throw ArgError("The bubble table and the colour table are written one at a time: not with --colors", "(--bubbles)");
 		if (bubbles && links) throw ArgError("The bubble table and the link table are written one at a time: not with --links", "(--bubbles)");
@@ -1007,10 +1129,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles && !distances) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || distances || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -1020,6 +1142,12 @@ int main(int argc, char * argv[])
 		const bool deviceText = lib && textOnDevice;
 		stats.text = deviceText ? "device" : "host";
 		Out out(!deviceText && !compact);  // --text device, --compact: the header lines wait until the table is known to be good
+		// --distances beside --colors or --bubbles (the same colours, checked above): that table's walk or segment build and its
+		// colour table serve the distance table too, which is written after it
+		DistancesWanted also;
+		also.on = distances && (colors || bubbles);
+		also.out = distancesOut;
+		also.phylip = distancesPhylip;
 		if (colors && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -1027,9 +1155,9 @@ int main(int argc, char * argv[])
 			LoadedSequences loaded;
 			LoadSequences(fasta, prefix, threads, seq, loaded);
 			stats.loadMs = MsSince(t0);
-			DumpColorsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, colorsBy == "sequence", colorsOut, stats);
+			DumpColorsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, colorsBy == "sequence", colorsOut, stats, also);
 		}
-		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut);
+		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
 		else if (links && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -1047,9 +1175,19 @@ int main(int argc, char * argv[])
 			LoadedSequences loaded;
 			LoadSequences(fasta, prefix, threads, seq, loaded);
 			stats.loadMs = MsSince(t0);
-			DumpBubblesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, bubblesBy == "sequence", bubblesOut, stats);
+			DumpBubblesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, bubblesBy == "sequence", bubblesOut, stats, also);
 		}
-		else if (bubbles) DumpBubbles(binFile, fasta, k, prefix, bubblesBy == "sequence", bubblesOut);
+		else if (bubbles) DumpBubbles(binFile, fasta, k, prefix, bubblesBy == "sequence", bubblesOut, also);
+		else if (distances && lib)
+		{
+			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+			InputSequences seq;
+			LoadedSequences loaded;
+			LoadSequences(fasta, prefix, threads, seq, loaded);
+			stats.loadMs = MsSince(t0);
+			DumpDistancesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, distancesBy == "sequence", distancesOut, distancesPhylip, stats);
+		}
+		else if (distances) DumpDistances(binFile, fasta, k, prefix, distancesBy == "sequence", distancesOut, distancesPhylip);
 		else if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device

@@ -350,6 +350,12 @@ namespace TwoPaCo
 				if (bubbles && options.bubblesBy != "file" && options.bubblesBy != "sequence") throw std::runtime_error("The bubble table's colours must be one of file, sequence");
 				if (bubbles && colors && options.bubblesBy != options.colorsBy) throw std::runtime_error("The bubble table and the colour table share one set of colours: both by file or both by sequence");
 				if (bubbles && sharded) throw std::runtime_error("The bubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				const bool distances = !options.distancesFile.empty();
+				if (distances && options.distancesBy != "file" && options.distancesBy != "sequence") throw std::runtime_error("The distance table's colours must be one of file, sequence");
+				if (distances && colors && options.distancesBy != options.colorsBy) throw std::runtime_error("The distance table and the colour table share one set of colours: both by file or both by sequence");
+				if (distances && bubbles && options.distancesBy != options.bubblesBy) throw std::runtime_error("The distance table and the bubble table share one set of colours: both by file or both by sequence");
+				if (distances && sharded) throw std::runtime_error("The distance table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (!distances && !options.distancesPhylipFile.empty()) throw std::runtime_error("The PHYLIP matrix is written with the distance table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -484,7 +490,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles)
+				if (graph || colors || links || bubbles || distances)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -982,7 +988,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles || distances) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -994,11 +1000,15 @@ namespace TwoPaCo
 			// --colors: the same table, built once for both, grouped by segment on the device and written to options.colorsFile.
 			// --bubbles: the colour rows and the link table of the same build, then the bubble stage (csrc/tpc_bubbles.hip) over the
 			// link rows where they lie; written to options.bubblesFile after the graph and the link file.
+			// --distances: the colour build of the same table, then the distance stage (csrc/tpc_distances.hip) over the presence bits
+			// where they lie; options.distancesFile and the PHYLIP file are written last of all, both or neither (WriteDistanceFiles), so that
+			// a step that throws leaves no file of theirs.
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
-				const bool bubbles = !options.bubblesFile.empty(), colorRows = colors || bubbles, bySequence = (colors ? options.colorsBy : options.bubblesBy) == "sequence";
+				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), colorRows = colors || bubbles || distances;
+				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : options.distancesBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1047,6 +1057,9 @@ namespace TwoPaCo
 					GraphFormat::BubbleTable deviceBubbles;
 					uint64_t linkRows = 0;
 					if (bubbles) BubblesFromDevice(deviceBubbles, linkRows, timer);
+					// the distance matrices over the presence bits on the device, likewise before anything is written
+					GraphFormat::DistanceTable deviceDistances;
+					if (distances) DistancesFromDevice(deviceColors.map.label.size(), counts[1], deviceDistances, timer);
 					if (graph && options.graphTextOnDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph)
 					{
@@ -1073,6 +1086,12 @@ namespace TwoPaCo
 					{
 						GraphFormat::WriteBubbles(deviceColors.events, k, deviceColors.map, deviceColors.table, linkRows, deviceBubbles, options.bubblesFile);
 						timer.Lap("bubble table writing");
+					}
+
+					if (distances)
+					{
+						GraphFormat::WriteDistanceFiles(k, deviceColors.map, counts[1], deviceDistances, options.distancesFile, options.distancesPhylipFile);
+						timer.Lap("distance table writing");
 					}
 
 					return;
@@ -1122,6 +1141,39 @@ namespace TwoPaCo
 					GraphFormat::WriteBubbles(empty, k, map, table, 0, found, options.bubblesFile);
 					timer.Lap("bubble table writing");
 				}
+
+				if (distances)
+				{
+					// nothing dispatched: no segment, the header, the colours and two matrices of zeros
+					GraphFormat::EventTable empty;
+					empty.sequences = sequences;
+					empty.seqEventBegin = seqEventBegin.data();
+					GraphFormat::ColorMap map;
+					GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
+					GraphFormat::ColorTable table;
+					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
+					GraphFormat::DistanceTable none;
+					GraphFormat::ComputeDistances(empty, table, none);
+					GraphFormat::WriteDistanceFiles(k, map, 0, none, options.distancesFile, options.distancesPhylipFile);
+					timer.Lap("distance table writing");
+				}
+			}
+
+			// --distances: the two colour x colour matrices summed on the device (csrc/tpc_distances.hip) over the presence bits of the
+			// colour build; fetched are the matrices alone.
+			void DistancesFromDevice(uint64_t colors, uint64_t rows, GraphFormat::DistanceTable & out, PhaseTimer & timer)
+			{
+				Check(tpc_segments_distances_build(ctx_), "segments_distances_build");
+				timer.Lap("segment distances");
+				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   distances_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_DISTANCES) << " ms" << std::endl;
+				uint64_t info[4] = {0, 0, 0, 0};
+				Check(tpc_segments_distances_info(ctx_, info), "segments_distances_info");
+				if (info[0] != colors || info[1] != rows) throw std::runtime_error("The distance stage and the colour table disagree about the colours or the segments");
+				out.colors = info[0];
+				out.segments.resize(size_t(info[0] * info[0]));
+				out.edges.resize(size_t(info[0] * info[0]));
+				Check(tpc_segments_distances_fetch(ctx_, 0, info[0], out.segments.data(), out.edges.data()), "segments_distances_fetch");
+				timer.Lap("segment distances fetch");
 			}
 
 			// --bubbles: the simple bubbles of the link table on the device found there (csrc/tpc_bubbles.hip); fetched are the bubble

@@ -89,6 +89,13 @@ namespace TwoPaCo
 		// link table of the same segment table.  One GPU.
 		std::string bubblesBy;
 		std::string bubblesFile;
+		// The genome distance matrices (graphformat.h: WriteDistances; `graphdump --distances` writes the same bytes for the junction
+		// stream of this run): distancesFile (empty: off), distancesBy = "file" | "sequence" -- the same as colorsBy and bubblesBy
+		// when those are given -- and distancesPhylipFile (empty: off) for the PHYLIP square matrix of Jaccard distances over edges.
+		// Summed on the device (tpc_segments_distances_build) over the colour build of the same segment table.  One GPU.
+		std::string distancesBy;
+		std::string distancesFile;
+		std::string distancesPhylipFile;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
