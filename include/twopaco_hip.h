@@ -689,6 +689,13 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      geometry, the insert stops after its level-2 binning and the lookup kernel of the query's FIRST batch builds
  *                      each filter slice itself (the filter is written once and not read back by that batch); TPC_K_INSERT then
  *                      covers hash + split only and TPC_K_FUSED the shared kernel; 0: off
+ *   verify_marks       1 (default): the partitioned query's verification writes one verdict per survivor and two kernels OR the marked
+ *                      positions into the candidate mask through LDS, in whole lines (k_mark_split, k_mark_apply); 0: it marks with
+ *                      one device atomic per passing survivor.  TPC_VERIFY_MARKS=0 / 1 in the environment overrides the option
+ *                      (measurements; read once per process).  The sharded first pass always marks with atomics
+ *   mark_bucket_bits / mark_region_cap / mark_slice_bits   tests only, process-wide (0 = automatic): log2 positions of a bucket of the
+ *                      mark lists (14..21), entries of a (workgroup, bucket) region (tiny: most entries take the atomic fallback),
+ *                      log2 bits of the LDS slice k_mark_apply holds (10..20: a larger bucket is cut into sub-slices)
  *   test_sched_cap     tests only, process-wide: rounds per segment of the split kernels' round schedule (0 = what fits in LDS)
  *   test_fail_mallocs  tests only, process-wide: the next N second-pass / output allocations fail at their first attempt, as if
  *                      the device were full (they then give the partition buffers back and try again, see "pbuf_releases")
@@ -721,6 +728,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);
  * "query_hash_kernel" = 0 none (direct), 1 the lean k_q_hash2, 2 k_q_hash, 4 the closed form;
  * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify;
+ * "query_mark_path" = how the last query set the marks of its mask: 1 the write-combined lists, 0 device atomics (option verify_marks, a
+ * plan whose lists do not fit the level-1 buffer) or the direct kernel (also when it completed an overflowed partitioned pass);
+ * "query_mark_fallback" = entries of those lists that found a ring or a region full and were ORed straight into the mask (0 on path 0);
  * "text_word_begin" / "text_word_end" = the packed words [begin, end) of the text this context holds ("text_words" is their difference);
  * "periodic_any_query" / "periodic_any_insert" = 1 when the detection-only launch of the periodic-window masks found a position that
  * copies its verdict / drops its insert (0 before the masks of this text and k were asked for, or with the option off).

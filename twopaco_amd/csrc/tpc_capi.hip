@@ -241,7 +241,8 @@ uint64_t pass_tile_count(const tpc_ctx *c) { uint64_t a, b; pass_tiles(c, a, b);
 // level 2 has split it), as in the insert -- a batch holds two of the three large buffers, not three.
 size_t qpart_need(const TpcQPlan &pl, int i)
 {
-    if (i == 0) return std::max(tpc_qpart_bytes(pl, 0), tpc_qpart_bytes(pl, 9));
+    // ... and the mark lists of the verification live in the same buffer (pass1_query_impl states the invariant)
+    if (i == 0) return std::max({tpc_qpart_bytes(pl, 0), tpc_qpart_bytes(pl, 9), tpc_qpart_bytes(pl, 19)});
     if (i == 9) return 0;
     return tpc_qpart_bytes(pl, i);
 }
@@ -367,6 +368,10 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "part_levels")) { c->opt_part_levels = (int)value; return 0; }
     if (!strcmp(name, "shard_tight_regions")) { c->opt_shard_tight = value ? 1 : 0; c->sh_have[0] = c->sh_have[1] = false; return 0; }
     if (!strcmp(name, "part_min_tiles")) { c->opt_part_min_tiles = value < 1 ? 1 : value; return 0; }
+    if (!strcmp(name, "verify_marks")) { c->opt_verify_marks = value != 0; return 0; }
+    if (!strcmp(name, "mark_bucket_bits")) { tpc_test_mark_bucket_bits = (int)value; return 0; }  // process-wide, tests only
+    if (!strcmp(name, "mark_region_cap")) { tpc_test_mark_region_cap = (int)value; return 0; }    // process-wide, tests only
+    if (!strcmp(name, "mark_slice_bits")) { tpc_test_mark_slice_bits = (int)value; return 0; }    // process-wide, tests only
     if (!strcmp(name, "fuse_apply_lookup")) { c->opt_fuse = value != 0; return 0; }
     if (!strcmp(name, "test_q6_pb2")) { tpc_test_q6_pb2 = (int)value; return 0; }  // process-wide, tests only
     if (!strcmp(name, "insert_entry_fmt")) { tpc_test_insert_p3 = value == 3; return 0; }  // process-wide; 3 = blocked 24-bit level-2 insert entries (off by default: tpc_partition.hip)
@@ -419,6 +424,8 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "insert_hash_kernel")) return c->stat_kernel[0];
     if (!strcmp(name, "query_hash_kernel")) return c->stat_kernel[1];
     if (!strcmp(name, "query_verify_kernel")) return c->stat_kernel[2];
+    if (!strcmp(name, "query_mark_path")) return c->stat_mark_path;
+    if (!strcmp(name, "query_mark_fallback")) return c->stat_mark_fallback;
     if (!strcmp(name, "insert_batches")) return c->stat_batches[0];
     if (!strcmp(name, "query_batches")) return c->stat_batches[1];
     if (!strcmp(name, "query_tiles_per_batch")) return c->stat_q_plan[0];  // plan of the last partitioned query: 512-word tiles per batch, level-1 / level-2 bits
@@ -883,18 +890,28 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
         }
         pl.buf3 = (uint64_t *)c->pbuf[0]; pl.cnt3 = (uint32_t *)c->pbuf[10]; pl.off3 = (const uint64_t *)c->pbuf[11];  // qpart_need
         pl.bnd = (uint32_t *)c->pbuf[18];
+        // The verification's mark lists (verdicts, regions, counts: ~10 bytes per position against the ~60 of the level-1 regions) alias
+        // the level-1 buffer.  Invariant: on this stream nothing reads or writes pbuf[0] between the end of a batch's level-2 binning
+        // (k_q_split has consumed the level-1 regions; with three levels k_q_lookup has consumed the level-3 regions that live there
+        // too) and the next batch's k_q_hash -- the verification and the two mark kernels run inside that window, also when hash and
+        // binning of this batch ran early (tpc_pass1_query_begin), and a begun batch of the NEXT query is enqueued behind them.
+        pl.pass = pl.mark_buf = pl.mark_cnt = nullptr;  // (a begun plan carries the pointers of its own call)
+        const int env_marks = TpcEnv::get().verify_marks;
+        const bool mark_lists = env_marks >= 0 ? env_marks != 0 : c->opt_verify_marks != 0;
+        if (mark_lists && tpc_qpart_bytes(pl, 19) <= c->pbytes[0]) tpc_qpart_mark_pointers(pl, c->pbuf[0]);
         if (pl.b3 && c->off3_uploaded != pl.off3_host) {
             HIPCHK(c, hipMemcpy(c->pbuf[11], pl.off3_host.data(), pl.off3_host.size() * 8, hipMemcpyHostToDevice));
             c->off3_uploaded = pl.off3_host;
         }
-        unsigned long long f1[2] = {0, 0}, f2 = 0;
-        bool overflowed = false;
+        unsigned long long f1[3] = {0, 0, 0}, f2 = 0, lost_marks = 0;  // f1: the batch's overflow cursor, its flag, the marks k_mark_split ORed straight into the mask
+        bool overflowed = false, f1_counted = false;  // f1_counted: the loop has already added this batch's f1[2]
         uint64_t per_batch = 1;
         {
             Timed t(c, TPC_K_QUERY);
             const uint64_t per = pl.n_tiles;
             per_batch = per;
             for (uint64_t t0 = t_begin; (t0 < t_end || t0 == t_begin) && !overflowed; t0 += per) {  // (an empty chunk: one batch of no tiles -- a pending apply is still carried out)
+                f1_counted = false;
                 pl.tile0 = t0;
                 pl.tile0_global = t0;
                 pl.n_tiles = t0 < t_end ? std::min<uint64_t>(per, t_end - t0) : 0;
@@ -952,6 +969,8 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
                     if (wn) HIPCHK(c, hipMemcpyAsync(&batch_marks, c->counters + 3, sizeof batch_marks, hipMemcpyDeviceToHost, c->stream));
                     HIPCHK(c, hipStreamSynchronize(c->stream));
                     overflowed = f1[1] != 0 || f2 != 0;
+                    lost_marks += f1[2];
+                    f1_counted = true;
                     unsigned long long surv = 0;
                     for (int i = 0; i < 64; i++) surv += std::min<unsigned long long>(sc[i], pl.surv_cap);
                     if (surv > 0) pl.group_survivors = batch_marks * 4 >= surv;
@@ -965,8 +984,11 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
         int rc = read_counter(c, 1, &n);
         if (rc) return rc;
         overflowed = overflowed || f1[1] != 0 || f2 != 0;
+        if (!f1_counted) lost_marks += f1[2];  // (the last batch's, read back by the synchronisation above; a pass that an overflow ended inside the loop has counted it)
         c->stat_query_overflow = (int64_t)f1[0];
         c->stat_path[1] = (pl.b3 ? 3 : 2) + (overflowed ? 10 : 0);
+        c->stat_mark_path = pl.pass && !overflowed ? 1 : 0;  // (an overflowed pass: the direct kernel below rewrites the whole mask)
+        c->stat_mark_fallback = c->stat_mark_path ? (int64_t)lost_marks : 0;
         c->stat_fmt[1] = pl.fmt;
         c->stat_batches[1] = (int64_t)((pass_tile_count(c) + per_batch - 1) / per_batch);
         c->stat_q_plan[0] = (int64_t)per_batch; c->stat_q_plan[1] = pl.b1; c->stat_q_plan[2] = pl.b2;
@@ -1040,7 +1062,7 @@ int pass1_query_impl(tpc_ctx *c, uint64_t lo, uint64_t hi, uint64_t *n_marks, bo
         // an overflow list overflowed (pathological skew): the direct kernel below rewrites the whole mask
         if (replicated(c)) return fail(c, -20, "overflow or survivor list overflowed (address skew beyond what the sharded path handles)");  // (the direct kernel scans the whole text)
     }
-    if (!part) { c->stat_path[1] = 1; c->stat_batches[1] = 1; }
+    if (!part) { c->stat_path[1] = 1; c->stat_batches[1] = 1; c->stat_mark_path = 0; c->stat_mark_fallback = 0; }
     HIPCHK(c, hipMemsetAsync(c->counters + 1, 0, sizeof(unsigned long long), c->stream));
     {
         Timed t(c, TPC_K_QUERY);

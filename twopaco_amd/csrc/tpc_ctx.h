@@ -165,6 +165,9 @@ struct tpc_ctx {
     int64_t stat_filter2_retries = 0;  // exact-filter passes repeated with the full-size table (last tpc_pass2_filter)
     int64_t stat_aggregate_retries = 0;  // ... by the last tpc_pass2_aggregate_records
     int stat_filter2_counted = 0;        // the last exact-filter launch counted occurrences (k_filter2 / k_filter2_rec <C, true>)
+    int opt_verify_marks = 1;  // the partitioned query's marks: 1 = write-combined lists (k_mark_split / k_mark_apply), 0 = device atomics in the verification kernel
+    int stat_mark_path = 0;    // the marks of the last query's mask: 1 = through the lists, 0 = device atomics or the direct kernel ("query_mark_path")
+    int64_t stat_mark_fallback = 0;  // entries of the last query's lists that found a ring or region full and were ORed straight into the mask ("query_mark_fallback")
     int64_t opt_part_min_tiles = 256;  // never cut batches smaller than this many 512-word tiles
     int64_t opt_part_budget = 0;  // bytes of partition buffers per batch; 0 = automatic (part_budget())
     int opt_query_mode = 0;    // 0 auto, 1 direct loads, 2 partitioned

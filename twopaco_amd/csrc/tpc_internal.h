@@ -7,9 +7,11 @@
 
 // Measurement switches of the kernels' launch and planning code: read from the environment ONCE per process (they used to be looked up
 // on every pass).  TPC_NO_LEAN: the generic hash kernels; TPC_RB_HASH: the barrier-free rings in the 512-bin hash; TPC_VERIFY_LAZY=0:
-// all q - 1 probes at once; TPC_GATED_FULL_REGIONS: gated rounds sized for all entries; TPC_PPR_INSERT / TPC_GATED_LOADS: round sizes.
+// all q - 1 probes at once; TPC_GATED_FULL_REGIONS: gated rounds sized for all entries; TPC_PPR_INSERT / TPC_GATED_LOADS: round sizes;
+// TPC_VERIFY_MARKS=0 / 1: the verification's marks as device atomics / as write-combined lists, whatever option "verify_marks" says.
 struct TpcEnv {
     bool no_lean, rb_hash, verify_eager, gated_full;
+    int verify_marks;  // -1: not set
     int ppr_insert, gated_loads, split_loads9;  // 0: not set
     int slice_grid;  // workgroups of a one-slice-at-a-time kernel (tpc_slice_grid); 0: one per slice
     static const TpcEnv &get()
@@ -21,6 +23,8 @@ struct TpcEnv {
             const char *lz = getenv("TPC_VERIFY_LAZY");
             v.verify_eager = lz && lz[0] == '0';
             v.gated_full = getenv("TPC_GATED_FULL_REGIONS") != nullptr;
+            const char *vm = getenv("TPC_VERIFY_MARKS");
+            v.verify_marks = vm && vm[0] ? (vm[0] != '0' ? 1 : 0) : -1;
             const char *p = getenv("TPC_PPR_INSERT"), *g = getenv("TPC_GATED_LOADS");
             v.ppr_insert = p ? atoi(p) : 0;
             v.gated_loads = g ? atoi(g) : 0;
@@ -170,10 +174,20 @@ struct TpcQPlan {
     bool presplit = false;  // the level-2 (and 3) binning of this batch has already run (tpc_pass1_query_begin): the lookup launches skip it
     uint32_t tiles_per_wg = 0, n_groups = 0, pb2 = 0;  // pb2: position bits a level-2 entry carries (groups of 2^pb2 positions)
     uint32_t *bnd = nullptr;
+    // Mark lists (k_mark_split / k_mark_apply): with `pass` set the verification stores one verdict per survivor -- its batch-relative
+    // position, or all-ones -- instead of an atomicOr into the mask; the positions are then binned by position >> MB into one private
+    // region of mark_cap entries (the low MB bits) per (workgroup, bucket) and ORed into the mask one LDS slice at a time.  pass == nullptr
+    // (the sharded callers, option verify_marks = 0): the verification marks with device atomics.
+    uint32_t *pass = nullptr;      // [64][surv_cap]
+    uint32_t *mark_buf = nullptr;  // [mark_wg][mark_nb] regions of mark_cap entries
+    uint32_t *mark_cnt = nullptr;  // [mark_wg << mark_lnb] entries per region, padded to whole 32-entry lines
+    int MB = 0, mark_lnb = 0, mark_sub_bits = 0;  // bucket bits; log2 of the bins of k_mark_split; bits of an LDS sub-slice of a bucket (<= 20)
+    uint32_t mark_nb = 0, mark_wg = 0, mark_cap = 0;  // buckets of the batch, workgroups of k_mark_split (a multiple of 64), entries per region (a multiple of 32)
 };
 #define TPC_SURV_CUR_WORDS 72  // surv_cur: [0..63] sub-list cursors, [64] overflow flag
 bool tpc_qpart_plan(int L, int slice_bits, uint64_t n_tiles, double frac, TpcQPlan &pl, int levels = 0);  // n_tiles: 512-word tiles per batch
-size_t tpc_qpart_bytes(const TpcQPlan &pl, int which);  // 0 buf1, 1 cnt1, 2 buf2, 3 cnt2, 4 ovf, 5 ovf_cur, 6 surv, 7 surv_cur, 8 off2, 9 buf3, 10 cnt3, 11 off3, 18 bnd (fmt 6)
+size_t tpc_qpart_bytes(const TpcQPlan &pl, int which);  // 0 buf1, 1 cnt1, 2 buf2, 3 cnt2, 4 ovf, 5 ovf_cur, 6 surv, 7 surv_cur, 8 off2, 9 buf3, 10 cnt3, 11 off3, 18 bnd (fmt 6), 19 the mark lists (verdicts + regions + counts)
+void tpc_qpart_mark_pointers(TpcQPlan &pl, void *base);  // pass / mark_buf / mark_cnt inside a buffer of tpc_qpart_bytes(pl, 19) bytes
 bool tpc_qpart_plan_sharded(int L, int slice_bits, uint64_t n_tiles, double frac, uint32_t rank, uint32_t world, TpcQPlan &pl, int levels = 0, bool tight = false,
                             bool packed = false);
 int tpc_launch_query_partitioned(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask, uint64_t lo, uint64_t hi, bool gated);
@@ -189,6 +203,7 @@ int tpc_launch_ovf_by_slice(const TpcLaunch &a, const uint64_t *list, uint64_t n
 #define TPC_FUSE_MAX_OVF (16ull << 20)  // insert overflow entries (ring or region full) up to which the apply is still deferred
 int tpc_launch_query_verify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask);
 extern int tpc_test_tight_pinch;     // tpc_partition.hip: option "test_tight_pinch" (tests: tight regions of a sharded pass at N % of their expected fill + a 64-entry overflow list)
+extern int tpc_test_mark_bucket_bits, tpc_test_mark_region_cap, tpc_test_mark_slice_bits;  // tpc_qpartition.hip: options "mark_bucket_bits" / "mark_region_cap" / "mark_slice_bits" (tests: MB, a tiny region capacity, the LDS sub-slice limit of k_mark_apply; process-wide)
 extern int tpc_test_q6_pb2;          // tpc_qpartition.hip: option "test_q6_pb2" (tests: position bits of a 6-byte level-2 entry, to get many groups on small inputs; process-wide)
 extern int tpc_test_insert_p3;       // tpc_partition.hip: option "insert_entry_fmt" (3: the level-2 insert entries as blocked 24-bit lines; process-wide)
 extern uint32_t tpc_test_sched_cap;  // tpc_partition.hip: option "test_sched_cap" (tests: rounds per schedule segment of the split kernels)

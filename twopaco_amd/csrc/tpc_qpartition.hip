@@ -16,7 +16,10 @@
 //                  tests its bit there; survivors (first probe hit: Bloom false positives ~ fill
 //                  rate, plus true second edges) are appended to 64 survivor sub-lists
 //   D  k_q_verify  one thread per survivor: recomputes the vertex hashes from the text, probes
-//                  functions 1..q-1 directly, and ORs the mark bit.
+//                  functions 1..q-1 directly, and stores its verdict (the position, or all-ones).
+//   E  k_mark_split, k_mark_apply  the positions that passed, binned by their top bits into whole
+//                  lines and ORed into the mask one LDS slice at a time (a plan without mark lists:
+//                  D ORs the mark bit itself, one device atomic per passing survivor).
 //
 // mark(g) <=> some unknown edge is present: with prev and next definite the known in- and out-edge
 // count 1 each, so "inCount > 1 || outCount > 1" (VE.h:656) holds exactly when one more edge passes
@@ -38,6 +41,7 @@
 
 #if TPC_QPARTITION_PART == 0
 int tpc_test_q6_pb2 = 0;  // option "test_q6_pb2" (tests)
+int tpc_test_mark_bucket_bits = 0, tpc_test_mark_region_cap = 0, tpc_test_mark_slice_bits = 0;  // options "mark_bucket_bits", "mark_region_cap", "mark_slice_bits" (tests)
 #endif
 
 namespace {
@@ -905,7 +909,7 @@ __global__ void k_q_ovf(const uint64_t *__restrict__ list, const unsigned long l
 template <int Q>
 __global__ void __launch_bounds__(256)
 k_q_verify(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__restrict__ bases, const uint32_t *__restrict__ filter,
-           const uint64_t *__restrict__ surv, const unsigned long long *__restrict__ surv_cur, uint64_t surv_cap, uint64_t gbase, uint32_t *rmask)
+           const uint64_t *__restrict__ surv, const unsigned long long *__restrict__ surv_cur, uint64_t surv_cap, uint64_t gbase, uint32_t *rmask, uint32_t *__restrict__ pass)
 {
     __shared__ uint64_t s_h[Q * 5], s_hk[Q * 5];
     if (threadIdx.x < Q * 5) { s_h[threadIdx.x] = tab[threadIdx.x]; s_hk[threadIdx.x] = tab[TPC_TAB_HK + threadIdx.x]; }
@@ -913,10 +917,14 @@ k_q_verify(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__
     const int list = blockIdx.y;
     const uint64_t n = min((uint64_t)surv_cur[list], surv_cap);
     const uint64_t *my = surv + (uint64_t)list * surv_cap;
+    uint32_t *my_pass = pass ? pass + (uint64_t)list * surv_cap : nullptr;  // (uniform) the verdict list of this sub-list, see below
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += stride) {
         const uint64_t sid = my[idx];
-        if (sid == ~0ull) continue;  // a padding entry of the 6-byte path (tpc_qpart6.h)
+        if (sid == ~0ull) {  // a padding entry of the 6-byte path (tpc_qpart6.h)
+            if (my_pass) my_pass[idx] = 0xFFFFFFFFu;
+            continue;
+        }
         const int e = (int)(sid & 7);
         const uint64_t g = gbase + (sid >> 3);
         // (no "is the position marked already?" test: that scattered read cost more than the work it saved, 3.73 -> 3.40 ms.
@@ -998,10 +1006,15 @@ k_q_verify(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__
 #pragma unroll
             for (int i = 1; i < Q; i++) present = present && probe(ng ? nn[i] : p[i]);
         }
-        // (Round 4 tried marking with plain byte stores -- one byte per position of the batch, folded into the mask by a small kernel
-        //  afterwards -- instead of these 54 M device-scope atomics: 3.14 -> 3.27 ms + 0.06 for the fold, profiles/r04a_*.  A scattered
-        //  partial-line store costs the memory system what the atomic does.)
-        if (present) atomicOr(&rmask[g >> 5], 1u << ((uint32_t)g & 31u));
+        // The mark.  With a verdict list (TpcQPlan::pass) it is one coalesced 4-byte store per survivor -- the batch-relative position, or
+        // all-ones for a survivor that failed -- and k_mark_split / k_mark_apply OR the positions into the mask through LDS, in whole
+        // lines.  Without one (the sharded callers, option verify_marks = 0) it is a device-scope atomicOr: a wave's 64 lanes hit 64
+        // unrelated lines, because a sub-list is grouped by filter address and not by position.  (Round 4 tried plain byte stores
+        // instead of those atomics -- one byte per position of the batch, folded into the mask by a small kernel afterwards: 3.14 ->
+        // 3.27 ms + 0.06 for the fold, profiles/r04a_*.  A scattered partial-line store costs the memory system what the atomic does;
+        // the lists are neither scattered nor partial.)
+        if (my_pass) my_pass[idx] = present ? (uint32_t)(sid >> 3) : 0xFFFFFFFFu;
+        else if (present) atomicOr(&rmask[g >> 5], 1u << ((uint32_t)g & 31u));
     }
 }
 
@@ -1020,7 +1033,7 @@ k_q_verify(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__
 template <int Q, bool LAZY>
 __global__ void __launch_bounds__(256)
 k_q_verify2(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__restrict__ bases, const uint32_t *__restrict__ filter,
-            const uint64_t *__restrict__ surv, const unsigned long long *__restrict__ surv_cur, uint64_t surv_cap, uint64_t gbase, uint32_t *rmask)
+            const uint64_t *__restrict__ surv, const unsigned long long *__restrict__ surv_cur, uint64_t surv_cap, uint64_t gbase, uint32_t *rmask, uint32_t *__restrict__ pass)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint4 *s_t = reinterpret_cast<uint4 *>(smem);  // [k + 1][4][Q]: {rotl(h_i[c], k - t), rotl(h_i[3 - c], t)}
@@ -1034,6 +1047,7 @@ k_q_verify2(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *_
     const int list = blockIdx.y;
     const uint64_t n = min((uint64_t)surv_cur[list], surv_cap);
     const uint64_t *my = surv + (uint64_t)list * surv_cap;
+    uint32_t *my_pass = pass ? pass + (uint64_t)list * surv_cap : nullptr;  // (uniform)
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t wmask = (1ull << (2 * k)) - 1ull;  // k <= 31
     // software pipeline: the survivor id and the text word of the NEXT survivor are loaded before this one is hashed (the
@@ -1049,7 +1063,10 @@ k_q_verify2(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *_
             sid_n = my[idx + stride];
             w_n = tpc_text_word_x2(bases, gbase + (sid_n == ~0ull ? 0ull : sid_n >> 3));
         }
-        if (sid == ~0ull) continue;
+        if (sid == ~0ull) {
+            if (my_pass) my_pass[idx] = 0xFFFFFFFFu;
+            continue;
+        }
         const int e = (int)(sid & 7), c = e & 3;
         const uint64_t g = gbase + (sid >> 3);
         // the edge's k + 1 letters, first letter in the low bits: in-edge c + v, out-edge v + c
@@ -1149,10 +1166,9 @@ k_q_verify2(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *_
                 for (int i = 2; i < Q; i++) present = present && ((wv[i] >> ((uint32_t)a[i] & 31u)) & 1u);
             }
         }
-        // (Round 4 tried marking with plain byte stores -- one byte per position of the batch, folded into the mask by a small kernel
-        //  afterwards -- instead of these 54 M device-scope atomics: 3.14 -> 3.27 ms + 0.06 for the fold, profiles/r04a_*.  A scattered
-        //  partial-line store costs the memory system what the atomic does.)
-        if (present) atomicOr(&rmask[g >> 5], 1u << ((uint32_t)g & 31u));
+        // The mark: a verdict for the lists, or the device atomic -- see the comment at the end of k_q_verify above.
+        if (my_pass) my_pass[idx] = present ? (uint32_t)(sid >> 3) : 0xFFFFFFFFu;
+        else if (present) atomicOr(&rmask[g >> 5], 1u << ((uint32_t)g & 31u));
     }
 }
 
@@ -1770,6 +1786,160 @@ void launch_qsplit6(const TpcLaunch &a, const TpcQPlan &pl, QOverflow ovf)
                        pl.bnd, pl.n_groups, pl.tiles_per_wg, (uint32_t)pl.n_tiles, pl.pb2);
 }
 
+// ------------------------------------------------------------------------------------------ E, the marks as lists
+// The verification's marks are bits of a mask of up to 2^30 positions, set in no particular order: as device atomics they were what
+// bounded k_q_verify2 (54 M of them per step of the headline workload, 64 unrelated lines per wave).  With TpcQPlan::pass the kernels
+// above store one verdict per survivor instead, and the two kernels here do what the insert's level-2 split and slice apply do for
+// filter bits: bin the positions by their top bits through LDS rings into whole 128-byte lines, then OR every bucket's entries into
+// its slice of the mask in LDS.
+//
+// k_mark_split: workgroup w streams share w % per of verdict list w / per (per = gridDim.x / 64), skips the all-ones verdicts and bins
+// the others by position >> MB.  An entry is the low MB bits (MB <= 21: never the ring sentinel).  One private region of `cap` entries
+// per (workgroup, bucket); an entry that finds its ring or its region full is ORed straight into the mask -- exact, OR is idempotent --
+// and counted in n_lost (the batch's ovf_cur[2], which the caller zeroes with the cursors).
+constexpr int MK_LOADS = 4;  // verdicts per thread and round: 4096 a round against rings of 32768 entries in all, half of them kept free
+__global__ void __launch_bounds__(1024)
+k_mark_split(const uint32_t *__restrict__ pass, const unsigned long long *__restrict__ surv_cur, uint64_t surv_cap, int MB, int LOG_NB, uint32_t nb, uint32_t *mark_buf,
+             uint32_t *mark_cnt, uint32_t cap, uint64_t gbase, uint32_t *rmask, unsigned long long *n_lost)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    Bins3<uint32_t, 1024> bins;
+    (void)bins.carve(smem, LOG_NB);
+    const uint32_t wg = blockIdx.x, per = gridDim.x / QS_LISTS;
+    // bins nb .. 2^LOG_NB - 1 receive nothing (a position is below nb << MB) and own no region
+    bins.init(mark_buf, [=](uint32_t b) { return b < nb ? make_uint2((uint32_t)((((uint64_t)wg * nb + b) * cap) >> 5), cap) : make_uint2(0u, 0u); });
+    // Two device atomics per fallback entry, the second on one address.  That is affordable only because the path is rare where time
+    // matters: a ring is full before its first flush only in a batch smaller than one round (a small text, whose whole query is
+    // microseconds), a region only under heavy skew; the headline workload takes it for no entry.  Should a skewed large input ever
+    // send a sizeable share of its marks here, count per wave (one add of the popcount of the active lanes) before anything else.
+    auto lost = [=](uint32_t b, uint32_t val) {
+        const uint64_t g = gbase + ((uint64_t)b << MB) + val;
+        atomicOr(&rmask[g >> 5], 1u << ((uint32_t)g & 31u));
+        atomicAdd(n_lost, 1ull);  // (stat "query_mark_fallback"; none on a text without heavy skew)
+    };
+    __syncthreads();
+    const uint32_t list = wg / per, part = wg % per;
+    const uint64_t n = min((uint64_t)surv_cur[list], surv_cap);
+    const uint64_t chunk = ((n + per - 1) / per + 3) & ~3ull;
+    const uint64_t begin = min(n, (uint64_t)part * chunk), end = min(n, begin + chunk);  // (uniform)
+    const uint32_t *src = pass + (uint64_t)list * surv_cap;
+    const uint32_t low = (1u << MB) - 1u;
+    constexpr uint64_t STEP = (uint64_t)MK_LOADS * 1024;
+    if (begin < end) {
+        // the next round's loads are issued before this round is binned; unpredicated (a lane past the end reads the last verdict of
+        // the share and is masked when the round is consumed)
+        uint32_t va[MK_LOADS], vb[MK_LOADS];
+        auto load = [&](uint32_t (&d)[MK_LOADS], uint64_t base) {
+#pragma unroll
+            for (int i = 0; i < MK_LOADS; i++) d[i] = src[min(base + (uint64_t)i * 1024 + threadIdx.x, end - 1)];
+        };
+        auto round = [&](const uint32_t (&cur)[MK_LOADS], uint64_t base) {
+            uint32_t bb[MK_LOADS], val[MK_LOADS];
+            bool ok[MK_LOADS];
+#pragma unroll
+            for (int i = 0; i < MK_LOADS; i++) {
+                ok[i] = base + (uint64_t)i * 1024 + threadIdx.x < end && cur[i] != 0xFFFFFFFFu;
+                bb[i] = ok[i] ? cur[i] >> MB : 0u;
+                val[i] = cur[i] & low;
+            }
+            bins.template push_batch<MK_LOADS>(bb, val, ok, lost);
+            bins.template flush<false>(lost);
+        };
+        load(va, begin);
+        for (uint64_t base = begin;; base += 2 * STEP) {
+            if (base + STEP < end) load(vb, base + STEP);
+            round(va, base);
+            if (base + STEP >= end) break;
+            if (base + 2 * STEP < end) load(va, base + 2 * STEP);
+            round(vb, base + STEP);
+            if (base + 2 * STEP >= end) break;
+        }
+    }
+    bins.template flush<true>(lost);
+    bins.store_counts(mark_cnt + ((uint64_t)wg << LOG_NB), [](uint32_t b) { return b; });
+}
+
+// k_mark_apply: one unit at a time per long-lived workgroup (tpc_slice_grid).  A unit is a bucket, or -- when a bucket's 2^MB bits do not
+// fit LDS (MB > sub_bits) -- one 2^sub_bits-bit sub-slice of a bucket: the workgroup then reads the bucket's entries and skips those of
+// the other sub-slices (re-reading a few MB is free).  The slice of the mask is LOADED, not zeroed: k_q_hash has already written the
+// N-neighbour marks of the batch into these words.  The bucket's nwg regions are short (a few hundred entries each), so they are not
+// streamed one after the other: their 16-byte pieces form one flat list (a prefix sum of the counts in LDS), every thread takes every
+// 1024th piece and finds its region by bisection -- all loads are independent.
+__global__ void __launch_bounds__(PT_APPLY_THREADS)
+k_mark_apply(int MB, int sub_bits, int LOG_NB, uint32_t nb, uint32_t nwg, const uint32_t *__restrict__ mark_buf, const uint32_t *__restrict__ mark_cnt, uint32_t cap,
+             uint64_t word_base, uint64_t n_words, uint32_t *rmask, uint32_t n_units)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *slice = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t words = 1u << (sub_bits - 5), sub_log = (uint32_t)(MB - sub_bits), sub_mask = (1u << sub_bits) - 1u;
+    uint32_t *s_off = slice + words;   // [nwg + 1] first 16-byte piece of every region in the bucket's flat list
+    uint32_t *s_w = s_off + nwg + 1;  // [16] scratch of the block scan
+    for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const uint32_t b = u >> sub_log, sub = u & ((1u << sub_log) - 1u);
+        const uint64_t w0 = word_base + ((uint64_t)b << (MB - 5)) + ((uint64_t)sub << (sub_bits - 5));
+        const uint32_t nw = w0 < n_words ? (uint32_t)min((uint64_t)words, n_words - w0) : 0u;  // the last slice ends with the mask
+        for (uint32_t i = threadIdx.x; i < words; i += PT_APPLY_THREADS) slice[i] = i < nw ? rmask[w0 + i] : 0u;
+        uint32_t running = 0;
+        for (uint32_t r0 = 0; r0 < nwg; r0 += PT_APPLY_THREADS) {  // (nwg <= 1024: one pass)
+            const uint32_t r = r0 + threadIdx.x;
+            const uint32_t n4 = r < nwg ? (min(mark_cnt[((uint64_t)r << LOG_NB) + b], cap) + 3u) >> 2 : 0u;
+            uint32_t total;
+            const uint32_t off = running + pt_block_excl_scan<PT_APPLY_THREADS>(n4, s_w, total);
+            if (r < nwg) s_off[r] = off;
+            running += total;
+            pt_barrier_lds();
+        }
+        if (threadIdx.x == 0) s_off[nwg] = running;
+        __syncthreads();
+        const uint32_t total4 = running;
+        constexpr int UNR = 4;
+        for (uint32_t i0 = threadIdx.x; i0 < total4; i0 += UNR * PT_APPLY_THREADS) {
+            uint4 v[UNR];
+#pragma unroll
+            for (int k = 0; k < UNR; k++) {
+                const uint32_t i = i0 + (uint32_t)k * PT_APPLY_THREADS;
+                v[k] = make_uint4(~0u, ~0u, ~0u, ~0u);
+                if (i < total4) {
+                    uint32_t lo = 0, hi = nwg;  // the region r with s_off[r] <= i < s_off[r + 1]
+                    while (hi - lo > 1u) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (s_off[mid] <= i) lo = mid; else hi = mid;
+                    }
+                    v[k] = reinterpret_cast<const uint4 *>(mark_buf + ((uint64_t)lo * nb + b) * cap)[i - s_off[lo]];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < UNR; k++) {
+                const uint32_t e[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (e[j] != 0xFFFFFFFFu && (e[j] >> sub_bits) == sub) atomicOr(&slice[(e[j] & sub_mask) >> 5], 1u << (e[j] & 31u));
+            }
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < nw; i += PT_APPLY_THREADS) rmask[w0 + i] = slice[i];
+        __syncthreads();
+    }
+}
+
+void launch_marks(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
+{
+    const uint64_t gbase = pl.tile0_global * (uint64_t)(PT_THREADS * TPC_RUN);
+    const size_t lds_split = Bins3<uint32_t, 1024>::lds_bytes(pl.mark_lnb);
+    (void)hipFuncSetAttribute((const void *)k_mark_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_split);
+    hipLaunchKernelGGL(k_mark_split, dim3(pl.mark_wg), dim3(1024), lds_split, a.stream, pl.pass, pl.surv_cur, pl.surv_cap, pl.MB, pl.mark_lnb, pl.mark_nb, pl.mark_buf, pl.mark_cnt,
+                       pl.mark_cap, gbase, rmask, pl.ovf_cur + 2);
+    // The geometry is that of a full batch (qpart_plan_marks); a short last batch, or a replicated rank's chunk, has marks in its own
+    // tiles only, so only the buckets those tiles reach are applied: the words behind them are neither loaded nor rewritten.
+    const uint64_t n_pos = std::max<uint64_t>(1, pl.n_tiles) * (uint64_t)(PT_THREADS * TPC_RUN);
+    const uint32_t nb_used = (uint32_t)std::min<uint64_t>(pl.mark_nb, (n_pos + (1ull << pl.MB) - 1) >> pl.MB);
+    const uint32_t n_units = nb_used << (pl.MB - pl.mark_sub_bits);
+    const size_t lds_apply = ((size_t)4 << (pl.mark_sub_bits - 5)) + ((size_t)pl.mark_wg + 1 + 16) * 4;
+    (void)hipFuncSetAttribute((const void *)k_mark_apply, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_apply);
+    hipLaunchKernelGGL(k_mark_apply, dim3(tpc_slice_grid(n_units)), dim3(PT_APPLY_THREADS), lds_apply, a.stream, pl.MB, pl.mark_sub_bits, pl.mark_lnb, pl.mark_nb, pl.mark_wg, pl.mark_buf,
+                       pl.mark_cnt, pl.mark_cap, gbase >> 5, (a.n_text >> 5) + 1, rmask, n_units);
+}
+
 #endif  // part 0 only
 template <int Q>
 void launch_qverify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
@@ -1782,16 +1952,16 @@ void launch_qverify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
         if (lazy) {
             (void)hipFuncSetAttribute((const void *)k_q_verify2<Q, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table);
             hipLaunchKernelGGL((k_q_verify2<Q, true>), dim3(256, QS_LISTS), dim3(256), table, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase,
-                               rmask);
+                               rmask, pl.pass);
         } else {
             (void)hipFuncSetAttribute((const void *)k_q_verify2<Q, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table);
             hipLaunchKernelGGL((k_q_verify2<Q, false>), dim3(256, QS_LISTS), dim3(256), table, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase,
-                               rmask);
+                               rmask, pl.pass);
         }
         return;
     }
     if (a.stat_kernel) a.stat_kernel[2] = 3;
-    hipLaunchKernelGGL((k_q_verify<Q>), dim3(256, QS_LISTS), dim3(256), 0, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase, rmask);
+    hipLaunchKernelGGL((k_q_verify<Q>), dim3(256, QS_LISTS), dim3(256), 0, a.stream, a.P, a.tab, a.bases, a.filter, pl.surv, pl.surv_cur, pl.surv_cap, gbase, rmask, pl.pass);
 }
 
 }  // namespace
@@ -1805,6 +1975,7 @@ bool tpc_qpart_plan(int L, int slice_bits, uint64_t n_tiles, double frac, TpcQPl
 // n_tiles: the tiles THIS rank hashes; the level-2 regions cover the slices this rank owns and are sized
 // for the entries of all ranks
 static bool qpart_plan_compute(int L, int slice_bits, uint64_t n_tiles, double frac, uint32_t rank, uint32_t world, TpcQPlan &pl, int levels, bool tight, bool packed);
+static void qpart_plan_marks(TpcQPlan &pl);
 
 bool tpc_qpart_plan_sharded(int L, int slice_bits, uint64_t n_tiles, double frac, uint32_t rank, uint32_t world, TpcQPlan &pl, int levels, bool tight, bool packed)
 {
@@ -1818,13 +1989,49 @@ bool tpc_qpart_plan_sharded(int L, int slice_bits, uint64_t n_tiles, double frac
     const Key k{L, slice_bits, levels, tpc_test_q6_pb2 + (tpc_test_tight_pinch << 8), n_tiles, frac, rank, world, tight, packed};
     if (have && k.L == last.L && k.slice_bits == last.slice_bits && k.levels == last.levels && k.q6 == last.q6 && k.n_tiles == last.n_tiles && k.frac == last.frac &&
         k.rank == last.rank && k.world == last.world && k.tight == last.tight && k.packed == last.packed) {
-        if (last_ok) pl = last_pl;
+        if (last_ok) { pl = last_pl; qpart_plan_marks(pl); }
         return last_ok;
     }
     last_ok = qpart_plan_compute(L, slice_bits, n_tiles, frac, rank, world, pl, levels, tight, packed);
     last = k; have = true;
-    if (last_ok) last_pl = pl;
+    if (last_ok) { last_pl = pl; qpart_plan_marks(pl); }
     return last_ok;
+}
+
+// Geometry of the mark lists (k_mark_split / k_mark_apply) of a plan: from n_tiles and surv_cap alone, so it is worked out after the
+// cached part of the plan (the test options below are process-wide and may change between two passes).
+static void qpart_plan_marks(TpcQPlan &pl)
+{
+    const uint64_t n_text = std::max<uint64_t>(1, pl.n_tiles) * PT_THREADS * TPC_RUN;  // <= 2^30
+    // buckets of 2^MB positions, at most 512 of them (the bins of one Bins3) and at least a tile each
+    int MB = 14;
+    while (((n_text + (1ull << MB) - 1) >> MB) > 512) ++MB;
+    const int tb = tpc_test_mark_bucket_bits;  // tests: another bucket size, where it keeps the buckets within the 512 bins
+    if (tb >= 14 && tb <= 21 && ((n_text + (1ull << tb) - 1) >> tb) <= 512) MB = tb;
+    pl.MB = MB;
+    pl.mark_nb = (uint32_t)((n_text + (1ull << MB) - 1) >> MB);
+    pl.mark_lnb = 4;
+    while ((1u << pl.mark_lnb) < pl.mark_nb) ++pl.mark_lnb;
+    // a bucket's slice of the mask lives in LDS: at most 2^20 bits at a time
+    int sub = std::min(MB, 20);
+    if (tpc_test_mark_slice_bits >= 10 && tpc_test_mark_slice_bits < sub) sub = tpc_test_mark_slice_bits;
+    pl.mark_sub_bits = sub;
+    pl.mark_wg = QS_LISTS * (n_text >= (1ull << 24) ? 4u : 1u);  // long-lived workgroups: a quarter of a verdict list each on a large batch
+    // regions: as the one-GPU partition sizes its own -- mean x 1.3 + 8 sigma -- for as many marks as the survivor lists can hold
+    const double mean = (double)QS_LISTS * (double)pl.surv_cap / ((double)pl.mark_wg * (double)pl.mark_nb);
+    pl.mark_cap = (uint32_t)(((uint64_t)(mean * 1.3 + 8 * std::sqrt(mean) + 32) + 31) & ~31ull);
+    if (tpc_test_mark_region_cap > 0) pl.mark_cap = (uint32_t)((std::min(tpc_test_mark_region_cap, 1 << 20) + 31) & ~31);  // tests: most entries find their region full
+}
+
+static size_t mark_pass_bytes(const TpcQPlan &pl) { return (((size_t)QS_LISTS * pl.surv_cap * 4) + 127) & ~(size_t)127; }
+static size_t mark_buf_bytes(const TpcQPlan &pl) { return (size_t)pl.mark_wg * pl.mark_nb * pl.mark_cap * 4; }  // (whole 128-byte lines: mark_cap is a multiple of 32)
+
+void tpc_qpart_mark_pointers(TpcQPlan &pl, void *base)
+{
+    unsigned char *p = static_cast<unsigned char *>(base);
+    pl.pass = reinterpret_cast<uint32_t *>(p);
+    pl.mark_buf = reinterpret_cast<uint32_t *>(p + mark_pass_bytes(pl));
+    pl.mark_cnt = reinterpret_cast<uint32_t *>(p + mark_pass_bytes(pl) + mark_buf_bytes(pl));
 }
 
 static bool qpart_plan_compute(int L, int slice_bits, uint64_t n_tiles, double frac, uint32_t rank, uint32_t world, TpcQPlan &pl, int levels, bool tight, bool packed)
@@ -2001,6 +2208,7 @@ size_t tpc_qpart_bytes(const TpcQPlan &pl, int which)
     case 9: return (size_t)pl.buf3_entries * 8;
     case 10: return pl.b3 ? (((size_t)pl.wpb3 << (pl.b1 + pl.b2 + pl.b3)) / pl.world) * 4 : 0;
     case 11: return pl.off3_host.size() * 8;
+    case 19: return mark_pass_bytes(pl) + mark_buf_bytes(pl) + ((size_t)pl.mark_wg << pl.mark_lnb) * 4;
     }
     return 0;
 }
@@ -2128,8 +2336,12 @@ int tpc_launch_query_verify_other(const TpcLaunch &a, const TpcQPlan &pl, uint32
 #if TPC_QPARTITION_PART == 0
 int tpc_launch_query_verify(const TpcLaunch &a, const TpcQPlan &pl, uint32_t *rmask)
 {
-    if (a.P.q == 5) { launch_qverify<5>(a, pl, rmask); return 0; }
-    return tpc_launch_query_verify_other(a, pl, rmask);
+    if (a.P.q == 5) launch_qverify<5>(a, pl, rmask);
+    else if (int rc = tpc_launch_query_verify_other(a, pl, rmask)) return rc;
+    // a plan with mark lists: the verdicts just written become marks here, back to back on the same stream -- whatever reads the mask
+    // after the verification (k_periodic_copy, the mask counts, the direct kernel after an overflow) is launched after this call
+    if (pl.pass) launch_marks(a, pl, rmask);
+    return 0;
 }
 
 // Launches A-D on the stream (one rank, whole filter).  The caller zeroes ovf_cur / surv_cur first and
