@@ -500,6 +500,28 @@ def test_twopaco_writes_the_oracle_bytes_beside_everything_else(tmp_path, made, 
     assert open(os.path.join(d, "distances.tsv"), "rb").read() == want and sorted(os.listdir(d)) == ["distances.tsv", "j.bin"]
 
 
+def test_twopaco_writes_every_table_when_no_record_reaches_k(tmp_path):
+    """Two records of 5 and 7 bases at k = 9: nothing is dispatched to the device, and the graph and the four tables are still what
+    serial graphdump writes from that run's junction file."""
+    d = str(tmp_path)
+    fasta, stream = os.path.join(d, "tiny.fa"), os.path.join(d, "j.bin")
+    with open(fasta, "w") as f:
+        f.write(">a\nACGTA\n>b\nGATTACA\n")
+    case = {"k": 9, "L": 16, "q": 5, "n_rounds": 1, "seed": 7, "abundance": None}
+    names = {"--graph": "graph.gfa", "--colors": "colors.tsv", "--links": "links.tsv", "--bubbles": "bubbles.tsv", "--distances": "distances.tsv"}
+    out = {flag: os.path.join(d, f) for flag, f in names.items()}
+    r = cli(case, ["--tmpdir", d, "-o", stream, "--graph", "gfa1", "--graph-out", out["--graph"], "--colors", "file", "--colors-out", out["--colors"], "--links",
+                   "--links-out", out["--links"], "--bubbles", "file", "--bubbles-out", out["--bubbles"], "--distances", "file", "--distances-out", out["--distances"]],
+            fasta, cwd=d)
+    assert r.returncode == 0 and r.stderr == b"", r.stderr[-400:]
+    assert sorted(os.listdir(d)) == sorted(list(names.values()) + ["tiny.fa", "j.bin"])
+    serial = {"--graph": ["-f", "gfa1"], "--colors": ["--colors", "file"], "--links": ["--links"], "--bubbles": ["--bubbles", "file"], "--distances": ["--distances", "file"]}
+    for flag, args in serial.items():
+        want = R.run_graphdump([stream, "-k", "9", "-s", fasta] + args, cwd=d)
+        assert want.returncode == 0 and want.stderr == b"" and want.stdout, flag
+        assert open(out[flag], "rb").read() == want.stdout, flag
+
+
 def test_twopaco_default_file_timing_lines_and_refusals(tmp_path, made):
     case, fasta, _, _, gfa1, _, _, _ = inputs("short", made)
     d = str(tmp_path)

@@ -20,10 +20,7 @@
 // the call 4 B / event of ranks, the first-sight table (counts[3] of tpc_segments_counts), 4 B / side of flags and the scan's
 // scratch.  None of it exists in a context that never asks for bubbles, and the segment, colour and link outputs are what they were.
 // What does not fit the free device memory is refused with an error text.
-#include "tpc_ctx.h"
 #include "tpc_segrows.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -119,149 +116,112 @@ __global__ void k_bub_hist(const uint32_t *__restrict__ deg, uint64_t n_sides, u
 
 }  // namespace
 
-namespace tpch {
-
-void bubbles_drop(tpc_ctx *c)
-{
-    for (void *p : { (void *)c->bub_rows, (void *)c->bub_sides, (void *)c->bub_hist }) if (p) (void)hipFree(p);
-    c->bub_rows = nullptr; c->bub_sides = nullptr; c->bub_hist = nullptr;
-    c->bub_n_rows = c->bub_n_sides = c->bub_arcs = c->bub_peak_bytes = 0;
-    c->bub_valid = false;
-}
-
-}  // namespace tpch
-
 extern "C" {
 
 int tpc_segments_bubbles_build(tpc_ctx *c)
 {
     if (!c) return -1;
     bubbles_drop(c);
-    if (!c->seg_valid) return fail(c, -1, "segment bubbles: build the segment table first (tpc_segments_build_host / _resident)");
-    if (c->seg_err_kind != TPC_SEG_OK)
-        return fail(c, -1, "segment bubbles: the segment table holds the walk's error %d at slot %llu, there are no segments to join", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
-    if (!c->lnk_valid) return fail(c, -1, "segment bubbles: build the link table first (tpc_segments_links_build)");
-    const uint64_t n_events = c->seg_events, n_rows = c->seg_segments, n_table = c->seg_table_bytes / sizeof(uint32_t), n_links = c->lnk_n_rows;
+    if (int rc = stage_needs_segments(c, "bubbles", "join")) return rc;
+    if (!c->lnk.valid) return fail(c, -1, "segment bubbles: build the link table first (tpc_segments_links_build)");
+    const uint64_t n_events = c->seg.events, n_rows = c->seg.segments, n_links = c->lnk.n_rows;
     if (n_rows > BUB_MAX_ROWS) return fail(c, -1, "segment bubbles: %llu segments, a side holds at most %llu", (unsigned long long)n_rows, (unsigned long long)BUB_MAX_ROWS);
     HIPCHK(c, hipSetDevice(c->device));
     const uint64_t n_sides = 2 * n_rows;
 
     // sizes in 64 bits, summed before the first allocation; the rows are not counted yet: their bound is one per two sides
-    const uint64_t sides_bytes = n_sides * 12 + 16, hist_bytes = BUB_BINS * 8, rank_bytes = (n_events + 1) * 4, table_bytes = n_table * 4 + 16, flag_bytes = (n_sides + 1) * 4;
+    const uint64_t sides_bytes = n_sides * 12 + 16, hist_bytes = BUB_BINS * 8, flag_bytes = (n_sides + 1) * 4;
     const uint64_t rows_bound = n_rows * 16 + 16;
-    size_t scan_rank = 0, scan_flag = 0;
-    uint32_t *rank = nullptr, *table = nullptr, *flag = nullptr, *flags = nullptr;
-    void *scan_tmp = nullptr;
-    if (rocprim::exclusive_scan(nullptr, scan_rank, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), c->stream) != hipSuccess ||
-        rocprim::exclusive_scan(nullptr, scan_flag, flag, flag, 0u, n_sides + 1, rocprim::plus<uint32_t>(), c->stream) != hipSuccess)
+    size_t scan_flag = 0;
+    uint32_t *flag = nullptr, *flags = nullptr;
+    SegRows idx;
+    if (!idx.size(c) || rocprim::exclusive_scan(nullptr, scan_flag, flag, flag, 0u, n_sides + 1, rocprim::plus<uint32_t>(), c->stream) != hipSuccess)
         return fail(c, -10, "segment bubbles: the scan could not be sized");
-    const uint64_t scan_bytes = std::max<uint64_t>(scan_rank, scan_flag);
-    const uint64_t need = sides_bytes + hist_bytes + rank_bytes + table_bytes + flag_bytes + rows_bound + scan_bytes + 16 + 64;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // after a whole run in this context the first pass's partition buffers are still held: they are given back before this is refused
-    if (need + ((uint64_t)64 << 20) > free_b && release_partition_buffers(c)) HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (need + ((uint64_t)64 << 20) > free_b)
-        return fail(c, -20, "segment bubbles: %llu bytes (%llu of them the degree, smallest and largest neighbour of %llu sides) do not fit the free device memory",
-                    (unsigned long long)need, (unsigned long long)sides_bytes, (unsigned long long)n_sides);
+    idx.scan_alloc = std::max(idx.scan_alloc, scan_flag);   // one scratch for both scans
+    const uint64_t need = sides_bytes + hist_bytes + flag_bytes + rows_bound + idx.bytes() + 16 + 64;
+    if (int rc = stage_fits(c, "bubbles", need, "%llu of them the degree, smallest and largest neighbour of %llu sides", (unsigned long long)sides_bytes, (unsigned long long)n_sides))
+        return rc;
+    StageTemps temps;
     auto done = [&](int code) {
-        for (void *p : { (void *)rank, (void *)table, (void *)flag, (void *)flags, scan_tmp }) if (p) (void)hipFree(p);
         if (code) bubbles_drop(c);
         return code;
     };
-    if (dev_malloc(c, (void **)&c->bub_sides, sides_bytes) != hipSuccess || dev_malloc(c, (void **)&c->bub_hist, hist_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&rank, rank_bytes) != hipSuccess || dev_malloc(c, (void **)&table, table_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&flag, flag_bytes) != hipSuccess || dev_malloc(c, (void **)&flags, 64) != hipSuccess ||
-        dev_malloc(c, &scan_tmp, scan_bytes + 16) != hipSuccess)
+    if (dev_malloc(c, (void **)&c->bub.sides, sides_bytes) != hipSuccess || dev_malloc(c, (void **)&c->bub.hist, hist_bytes) != hipSuccess || !idx.alloc(c, temps) ||
+        !temps.get(c, &flag, flag_bytes) || !temps.get(c, &flags, 64))
         return done(fail(c, -10, "segment bubbles: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
-    uint32_t *deg = c->bub_sides, *lo = deg + n_sides, *hi = lo + n_sides;
+    uint32_t *deg = c->bub.sides, *lo = deg + n_sides, *hi = lo + n_sides;
     unsigned long long *counters = (unsigned long long *)(flags + 2);   // 8 bytes into the 64: flags[0], then counters[0]
     hipStream_t s = c->stream;
     // degrees and largest neighbours zero, smallest neighbours all ones
-    bool ok = hipMemsetAsync(c->bub_sides, 0, sides_bytes, s) == hipSuccess && (!n_sides || hipMemsetAsync(lo, 0xFF, n_sides * 4, s) == hipSuccess) &&
-              hipMemsetAsync(c->bub_hist, 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(table, 0xFF, table_bytes, s) == hipSuccess &&
+    bool ok = hipMemsetAsync(c->bub.sides, 0, sides_bytes, s) == hipSuccess && (!n_sides || hipMemsetAsync(lo, 0xFF, n_sides * 4, s) == hipSuccess) &&
+              hipMemsetAsync(c->bub.hist, 0, hist_bytes, s) == hipSuccess && idx.fill(s) &&
               hipMemsetAsync(flags, 0, 64, s) == hipSuccess;
-    uint32_t scanned_rows = 0, n_bubbles = 0, raised = 0;
+    uint32_t n_bubbles = 0, raised = 0;
     unsigned long long own_reverse = 0;
     if (ok) {
         Timed t(c, TPC_K_BUBBLES);   // the whole stage on the stream, the wait for the bubble count included (as TPC_K_LINKS)
-        hipLaunchKernelGGL(k_col_flags, dim3(col_grid(n_events + 1)), dim3(256), 0, s, c->seg_first, n_events, rank);
-        ok = rocprim::exclusive_scan(scan_tmp, scan_rank, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
-        if (ok && n_events) hipLaunchKernelGGL(k_col_min, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg_name, n_events, table, n_table);
+        ok = idx.enqueue(c);
         if (ok && n_links)
-            hipLaunchKernelGGL(k_bub_arcs, dim3(col_grid(n_links)), dim3(256), 0, s, c->lnk_rows, n_links, c->seg_name, n_events, table, n_table, rank, n_rows, deg, lo, hi,
+            hipLaunchKernelGGL(k_bub_arcs, dim3(col_grid(n_links)), dim3(256), 0, s, c->lnk.rows, n_links, c->seg.name, n_events, idx.table, idx.n_table, idx.rank, n_rows, deg, lo, hi,
                                counters, flags);
         if (ok) {
             hipLaunchKernelGGL(k_bub_find, dim3(col_grid(n_sides + 1)), dim3(256), 0, s, deg, lo, hi, n_sides, flag);
-            ok = rocprim::exclusive_scan(scan_tmp, scan_flag, flag, flag, 0u, n_sides + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
+            ok = rocprim::exclusive_scan(idx.scan_tmp, scan_flag, flag, flag, 0u, n_sides + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
         }
-        if (ok && n_sides) hipLaunchKernelGGL(k_bub_hist, dim3(std::min(col_grid(n_sides), 1024u)), dim3(256), 0, s, deg, n_sides, c->bub_hist);
+        if (ok && n_sides) hipLaunchKernelGGL(k_bub_hist, dim3(std::min(col_grid(n_sides), 1024u)), dim3(256), 0, s, deg, n_sides, c->bub.hist);
         // the number of bubbles decides the size of what is kept: the one wait in the middle
-        ok = ok && hipMemcpyAsync(&scanned_rows, rank + n_events, sizeof scanned_rows, hipMemcpyDeviceToHost, s) == hipSuccess &&
-             hipMemcpyAsync(&n_bubbles, flag + n_sides, sizeof n_bubbles, hipMemcpyDeviceToHost, s) == hipSuccess &&
+        ok = ok && idx.total(s) && hipMemcpyAsync(&n_bubbles, flag + n_sides, sizeof n_bubbles, hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipMemcpyAsync(&raised, flags, sizeof raised, hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipMemcpyAsync(&own_reverse, counters, sizeof own_reverse, hipMemcpyDeviceToHost, s) == hipSuccess;
-        hipError_t e = hipStreamSynchronize(s);
-        if (!ok || e != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(c, -10, "segment bubbles: the kernels failed: %s", hipGetErrorString(e)));
-        if (scanned_rows != n_rows) return done(fail(c, -10, "segment bubbles: the first bits hold %u segments, the build counted %llu", scanned_rows, (unsigned long long)n_rows));
+        if (int rc = stage_wait(c, "bubbles", ok)) return done(rc);
+        if (idx.scanned != n_rows) return done(fail(c, -10, "segment bubbles: the first bits hold %u segments, the build counted %llu", idx.scanned, (unsigned long long)n_rows));
         if (raised & BUB_FLAG_EVENT) return done(fail(c, -10, "segment bubbles: a link row's first event lies outside the event table"));
         if (raised & BUB_FLAG_ROW) return done(fail(c, -10, "segment bubbles: an event's segment is missing from the first-sight table"));
         if (2 * (uint64_t)n_bubbles > n_sides || own_reverse > n_links)
             return done(fail(c, -10, "segment bubbles: %u bubbles on %llu sides", n_bubbles, (unsigned long long)n_sides));
         const uint64_t rows_bytes = (uint64_t)n_bubbles * 16 + 16;
-        if (dev_malloc(c, (void **)&c->bub_rows, rows_bytes) != hipSuccess) return done(fail(c, -10, "segment bubbles: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
-        if (n_bubbles) hipLaunchKernelGGL(k_bub_rows, dim3(col_grid(n_sides)), dim3(256), 0, s, deg, lo, hi, n_sides, flag, c->bub_rows, (uint64_t)n_bubbles, flags);
+        if (dev_malloc(c, (void **)&c->bub.rows, rows_bytes) != hipSuccess) return done(fail(c, -10, "segment bubbles: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
+        if (n_bubbles) hipLaunchKernelGGL(k_bub_rows, dim3(col_grid(n_sides)), dim3(256), 0, s, deg, lo, hi, n_sides, flag, c->bub.rows, (uint64_t)n_bubbles, flags);
         ok = hipMemcpyAsync(&raised, flags, sizeof raised, hipMemcpyDeviceToHost, s) == hipSuccess;
-        c->bub_peak_bytes = need - rows_bound + rows_bytes;
+        c->bub.peak_bytes = need - rows_bound + rows_bytes;
     }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (!ok || e != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(c, -10, "segment bubbles: the kernels failed: %s", hipGetErrorString(e)));
+    if (int rc = stage_wait(c, "bubbles", ok)) return done(rc);
     if (raised) return done(fail(c, -10, "segment bubbles: a flagged side holds no bubble"));
-    c->bub_n_rows = n_bubbles; c->bub_n_sides = n_sides; c->bub_arcs = 2 * n_links - own_reverse;
-    c->bub_valid = true;
-    return done(0);
+    c->bub.n_rows = n_bubbles; c->bub.n_sides = n_sides; c->bub.arcs = 2 * n_links - own_reverse;
+    c->bub.valid = true;
+    return 0;
 }
 
 int tpc_segments_bubbles_info(tpc_ctx *c, uint64_t *info)
 {
     if (!c) return -1;
-    if (!c->bub_valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
+    if (!c->bub.valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
     if (!info) return fail(c, -1, "segment bubbles: info required");
-    info[0] = c->bub_n_rows; info[1] = c->bub_n_sides; info[2] = c->bub_arcs; info[3] = c->bub_peak_bytes;
+    info[0] = c->bub.n_rows; info[1] = c->bub.n_sides; info[2] = c->bub.arcs; info[3] = c->bub.peak_bytes;
     return 0;
 }
 
 int tpc_segments_bubbles_fetch_rows(tpc_ctx *c, uint64_t b0, uint64_t n, uint32_t *source_host, uint32_t *arm_a_host, uint32_t *arm_b_host, uint32_t *sink_host)
 {
     if (!c) return -1;
-    if (!c->bub_valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
-    if ((n && (!source_host || !arm_a_host || !arm_b_host || !sink_host)) || b0 > c->bub_n_rows || n > c->bub_n_rows - b0)
-        return fail(c, -1, "segment bubbles: bad row range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)b0, (unsigned long long)c->bub_n_rows);
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *dst[4] = { source_host, arm_a_host, arm_b_host, sink_host };
-    for (int i = 0; n && i < 4; i++) HIPCHK(c, hipMemcpy(dst[i], c->bub_rows + (uint64_t)i * c->bub_n_rows + b0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    if (!c->bub.valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
+    return fetch_planes(c, "bubbles", "row", c->bub.rows, c->bub.n_rows, b0, n, { source_host, arm_a_host, arm_b_host, sink_host });
 }
 
 int tpc_segments_bubbles_fetch_sides(tpc_ctx *c, uint64_t c0, uint64_t n, uint32_t *deg_host, uint32_t *lo_host, uint32_t *hi_host)
 {
     if (!c) return -1;
-    if (!c->bub_valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
-    if ((n && (!deg_host || !lo_host || !hi_host)) || c0 > c->bub_n_sides || n > c->bub_n_sides - c0)
-        return fail(c, -1, "segment bubbles: bad side range (%llu sides at %llu of %llu)", (unsigned long long)n, (unsigned long long)c0, (unsigned long long)c->bub_n_sides);
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *dst[3] = { deg_host, lo_host, hi_host };
-    for (int i = 0; n && i < 3; i++) HIPCHK(c, hipMemcpy(dst[i], c->bub_sides + (uint64_t)i * c->bub_n_sides + c0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    if (!c->bub.valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
+    return fetch_planes(c, "bubbles", "side", c->bub.sides, c->bub.n_sides, c0, n, { deg_host, lo_host, hi_host });
 }
 
 int tpc_segments_bubbles_fetch_hist(tpc_ctx *c, uint64_t *hist_host)
 {
     if (!c) return -1;
-    if (!c->bub_valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
+    if (!c->bub.valid) return fail(c, -1, "segment bubbles: tpc_segments_bubbles_build first");
     if (!hist_host) return fail(c, -1, "segment bubbles: the histogram array is required");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(hist_host, c->bub_hist, BUB_BINS * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hist_host, c->bub.hist, BUB_BINS * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -333,14 +333,12 @@ void tpc_ctx_destroy(tpc_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     void *ptrs[] = { c->tab, c->bases_alloc, c->nmask_alloc, c->filter, c->rmask, c->mask, c->marks, c->block_sums, c->table,
-                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg_name, c->seg_first, c->seg_ev[0], c->seg_ev[1], c->seg_ev[2],
-                     c->seg_rec, c->seg_amb, c->text_plan.off, c->text_plan.piece, c->text_names, c->text_win };
+                     c->keys, c->idtab, c->emit_id, c->stream_buf, c->counters, c->route_scratch, c->sh_off, c->scan_blocks, c->sort_scratch, c->seg.name, c->seg.first, c->seg.ev[0], c->seg.ev[1], c->seg.ev[2],
+                     c->seg.rec, c->seg.amb, c->text_plan.off, c->text_plan.piece, c->text_names, c->text_win };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     stream_part_release(c);
     colors_drop(c);
     links_drop(c);
-    bubbles_drop(c);
-    distances_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);

@@ -23,19 +23,38 @@ void text_plan_drop(tpc_ctx *c)
     c->text_ms = 0;
 }
 
-int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k, const uint64_t *rec_start, const uint64_t *rec_len, uint32_t n_rec,
-                   const uint64_t *amb_pos, uint64_t n_amb)
+// WHO DROPS WHOM, written once: dropping a table drops what was built over it.
+//   segments <- colours <- distances        (the matrices were summed over the colour table)
+//   segments <- links   <- bubbles          (the bubbles were found over the link table)
+//   segments <- the graph text's plan
+void free_all(std::initializer_list<const void *> ps) { for (const void *p : ps) if (p) (void)hipFree(const_cast<void *>(p)); }
+
+}  // namespace
+
+namespace tpch {
+
+void distances_drop(tpc_ctx *c) { free_all({c->dst.mat}); c->dst = {}; }
+void bubbles_drop(tpc_ctx *c) { free_all({c->bub.rows, c->bub.sides, c->bub.hist}); c->bub = {}; }
+void colors_drop(tpc_ctx *c) { distances_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
+void links_drop(tpc_ctx *c) { bubbles_drop(c); free_all({c->lnk.rows, c->lnk.first}); c->lnk = {}; }
+
+}  // namespace tpch
+
+namespace {
+
+void segments_drop(tpc_ctx *c)
 {
-    c->seg_valid = false;
     text_plan_drop(c);
     colors_drop(c);
     links_drop(c);
-    bubbles_drop(c);
-    distances_drop(c);
-    for (void *p : { (void *)c->seg_name, (void *)c->seg_first, (void *)c->seg_ev[0], (void *)c->seg_ev[1], (void *)c->seg_ev[2], (void *)c->seg_rec, (void *)c->seg_amb }) if (p) (void)hipFree(p);
-    c->seg_name = nullptr; c->seg_first = nullptr;
-    c->seg_rec = c->seg_amb = nullptr;
-    c->seg_ev[0] = c->seg_ev[1] = c->seg_ev[2] = nullptr;
+    free_all({c->seg.name, c->seg.first, c->seg.ev[0], c->seg.ev[1], c->seg.ev[2], c->seg.rec, c->seg.amb});
+    c->seg = {};
+}
+
+int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k, const uint64_t *rec_start, const uint64_t *rec_len, uint32_t n_rec,
+                   const uint64_t *amb_pos, uint64_t n_amb)
+{
+    segments_drop(c);
     if (k < 0) return fail(c, -1, "segment table: k must not be negative");
     if (!c->bases || !c->nmask || c->text_windowed) return fail(c, -1, "segment table: tpc_seq_upload the whole text first");
     if (n_rec && (!rec_start || !rec_len)) return fail(c, -1, "segment table: records required");
@@ -55,19 +74,19 @@ int segments_build(tpc_ctx *c, const uint32_t *d_slots, uint64_t n_slots, int k,
     char text[TPC_SEG_ERR_TEXT] = "";
     if (rc == 0) {
         Timed t(c, TPC_K_SEGMENTS);
-        rc = tpc_launch_segments(c->stream, d_slots, n_slots, k, c->bases, c->nmask, d_rec, d_rec + n_rec, n_rec, d_amb, n_amb, &c->seg_name, &c->seg_first, c->seg_ev, &res, text);
+        rc = tpc_launch_segments(c->stream, d_slots, n_slots, k, c->bases, c->nmask, d_rec, d_rec + n_rec, n_rec, d_amb, n_amb, &c->seg.name, &c->seg.first, c->seg.ev, &res, text);
     }
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (rc || e != hipSuccess) { for (void *p : { (void *)d_rec, (void *)d_amb }) if (p) (void)hipFree(p); }
-    else { c->seg_rec = d_rec; c->seg_amb = d_amb; }  // the graph text reads them (tpc_segments_text_plan)
+    else { c->seg.rec = d_rec; c->seg.amb = d_amb; }  // the graph text reads them (tpc_segments_text_plan)
     if (rc) return text[0] ? fail(c, rc, "%s", text) : fail(c, rc, "segment table failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
     HIPCHK(c, e);
-    c->seg_events = res.events; c->seg_segments = res.segments; c->seg_named = res.named; c->seg_table_bytes = res.table_bytes;
-    c->seg_slots = n_slots; c->seg_peak_bytes = res.peak_bytes; c->seg_n_rec = n_rec;
-    c->seg_err_slot = res.err_slot; c->seg_err_kind = res.err_kind;
-    c->seg_n_amb = n_amb; c->seg_k = k;
-    c->seg_text_bases = c->bases; c->seg_text_n = c->n_text; c->seg_text_uploads = c->text_uploads;
-    c->seg_valid = true;
+    c->seg.events = res.events; c->seg.segments = res.segments; c->seg.named = res.named; c->seg.table_bytes = res.table_bytes;
+    c->seg.slots = n_slots; c->seg.peak_bytes = res.peak_bytes; c->seg.n_rec = n_rec;
+    c->seg.err_slot = res.err_slot; c->seg.err_kind = res.err_kind;
+    c->seg.n_amb = n_amb; c->seg.k = k;
+    c->seg.text_bases = c->bases; c->seg.text_n = c->n_text; c->seg.text_uploads = c->text_uploads;
+    c->seg.valid = true;
     return 0;
 }
 
@@ -81,7 +100,7 @@ struct TextTimer {
 
 size_t text_tiles(uint64_t n) { return (size_t)((n + TPC_TEXT_TILE - 1) / TPC_TEXT_TILE * TPC_TEXT_TILE); }
 
-bool text_ready(tpc_ctx *c) { return c && c->seg_valid && c->text_valid && c->bases == c->seg_text_bases && c->n_text == c->seg_text_n && c->text_uploads == c->seg_text_uploads && !c->text_windowed; }
+bool text_ready(tpc_ctx *c) { return c && c->seg.valid && c->text_valid && c->bases == c->seg.text_bases && c->n_text == c->seg.text_n && c->text_uploads == c->seg.text_uploads && !c->text_windowed; }
 
 }  // namespace
 
@@ -123,54 +142,54 @@ int tpc_segments_build_resident(tpc_ctx *c, int k, const uint64_t *rec_start, co
 
 int tpc_segments_counts(const tpc_ctx *c, uint64_t *counts)
 {
-    if (!c || !counts || !c->seg_valid) return -1;
-    counts[0] = c->seg_events; counts[1] = c->seg_segments; counts[2] = c->seg_named; counts[3] = c->seg_table_bytes; counts[4] = c->seg_slots;
-    counts[5] = c->seg_peak_bytes;
+    if (!c || !counts || !c->seg.valid) return -1;
+    counts[0] = c->seg.events; counts[1] = c->seg.segments; counts[2] = c->seg.named; counts[3] = c->seg.table_bytes; counts[4] = c->seg.slots;
+    counts[5] = c->seg.peak_bytes;
     return 0;
 }
 
 int tpc_segments_error(const tpc_ctx *c, uint64_t *slot, int *kind)
 {
-    if (!c || !c->seg_valid) return -1;
-    if (slot) *slot = c->seg_err_slot;
-    if (kind) *kind = c->seg_err_kind;
+    if (!c || !c->seg.valid) return -1;
+    if (slot) *slot = c->seg.err_slot;
+    if (kind) *kind = c->seg.err_kind;
     return 0;
 }
 
 int tpc_segments_fetch_names(tpc_ctx *c, uint64_t e0, uint64_t n, int64_t *name_host)
 {
-    if (!c || !c->seg_valid || (n && !name_host) || e0 > c->seg_events || n > c->seg_events - e0) return fail(c, -1, "segment table: bad name range");
+    if (!c || !c->seg.valid || (n && !name_host) || e0 > c->seg.events || n > c->seg.events - e0) return fail(c, -1, "segment table: bad name range");
     HIPCHK(c, hipSetDevice(c->device));
-    if (n) HIPCHK(c, hipMemcpy(name_host, c->seg_name + e0, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(c, hipMemcpy(name_host, c->seg.name + e0, n * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int tpc_segments_fetch_first(tpc_ctx *c, uint64_t word0, uint64_t n_words, uint32_t *first_host)
 {
-    const uint64_t words = c ? (c->seg_events + 31) / 32 : 0;
-    if (!c || !c->seg_valid || (n_words && !first_host) || word0 > words || n_words > words - word0) return fail(c, -1, "segment table: bad first-bit range");
+    const uint64_t words = c ? (c->seg.events + 31) / 32 : 0;
+    if (!c || !c->seg.valid || (n_words && !first_host) || word0 > words || n_words > words - word0) return fail(c, -1, "segment table: bad first-bit range");
     HIPCHK(c, hipSetDevice(c->device));
-    if (n_words) HIPCHK(c, hipMemcpy(first_host, c->seg_first + word0, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_words) HIPCHK(c, hipMemcpy(first_host, c->seg.first + word0, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int tpc_segments_fetch_events(tpc_ctx *c, uint64_t e0, uint64_t n, uint32_t *begin_host, uint32_t *end_host)
 {
-    if (!c || !c->seg_valid || (n && (!begin_host || !end_host)) || e0 > c->seg_events || n > c->seg_events - e0) return fail(c, -1, "segment table: bad event range");
+    if (!c || !c->seg.valid || (n && (!begin_host || !end_host)) || e0 > c->seg.events || n > c->seg.events - e0) return fail(c, -1, "segment table: bad event range");
     HIPCHK(c, hipSetDevice(c->device));
     if (n) {
-        HIPCHK(c, hipMemcpy(begin_host, c->seg_ev[0] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(end_host, c->seg_ev[1] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(begin_host, c->seg.ev[0] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(end_host, c->seg.ev[1] + e0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     return 0;
 }
 
 int tpc_segments_fetch_sequences(tpc_ctx *c, uint64_t s0, uint64_t n, uint32_t *first_event_host)
 {
-    const uint64_t entries = c ? (uint64_t)c->seg_n_rec + 1 : 0;
-    if (!c || !c->seg_valid || (n && !first_event_host) || s0 > entries || n > entries - s0) return fail(c, -1, "segment table: bad sequence range");
+    const uint64_t entries = c ? (uint64_t)c->seg.n_rec + 1 : 0;
+    if (!c || !c->seg.valid || (n && !first_event_host) || s0 > entries || n > entries - s0) return fail(c, -1, "segment table: bad sequence range");
     HIPCHK(c, hipSetDevice(c->device));
-    if (n) HIPCHK(c, hipMemcpy(first_event_host, c->seg_ev[2] + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(c, hipMemcpy(first_event_host, c->seg.ev[2] + s0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -180,26 +199,26 @@ int tpc_segments_text_plan(tpc_ctx *c, int format, const char *seq_names, const 
     if (!total_bytes) return fail(c, -1, "graph text: total_bytes required");
     *total_bytes = 0;
     text_plan_drop(c);
-    if (!c->seg_valid) return fail(c, -1, "graph text: build the segment table first (tpc_segments_build_host / _resident)");
-    if (c->seg_err_kind != TPC_SEG_OK)
-        return fail(c, -1, "graph text: the segment table holds the walk's error %d at slot %llu, there is no text to render", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
+    if (!c->seg.valid) return fail(c, -1, "graph text: build the segment table first (tpc_segments_build_host / _resident)");
+    if (c->seg.err_kind != TPC_SEG_OK)
+        return fail(c, -1, "graph text: the segment table holds the walk's error %d at slot %llu, there is no text to render", c->seg.err_kind, (unsigned long long)c->seg.err_slot);
     if (format != TPC_TEXT_GFA1 && format != TPC_TEXT_GFA2 && format != TPC_TEXT_FASTA) return fail(c, -1, "graph text: format %d is none of gfa1 (1), gfa2 (2), fasta (3)", format);
-    if (!c->bases || !c->nmask || c->text_windowed || c->bases != c->seg_text_bases || c->n_text != c->seg_text_n || c->text_uploads != c->seg_text_uploads)
+    if (!c->bases || !c->nmask || c->text_windowed || c->bases != c->seg.text_bases || c->n_text != c->seg.text_n || c->text_uploads != c->seg.text_uploads)
         return fail(c, -1, "graph text: the text of tpc_seq_upload the table was built over is no longer resident");
-    const uint32_t n_rec = c->seg_n_rec;
+    const uint32_t n_rec = c->seg.n_rec;
     if (!seq_name_off || (seq_name_off[n_rec] && !seq_names)) return fail(c, -1, "graph text: sequence names required");
     if (seq_name_off[0] != 0) return fail(c, -1, "graph text: the names' offsets must begin at 0");
     for (uint32_t r = 0; r < n_rec; r++)
         if (seq_name_off[r] > seq_name_off[r + 1]) return fail(c, -1, "graph text: the names' offsets must ascend");
-    if (c->seg_n_amb && !amb_letter) return fail(c, -1, "graph text: the letters of the %llu ambiguity positions are required", (unsigned long long)c->seg_n_amb);
+    if (c->seg.n_amb && !amb_letter) return fail(c, -1, "graph text: the letters of the %llu ambiguity positions are required", (unsigned long long)c->seg.n_amb);
     HIPCHK(c, hipSetDevice(c->device));
     // the table's own consistency: every event belongs to one of the n_rec sequences
     uint32_t last = 0;
-    HIPCHK(c, hipMemcpy(&last, c->seg_ev[2] + n_rec, sizeof last, hipMemcpyDeviceToHost));
-    if (last != c->seg_events) return fail(c, -1, "graph text: the stream holds events of more sequences than the %u given", n_rec);
+    HIPCHK(c, hipMemcpy(&last, c->seg.ev[2] + n_rec, sizeof last, hipMemcpyDeviceToHost));
+    if (last != c->seg.events) return fail(c, -1, "graph text: the stream holds events of more sequences than the %u given", n_rec);
     // names' blob | offsets | letters in one allocation
     const uint64_t blob = seq_name_off[n_rec];
-    const size_t off_at = (size_t)((blob + 7) / 8 * 8), let_at = off_at + ((size_t)n_rec + 1) * 8, bytes = let_at + (size_t)c->seg_n_amb + 8;
+    const size_t off_at = (size_t)((blob + 7) / 8 * 8), let_at = off_at + ((size_t)n_rec + 1) * 8, bytes = let_at + (size_t)c->seg.n_amb + 8;
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     if (bytes + ((size_t)64 << 20) > free_b) return fail(c, -20, "graph text: %zu bytes of sequence names and letters do not fit the free device memory", bytes);
@@ -207,14 +226,14 @@ int tpc_segments_text_plan(tpc_ctx *c, int format, const char *seq_names, const 
     uint8_t *base = (uint8_t *)c->text_names;
     if (blob) HIPCHK(c, hipMemcpyAsync(base, seq_names, blob, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(base + off_at, seq_name_off, ((size_t)n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (c->seg_n_amb) HIPCHK(c, hipMemcpyAsync(base + let_at, amb_letter, c->seg_n_amb, hipMemcpyHostToDevice, c->stream));
+    if (c->seg.n_amb) HIPCHK(c, hipMemcpyAsync(base + let_at, amb_letter, c->seg.n_amb, hipMemcpyHostToDevice, c->stream));
     TpcTextPlan &T = c->text_plan;
-    T.format = format; T.k = c->seg_k;
-    T.n_events = c->seg_events; T.n_rec = n_rec;
-    T.name = c->seg_name; T.first = c->seg_first; T.begin = c->seg_ev[0]; T.end = c->seg_ev[1]; T.seq_begin = c->seg_ev[2];
-    T.rec_start = c->seg_rec; T.rec_len = c->seg_rec + n_rec;
+    T.format = format; T.k = c->seg.k;
+    T.n_events = c->seg.events; T.n_rec = n_rec;
+    T.name = c->seg.name; T.first = c->seg.first; T.begin = c->seg.ev[0]; T.end = c->seg.ev[1]; T.seq_begin = c->seg.ev[2];
+    T.rec_start = c->seg.rec; T.rec_len = c->seg.rec + n_rec;
     T.bases = c->bases; T.nmask = c->nmask;
-    T.amb = c->seg_amb; T.amb_letter = base + let_at; T.n_amb = c->seg_n_amb;
+    T.amb = c->seg.amb; T.amb_letter = base + let_at; T.n_amb = c->seg.n_amb;
     T.seq_names = (const char *)base; T.seq_name_off = (const uint64_t *)(base + off_at);
     char text[TPC_SEG_ERR_TEXT] = "";
     TextTimer timer;
@@ -230,7 +249,7 @@ int tpc_segments_text_plan(tpc_ctx *c, int format, const char *seq_names, const 
     c->text_ms = 0;
     timer.add(c);
     size_t fb = 0, tb = 0;
-    if (hipMemGetInfo(&fb, &tb) == hipSuccess) c->seg_peak_bytes = std::max<uint64_t>(c->seg_peak_bytes, tb - fb);
+    if (hipMemGetInfo(&fb, &tb) == hipSuccess) c->seg.peak_bytes = std::max<uint64_t>(c->seg.peak_bytes, tb - fb);
     c->text_valid = true;
     *total_bytes = c->text_total;
     return 0;

@@ -22,10 +22,7 @@
 // per row of presence, 16 B x (C + 1) of histogram; during the call also the first-sight table (counts[3] of tpc_segments_counts),
 // 4 B / event of ranks, 4 B / sequence of colours.  None of it exists in a context that never asks for colours, and
 // tpc_segments_counts reports what it reported before.  What does not fit the free device memory is refused with an error text.
-#include "tpc_ctx.h"
 #include "tpc_segrows.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -48,9 +45,7 @@ __global__ void k_col_scatter(const int64_t *__restrict__ name, uint64_t n_event
             const uint64_t m = col_mag(nm);
             const uint32_t e0 = (nm >= COL_FRESH || m >= n_table) ? (uint32_t)e : table[m];
             row = e0 < n_events ? rank[e0] : 0xFFFFFFFFu;
-            // the last s with seq_begin[s] <= e (sequences without events share their entry with the next one that has some)
-            uint32_t lo = 0, hi = n_rec + 1;
-            while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (seq_begin[mid] <= (uint32_t)e) lo = mid + 1; else hi = mid; }
+            const uint32_t lo = col_seq_end(seq_begin, n_rec, (uint32_t)e);
             active = row < n_rows && lo >= 1 && lo <= n_rec;  // (the build's caller checked that every event has a sequence)
             if (active) {
                 col = color[lo - 1];
@@ -62,9 +57,7 @@ __global__ void k_col_scatter(const int64_t *__restrict__ name, uint64_t n_event
         const bool head = active && (lane == 0 || row_below != row || col_below != col);
         const unsigned long long heads = __ballot(head), actives = __ballot(active), forwards = __ballot(active && forward);
         if (head) {
-            const unsigned long long from = ~0ull << lane;
-            const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-            const unsigned long long run = from & actives & (above ? ((1ull << (__ffsll((long long)above) - 1)) - 1) : ~0ull);
+            const unsigned long long run = col_run(lane, heads, actives);
             // (inactive lanes sit between runs only behind the last event, or where a row was refused: they cut no run short that matters)
             atomicAdd(&rows[n_rows + row], (uint32_t)__popcll(run));
             const uint32_t nf = (uint32_t)__popcll(run & forwards);
@@ -104,143 +97,108 @@ __global__ void k_col_rows(uint32_t *__restrict__ rows, uint64_t n_rows, const u
 
 }  // namespace
 
-namespace tpch {
-
-void colors_drop(tpc_ctx *c)
-{
-    for (void *p : { (void *)c->col_rows, (void *)c->col_presence, (void *)c->col_hist }) if (p) (void)hipFree(p);
-    c->col_rows = nullptr; c->col_presence = nullptr; c->col_hist = nullptr;
-    c->col_n_rows = 0; c->col_n_colors = 0; c->col_words = 0;
-    c->col_valid = false;
-}
-
-}  // namespace tpch
-
 extern "C" {
 
 int tpc_segments_colors_build(tpc_ctx *c, const uint32_t *color_of_seq, uint32_t n_colors)
 {
     if (!c) return -1;
     colors_drop(c);
-    distances_drop(c);   // they were summed over the colour table that goes
-    if (!c->seg_valid) return fail(c, -1, "segment colours: build the segment table first (tpc_segments_build_host / _resident)");
-    if (c->seg_err_kind != TPC_SEG_OK)
-        return fail(c, -1, "segment colours: the segment table holds the walk's error %d at slot %llu, there are no segments to colour", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
+    if (int rc = stage_needs_segments(c, "colours", "colour")) return rc;
     if (n_colors == 0) return fail(c, -1, "segment colours: at least one colour is required");
     // C + 1 bins and ceil(C / 32) words are 32-bit quantities in the kernels: neither may wrap
     if (n_colors > COL_MAX_COLORS) return fail(c, -1, "segment colours: %u colours, at most %u are supported", n_colors, COL_MAX_COLORS);
-    const uint32_t n_rec = c->seg_n_rec;
+    const uint32_t n_rec = c->seg.n_rec;
     if (n_rec && !color_of_seq) return fail(c, -1, "segment colours: the colour of every one of the %u sequences is required", n_rec);
     for (uint32_t s = 0; s < n_rec; s++)
         if (color_of_seq[s] >= n_colors) return fail(c, -1, "segment colours: sequence %u has colour %u, there are %u colours", s, color_of_seq[s], n_colors);
     HIPCHK(c, hipSetDevice(c->device));
     // the table's own consistency: every event belongs to one of the n_rec sequences
     uint32_t last = 0;
-    HIPCHK(c, hipMemcpy(&last, c->seg_ev[2] + n_rec, sizeof last, hipMemcpyDeviceToHost));
-    if (last != c->seg_events) return fail(c, -1, "segment colours: the stream holds events of more sequences than the %u given", n_rec);
+    HIPCHK(c, hipMemcpy(&last, c->seg.ev[2] + n_rec, sizeof last, hipMemcpyDeviceToHost));
+    if (last != c->seg.events) return fail(c, -1, "segment colours: the stream holds events of more sequences than the %u given", n_rec);
 
-    const uint64_t n_events = c->seg_events, n_rows = c->seg_segments, n_table = c->seg_table_bytes / sizeof(uint32_t);
+    const uint64_t n_events = c->seg.events, n_rows = c->seg.segments;
     // sizes in 64 bits: S x W x 4 B of presence is the large term, and the refusal below must see it whole
     const uint32_t words = (uint32_t)(((uint64_t)n_colors + 31) / 32), bins = n_colors + 1;
     const uint64_t presence_words = n_rows * (uint64_t)words;  // below 2^32 x 2^26
     const size_t rows_bytes = (size_t)n_rows * 16 + 16, presence_bytes = (size_t)presence_words * 4 + 16, hist_bytes = (size_t)bins * 16;
-    const size_t rank_bytes = ((size_t)n_events + 1) * 4, table_bytes = (size_t)n_table * 4 + 16, color_bytes = (size_t)n_rec * 4 + 16;
-    size_t scan_bytes = 0;
-    uint32_t *rank = nullptr, *table = nullptr, *color = nullptr;
-    void *scan_tmp = nullptr;
-    if (rocprim::exclusive_scan(nullptr, scan_bytes, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), c->stream) != hipSuccess)
-        return fail(c, -10, "segment colours: the scan could not be sized");
-    const size_t need = rows_bytes + presence_bytes + hist_bytes + rank_bytes + table_bytes + color_bytes + scan_bytes;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // after a whole run in this context the first pass's partition buffers are still held: they are given back before this is refused
-    if (need + ((size_t)64 << 20) > free_b && release_partition_buffers(c)) HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (need + ((size_t)64 << 20) > free_b)
-        return fail(c, -20, "segment colours: %zu bytes (%zu of them the presence bits of %llu segments x %u colours) do not fit the free device memory", need, presence_bytes,
-                    (unsigned long long)n_rows, n_colors);
+    const size_t color_bytes = (size_t)n_rec * 4 + 16;
+    SegRows idx;
+    if (!idx.size(c)) return fail(c, -10, "segment colours: the scan could not be sized");
+    const size_t need = rows_bytes + presence_bytes + hist_bytes + color_bytes + idx.bytes();
+    if (int rc = stage_fits(c, "colours", need, "%zu of them the presence bits of %llu segments x %u colours", presence_bytes, (unsigned long long)n_rows, n_colors)) return rc;
+    StageTemps temps;
+    uint32_t *color = nullptr;
     auto done = [&](int code) {
-        for (void *p : { (void *)rank, (void *)table, (void *)color, scan_tmp }) if (p) (void)hipFree(p);
         if (code) colors_drop(c);
         return code;
     };
-    if (dev_malloc(c, (void **)&c->col_rows, rows_bytes) != hipSuccess || dev_malloc(c, (void **)&c->col_presence, presence_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&c->col_hist, hist_bytes) != hipSuccess || dev_malloc(c, (void **)&rank, rank_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&table, table_bytes) != hipSuccess || dev_malloc(c, (void **)&color, color_bytes) != hipSuccess ||
-        dev_malloc(c, &scan_tmp, scan_bytes + 16) != hipSuccess)
+    if (dev_malloc(c, (void **)&c->col.rows, rows_bytes) != hipSuccess || dev_malloc(c, (void **)&c->col.presence, presence_bytes) != hipSuccess ||
+        dev_malloc(c, (void **)&c->col.hist, hist_bytes) != hipSuccess || !idx.alloc(c, temps) || !temps.get(c, &color, color_bytes))
         return done(fail(c, -10, "segment colours: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
     hipStream_t s = c->stream;
-    bool ok = hipMemsetAsync(c->col_rows, 0, rows_bytes, s) == hipSuccess && hipMemsetAsync(c->col_presence, 0, presence_bytes, s) == hipSuccess &&
-              hipMemsetAsync(c->col_hist, 0, hist_bytes, s) == hipSuccess && hipMemsetAsync(table, 0xFF, table_bytes, s) == hipSuccess &&
+    bool ok = hipMemsetAsync(c->col.rows, 0, rows_bytes, s) == hipSuccess && hipMemsetAsync(c->col.presence, 0, presence_bytes, s) == hipSuccess &&
+              hipMemsetAsync(c->col.hist, 0, hist_bytes, s) == hipSuccess && idx.fill(s) &&
               (!n_rec || hipMemcpyAsync(color, color_of_seq, (size_t)n_rec * 4, hipMemcpyHostToDevice, s) == hipSuccess);
     if (ok) {
         Timed t(c, TPC_K_COLORS);
-        hipLaunchKernelGGL(k_col_flags, dim3(col_grid(n_events + 1)), dim3(256), 0, s, c->seg_first, n_events, rank);
-        ok = rocprim::exclusive_scan(scan_tmp, scan_bytes, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
-        if (ok && n_events) {
-            hipLaunchKernelGGL(k_col_min, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg_name, n_events, table, n_table);
-            hipLaunchKernelGGL(k_col_scatter, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg_name, n_events, table, n_table, rank, c->seg_ev[2], n_rec, color,
-                               c->col_rows, n_rows, c->col_presence, words);
-        }
+        ok = idx.enqueue(c);
+        if (ok && n_events)
+            hipLaunchKernelGGL(k_col_scatter, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg.name, n_events, idx.table, idx.n_table, idx.rank, c->seg.ev[2], n_rec, color,
+                               c->col.rows, n_rows, c->col.presence, words);
         if (ok && n_rows) {
             if (bins <= COL_LDS_BINS)
-                hipLaunchKernelGGL(k_col_rows<true>, dim3(std::min(col_grid(n_rows), 1024u)), dim3(256), (size_t)bins * 16, s, c->col_rows, n_rows, c->col_presence, words,
-                                   c->seg_ev[0], c->seg_ev[1], (uint32_t)c->seg_k, c->col_hist, n_colors);
+                hipLaunchKernelGGL(k_col_rows<true>, dim3(std::min(col_grid(n_rows), 1024u)), dim3(256), (size_t)bins * 16, s, c->col.rows, n_rows, c->col.presence, words,
+                                   c->seg.ev[0], c->seg.ev[1], (uint32_t)c->seg.k, c->col.hist, n_colors);
             else
-                hipLaunchKernelGGL(k_col_rows<false>, dim3(col_grid(n_rows)), dim3(256), 0, s, c->col_rows, n_rows, c->col_presence, words, c->seg_ev[0], c->seg_ev[1],
-                                   (uint32_t)c->seg_k, c->col_hist, n_colors);
+                hipLaunchKernelGGL(k_col_rows<false>, dim3(col_grid(n_rows)), dim3(256), 0, s, c->col.rows, n_rows, c->col.presence, words, c->seg.ev[0], c->seg.ev[1],
+                                   (uint32_t)c->seg.k, c->col.hist, n_colors);
         }
     }
-    uint32_t scanned_rows = 0;
-    ok = ok && hipMemcpyAsync(&scanned_rows, rank + n_events, sizeof scanned_rows, hipMemcpyDeviceToHost, s) == hipSuccess;
-    const hipError_t e = hipStreamSynchronize(s);
-    if (!ok || e != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(c, -10, "segment colours: the kernels failed: %s", hipGetErrorString(e)));
-    if (scanned_rows != n_rows) return done(fail(c, -10, "segment colours: the first bits hold %u segments, the build counted %llu", scanned_rows, (unsigned long long)n_rows));
-    c->col_n_rows = n_rows; c->col_n_colors = n_colors; c->col_words = words;
-    c->col_valid = true;
-    return done(0);
+    ok = ok && idx.total(s);
+    if (int rc = stage_wait(c, "colours", ok)) return done(rc);
+    if (idx.scanned != n_rows) return done(fail(c, -10, "segment colours: the first bits hold %u segments, the build counted %llu", idx.scanned, (unsigned long long)n_rows));
+    c->col.n_rows = n_rows; c->col.n_colors = n_colors; c->col.words = words;
+    c->col.valid = true;
+    return 0;
 }
 
 int tpc_segments_colors_info(tpc_ctx *c, uint64_t *info)
 {
     if (!c) return -1;
-    if (!c->col_valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
+    if (!c->col.valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
     if (!info) return fail(c, -1, "segment colours: info required");
-    info[0] = c->col_n_rows; info[1] = c->col_n_colors; info[2] = c->col_words;
+    info[0] = c->col.n_rows; info[1] = c->col.n_colors; info[2] = c->col.words;
     return 0;
 }
 
 int tpc_segments_colors_fetch_rows(tpc_ctx *c, uint64_t r0, uint64_t n, uint32_t *first_event_host, uint32_t *occ_host, uint32_t *fwd_host, uint32_t *ncol_host)
 {
     if (!c) return -1;
-    if (!c->col_valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
-    if ((n && (!first_event_host || !occ_host || !fwd_host || !ncol_host)) || r0 > c->col_n_rows || n > c->col_n_rows - r0)
-        return fail(c, -1, "segment colours: bad row range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)r0, (unsigned long long)c->col_n_rows);
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *dst[4] = { first_event_host, occ_host, fwd_host, ncol_host };
-    for (int i = 0; n && i < 4; i++) HIPCHK(c, hipMemcpy(dst[i], c->col_rows + (uint64_t)i * c->col_n_rows + r0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    if (!c->col.valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
+    return fetch_planes(c, "colours", "row", c->col.rows, c->col.n_rows, r0, n, { first_event_host, occ_host, fwd_host, ncol_host });
 }
 
 int tpc_segments_colors_fetch_presence(tpc_ctx *c, uint64_t r0, uint64_t n, uint32_t *words_host)
 {
     if (!c) return -1;
-    if (!c->col_valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
-    if ((n && !words_host) || r0 > c->col_n_rows || n > c->col_n_rows - r0)
-        return fail(c, -1, "segment colours: bad presence range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)r0, (unsigned long long)c->col_n_rows);
+    if (!c->col.valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
+    if ((n && !words_host) || r0 > c->col.n_rows || n > c->col.n_rows - r0)
+        return fail(c, -1, "segment colours: bad presence range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)r0, (unsigned long long)c->col.n_rows);
     HIPCHK(c, hipSetDevice(c->device));
-    if (n) HIPCHK(c, hipMemcpy(words_host, c->col_presence + r0 * c->col_words, n * c->col_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n) HIPCHK(c, hipMemcpy(words_host, c->col.presence + r0 * c->col.words, n * c->col.words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
 int tpc_segments_colors_fetch_hist(tpc_ctx *c, uint64_t *segments_host, uint64_t *bases_host)
 {
     if (!c) return -1;
-    if (!c->col_valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
+    if (!c->col.valid) return fail(c, -1, "segment colours: tpc_segments_colors_build first");
     if (!segments_host || !bases_host) return fail(c, -1, "segment colours: both histogram arrays are required");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t bins = (size_t)c->col_n_colors + 1;
-    HIPCHK(c, hipMemcpy(segments_host, c->col_hist, bins * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(bases_host, c->col_hist + bins, bins * 8, hipMemcpyDeviceToHost));
+    const size_t bins = (size_t)c->col.n_colors + 1;
+    HIPCHK(c, hipMemcpy(segments_host, c->col.hist, bins * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(bases_host, c->col.hist + bins, bins * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

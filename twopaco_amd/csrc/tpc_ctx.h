@@ -8,6 +8,8 @@
 //   tpc_links.hip         the link table of the compacted graph (tpc_segments_links_*), kernels and entry points
 //   tpc_bubbles.hip       the simple bubbles of the compacted graph (tpc_segments_bubbles_*), kernels and entry points
 //   tpc_distances.hip     the genome distance matrices over the colour table (tpc_segments_distances_*), kernels and entry points
+//   tpc_stage.h           what the four stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
+//   tpc_segrows.h         the row of every event, rebuilt by the colour, link and bubble stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -27,6 +29,7 @@
 #include <map>
 
 struct tpc_ctx {
+    __attribute__((always_inline)) tpc_ctx() = default;  // into tpc_ctx_create, its one caller: the library exports no constructor
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -92,21 +95,26 @@ struct tpc_ctx {
     uint64_t *sp_rec = nullptr, *sp_vscan = nullptr, *sp_cnt = nullptr, *sp_lo = nullptr;
     uint32_t *sp_flags = nullptr;
     uint32_t sp_n_rec = 0;
+    // The tables of the compacted graph, one group each.  A group's drop (tpc_capi_segments.hip: segments_drop ... distances_drop) frees
+    // its pointers, assigns {} and drops what was built over it.
     // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed and the event table, of the last build
-    int64_t *seg_name = nullptr;
-    uint32_t *seg_first = nullptr;
-    uint32_t *seg_ev[3] = {nullptr, nullptr, nullptr};  // the event table: begin[e], end[e], seq_event_begin[0 .. seg_n_rec]
-    uint32_t seg_n_rec = 0;
-    uint64_t seg_events = 0, seg_segments = 0, seg_named = 0, seg_table_bytes = 0, seg_slots = 0, seg_peak_bytes = 0;
-    uint64_t seg_err_slot = 0;
-    int seg_err_kind = 0;
-    bool seg_valid = false;
-    // ... kept for the graph text (tpc_segments_text_*, tpc_segtext.hip): the build's sequence records and ambiguity positions, the
-    // text they index, and the plan of the last tpc_segments_text_plan
-    uint64_t *seg_rec = nullptr, *seg_amb = nullptr;   // device: rec_start[n_rec] then rec_len[n_rec]; amb_pos[n_amb]
-    uint64_t seg_n_amb = 0, seg_text_n = 0, seg_text_uploads = 0;
-    const void *seg_text_bases = nullptr;
-    int seg_k = 0;
+    struct Segments {
+        int64_t *name = nullptr;
+        uint32_t *first = nullptr;
+        uint32_t *ev[3] = {nullptr, nullptr, nullptr};  // the event table: begin[e], end[e], seq_event_begin[0 .. n_rec]
+        uint32_t n_rec = 0;
+        uint64_t events = 0, segments = 0, named = 0, table_bytes = 0, slots = 0, peak_bytes = 0;
+        uint64_t err_slot = 0;
+        int err_kind = 0;
+        bool valid = false;
+        // ... kept for the graph text (tpc_segments_text_*, tpc_segtext.hip): the build's sequence records and ambiguity positions, and
+        // the text they index
+        uint64_t *rec = nullptr, *amb = nullptr;   // device: rec_start[n_rec] then rec_len[n_rec]; amb_pos[n_amb]
+        uint64_t n_amb = 0, text_n = 0, text_uploads = 0;
+        const void *text_bases = nullptr;
+        int k = 0;
+    } seg;
+    // the plan of the last tpc_segments_text_plan
     TpcTextPlan text_plan;
     void *text_names = nullptr;       // device: the names' blob, then (8-aligned) its offsets, then amb_letter
     uint8_t *text_win = nullptr;      // device: the window buffer of tpc_segments_text_fetch, whole tiles
@@ -115,30 +123,37 @@ struct tpc_ctx {
     uint64_t text_total = 0;
     double text_ms = 0;               // TPC_K_SEGTEXT: kernels since the last plan
     int64_t text_write_us = 0, text_wait_us = 0, text_window_bytes = 0;  // of the last tpc_segments_text_write (tpc_get_stat)
-    // segment colour table (tpc_segments_colors_*, tpc_colors.hip) of the last tpc_segments_colors_build; a new segment build drops it
-    uint32_t *col_rows = nullptr;            // device, [4][col_n_rows]: first event, occurrences, forward, n_colors
-    uint32_t *col_presence = nullptr;        // device, [col_n_rows][col_words]
-    unsigned long long *col_hist = nullptr;  // device, [2][col_n_colors + 1]: segments, bases
-    uint64_t col_n_rows = 0;
-    uint32_t col_n_colors = 0, col_words = 0;
-    bool col_valid = false;
-    // link table (tpc_segments_links_*, tpc_links.hip) of the last tpc_segments_links_build; a new segment build drops it
-    uint32_t *lnk_rows = nullptr;            // device, [3][lnk_n_rows]: first event, count, same
-    uint32_t *lnk_first = nullptr;           // device, [(seg_events + 31) / 32]: link_first bits
-    uint64_t lnk_n_rows = 0, lnk_occurrences = 0, lnk_slots = 0, lnk_peak_bytes = 0;
-    bool lnk_valid = false;
+    // segment colour table (tpc_segments_colors_*, tpc_colors.hip) of the last tpc_segments_colors_build
+    struct Colors {
+        uint32_t *rows = nullptr;            // device, [4][n_rows]: first event, occurrences, forward, n_colors
+        uint32_t *presence = nullptr;        // device, [n_rows][words]
+        unsigned long long *hist = nullptr;  // device, [2][n_colors + 1]: segments, bases
+        uint64_t n_rows = 0;
+        uint32_t n_colors = 0, words = 0;
+        bool valid = false;
+    } col;
+    // link table (tpc_segments_links_*, tpc_links.hip) of the last tpc_segments_links_build
+    struct Links {
+        uint32_t *rows = nullptr;            // device, [3][n_rows]: first event, count, same
+        uint32_t *first = nullptr;           // device, [(seg.events + 31) / 32]: link_first bits
+        uint64_t n_rows = 0, occurrences = 0, slots = 0, peak_bytes = 0;
+        bool valid = false;
+    } lnk;
     int opt_links_slots_log2 = 0;            // option test_links_slots_log2 (tests only): slots of the link set, 0 = by the occurrences
-    // simple bubbles (tpc_segments_bubbles_*, tpc_bubbles.hip) of the last tpc_segments_bubbles_build; a new segment or link build drops them
-    uint32_t *bub_rows = nullptr;            // device, [4][bub_n_rows]: source, arm_a, arm_b, sink
-    uint32_t *bub_sides = nullptr;           // device, [3][bub_n_sides]: degree, smallest and largest neighbour
-    unsigned long long *bub_hist = nullptr;  // device, [6]: sides of degree 0, 1, 2, 3, 4, 5 or more
-    uint64_t bub_n_rows = 0, bub_n_sides = 0, bub_arcs = 0, bub_peak_bytes = 0;
-    bool bub_valid = false;
-    // genome distance matrices (tpc_segments_distances_*, tpc_distances.hip) of the last tpc_segments_distances_build; a new segment or
-    // colour build drops them
-    unsigned long long *dst_mat = nullptr;   // device, [2][dst_n_colors][dst_n_colors]: segments, edges
-    uint64_t dst_n_colors = 0, dst_n_rows = 0, dst_planes = 0, dst_peak_bytes = 0;
-    bool dst_valid = false;
+    // simple bubbles (tpc_segments_bubbles_*, tpc_bubbles.hip) of the last tpc_segments_bubbles_build
+    struct Bubbles {
+        uint32_t *rows = nullptr;            // device, [4][n_rows]: source, arm_a, arm_b, sink
+        uint32_t *sides = nullptr;           // device, [3][n_sides]: degree, smallest and largest neighbour
+        unsigned long long *hist = nullptr;  // device, [6]: sides of degree 0, 1, 2, 3, 4, 5 or more
+        uint64_t n_rows = 0, n_sides = 0, arcs = 0, peak_bytes = 0;
+        bool valid = false;
+    } bub;
+    // genome distance matrices (tpc_segments_distances_*, tpc_distances.hip) of the last tpc_segments_distances_build
+    struct Distances {
+        unsigned long long *mat = nullptr;   // device, [2][n_colors][n_colors]: segments, edges
+        uint64_t n_colors = 0, n_rows = 0, planes = 0, peak_bytes = 0;
+        bool valid = false;
+    } dst;
     int opt_distances_chunk_words = 0;       // option test_distances_chunk_words (tests only): column words a block stages at once, 0 = the kernel's own
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
@@ -254,10 +269,10 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // tpc_colors.hip
-void links_drop(tpc_ctx *c);            // tpc_links.hip
-void bubbles_drop(tpc_ctx *c);          // tpc_bubbles.hip
-void distances_drop(tpc_ctx *c);        // tpc_distances.hip
+void colors_drop(tpc_ctx *c);           // these four and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void links_drop(tpc_ctx *c);
+void bubbles_drop(tpc_ctx *c);
+void distances_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -23,7 +23,7 @@
 // Memory: kept until the next segment, colour or distance build 16 B x C^2; during the call 8 B x C x ceil(S / 64) of columns,
 // 32 x 8 B x ceil(S / 64) of planes and 64 B of scalars.  None of it exists in a context that never asks for distances, and the
 // segment, colour, link and bubble outputs are what they were.  What does not fit the free device memory is refused with an error text.
-#include "tpc_ctx.h"
+#include "tpc_stage.h"
 
 namespace {
 
@@ -149,72 +149,52 @@ unsigned dst_grid(uint64_t n, uint64_t per_block) { return (unsigned)std::max<ui
 
 }  // namespace
 
-namespace tpch {
-
-void distances_drop(tpc_ctx *c)
-{
-    if (c->dst_mat) (void)hipFree(c->dst_mat);
-    c->dst_mat = nullptr;
-    c->dst_n_colors = c->dst_n_rows = c->dst_planes = c->dst_peak_bytes = 0;
-    c->dst_valid = false;
-}
-
-}  // namespace tpch
-
 extern "C" {
 
 int tpc_segments_distances_build(tpc_ctx *c)
 {
     if (!c) return -1;
     distances_drop(c);
-    if (!c->seg_valid) return fail(c, -1, "segment distances: build the segment table first (tpc_segments_build_host / _resident)");
-    if (c->seg_err_kind != TPC_SEG_OK)
-        return fail(c, -1, "segment distances: the segment table holds the walk's error %d at slot %llu, there are no segments to compare", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
-    if (!c->col_valid) return fail(c, -1, "segment distances: build the colour table first (tpc_segments_colors_build)");
+    if (int rc = stage_needs_segments(c, "distances", "compare")) return rc;
+    if (!c->col.valid) return fail(c, -1, "segment distances: build the colour table first (tpc_segments_colors_build)");
     if (c->opt_distances_chunk_words < 0 || c->opt_distances_chunk_words > (int)DST_CHUNK)
         return fail(c, -1, "segment distances: option test_distances_chunk_words = %d is not in 0 .. %u", c->opt_distances_chunk_words, DST_CHUNK);
     // before any arithmetic with it: the colour stage takes up to 2^31 colours, whose square times 16 B wraps 64 bits
-    if (c->col_n_colors > DST_MAX_COLORS)
-        return fail(c, -20, "segment distances: %u colours, the two matrices of 16 B x colours^2 are refused beyond %llu colours", c->col_n_colors, (unsigned long long)DST_MAX_COLORS);
+    if (c->col.n_colors > DST_MAX_COLORS)
+        return fail(c, -20, "segment distances: %u colours, the two matrices of 16 B x colours^2 are refused beyond %llu colours", c->col.n_colors, (unsigned long long)DST_MAX_COLORS);
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t n_rows = c->col_n_rows, n_colors = c->col_n_colors, n_events = c->seg_events, nw = (n_rows + 63) / 64;
+    const uint64_t n_rows = c->col.n_rows, n_colors = c->col.n_colors, n_events = c->seg.events, nw = (n_rows + 63) / 64;
     const uint32_t cw = c->opt_distances_chunk_words ? (uint32_t)c->opt_distances_chunk_words : DST_CHUNK;
 
     // sizes in 64 bits, summed before the first allocation: C <= 2^24 (checked above) and nw < 2^26, so 16 C^2 <= 2^52 and 8 C nw < 2^53
     const uint64_t mat_bytes = 16 * n_colors * n_colors, col_bytes = 8 * n_colors * nw + 16, plane_bytes = 8 * (uint64_t)DST_PLANES * nw + 16;
     const uint64_t need = mat_bytes + col_bytes + plane_bytes + 64;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // after a whole run in this context the first pass's partition buffers are still held: they are given back before this is refused
-    if (need + ((uint64_t)64 << 20) > free_b && release_partition_buffers(c)) HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (need + ((uint64_t)64 << 20) > free_b)
-        return fail(c, -20, "segment distances: %llu bytes (%llu of them the two matrices of %llu x %llu colours, %llu the bit columns of %llu segments) do not fit the free device memory",
-                    (unsigned long long)need, (unsigned long long)mat_bytes, (unsigned long long)n_colors, (unsigned long long)n_colors, (unsigned long long)col_bytes,
-                    (unsigned long long)n_rows);
+    if (int rc = stage_fits(c, "distances", need, "%llu of them the two matrices of %llu x %llu colours, %llu the bit columns of %llu segments", (unsigned long long)mat_bytes,
+                            (unsigned long long)n_colors, (unsigned long long)n_colors, (unsigned long long)col_bytes, (unsigned long long)n_rows))
+        return rc;
+    StageTemps temps;
     unsigned long long *col = nullptr, *plane = nullptr;
     uint32_t *scalars = nullptr;
     auto done = [&](int code) {
-        for (void *p : { (void *)col, (void *)plane, (void *)scalars }) if (p) (void)hipFree(p);
         if (code) distances_drop(c);
         return code;
     };
-    if (dev_malloc(c, (void **)&c->dst_mat, mat_bytes) != hipSuccess || dev_malloc(c, (void **)&col, col_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&plane, plane_bytes) != hipSuccess || dev_malloc(c, (void **)&scalars, 64) != hipSuccess)
+    if (dev_malloc(c, (void **)&c->dst.mat, mat_bytes) != hipSuccess || !temps.get(c, &col, col_bytes) || !temps.get(c, &plane, plane_bytes) || !temps.get(c, &scalars, 64))
         return done(fail(c, -10, "segment distances: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
     hipStream_t s = c->stream;
-    bool ok = hipMemsetAsync(c->dst_mat, 0, mat_bytes, s) == hipSuccess && hipMemsetAsync(scalars, 0, 64, s) == hipSuccess;
+    bool ok = hipMemsetAsync(c->dst.mat, 0, mat_bytes, s) == hipSuccess && hipMemsetAsync(scalars, 0, 64, s) == hipSuccess;
     uint32_t host_scalars[2] = {0, 0};
     if (ok) {
         Timed t(c, TPC_K_DISTANCES);
         if (nw) {
             const uint64_t n_tiles = (n_colors + DST_TILE - 1) / DST_TILE, n_pairs = n_tiles * (n_tiles + 1) / 2, n_chunks = (nw + cw - 1) / cw;
-            hipLaunchKernelGGL(k_dst_columns, dim3(dst_grid(nw * c->col_words, 4)), dim3(256), 0, s, c->col_presence, n_rows, c->col_words, (uint32_t)n_colors, nw, col);
-            hipLaunchKernelGGL(k_dst_planes, dim3(dst_grid(nw, 4)), dim3(256), 0, s, c->col_rows, c->seg_ev[0], c->seg_ev[1], n_rows, n_events, nw, plane, scalars);
+            hipLaunchKernelGGL(k_dst_columns, dim3(dst_grid(nw * c->col.words, 4)), dim3(256), 0, s, c->col.presence, n_rows, c->col.words, (uint32_t)n_colors, nw, col);
+            hipLaunchKernelGGL(k_dst_planes, dim3(dst_grid(nw, 4)), dim3(256), 0, s, c->col.rows, c->seg.ev[0], c->seg.ev[1], n_rows, n_events, nw, plane, scalars);
             // a few thousand blocks in all: few tile pairs leave a block several chunks, whose sums it keeps in registers
             const uint64_t gy = std::min<uint64_t>(n_pairs, 65535), gx = std::max<uint64_t>(1, std::min<uint64_t>(n_chunks, 4096 / gy));
             hipLaunchKernelGGL(k_dst_gram, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, col, plane, scalars, (uint32_t)n_colors, nw, cw, (uint32_t)n_tiles, n_pairs,
-                               n_chunks, c->dst_mat);
-            hipLaunchKernelGGL(k_dst_mirror, dim3(dst_grid(n_colors * n_colors, 256)), dim3(256), 0, s, c->dst_mat, n_colors);
+                               n_chunks, c->dst.mat);
+            hipLaunchKernelGGL(k_dst_mirror, dim3(dst_grid(n_colors * n_colors, 256)), dim3(256), 0, s, c->dst.mat, n_colors);
         }
     }
     ok = ok && hipMemcpyAsync(host_scalars, scalars, sizeof host_scalars, hipMemcpyDeviceToHost, s) == hipSuccess;
@@ -223,32 +203,32 @@ int tpc_segments_distances_build(tpc_ctx *c)
         return done(fail(c, -10, "segment distances: the kernels failed: %s", hipGetErrorString(waited != hipSuccess ? waited : launched)));
     if (!ok) return done(fail(c, -10, "segment distances: a fill or a copy of the stage could not be enqueued"));
     if (host_scalars[1] & DST_FLAG_EVENT) return done(fail(c, -10, "segment distances: a colour row's first event lies outside the event table"));
-    c->dst_n_colors = n_colors; c->dst_n_rows = n_rows; c->dst_peak_bytes = need;
-    c->dst_planes = host_scalars[0] ? 32 - (uint64_t)__builtin_clz(host_scalars[0]) : 0;
-    c->dst_valid = true;
-    return done(0);
+    c->dst.n_colors = n_colors; c->dst.n_rows = n_rows; c->dst.peak_bytes = need;
+    c->dst.planes = host_scalars[0] ? 32 - (uint64_t)__builtin_clz(host_scalars[0]) : 0;
+    c->dst.valid = true;
+    return 0;
 }
 
 int tpc_segments_distances_info(tpc_ctx *c, uint64_t *info)
 {
     if (!c) return -1;
-    if (!c->dst_valid) return fail(c, -1, "segment distances: tpc_segments_distances_build first");
+    if (!c->dst.valid) return fail(c, -1, "segment distances: tpc_segments_distances_build first");
     if (!info) return fail(c, -1, "segment distances: info required");
-    info[0] = c->dst_n_colors; info[1] = c->dst_n_rows; info[2] = c->dst_planes; info[3] = c->dst_peak_bytes;
+    info[0] = c->dst.n_colors; info[1] = c->dst.n_rows; info[2] = c->dst.planes; info[3] = c->dst.peak_bytes;
     return 0;
 }
 
 int tpc_segments_distances_fetch(tpc_ctx *c, uint64_t i0, uint64_t n, uint64_t *segments_host, uint64_t *edges_host)
 {
     if (!c) return -1;
-    if (!c->dst_valid) return fail(c, -1, "segment distances: tpc_segments_distances_build first");
-    if ((n && (!segments_host || !edges_host)) || i0 > c->dst_n_colors || n > c->dst_n_colors - i0)
-        return fail(c, -1, "segment distances: bad row range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)i0, (unsigned long long)c->dst_n_colors);
+    if (!c->dst.valid) return fail(c, -1, "segment distances: tpc_segments_distances_build first");
+    if ((n && (!segments_host || !edges_host)) || i0 > c->dst.n_colors || n > c->dst.n_colors - i0)
+        return fail(c, -1, "segment distances: bad row range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)i0, (unsigned long long)c->dst.n_colors);
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t C = c->dst_n_colors;
+    const uint64_t C = c->dst.n_colors;
     if (n) {
-        HIPCHK(c, hipMemcpy(segments_host, c->dst_mat + i0 * C, n * C * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(edges_host, c->dst_mat + C * C + i0 * C, n * C * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(segments_host, c->dst.mat + i0 * C, n * C * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(edges_host, c->dst.mat + C * C + i0 * C, n * C * 8, hipMemcpyDeviceToHost));
     }
     return 0;
 }

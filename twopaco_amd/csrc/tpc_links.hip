@@ -23,10 +23,7 @@
 // event, two counters), 2 x 4 B / event of ranks, the first-sight table (counts[3] of tpc_segments_counts) and the scan's scratch.
 // slots = the smallest power of two >= 2 x occurrences, at least 1024.  None of it exists in a context that never asks for links,
 // and tpc_segments_counts reports what it reported before.  What does not fit the free device memory is refused with an error text.
-#include "tpc_ctx.h"
 #include "tpc_segrows.h"
-
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -45,9 +42,7 @@ __device__ __forceinline__ unsigned long long link_spelling(const int64_t *__res
                                                             uint64_t n_table, const uint32_t *__restrict__ rank, uint64_t n_rows,
                                                             const uint32_t *__restrict__ seq_begin, uint32_t n_rec, bool *bad)
 {
-    // the last s with seq_begin[s] <= e (sequences without events share their entry with the next one that has some)
-    uint32_t lo = 0, hi = n_rec + 1;
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (seq_begin[mid] <= (uint32_t)e) lo = mid + 1; else hi = mid; }
+    const uint32_t lo = col_seq_end(seq_begin, n_rec, (uint32_t)e);
     if (lo == 0 || seq_begin[lo - 1] == (uint32_t)e) return LINK_EMPTY;
     const uint32_t a = link_side(name, e - 1, n_events, table, n_table, rank, n_rows), b = link_side(name, e, n_events, table, n_table, rank, n_rows);
     if (a == 0xFFFFFFFFu || b == 0xFFFFFFFFu) { *bad = true; return LINK_EMPTY; }
@@ -82,10 +77,8 @@ __global__ void k_link_insert(const int64_t *__restrict__ name, uint64_t n_event
         const bool head = active && (lane == 0 || lo_below != (uint32_t)key || hi_below != (uint32_t)(key >> 32));
         const unsigned long long heads = __ballot(head), actives = __ballot(active), canons = __ballot(active && canon);
         if (head) {
-            const unsigned long long from = ~0ull << lane;
-            const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
             // (an inactive lane has no key, so the active lane above it leads a run of its own: no run spans one)
-            const unsigned long long run = from & actives & (above ? ((1ull << (__ffsll((long long)above) - 1)) - 1) : ~0ull);
+            const unsigned long long run = col_run(lane, heads, actives);
             uint64_t at = link_hash(key) & (slots - 1);
             bool placed = false;
             for (uint64_t probes = 0; probes < slots; probes++) {
@@ -139,36 +132,21 @@ __global__ void k_link_rows(const unsigned long long *__restrict__ key_of, const
 
 }  // namespace
 
-namespace tpch {
-
-void links_drop(tpc_ctx *c)
-{
-    for (void *p : { (void *)c->lnk_rows, (void *)c->lnk_first }) if (p) (void)hipFree(p);
-    c->lnk_rows = nullptr; c->lnk_first = nullptr;
-    c->lnk_n_rows = c->lnk_occurrences = c->lnk_slots = c->lnk_peak_bytes = 0;
-    c->lnk_valid = false;
-}
-
-}  // namespace tpch
-
 extern "C" {
 
 int tpc_segments_links_build(tpc_ctx *c)
 {
     if (!c) return -1;
     links_drop(c);
-    bubbles_drop(c);   // they were found over the link table that goes
-    if (!c->seg_valid) return fail(c, -1, "segment links: build the segment table first (tpc_segments_build_host / _resident)");
-    if (c->seg_err_kind != TPC_SEG_OK)
-        return fail(c, -1, "segment links: the segment table holds the walk's error %d at slot %llu, there are no segments to link", c->seg_err_kind, (unsigned long long)c->seg_err_slot);
-    const uint64_t n_events = c->seg_events, n_rows = c->seg_segments, n_table = c->seg_table_bytes / sizeof(uint32_t);
-    const uint32_t n_rec = c->seg_n_rec;
+    if (int rc = stage_needs_segments(c, "links", "link")) return rc;
+    const uint64_t n_events = c->seg.events, n_rows = c->seg.segments;
+    const uint32_t n_rec = c->seg.n_rec;
     if (n_rows > LINK_MAX_ROWS) return fail(c, -1, "segment links: %llu segments, a link's key holds at most %llu", (unsigned long long)n_rows, (unsigned long long)LINK_MAX_ROWS);
     if (c->opt_links_slots_log2 < 0 || c->opt_links_slots_log2 > 40) return fail(c, -1, "segment links: option test_links_slots_log2 = %d is not in 0 .. 40", c->opt_links_slots_log2);
     HIPCHK(c, hipSetDevice(c->device));
     // occurrences: every event but the first of its sequence; the table's own consistency: every event belongs to one of the n_rec sequences
     std::vector<uint32_t> seq_begin((size_t)n_rec + 1);
-    HIPCHK(c, hipMemcpy(seq_begin.data(), c->seg_ev[2], seq_begin.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(seq_begin.data(), c->seg.ev[2], seq_begin.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (seq_begin[0] != 0 || seq_begin[n_rec] != n_events) return fail(c, -1, "segment links: the stream holds events of more sequences than the %u given", n_rec);
     uint64_t with_events = 0;
     for (uint32_t s = 0; s < n_rec; s++) {
@@ -182,110 +160,91 @@ int tpc_segments_links_build(tpc_ctx *c)
 
     // sizes in 64 bits, summed before the first allocation; the rows are not counted yet: their bound is one per occurrence
     const uint64_t first_words = (n_events + 31) / 32;
-    const uint64_t slot_bytes = slots * 20 + 64, rank_bytes = (n_events + 1) * 4, table_bytes = n_table * 4 + 16, first_bytes = first_words * 4 + 16;
+    const uint64_t slot_bytes = slots * 20 + 64, first_bytes = first_words * 4 + 16;
     const uint64_t rows_bound = occurrences * 12 + 16;
-    size_t scan_bytes = 0;
-    uint32_t *rank = nullptr, *link_rank = nullptr, *table = nullptr, *flags = nullptr;
+    SegRows idx;
+    if (!idx.size(c)) return fail(c, -10, "segment links: the scan could not be sized");
+    // (the second rank_bytes: link_rank, scanned over the same scratch)
+    const uint64_t need = slot_bytes + idx.bytes() + idx.rank_bytes + first_bytes + rows_bound + 16 + 64;
+    if (int rc = stage_fits(c, "links", need, "%llu of them the %llu slots of the link set", (unsigned long long)slot_bytes, (unsigned long long)slots)) return rc;
+    StageTemps temps;
+    uint32_t *link_rank = nullptr, *flags = nullptr;
     unsigned long long *key_of = nullptr;
-    void *scan_tmp = nullptr;
-    if (rocprim::exclusive_scan(nullptr, scan_bytes, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), c->stream) != hipSuccess)
-        return fail(c, -10, "segment links: the scan could not be sized");
-    const uint64_t need = slot_bytes + 2 * rank_bytes + table_bytes + first_bytes + rows_bound + scan_bytes + 16 + 64;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    // after a whole run in this context the first pass's partition buffers are still held: they are given back before this is refused
-    if (need + ((uint64_t)64 << 20) > free_b && release_partition_buffers(c)) HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    if (need + ((uint64_t)64 << 20) > free_b)
-        return fail(c, -20, "segment links: %llu bytes (%llu of them the %llu slots of the link set) do not fit the free device memory", (unsigned long long)need,
-                    (unsigned long long)slot_bytes, (unsigned long long)slots);
     auto done = [&](int code) {
-        for (void *p : { (void *)rank, (void *)link_rank, (void *)table, (void *)flags, (void *)key_of, scan_tmp }) if (p) (void)hipFree(p);
         if (code) links_drop(c);
         return code;
     };
-    if (dev_malloc(c, (void **)&c->lnk_first, first_bytes) != hipSuccess || dev_malloc(c, (void **)&key_of, slot_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&rank, rank_bytes) != hipSuccess || dev_malloc(c, (void **)&link_rank, rank_bytes) != hipSuccess ||
-        dev_malloc(c, (void **)&table, table_bytes) != hipSuccess || dev_malloc(c, (void **)&flags, 64) != hipSuccess ||
-        dev_malloc(c, &scan_tmp, scan_bytes + 16) != hipSuccess)
+    if (dev_malloc(c, (void **)&c->lnk.first, first_bytes) != hipSuccess || !temps.get(c, &key_of, slot_bytes) || !idx.alloc(c, temps) ||
+        !temps.get(c, &link_rank, idx.rank_bytes) || !temps.get(c, &flags, 64))
         return done(fail(c, -10, "segment links: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
     uint32_t *first_of = (uint32_t *)(key_of + slots), *count_of = first_of + slots, *canon_of = count_of + slots;
     hipStream_t s = c->stream;
     // keys and first events all ones (no key, no event), the counters zero
     bool ok = hipMemsetAsync(key_of, 0xFF, slots * 12, s) == hipSuccess && hipMemsetAsync(count_of, 0, slots * 8, s) == hipSuccess &&
-              hipMemsetAsync(c->lnk_first, 0, first_bytes, s) == hipSuccess && hipMemsetAsync(table, 0xFF, table_bytes, s) == hipSuccess &&
+              hipMemsetAsync(c->lnk.first, 0, first_bytes, s) == hipSuccess && idx.fill(s) &&
               hipMemsetAsync(flags, 0, 64, s) == hipSuccess;
-    uint32_t scanned_rows = 0, n_links = 0, raised = 0;
+    uint32_t n_links = 0, raised = 0;
     if (ok) {
         Timed t(c, TPC_K_LINKS);
-        hipLaunchKernelGGL(k_col_flags, dim3(col_grid(n_events + 1)), dim3(256), 0, s, c->seg_first, n_events, rank);
-        ok = rocprim::exclusive_scan(scan_tmp, scan_bytes, rank, rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
+        ok = idx.enqueue(c);
         if (ok && n_events) {
-            hipLaunchKernelGGL(k_col_min, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg_name, n_events, table, n_table);
-            hipLaunchKernelGGL(k_link_insert, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg_name, n_events, table, n_table, rank, n_rows, c->seg_ev[2], n_rec,
+            hipLaunchKernelGGL(k_link_insert, dim3(col_grid(n_events)), dim3(256), 0, s, c->seg.name, n_events, idx.table, idx.n_table, idx.rank, n_rows, c->seg.ev[2], n_rec,
                                key_of, first_of, count_of, canon_of, slots, flags);
-            hipLaunchKernelGGL(k_link_bits, dim3(col_grid(slots)), dim3(256), 0, s, key_of, first_of, slots, n_events, c->lnk_first);
+            hipLaunchKernelGGL(k_link_bits, dim3(col_grid(slots)), dim3(256), 0, s, key_of, first_of, slots, n_events, c->lnk.first);
         }
         if (ok) {
-            hipLaunchKernelGGL(k_col_flags, dim3(col_grid(n_events + 1)), dim3(256), 0, s, c->lnk_first, n_events, link_rank);
-            ok = rocprim::exclusive_scan(scan_tmp, scan_bytes, link_rank, link_rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
+            hipLaunchKernelGGL(k_col_flags, dim3(col_grid(n_events + 1)), dim3(256), 0, s, c->lnk.first, n_events, link_rank);
+            ok = rocprim::exclusive_scan(idx.scan_tmp, idx.scan_bytes, link_rank, link_rank, 0u, n_events + 1, rocprim::plus<uint32_t>(), s) == hipSuccess;
         }
         // the row count decides the size of what is kept: one wait in the middle
-        ok = ok && hipMemcpyAsync(&scanned_rows, rank + n_events, sizeof scanned_rows, hipMemcpyDeviceToHost, s) == hipSuccess &&
-             hipMemcpyAsync(&n_links, link_rank + n_events, sizeof n_links, hipMemcpyDeviceToHost, s) == hipSuccess &&
+        ok = ok && idx.total(s) && hipMemcpyAsync(&n_links, link_rank + n_events, sizeof n_links, hipMemcpyDeviceToHost, s) == hipSuccess &&
              hipMemcpyAsync(&raised, flags, sizeof raised, hipMemcpyDeviceToHost, s) == hipSuccess;
-        hipError_t e = hipStreamSynchronize(s);
-        if (!ok || e != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(c, -10, "segment links: the kernels failed: %s", hipGetErrorString(e)));
-        if (scanned_rows != n_rows) return done(fail(c, -10, "segment links: the first bits hold %u segments, the build counted %llu", scanned_rows, (unsigned long long)n_rows));
+        if (int rc = stage_wait(c, "links", ok)) return done(rc);
+        if (idx.scanned != n_rows) return done(fail(c, -10, "segment links: the first bits hold %u segments, the build counted %llu", idx.scanned, (unsigned long long)n_rows));
         if (raised & LINK_FLAG_FULL)
             return done(fail(c, -21, "segment links: the link set of %llu slots is full (%llu occurrences); no table was made", (unsigned long long)slots, (unsigned long long)occurrences));
         if (raised & LINK_FLAG_ROW) return done(fail(c, -10, "segment links: an event's segment is missing from the first-sight table"));
         if (n_links > occurrences) return done(fail(c, -10, "segment links: %u links out of %llu occurrences", n_links, (unsigned long long)occurrences));
         const uint64_t rows_bytes = (uint64_t)n_links * 12 + 16;
-        if (dev_malloc(c, (void **)&c->lnk_rows, rows_bytes) != hipSuccess) return done(fail(c, -10, "segment links: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
+        if (dev_malloc(c, (void **)&c->lnk.rows, rows_bytes) != hipSuccess) return done(fail(c, -10, "segment links: hipMalloc failed: %s", hipGetErrorString(hipGetLastError())));
         if (n_links)
-            hipLaunchKernelGGL(k_link_rows, dim3(col_grid(slots)), dim3(256), 0, s, key_of, first_of, count_of, canon_of, slots, link_rank, c->seg_name, n_events, table, n_table,
-                               rank, n_rows, c->seg_ev[2], n_rec, c->lnk_rows, (uint64_t)n_links, flags);
+            hipLaunchKernelGGL(k_link_rows, dim3(col_grid(slots)), dim3(256), 0, s, key_of, first_of, count_of, canon_of, slots, link_rank, c->seg.name, n_events, idx.table, idx.n_table,
+                               idx.rank, n_rows, c->seg.ev[2], n_rec, c->lnk.rows, (uint64_t)n_links, flags);
         ok = hipMemcpyAsync(&raised, flags, sizeof raised, hipMemcpyDeviceToHost, s) == hipSuccess;
-        c->lnk_peak_bytes = need - rows_bound + rows_bytes;
+        c->lnk.peak_bytes = need - rows_bound + rows_bytes;
     }
-    const hipError_t e = hipStreamSynchronize(s);
-    if (!ok || e != hipSuccess || hipGetLastError() != hipSuccess) return done(fail(c, -10, "segment links: the kernels failed: %s", hipGetErrorString(e)));
+    if (int rc = stage_wait(c, "links", ok)) return done(rc);
     if (raised) return done(fail(c, -10, "segment links: a slot's first occurrence does not spell its key"));
-    c->lnk_n_rows = n_links; c->lnk_occurrences = occurrences; c->lnk_slots = slots;
-    c->lnk_valid = true;
-    return done(0);
+    c->lnk.n_rows = n_links; c->lnk.occurrences = occurrences; c->lnk.slots = slots;
+    c->lnk.valid = true;
+    return 0;
 }
 
 int tpc_segments_links_info(tpc_ctx *c, uint64_t *info)
 {
     if (!c) return -1;
-    if (!c->lnk_valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
+    if (!c->lnk.valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
     if (!info) return fail(c, -1, "segment links: info required");
-    info[0] = c->lnk_n_rows; info[1] = c->lnk_occurrences; info[2] = c->lnk_slots; info[3] = c->lnk_peak_bytes;
+    info[0] = c->lnk.n_rows; info[1] = c->lnk.occurrences; info[2] = c->lnk.slots; info[3] = c->lnk.peak_bytes;
     return 0;
 }
 
 int tpc_segments_links_fetch_rows(tpc_ctx *c, uint64_t r0, uint64_t n, uint32_t *first_event_host, uint32_t *count_host, uint32_t *same_host)
 {
     if (!c) return -1;
-    if (!c->lnk_valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
-    if ((n && (!first_event_host || !count_host || !same_host)) || r0 > c->lnk_n_rows || n > c->lnk_n_rows - r0)
-        return fail(c, -1, "segment links: bad row range (%llu rows at %llu of %llu)", (unsigned long long)n, (unsigned long long)r0, (unsigned long long)c->lnk_n_rows);
-    HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *dst[3] = { first_event_host, count_host, same_host };
-    for (int i = 0; n && i < 3; i++) HIPCHK(c, hipMemcpy(dst[i], c->lnk_rows + (uint64_t)i * c->lnk_n_rows + r0, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
+    if (!c->lnk.valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
+    return fetch_planes(c, "links", "row", c->lnk.rows, c->lnk.n_rows, r0, n, { first_event_host, count_host, same_host });
 }
 
 int tpc_segments_links_fetch_first(tpc_ctx *c, uint64_t word0, uint64_t n_words, uint32_t *bits_host)
 {
     if (!c) return -1;
-    if (!c->lnk_valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
-    const uint64_t words = (c->seg_events + 31) / 32;
+    if (!c->lnk.valid) return fail(c, -1, "segment links: tpc_segments_links_build first");
+    const uint64_t words = (c->seg.events + 31) / 32;
     if ((n_words && !bits_host) || word0 > words || n_words > words - word0)
         return fail(c, -1, "segment links: bad first-bit range (%llu words at %llu of %llu)", (unsigned long long)n_words, (unsigned long long)word0, (unsigned long long)words);
     HIPCHK(c, hipSetDevice(c->device));
-    if (n_words) HIPCHK(c, hipMemcpy(bits_host, c->lnk_first + word0, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_words) HIPCHK(c, hipMemcpy(bits_host, c->lnk.first + word0, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,190 @@
+// devicegraph.h -- the tables of the compacted graph, built on the device (include/twopaco_hip.h, the tpc_segments_* groups) and
+// fetched into the structs of graphformat.h.  One layer for both programs: graphdump, which loads the device library with dlopen,
+// and twopaco, which links it.  What differs between them stays with them: their timers, their [timing] lines, and the text they
+// throw when an entry point fails (Api::check is the caller's).  Nothing here knows which program calls it.
+#ifndef _DEVICE_GRAPH_H_
+#define _DEVICE_GRAPH_H_
+
+#include <algorithm>
+#include <functional>
+#include <vector>
+
+#include "../../include/twopaco_hip.h"
+#include "graphformat.h"
+
+// The entry points both programs reach through Api, each as tpc_<name>: the one list behind the members, graphdump's dlsym loads
+// (Api::Load) and twopaco's direct addresses (filled where the symbols are linked: vertexenumerator.cpp).
+#define TPC_DEVICE_GRAPH_ENTRY_POINTS(X) \
+	X(ctx_create) X(ctx_destroy) X(last_error) X(seq_upload) X(kernel_ms) \
+	X(segments_build_host) X(segments_counts) X(segments_error) \
+	X(segments_fetch_names) X(segments_fetch_first) X(segments_fetch_events) X(segments_fetch_sequences) \
+	X(segments_text_plan) X(segments_text_write) \
+	X(segments_colors_build) X(segments_colors_fetch_rows) X(segments_colors_fetch_presence) X(segments_colors_fetch_hist) \
+	X(segments_links_build) X(segments_links_info) X(segments_links_fetch_rows) X(segments_links_fetch_first) \
+	X(segments_bubbles_build) X(segments_bubbles_info) X(segments_bubbles_fetch_rows) X(segments_bubbles_fetch_hist) \
+	X(segments_distances_build) X(segments_distances_info) X(segments_distances_fetch)
+
+namespace TwoPaCo
+{
+	// (hidden: every program compiles its own copy, libtwopaco_host.so exports none of it)
+	namespace DeviceGraph __attribute__((visibility("hidden")))
+	{
+		struct Api
+		{
+#define X(name) decltype(&tpc_##name) name;
+			TPC_DEVICE_GRAPH_ENTRY_POINTS(X)
+#undef X
+			tpc_ctx * ctx;
+			// the caller's: throws its own text when rc != 0.  what: the entry point without its tpc_
+			std::function<void(int rc, const char * what)> check;
+
+			Api() : ctx(0) {}
+
+			// every entry point from find("tpc_<name>"), which returns its address or throws
+			template<class Find> void Load(Find find)
+			{
+#define X(name) name = reinterpret_cast<decltype(name)>(find("tpc_" #name));
+				TPC_DEVICE_GRAPH_ENTRY_POINTS(X)
+#undef X
+			}
+		};
+
+		// The event table of the last segment build as far as it was fetched: `table` points into the arrays.
+		struct Events
+		{
+			std::vector<int64_t> name;
+			std::vector<uint32_t> first, begin, end, seqEventBegin;
+			GraphFormat::EventTable table;
+
+			// seqEventBegin is all zeros until FetchSequences
+			Events(uint64_t events, size_t sequences) : seqEventBegin(sequences + 1, 0)
+			{
+				table.events = events;
+				table.sequences = sequences;
+				table.seqEventBegin = seqEventBegin.data();
+			}
+		};
+
+		inline void FetchNames(const Api & api, Events & held)
+		{
+			held.name.resize(held.table.events);
+			api.check(api.segments_fetch_names(api.ctx, 0, held.table.events, held.name.data()), "segments_fetch_names");
+			held.table.name = held.name.data();
+		}
+
+		inline void FetchFirst(const Api & api, Events & held)
+		{
+			held.first.resize((held.table.events + 31) / 32);
+			api.check(api.segments_fetch_first(api.ctx, 0, held.first.size(), held.first.data()), "segments_fetch_first");
+			held.table.first = held.first.data();
+		}
+
+		inline void FetchPositions(const Api & api, Events & held)
+		{
+			held.begin.resize(held.table.events);
+			held.end.resize(held.table.events);
+			api.check(api.segments_fetch_events(api.ctx, 0, held.table.events, held.begin.data(), held.end.data()), "segments_fetch_events");
+			held.table.begin = held.begin.data();
+			held.table.end = held.end.data();
+		}
+
+		inline void FetchSequences(const Api & api, Events & held)
+		{
+			api.check(api.segments_fetch_sequences(api.ctx, 0, held.seqEventBegin.size(), held.seqEventBegin.data()), "segments_fetch_sequences");
+		}
+
+		// The colour table (csrc/tpc_colors.hip): the events of the table on the device grouped by segment there.
+		inline void BuildColors(const Api & api, const GraphFormat::ColorMap & map)
+		{
+			api.check(api.segments_colors_build(api.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "segments_colors_build");
+		}
+
+		// ... fetched: the rows, their presence words and the histogram
+		inline void FetchColors(const Api & api, const GraphFormat::ColorMap & map, uint64_t rows, GraphFormat::ColorTable & out)
+		{
+			out.colors = map.label.size();
+			out.firstEvent.resize(rows);
+			out.occurrences.resize(rows);
+			out.forward.resize(rows);
+			out.nColors.resize(rows);
+			out.presence.resize(rows * out.Words());
+			out.histSegments.resize(out.colors + 1);
+			out.histBases.resize(out.colors + 1);
+			api.check(api.segments_colors_fetch_rows(api.ctx, 0, rows, out.firstEvent.data(), out.occurrences.data(), out.forward.data(), out.nColors.data()), "segments_colors_fetch_rows");
+			api.check(api.segments_colors_fetch_presence(api.ctx, 0, rows, out.presence.data()), "segments_colors_fetch_presence");
+			api.check(api.segments_colors_fetch_hist(api.ctx, out.histSegments.data(), out.histBases.data()), "segments_colors_fetch_hist");
+		}
+
+		// The link table (csrc/tpc_links.hip): the distinct links of the table on the device found there.
+		inline void BuildLinks(const Api & api)
+		{
+			api.check(api.segments_links_build(api.ctx), "segments_links_build");
+		}
+
+		// ... fetched: the rows (for the link file and the bubbles' header) and / or the first bits (for the compact text, never an
+		// empty array).  Returns the number of rows, fetched or not.
+		inline uint64_t FetchLinks(const Api & api, uint64_t events, bool rows, bool bits, GraphFormat::LinkTable & out)
+		{
+			uint64_t info[4] = {0, 0, 0, 0};
+			api.check(api.segments_links_info(api.ctx, info), "segments_links_info");
+			out.occurrences = info[1];
+			if (rows)
+			{
+				out.firstEvent.resize(info[0]);
+				out.count.resize(info[0]);
+				out.same.resize(info[0]);
+				api.check(api.segments_links_fetch_rows(api.ctx, 0, info[0], out.firstEvent.data(), out.count.data(), out.same.data()), "segments_links_fetch_rows");
+			}
+
+			if (bits)
+			{
+				out.linkFirst.assign(std::max<size_t>(1, size_t((events + 31) / 32)), 0);
+				api.check(api.segments_links_fetch_first(api.ctx, 0, (events + 31) / 32, out.linkFirst.data()), "segments_links_fetch_first");
+			}
+
+			return info[0];
+		}
+
+		// The simple bubbles (csrc/tpc_bubbles.hip), found over the link rows where they lie.
+		inline void BuildBubbles(const Api & api)
+		{
+			api.check(api.segments_bubbles_build(api.ctx), "segments_bubbles_build");
+		}
+
+		// ... fetched: the bubble rows and the degree histogram
+		inline void FetchBubbles(const Api & api, GraphFormat::BubbleTable & out)
+		{
+			uint64_t info[4] = {0, 0, 0, 0};
+			api.check(api.segments_bubbles_info(api.ctx, info), "segments_bubbles_info");
+			out.sides = info[1];
+			out.arcs = info[2];
+			out.source.resize(info[0]);
+			out.armA.resize(info[0]);
+			out.armB.resize(info[0]);
+			out.sink.resize(info[0]);
+			api.check(api.segments_bubbles_fetch_rows(api.ctx, 0, info[0], out.source.data(), out.armA.data(), out.armB.data(), out.sink.data()), "segments_bubbles_fetch_rows");
+			api.check(api.segments_bubbles_fetch_hist(api.ctx, out.hist), "segments_bubbles_fetch_hist");
+		}
+
+		// The distance matrices (csrc/tpc_distances.hip), summed over the presence bits of the colour build where they lie.
+		inline void BuildDistances(const Api & api)
+		{
+			api.check(api.segments_distances_build(api.ctx), "segments_distances_build");
+		}
+
+		// ... fetched: the two matrices.  false, and nothing fetched, when the stage saw other colours or segments than the caller
+		inline bool FetchDistances(const Api & api, uint64_t colors, uint64_t rows, GraphFormat::DistanceTable & out)
+		{
+			uint64_t info[4] = {0, 0, 0, 0};
+			api.check(api.segments_distances_info(api.ctx, info), "segments_distances_info");
+			if (info[0] != colors || info[1] != rows) return false;
+			out.colors = info[0];
+			out.segments.resize(size_t(info[0] * info[0]));
+			out.edges.resize(size_t(info[0] * info[0]));
+			api.check(api.segments_distances_fetch(api.ctx, 0, info[0], out.segments.data(), out.edges.data()), "segments_distances_fetch");
+			return true;
+		}
+	}
+}
+
+#endif

@@ -22,6 +22,53 @@ namespace
 		std::memcpy(p, s.c_str(), s.size() + 1);
 		return p;
 	}
+
+	// What every tpch_create_enumerator* shares: the file names, the options every one sets, the log stream and what becomes of it,
+	// and the call.  `fill` sets the option fields of its entry point and throws its refusal.  outFile NULL: as empty.
+	template<class Fill>
+	void * Create(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds, uint64_t threads, uint64_t abundance,
+		const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device, char ** log, Fill fill)
+	{
+		std::stringstream ss;
+		try
+		{
+			std::vector<std::string> names(files, files + nfiles);
+			TwoPaCo::EnumeratorOptions opt;
+			opt.pinnedSeed = pinned != 0;
+			opt.seed = seed;
+			opt.device = device;
+			fill(opt);
+			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
+			if (log) *log = Dup(ss.str());
+			return e.release();
+		}
+		catch (std::exception & e)
+		{
+			g_error = e.what();
+			if (log) *log = Dup(ss.str());
+			return 0;
+		}
+	}
+
+	void SetGraph(TwoPaCo::EnumeratorOptions & opt, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads)
+	{
+		opt.graphFormat = graphFormat ? graphFormat : "";
+		opt.graphFile = graphFile ? graphFile : "";
+		opt.graphPrefix = graphPrefix != 0;
+		opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
+	}
+
+	void SetColors(TwoPaCo::EnumeratorOptions & opt, const char * colorsBy, const char * colorsFile)
+	{
+		opt.colorsBy = colorsBy ? colorsBy : "";
+		opt.colorsFile = colorsFile ? colorsFile : "";
+	}
+
+	void SetLinks(TwoPaCo::EnumeratorOptions & opt, const char * linksFile, int graphCompact)
+	{
+		opt.linksFile = linksFile ? linksFile : "";
+		opt.graphCompact = graphCompact != 0;
+	}
 }
 
 extern "C"
@@ -93,25 +140,10 @@ extern "C"
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		int testFirst, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same with EnumeratorOptions::autoFilterSize (`-f auto`): the filter size comes from the device's sketch of the distinct
@@ -120,28 +152,13 @@ extern "C"
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		const char * graphFormat, const char * graphFile, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, 0, q, rounds == 0 ? 1 : rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.autoFilterSize = true;
 			opt.autoRounds = rounds == 0;
 			opt.graphFormat = graphFormat ? graphFormat : "";
 			opt.graphFile = graphFile ? graphFile : "";
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, 0, q, rounds == 0 ? 1 : rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same with the multi-GPU knobs: gpus ranks, transport (rccl != 0: RCCL), emulate != 0: all ranks on `device`,
@@ -150,28 +167,13 @@ extern "C"
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		int gpus, int rccl, int emulate, int forceSharded, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.gpus = gpus;
 			opt.rccl = rccl != 0;
 			opt.emulateRanks = emulate != 0;
 			opt.forceSharded = forceSharded != 0;
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same as tpch_create_enumerator with --graph (EnumeratorOptions::graphFormat ...): graphFormat gfa1 | gfa2 | fasta into
@@ -180,30 +182,12 @@ extern "C"
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
-			opt.graphFormat = graphFormat ? graphFormat : "";
-			opt.graphFile = graphFile ? graphFile : "";
-			opt.graphPrefix = graphPrefix != 0;
-			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
+			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
 			if (opt.graphFormat.empty()) throw std::runtime_error("The graph format must be one of gfa1, gfa2, fasta");
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same as tpch_create_enumerator with --colors (EnumeratorOptions::colorsBy ...): colorsBy file | sequence into colorsFile;
@@ -212,32 +196,13 @@ extern "C"
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
-			opt.graphFormat = graphFormat ? graphFormat : "";
-			opt.graphFile = graphFile ? graphFile : "";
-			opt.graphPrefix = graphPrefix != 0;
-			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
-			opt.colorsBy = colorsBy ? colorsBy : "";
-			opt.colorsFile = colorsFile ? colorsFile : "";
+			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
+			SetColors(opt, colorsBy, colorsFile);
 			if (opt.colorsBy.empty()) throw std::runtime_error("The colours must be one of file, sequence");
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same as tpch_create_enumerator_colors with --links / --graph-compact (EnumeratorOptions::linksFile, graphCompact): linksFile
@@ -247,34 +212,14 @@ extern "C"
 		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile,
 		const char * linksFile, int graphCompact, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
-			opt.graphFormat = graphFormat ? graphFormat : "";
-			opt.graphFile = graphFile ? graphFile : "";
-			opt.graphPrefix = graphPrefix != 0;
-			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
-			opt.colorsBy = colorsBy ? colorsBy : "";
-			opt.colorsFile = colorsFile ? colorsFile : "";
-			opt.linksFile = linksFile ? linksFile : "";
-			opt.graphCompact = graphCompact != 0;
+			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
+			SetColors(opt, colorsBy, colorsFile);
+			SetLinks(opt, linksFile, graphCompact);
 			if (opt.linksFile.empty() && !opt.graphCompact) throw std::runtime_error("One of the link table's file and the compact graph is required");
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile ? outFile : "", ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// the same as tpch_create_enumerator_links with --distances (EnumeratorOptions::distancesBy, distancesFile, distancesPhylipFile):
@@ -286,40 +231,20 @@ extern "C"
 		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile,
 		const char * linksFile, int graphCompact, const char * distancesBy, const char * distancesFile, const char * phylipFile, int autoFilter, char ** log)
 	{
-		std::stringstream ss;
-		try
+		return Create(files, nfiles, k, autoFilter ? 0 : filterBits, q, autoFilter && rounds == 0 ? 1 : rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log,
+			[&](TwoPaCo::EnumeratorOptions & opt)
 		{
-			std::vector<std::string> names(files, files + nfiles);
-			TwoPaCo::EnumeratorOptions opt;
-			opt.pinnedSeed = pinned != 0;
-			opt.seed = seed;
-			opt.device = device;
 			opt.insertTestFirst = testFirst != 0;
-			opt.graphFormat = graphFormat ? graphFormat : "";
-			opt.graphFile = graphFile ? graphFile : "";
-			opt.graphPrefix = graphPrefix != 0;
-			opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
-			opt.colorsBy = colorsBy ? colorsBy : "";
-			opt.colorsFile = colorsFile ? colorsFile : "";
-			opt.linksFile = linksFile ? linksFile : "";
-			opt.graphCompact = graphCompact != 0;
+			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
+			SetColors(opt, colorsBy, colorsFile);
+			SetLinks(opt, linksFile, graphCompact);
 			opt.distancesBy = distancesBy ? distancesBy : "";
 			opt.distancesFile = distancesFile ? distancesFile : "";
 			opt.distancesPhylipFile = phylipFile ? phylipFile : "";
 			if (opt.distancesBy.empty() || opt.distancesFile.empty()) throw std::runtime_error("The distance table needs its colours, one of file, sequence, and a file name");
 			opt.autoFilterSize = autoFilter != 0;
 			opt.autoRounds = autoFilter != 0 && rounds == 0;
-			std::unique_ptr<TwoPaCo::VertexEnumerator> e = TwoPaCo::CreateEnumerator(names, k, autoFilter ? 0 : filterBits, q, autoFilter && rounds == 0 ? 1 : rounds, threads, abundance, tmpDir,
-				outFile ? outFile : "", ss, opt);
-			if (log) *log = Dup(ss.str());
-			return e.release();
-		}
-		catch (std::exception & e)
-		{
-			g_error = e.what();
-			if (log) *log = Dup(ss.str());
-			return 0;
-		}
+		});
 	}
 
 	// The text of the compacted graph from an EVENT TABLE (include/twopaco_hip.h: name / first bits / begin / end per event,

@@ -76,6 +76,7 @@
 #include <unistd.h>
 
 #include "../../include/twopaco_hip.h"
+#include "devicegraph.h"
 #include "dnachar.h"
 #include "graphformat.h"
 #include "junctionapi.h"
@@ -88,6 +89,7 @@ namespace
 	using TwoPaCo::JunctionPosition;
 
 	using namespace TwoPaCo::GraphFormat;  // Out, the sinks, LoadSequences, the parallel formatter (graphformat.h)
+	using namespace TwoPaCo::DeviceGraph;  // the tables built on the device and fetched (devicegraph.h)
 
 	// ---------------------------------------------------------------------------------------- seq / group / dot
 	void DumpSeq(const std::string & binFile, Out & out)
@@ -506,42 +508,12 @@ namespace
 		}
 	};
 
-	// libtwopaco_hip.so, loaded when --gpu is given: ../lib beside the directory of the executable
-	class DeviceLibrary
+	// libtwopaco_hip.so, loaded when --gpu is given: ../lib beside the directory of the executable.  The entry points are those of
+	// devicegraph.h, each found with dlsym.
+	class DeviceLibrary : public TwoPaCo::DeviceGraph::Api
 	{
 	public:
-		decltype(&tpc_ctx_create) ctxCreate;
-		decltype(&tpc_ctx_destroy) ctxDestroy;
-		decltype(&tpc_last_error) lastError;
-		decltype(&tpc_seq_upload) seqUpload;
-		decltype(&tpc_segments_build_host) segmentsBuildHost;
-		decltype(&tpc_segments_counts) segmentsCounts;
-		decltype(&tpc_segments_error) segmentsError;
-		decltype(&tpc_segments_fetch_names) segmentsFetchNames;
-		decltype(&tpc_segments_fetch_first) segmentsFetchFirst;
-		decltype(&tpc_segments_fetch_events) segmentsFetchEvents;
-		decltype(&tpc_segments_fetch_sequences) segmentsFetchSequences;
-		decltype(&tpc_segments_text_plan) segmentsTextPlan;
-		decltype(&tpc_segments_text_write) segmentsTextWrite;
-		decltype(&tpc_segments_colors_build) segmentsColorsBuild;
-		decltype(&tpc_segments_colors_fetch_rows) segmentsColorsFetchRows;
-		decltype(&tpc_segments_colors_fetch_presence) segmentsColorsFetchPresence;
-		decltype(&tpc_segments_colors_fetch_hist) segmentsColorsFetchHist;
-		decltype(&tpc_segments_links_build) segmentsLinksBuild;
-		decltype(&tpc_segments_links_info) segmentsLinksInfo;
-		decltype(&tpc_segments_links_fetch_rows) segmentsLinksFetchRows;
-		decltype(&tpc_segments_links_fetch_first) segmentsLinksFetchFirst;
-		decltype(&tpc_segments_bubbles_build) segmentsBubblesBuild;
-		decltype(&tpc_segments_bubbles_info) segmentsBubblesInfo;
-		decltype(&tpc_segments_bubbles_fetch_rows) segmentsBubblesFetchRows;
-		decltype(&tpc_segments_bubbles_fetch_hist) segmentsBubblesFetchHist;
-		decltype(&tpc_segments_distances_build) segmentsDistancesBuild;
-		decltype(&tpc_segments_distances_info) segmentsDistancesInfo;
-		decltype(&tpc_segments_distances_fetch) segmentsDistancesFetch;
-		decltype(&tpc_kernel_ms) kernelMs;
-		tpc_ctx * ctx;
-
-		explicit DeviceLibrary(int device) : ctx(0), handle_(0)
+		explicit DeviceLibrary(int device) : handle_(0)
 		{
 			char exe[4096];
 			const ssize_t n = ::readlink("/proc/self/exe", exe, sizeof(exe) - 1);
@@ -555,36 +527,19 @@ namespace
 				throw std::runtime_error("--gpu: cannot load " + path + (why ? std::string(": ") + why : std::string()));
 			}
 
-			Load(ctxCreate, "tpc_ctx_create");
-			Load(ctxDestroy, "tpc_ctx_destroy");
-			Load(lastError, "tpc_last_error");
-			Load(seqUpload, "tpc_seq_upload");
-			Load(segmentsBuildHost, "tpc_segments_build_host");
-			Load(segmentsCounts, "tpc_segments_counts");
-			Load(segmentsError, "tpc_segments_error");
-			Load(segmentsFetchNames, "tpc_segments_fetch_names");
-			Load(segmentsFetchFirst, "tpc_segments_fetch_first");
-			Load(segmentsFetchEvents, "tpc_segments_fetch_events");
-			Load(segmentsFetchSequences, "tpc_segments_fetch_sequences");
-			Load(segmentsTextPlan, "tpc_segments_text_plan");
-			Load(segmentsTextWrite, "tpc_segments_text_write");
-			Load(segmentsColorsBuild, "tpc_segments_colors_build");
-			Load(segmentsColorsFetchRows, "tpc_segments_colors_fetch_rows");
-			Load(segmentsColorsFetchPresence, "tpc_segments_colors_fetch_presence");
-			Load(segmentsColorsFetchHist, "tpc_segments_colors_fetch_hist");
-			Load(segmentsLinksBuild, "tpc_segments_links_build");
-			Load(segmentsLinksInfo, "tpc_segments_links_info");
-			Load(segmentsLinksFetchRows, "tpc_segments_links_fetch_rows");
-			Load(segmentsLinksFetchFirst, "tpc_segments_links_fetch_first");
-			Load(segmentsBubblesBuild, "tpc_segments_bubbles_build");
-			Load(segmentsBubblesInfo, "tpc_segments_bubbles_info");
-			Load(segmentsBubblesFetchRows, "tpc_segments_bubbles_fetch_rows");
-			Load(segmentsBubblesFetchHist, "tpc_segments_bubbles_fetch_hist");
-			Load(segmentsDistancesBuild, "tpc_segments_distances_build");
-			Load(segmentsDistancesInfo, "tpc_segments_distances_info");
-			Load(segmentsDistancesFetch, "tpc_segments_distances_fetch");
-			Load(kernelMs, "tpc_kernel_ms");
-			const int rc = ctxCreate(device, &ctx);
+			Load([this](const char * name)
+			{
+				void * fn = ::dlsym(handle_, name);
+				if (!fn) throw std::runtime_error(std::string("--gpu: libtwopaco_hip.so lacks ") + name);
+				return fn;
+			});
+
+			check = [this](int rc, const char * what)
+			{
+				if (rc != 0) throw std::runtime_error(std::string("--gpu: tpc_") + what + " failed: " + last_error(ctx));
+			};
+
+			const int rc = ctx_create(device, &ctx);
 			if (rc != 0 || !ctx)
 			{
 				ctx = 0;
@@ -594,22 +549,12 @@ namespace
 
 		~DeviceLibrary()
 		{
-			if (ctx) ctxDestroy(ctx);
-		}
-
-		void Check(int rc, const char * what) const
-		{
-			if (rc != 0) throw std::runtime_error(std::string("--gpu: ") + what + " failed: " + lastError(ctx));
+			if (ctx) ctx_destroy(ctx);
 		}
 
 	private:
 		DeviceLibrary(const DeviceLibrary &);
 		void operator = (const DeviceLibrary &);
-		template<class F> void Load(F & fn, const char * name)
-		{
-			fn = reinterpret_cast<F>(::dlsym(handle_, name));
-			if (!fn) throw std::runtime_error(std::string("--gpu: libtwopaco_hip.so lacks ") + name);
-		}
 
 		void * handle_;
 	};
@@ -653,15 +598,15 @@ namespace
 
 		// the device stage
 		t0 = std::chrono::steady_clock::now();
-		lib.Check(lib.seqUpload(lib.ctx, text.bases.data(), text.nmask.data(), text.length), "tpc_seq_upload");
-		lib.Check(lib.segmentsBuildHost(lib.ctx, bin.data(), bin.size(), int(k), text.recStart.data(), text.recLength.data(), uint32_t(text.recStart.size()),
-			ambiguous.data(), ambiguous.size()), "tpc_segments_build_host");
+		lib.check(lib.seq_upload(lib.ctx, text.bases.data(), text.nmask.data(), text.length), "seq_upload");
+		lib.check(lib.segments_build_host(lib.ctx, bin.data(), bin.size(), int(k), text.recStart.data(), text.recLength.data(), uint32_t(text.recStart.size()),
+			ambiguous.data(), ambiguous.size()), "segments_build_host");
 		std::vector<char>().swap(bin);
 		uint64_t errorSlot = 0;
 		int errorKind = 0;
 		sequences = text.recStart.size();
-		lib.Check(lib.segmentsCounts(lib.ctx, counts), "tpc_segments_counts");
-		lib.Check(lib.segmentsError(lib.ctx, &errorSlot, &errorKind), "tpc_segments_error");
+		lib.check(lib.segments_counts(lib.ctx, counts), "segments_counts");
+		lib.check(lib.segments_error(lib.ctx, &errorSlot, &errorKind), "segments_error");
 		stats.path = "device";
 		stats.events = counts[0];
 		stats.segments = counts[1];
@@ -670,7 +615,7 @@ namespace
 		stats.deviceBytes = counts[5];
 		stats.streamBytes = counts[4] * SLOT_BYTES;
 		stats.textBytes = ((text.length + 31) / 32) * 12;
-		stats.kernelMs = lib.kernelMs(lib.ctx, TPC_K_SEGMENTS);
+		stats.kernelMs = lib.kernel_ms(lib.ctx, TPC_K_SEGMENTS);
 		if (errorKind != TPC_SEG_OK)
 		{
 			stats.deviceMs = MsSince(t0);
@@ -680,216 +625,103 @@ namespace
 		}
 	}
 
-	// The event table of the last build, fetched: `held` owns the arrays the table points to.
-	struct FetchedTable
+	// The event table of the last build, fetched whole.  Returns the milliseconds of the second half: the positions and the sequences'
+	// ranges (DumpStats::indexMs)
+	double FetchTable(DeviceLibrary & lib, Events & held)
 	{
-		std::vector<int64_t> name;
-		std::vector<uint32_t> first, begin, end, seqEventBegin;
-		EventTable table;
-	};
-
-	// returns the milliseconds of the second half: the positions and the sequences' ranges (DumpStats::indexMs)
-	double FetchTable(DeviceLibrary & lib, uint64_t events, size_t sequences, FetchedTable & held)
-	{
-		held.name.resize(events);
-		held.first.resize((events + 31) / 32);
-		held.begin.resize(events);
-		held.end.resize(events);
-		held.seqEventBegin.resize(sequences + 1);
-		lib.Check(lib.segmentsFetchNames(lib.ctx, 0, events, held.name.data()), "tpc_segments_fetch_names");
-		lib.Check(lib.segmentsFetchFirst(lib.ctx, 0, held.first.size(), held.first.data()), "tpc_segments_fetch_first");
+		FetchNames(lib, held);
+		FetchFirst(lib, held);
 		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsFetchEvents(lib.ctx, 0, events, held.begin.data(), held.end.data()), "tpc_segments_fetch_events");
-		lib.Check(lib.segmentsFetchSequences(lib.ctx, 0, held.seqEventBegin.size(), held.seqEventBegin.data()), "tpc_segments_fetch_sequences");
-		held.table.events = events;
-		held.table.name = held.name.data();
-		held.table.first = held.first.data();
-		held.table.begin = held.begin.data();
-		held.table.end = held.end.data();
-		held.table.sequences = sequences;
-		held.table.seqEventBegin = held.seqEventBegin.data();
-		if (held.seqEventBegin[sequences] != events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
+		FetchPositions(lib, held);
+		FetchSequences(lib, held);
+		if (held.seqEventBegin[held.table.sequences] != held.table.events) throw std::runtime_error("--gpu: the device counted another number of segments than the stream holds");
 		return MsSince(t0);
 	}
 
-	// The colour table of the table on the device (csrc/tpc_colors.hip), fetched: rows, presence words and the histogram.
-	void ColorsOnDevice(DeviceLibrary & lib, const ColorMap & map, uint64_t rows, ColorTable & colors, DumpStats & stats)
+	void TimingLine(const char * what, double ms, double kernelMs)
 	{
-		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
-		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
-		colors.colors = map.label.size();
-		colors.firstEvent.resize(rows);
-		colors.occurrences.resize(rows);
-		colors.forward.resize(rows);
-		colors.nColors.resize(rows);
-		colors.presence.resize(rows * colors.Words());
-		colors.histSegments.resize(colors.colors + 1);
-		colors.histBases.resize(colors.colors + 1);
-		lib.Check(lib.segmentsColorsFetchRows(lib.ctx, 0, rows, colors.firstEvent.data(), colors.occurrences.data(), colors.forward.data(), colors.nColors.data()), "tpc_segments_colors_fetch_rows");
-		lib.Check(lib.segmentsColorsFetchPresence(lib.ctx, 0, rows, colors.presence.data()), "tpc_segments_colors_fetch_presence");
-		lib.Check(lib.segmentsColorsFetchHist(lib.ctx, colors.histSegments.data(), colors.histBases.data()), "tpc_segments_colors_fetch_hist");
-		stats.colorsMs = MsSince(c0);
+		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] %s on device: %.3f ms (kernels %.3f ms)\n", what, ms, kernelMs);
 	}
 
-	// The distance matrices over the colour build in the context (csrc/tpc_distances.hip), fetched.
-	void DistancesOnDevice(DeviceLibrary & lib, const ColorMap & map, uint64_t rows, DistanceTable & distances, DumpStats & stats)
-	{
-		const std::chrono::steady_clock::time_point d0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsDistancesBuild(lib.ctx), "tpc_segments_distances_build");
-		stats.distancesKernelMs = lib.kernelMs(lib.ctx, TPC_K_DISTANCES);
-		uint64_t info[4] = {0, 0, 0, 0};
-		lib.Check(lib.segmentsDistancesInfo(lib.ctx, info), "tpc_segments_distances_info");
-		if (info[0] != map.label.size() || info[1] != rows) throw std::runtime_error("--gpu: the distance stage and the colour map disagree about the colours or the segments");
-		distances.colors = info[0];
-		distances.segments.resize(size_t(info[0] * info[0]));
-		distances.edges.resize(size_t(info[0] * info[0]));
-		lib.Check(lib.segmentsDistancesFetch(lib.ctx, 0, info[0], distances.segments.data(), distances.edges.data()), "tpc_segments_distances_fetch");
-		stats.distancesMs = MsSince(d0);
-		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] distance matrices on device: %.3f ms (kernels %.3f ms)\n", stats.distancesMs, stats.distancesKernelMs);
-	}
-
-	// --colors with --gpu: the table stays on the device, where the colour stage groups its events by segment (csrc/tpc_colors.hip);
-	// what is fetched is the rows, their presence words, the histogram, and the event table for the names and lengths.
-	void DumpColorsOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats,
-		const DistancesWanted & also = DistancesWanted())
-	{
-		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-		size_t sequences = 0;
-		std::chrono::steady_clock::time_point t0;
-		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
-		ColorMap map;
-		MakeColorMap(seq, fasta, bySequence, map);
-		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-		ColorTable colors;
-		ColorsOnDevice(lib, map, counts[1], colors, stats);
-		DistanceTable distances;
-		if (also.on) DistancesOnDevice(lib, map, counts[1], distances, stats);
-		FetchedTable held;
-		FetchTable(lib, counts[0], sequences, held);
-		stats.deviceMs = MsSince(t0);
-		t0 = std::chrono::steady_clock::now();
-		WriteColors(held.table, k, map, colors, outPath);
-		if (also.on) WriteDistanceFiles(k, map, counts[1], distances, also.out, also.phylip);
-		stats.formatMs = MsSince(t0);
-		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] colour table on device: %.3f ms (kernels %.3f ms)\n", stats.colorsMs, stats.colorsKernelMs);
-	}
-
-	// The link table of the table on the device (csrc/tpc_links.hip), fetched: rows when wanted, and the first bits.
+	// The link table of the table on the device (csrc/tpc_links.hip), fetched: the rows, or else the first bits.
 	void LinksOnDevice(DeviceLibrary & lib, uint64_t events, bool rows, LinkTable & links, DumpStats & stats)
 	{
 		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsLinksBuild(lib.ctx), "tpc_segments_links_build");
-		stats.linksKernelMs = lib.kernelMs(lib.ctx, TPC_K_LINKS);
-		uint64_t info[4] = {0, 0, 0, 0};
-		lib.Check(lib.segmentsLinksInfo(lib.ctx, info), "tpc_segments_links_info");
-		stats.links = info[0];
-		stats.linkOccurrences = info[1];
-		links.occurrences = info[1];
-		if (rows)
-		{
-			links.firstEvent.resize(info[0]);
-			links.count.resize(info[0]);
-			links.same.resize(info[0]);
-			lib.Check(lib.segmentsLinksFetchRows(lib.ctx, 0, info[0], links.firstEvent.data(), links.count.data(), links.same.data()), "tpc_segments_links_fetch_rows");
-		}
-		else
-		{
-			links.linkFirst.resize((events + 31) / 32);
-			lib.Check(lib.segmentsLinksFetchFirst(lib.ctx, 0, links.linkFirst.size(), links.linkFirst.data()), "tpc_segments_links_fetch_first");
-		}
-
+		BuildLinks(lib);
+		stats.linksKernelMs = lib.kernel_ms(lib.ctx, TPC_K_LINKS);
+		stats.links = FetchLinks(lib, events, rows, !rows, links);
+		stats.linkOccurrences = links.occurrences;
 		stats.linksMs = MsSince(t0);
-		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] link table on device: %.3f ms (kernels %.3f ms)\n", stats.linksMs, stats.linksKernelMs);
+		TimingLine("link table", stats.linksMs, stats.linksKernelMs);
 	}
 
-	// --links with --gpu: the table stays on the device, where the link stage finds the distinct links (csrc/tpc_links.hip); what
-	// is fetched is the rows, and the event table for the names.
-	void DumpLinksOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const LoadedSequences & loaded, const std::string & outPath, DumpStats & stats)
+	// What a --gpu run instead of -f writes: one of the colour, link and bubble tables into `out`, and / or the distance table
+	// (alone, or beside the colour or the bubble table of the same colours, written after it).
+	struct TablesWanted
 	{
-		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-		size_t sequences = 0;
-		std::chrono::steady_clock::time_point t0;
-		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
-		LinkTable links;
-		LinksOnDevice(lib, counts[0], true, links, stats);
-		FetchedTable held;
-		FetchTable(lib, counts[0], sequences, held);
-		stats.deviceMs = MsSince(t0);
-		t0 = std::chrono::steady_clock::now();
-		WriteLinks(held.table, k, counts[1], links, outPath);
-		stats.formatMs = MsSince(t0);
-	}
+		bool colors, links, bubbles, distances, bySequence;
+		std::string out, distancesOut, distancesPhylip;
+	};
 
-	// --bubbles with --gpu: one segment build, then the colour, link and bubble stages on the device (csrc/tpc_bubbles.hip reads the
-	// link rows where they lie); what is fetched is the bubble rows, the degree histogram, the colour rows and the event table.
-	void DumpBubblesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, DumpStats & stats,
-		const DistancesWanted & also = DistancesWanted())
+	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
+	// wanted run there in this order: colours (csrc/tpc_colors.hip), distances over their presence bits (csrc/tpc_distances.hip), links
+	// (csrc/tpc_links.hip), bubbles over the link rows (csrc/tpc_bubbles.hip).  Fetched is what the files print and no more: the event
+	// table for the names and lengths of any rows; --distances alone fetches the two matrices, neither colour rows nor event table.
+	void DumpTablesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
+		const InputSequences & seq, const LoadedSequences & loaded, const TablesWanted & want, DumpStats & stats)
 	{
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 		size_t sequences = 0;
 		std::chrono::steady_clock::time_point t0;
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		ColorMap map;
-		MakeColorMap(seq, fasta, bySequence, map);
-		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
 		ColorTable colors;
-		ColorsOnDevice(lib, map, counts[1], colors, stats);
-		DistanceTable distances;
-		if (also.on) DistancesOnDevice(lib, map, counts[1], distances, stats);
-		LinkTable links;
-		LinksOnDevice(lib, counts[0], true, links, stats);
-		const std::chrono::steady_clock::time_point b0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsBubblesBuild(lib.ctx), "tpc_segments_bubbles_build");
-		stats.bubblesKernelMs = lib.kernelMs(lib.ctx, TPC_K_BUBBLES);
-		uint64_t info[4] = {0, 0, 0, 0};
-		lib.Check(lib.segmentsBubblesInfo(lib.ctx, info), "tpc_segments_bubbles_info");
-		BubbleTable bubbles;
-		bubbles.sides = info[1];
-		bubbles.arcs = info[2];
-		bubbles.source.resize(info[0]);
-		bubbles.armA.resize(info[0]);
-		bubbles.armB.resize(info[0]);
-		bubbles.sink.resize(info[0]);
-		lib.Check(lib.segmentsBubblesFetchRows(lib.ctx, 0, info[0], bubbles.source.data(), bubbles.armA.data(), bubbles.armB.data(), bubbles.sink.data()), "tpc_segments_bubbles_fetch_rows");
-		lib.Check(lib.segmentsBubblesFetchHist(lib.ctx, bubbles.hist), "tpc_segments_bubbles_fetch_hist");
-		stats.bubbles = info[0];
-		stats.bubblesMs = MsSince(b0);
-		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] bubble table on device: %.3f ms (kernels %.3f ms)\n", stats.bubblesMs, stats.bubblesKernelMs);
-		FetchedTable held;
-		FetchTable(lib, counts[0], sequences, held);
-		stats.deviceMs = MsSince(t0);
-		t0 = std::chrono::steady_clock::now();
-		WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, outPath);
-		if (also.on) WriteDistanceFiles(k, map, counts[1], distances, also.out, also.phylip);
-		stats.formatMs = MsSince(t0);
-	}
+		if (want.colors || want.bubbles || want.distances)
+		{
+			MakeColorMap(seq, fasta, want.bySequence, map);
+			if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
+			BuildColors(lib, map);
+			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
+			if (want.colors || want.bubbles) FetchColors(lib, map, counts[1], colors);
+			stats.colorsMs = MsSince(c0);
+		}
 
-	// --distances with --gpu: one segment build, the colour stage, then the distance stage over the presence bits where they lie
-	// (csrc/tpc_distances.hip); what is fetched is the two matrices.  Neither the colour rows nor the event table come back.
-	void DumpDistancesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, bool bySequence, const std::string & outPath, const std::string & phylipPath, DumpStats & stats)
-	{
-		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-		size_t sequences = 0;
-		std::chrono::steady_clock::time_point t0;
-		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
-		ColorMap map;
-		MakeColorMap(seq, fasta, bySequence, map);
-		if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-		const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
-		lib.Check(lib.segmentsColorsBuild(lib.ctx, map.colorOfSequence.data(), uint32_t(map.label.size())), "tpc_segments_colors_build");
-		stats.colorsKernelMs = lib.kernelMs(lib.ctx, TPC_K_COLORS);
-		stats.colorsMs = MsSince(c0);
 		DistanceTable distances;
-		DistancesOnDevice(lib, map, counts[1], distances, stats);
+		if (want.distances)
+		{
+			const std::chrono::steady_clock::time_point d0 = std::chrono::steady_clock::now();
+			BuildDistances(lib);
+			stats.distancesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_DISTANCES);
+			if (!FetchDistances(lib, map.label.size(), counts[1], distances)) throw std::runtime_error("--gpu: the distance stage and the colour map disagree about the colours or the segments");
+			stats.distancesMs = MsSince(d0);
+			TimingLine("distance matrices", stats.distancesMs, stats.distancesKernelMs);
+		}
+
+		LinkTable links;
+		if (want.links || want.bubbles) LinksOnDevice(lib, counts[0], true, links, stats);
+		BubbleTable bubbles;
+		if (want.bubbles)
+		{
+			const std::chrono::steady_clock::time_point b0 = std::chrono::steady_clock::now();
+			BuildBubbles(lib);
+			stats.bubblesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_BUBBLES);
+			FetchBubbles(lib, bubbles);
+			stats.bubbles = bubbles.source.size();
+			stats.bubblesMs = MsSince(b0);
+			TimingLine("bubble table", stats.bubblesMs, stats.bubblesKernelMs);
+		}
+
+		Events held(counts[0], sequences);
+		if (want.colors || want.links || want.bubbles) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
-		WriteDistanceFiles(k, map, counts[1], distances, outPath, phylipPath);
+		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
+		if (want.links) WriteLinks(held.table, k, counts[1], links, want.out);
+		if (want.bubbles) WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, want.out);
+		if (want.distances) WriteDistanceFiles(k, map, counts[1], distances, want.distancesOut, want.distancesPhylip);
 		stats.formatMs = MsSince(t0);
+		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
 	}
 
 	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The formatter of
@@ -907,10 +739,10 @@ namespace
 			TwoPaCo::GraphFormat::DeviceTextInput input;
 			TwoPaCo::GraphFormat::MakeDeviceTextInput(seq, loaded, input);
 			uint64_t total = 0, written = 0;
-			lib.Check(lib.segmentsTextPlan(lib.ctx, TwoPaCo::GraphFormat::DeviceTextFormat(format), input.names.data(), input.nameOffset.data(),
-				input.ambiguousLetter.empty() ? 0 : input.ambiguousLetter.data(), &total), "tpc_segments_text_plan");
+			lib.check(lib.segments_text_plan(lib.ctx, TwoPaCo::GraphFormat::DeviceTextFormat(format), input.names.data(), input.nameOffset.data(),
+				input.ambiguousLetter.empty() ? 0 : input.ambiguousLetter.data(), &total), "segments_text_plan");
 			uint64_t after[6] = {0, 0, 0, 0, 0, 0};
-			lib.Check(lib.segmentsCounts(lib.ctx, after), "tpc_segments_counts");
+			lib.check(lib.segments_counts(lib.ctx, after), "segments_counts");
 			stats.deviceBytes = after[5];
 			stats.deviceMs = MsSince(t0);
 			t0 = std::chrono::steady_clock::now();
@@ -919,19 +751,19 @@ namespace
 			std::fflush(stdout);
 			// a regular file is written at its offset (pwrite), anything else in order
 			const off_t at = ::lseek(STDOUT_FILENO, 0, SEEK_CUR);
-			lib.Check(lib.segmentsTextWrite(lib.ctx, STDOUT_FILENO, at >= 0 ? uint64_t(at) : 0, 0, &written), "tpc_segments_text_write");
+			lib.check(lib.segments_text_write(lib.ctx, STDOUT_FILENO, at >= 0 ? uint64_t(at) : 0, 0, &written), "segments_text_write");
 			if (written != total) throw std::runtime_error("--gpu: the text was not written in full");
 			if (at >= 0) (void)::lseek(STDOUT_FILENO, at + off_t(written), SEEK_SET);
 			stats.formatMs = MsSince(t0);
-			stats.textKernelMs = lib.kernelMs(lib.ctx, TPC_K_SEGTEXT);
+			stats.textKernelMs = lib.kernel_ms(lib.ctx, TPC_K_SEGTEXT);
 			if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] graph text on device: %.3f ms\n", stats.formatMs);
 			return;
 		}
 
 		// name and first sight, then where every event sits in the stream: its two positions and the events of every sequence, as
 		// the device's scans left them
-		FetchedTable held;
-		stats.indexMs = FetchTable(lib, counts[0], sequences, held);
+		Events held(counts[0], sequences);
+		stats.indexMs = FetchTable(lib, held);
 		EventTable & table = held.table;
 		LinkTable links;
 		if (compact)
@@ -1148,45 +980,27 @@ int main(int argc, char * argv[])
 		also.on = distances && (colors || bubbles);
 		also.out = distancesOut;
 		also.phylip = distancesPhylip;
-		if (colors && lib)
+		if ((colors || links || bubbles || distances) && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
 			LoadedSequences loaded;
 			LoadSequences(fasta, prefix, threads, seq, loaded);
 			stats.loadMs = MsSince(t0);
-			DumpColorsOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, colorsBy == "sequence", colorsOut, stats, also);
+			TablesWanted want;
+			want.colors = colors;
+			want.links = links;
+			want.bubbles = bubbles;
+			want.distances = distances;
+			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distancesBy) == "sequence";
+			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
+			want.distancesOut = distancesOut;
+			want.distancesPhylip = distancesPhylip;
+			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
-		else if (links && lib)
-		{
-			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-			InputSequences seq;
-			LoadedSequences loaded;
-			LoadSequences(fasta, prefix, threads, seq, loaded);
-			stats.loadMs = MsSince(t0);
-			DumpLinksOnDevice(*lib, binFile, fasta, k, threads, loaded, linksOut, stats);
-		}
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);
-		else if (bubbles && lib)
-		{
-			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-			InputSequences seq;
-			LoadedSequences loaded;
-			LoadSequences(fasta, prefix, threads, seq, loaded);
-			stats.loadMs = MsSince(t0);
-			DumpBubblesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, bubblesBy == "sequence", bubblesOut, stats, also);
-		}
 		else if (bubbles) DumpBubbles(binFile, fasta, k, prefix, bubblesBy == "sequence", bubblesOut, also);
-		else if (distances && lib)
-		{
-			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-			InputSequences seq;
-			LoadedSequences loaded;
-			LoadSequences(fasta, prefix, threads, seq, loaded);
-			stats.loadMs = MsSince(t0);
-			DumpDistancesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, distancesBy == "sequence", distancesOut, distancesPhylip, stats);
-		}
 		else if (distances) DumpDistances(binFile, fasta, k, prefix, distancesBy == "sequence", distancesOut, distancesPhylip);
 		else if (lib)
 		{

@@ -16,6 +16,7 @@
 #include <stdexcept>
 
 #include "../../include/twopaco_hip.h"
+#include "devicegraph.h"
 #include "filterplan.h"
 #include "graphformat.h"
 #include "multigpu.h"
@@ -1020,283 +1021,177 @@ namespace TwoPaCo
 				}
 
 				const size_t sequences = text.recStart.size();
-				uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
-				std::vector<int64_t> name;
-				std::vector<uint32_t> first, begin, end, seqEventBegin(sequences + 1, 0);
-				if (!nothing)  // (nothing dispatched: an empty stream, no event, and no text on the device)
+				GraphFormat::ColorMap map;
+				GraphFormat::ColorTable colorTable;
+				GraphFormat::LinkTable linkTable;
+				GraphFormat::BubbleTable bubbleTable;
+				GraphFormat::DistanceTable distanceTable;
+				uint64_t segments = 0, linkRows = 0;
+				DeviceGraph::Events held(0, sequences);
+				const std::vector<uint32_t> noBits(1, 0);
+				const uint32_t * linkFirst = compact ? noBits.data() : 0;
+				if (nothing)
 				{
+					// nothing dispatched: an empty stream and no text on the device.  No event, no segment, no side: the serial statements
+					// over the empty table give the headers, the colours and two matrices of zeros
+					if (colorRows)
+					{
+						GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
+						GraphFormat::ComputeColors(held.table, k, map.colorOfSequence, map.label.size(), colorTable);
+					}
+
+					if (links || bubbles) GraphFormat::ComputeLinks(held.table, linkTable);
+					if (bubbles) GraphFormat::ComputeBubbles(held.table, linkTable, bubbleTable);
+					if (distances) GraphFormat::ComputeDistances(held.table, colorTable, distanceTable);
+				}
+				else
+				{
+					const DeviceGraph::Api api = LinkedApi();
+					const bool timing = std::getenv("TWOPACO_TIMING") != 0;
+					auto kernelLine = [&](const char * name, int which)
+					{
+						if (timing) std::cerr << "[timing]   " << name << ": " << tpc_kernel_ms(ctx_, which) << " ms" << std::endl;
+					};
+
 					Check(tpc_segments_build_resident(ctx_, int(k), text.recStart.data(), text.recLength.data(), uint32_t(sequences), ambiguous.data(), ambiguous.size()), "segments_build");
+					uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 					uint64_t errorSlot = 0;
 					int errorKind = 0;
 					Check(tpc_segments_counts(ctx_, counts), "segments_counts");
 					Check(tpc_segments_error(ctx_, &errorSlot, &errorKind), "segments_error");
 					timer.Lap("segment table");
-					if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   segments_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_SEGMENTS) << " ms" << std::endl;
+					kernelLine("segments_kernel_ms", TPC_K_SEGMENTS);
 					if (errorKind != TPC_SEG_OK)
 					{
 						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 					}
 
-					// With both, everything of the colour table that can fail on the device comes first and its file is written last:
-					// a graph step that throws leaves no colour file behind (the graph file removes itself).
-					DeviceColors deviceColors;
-					if (colorRows && !(graph && options.graphTextOnDevice)) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
-					if (colorRows) ColorsFromDevice(bySequence, fileName, seq, counts, name, begin, end, seqEventBegin, deviceColors, timer);
-					// the link table likewise: found on the device before the graph is written (the compact graph needs its first
-					// bits), its file written after it
-					GraphFormat::LinkTable deviceLinks;
-					bool fetched = colorRows && !(graph && options.graphTextOnDevice);
-					if ((links || compact) && !fetched && !(graph && options.graphTextOnDevice))
+					held.table.events = counts[0];
+					segments = counts[1];
+					// Everything that can fail on the device comes before the first file is written: a step that throws leaves no table's
+					// file behind (the graph file removes itself).  --graph-text device keeps the table on the device: what the tables'
+					// files print of it is fetched piece by piece, the names and the positions alone.
+					const bool onDevice = graph && options.graphTextOnDevice;
+					bool fetched = false;
+					auto fetchTable = [&]()
 					{
-						FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
+						DeviceGraph::FetchNames(api, held);
+						DeviceGraph::FetchFirst(api, held);
+						DeviceGraph::FetchPositions(api, held);
+						DeviceGraph::FetchSequences(api, held);
+						timer.Lap("segment table fetch");
 						fetched = true;
+					};
+
+					if (colorRows)
+					{
+						// --colors: the events grouped by segment on the device (csrc/tpc_colors.hip); the rows' names and lengths come from
+						// the fetched event table
+						if (!onDevice) fetchTable();
+						else if (counts[0])
+						{
+							DeviceGraph::FetchNames(api, held);
+							DeviceGraph::FetchPositions(api, held);
+						}
+
+						GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
+						if (map.colorOfSequence.size() != sequences) throw std::runtime_error("The packer and the parser disagree about the input sequences");
+						DeviceGraph::BuildColors(api, map);
+						timer.Lap("segment colours");
+						kernelLine("colors_kernel_ms", TPC_K_COLORS);
+						DeviceGraph::FetchColors(api, map, segments, colorTable);
+						timer.Lap("segment colours fetch");
 					}
 
-					if (links || compact || bubbles) LinksFromDevice(counts[0], links, compact, name, deviceLinks, timer);
-					// the bubbles over the link rows on the device, before anything is written; their file comes last
-					GraphFormat::BubbleTable deviceBubbles;
-					uint64_t linkRows = 0;
-					if (bubbles) BubblesFromDevice(deviceBubbles, linkRows, timer);
-					// the distance matrices over the presence bits on the device, likewise before anything is written
-					GraphFormat::DistanceTable deviceDistances;
-					if (distances) DistancesFromDevice(deviceColors.map.label.size(), counts[1], deviceDistances, timer);
-					if (graph && options.graphTextOnDevice) WriteGraphOnDevice(options, seq, loaded, timer);
-					else if (graph)
+					if ((links || compact) && !fetched && !onDevice) fetchTable();
+					if (links || compact || bubbles)
 					{
-						if (!fetched) FetchEventTable(counts[0], name, first, begin, end, seqEventBegin, timer);
-						WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, compact ? deviceLinks.linkFirst.data() : 0, options, seq, loaded, k, threads, timer);
-					}
-
-					if (colors)
-					{
-						GraphFormat::WriteColors(deviceColors.events, k, deviceColors.map, deviceColors.table, options.colorsFile);
-						timer.Lap("colour table writing");
-					}
-
-					if (links)
-					{
-						GraphFormat::EventTable events;
-						events.events = counts[0];
-						events.name = name.data();
-						GraphFormat::WriteLinks(events, k, counts[1], deviceLinks, options.linksFile);
-						timer.Lap("link table writing");
+						// --links / the compact graph / --bubbles: the distinct links found on the device (csrc/tpc_links.hip), before the graph
+						// is written (the compact text needs their first bits); the rows' names come from name[]
+						DeviceGraph::BuildLinks(api);
+						timer.Lap("segment links");
+						kernelLine("links_kernel_ms", TPC_K_LINKS);
+						linkRows = DeviceGraph::FetchLinks(api, counts[0], links, compact, linkTable);
+						if (links && held.name.empty() && counts[0]) DeviceGraph::FetchNames(api, held);
+						timer.Lap("segment links fetch");
+						if (compact) linkFirst = linkTable.linkFirst.data();
 					}
 
 					if (bubbles)
 					{
-						GraphFormat::WriteBubbles(deviceColors.events, k, deviceColors.map, deviceColors.table, linkRows, deviceBubbles, options.bubblesFile);
-						timer.Lap("bubble table writing");
+						// over the link rows where they lie (csrc/tpc_bubbles.hip); the arms' names, lengths and colours are --colors'
+						DeviceGraph::BuildBubbles(api);
+						timer.Lap("segment bubbles");
+						kernelLine("bubbles_kernel_ms", TPC_K_BUBBLES);
+						DeviceGraph::FetchBubbles(api, bubbleTable);
+						timer.Lap("segment bubbles fetch");
 					}
 
 					if (distances)
 					{
-						GraphFormat::WriteDistanceFiles(k, deviceColors.map, counts[1], deviceDistances, options.distancesFile, options.distancesPhylipFile);
-						timer.Lap("distance table writing");
+						// over the presence bits where they lie (csrc/tpc_distances.hip); fetched are the matrices alone
+						DeviceGraph::BuildDistances(api);
+						timer.Lap("segment distances");
+						kernelLine("distances_kernel_ms", TPC_K_DISTANCES);
+						if (!DeviceGraph::FetchDistances(api, map.label.size(), segments, distanceTable))
+						{
+							throw std::runtime_error("The distance stage and the colour table disagree about the colours or the segments");
+						}
+
+						timer.Lap("segment distances fetch");
 					}
 
-					return;
-				}
-				else if (colors)
-				{
-					// nothing dispatched: no event, the header and the colours alone
-					GraphFormat::EventTable empty;
-					empty.sequences = sequences;
-					empty.seqEventBegin = seqEventBegin.data();
-					GraphFormat::ColorMap map;
-					GraphFormat::MakeColorMap(seq, fileName, options.colorsBy == "sequence", map);
-					GraphFormat::ColorTable table;
-					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
-					GraphFormat::WriteColors(empty, k, map, table, options.colorsFile);
-					timer.Lap("colour table writing");
+					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
+					else if (graph && !fetched) fetchTable();
 				}
 
-				const std::vector<uint32_t> noBits(1, 0);
-				if (graph) WriteGraphFromTable(counts[0], name, first, begin, end, seqEventBegin, compact ? noBits.data() : 0, options, seq, loaded, k, threads, timer);
+				// the files: the graph, then the tables.  (With nothing dispatched the colour table is written before the graph.)
+				auto writeColors = [&]()
+				{
+					GraphFormat::WriteColors(held.table, k, map, colorTable, options.colorsFile);
+					timer.Lap("colour table writing");
+				};
+
+				if (colors && nothing) writeColors();
+				if (graph && (nothing || !options.graphTextOnDevice))
+				{
+					GraphFormat::EventTable table = held.table;
+					table.linkFirst = linkFirst;   // given: the compact gfa1
+					GraphFormat::CheckEventTable(table, loaded, k, threads);
+					GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
+					timer.Lap("graph formatting + writing");
+				}
+
+				if (colors && !nothing) writeColors();
 				if (links)
 				{
-					// nothing dispatched: no event, the header alone
-					GraphFormat::EventTable empty;
-					empty.sequences = sequences;
-					empty.seqEventBegin = seqEventBegin.data();
-					GraphFormat::LinkTable table;
-					GraphFormat::ComputeLinks(empty, table);
-					GraphFormat::WriteLinks(empty, k, 0, table, options.linksFile);
+					GraphFormat::WriteLinks(held.table, k, segments, linkTable, options.linksFile);
 					timer.Lap("link table writing");
 				}
 
 				if (bubbles)
 				{
-					// nothing dispatched: no event, no side, the header and the colours alone
-					GraphFormat::EventTable empty;
-					empty.sequences = sequences;
-					empty.seqEventBegin = seqEventBegin.data();
-					GraphFormat::ColorMap map;
-					GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-					GraphFormat::ColorTable table;
-					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
-					GraphFormat::LinkTable none;
-					GraphFormat::ComputeLinks(empty, none);
-					GraphFormat::BubbleTable found;
-					GraphFormat::ComputeBubbles(empty, none, found);
-					GraphFormat::WriteBubbles(empty, k, map, table, 0, found, options.bubblesFile);
+					GraphFormat::WriteBubbles(held.table, k, map, colorTable, linkRows, bubbleTable, options.bubblesFile);
 					timer.Lap("bubble table writing");
 				}
 
 				if (distances)
 				{
-					// nothing dispatched: no segment, the header, the colours and two matrices of zeros
-					GraphFormat::EventTable empty;
-					empty.sequences = sequences;
-					empty.seqEventBegin = seqEventBegin.data();
-					GraphFormat::ColorMap map;
-					GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-					GraphFormat::ColorTable table;
-					GraphFormat::ComputeColors(empty, k, map.colorOfSequence, map.label.size(), table);
-					GraphFormat::DistanceTable none;
-					GraphFormat::ComputeDistances(empty, table, none);
-					GraphFormat::WriteDistanceFiles(k, map, 0, none, options.distancesFile, options.distancesPhylipFile);
+					GraphFormat::WriteDistanceFiles(k, map, segments, distanceTable, options.distancesFile, options.distancesPhylipFile);
 					timer.Lap("distance table writing");
 				}
 			}
 
-			// --distances: the two colour x colour matrices summed on the device (csrc/tpc_distances.hip) over the presence bits of the
-			// colour build; fetched are the matrices alone.
-			void DistancesFromDevice(uint64_t colors, uint64_t rows, GraphFormat::DistanceTable & out, PhaseTimer & timer)
+			// the entry points of devicegraph.h at their linked addresses, on this enumerator's context and with its Check
+			DeviceGraph::Api LinkedApi()
 			{
-				Check(tpc_segments_distances_build(ctx_), "segments_distances_build");
-				timer.Lap("segment distances");
-				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   distances_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_DISTANCES) << " ms" << std::endl;
-				uint64_t info[4] = {0, 0, 0, 0};
-				Check(tpc_segments_distances_info(ctx_, info), "segments_distances_info");
-				if (info[0] != colors || info[1] != rows) throw std::runtime_error("The distance stage and the colour table disagree about the colours or the segments");
-				out.colors = info[0];
-				out.segments.resize(size_t(info[0] * info[0]));
-				out.edges.resize(size_t(info[0] * info[0]));
-				Check(tpc_segments_distances_fetch(ctx_, 0, info[0], out.segments.data(), out.edges.data()), "segments_distances_fetch");
-				timer.Lap("segment distances fetch");
-			}
-
-			// --bubbles: the simple bubbles of the link table on the device found there (csrc/tpc_bubbles.hip); fetched are the bubble
-			// rows and the degree histogram.  The arms' names, lengths and colours come from what --colors fetches.
-			void BubblesFromDevice(GraphFormat::BubbleTable & out, uint64_t & linkRows, PhaseTimer & timer)
-			{
-				Check(tpc_segments_bubbles_build(ctx_), "segments_bubbles_build");
-				timer.Lap("segment bubbles");
-				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   bubbles_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_BUBBLES) << " ms" << std::endl;
-				uint64_t info[4] = {0, 0, 0, 0}, linkInfo[4] = {0, 0, 0, 0};
-				Check(tpc_segments_bubbles_info(ctx_, info), "segments_bubbles_info");
-				Check(tpc_segments_links_info(ctx_, linkInfo), "segments_links_info");
-				linkRows = linkInfo[0];
-				out.sides = info[1];
-				out.arcs = info[2];
-				out.source.resize(info[0]); out.armA.resize(info[0]); out.armB.resize(info[0]); out.sink.resize(info[0]);
-				Check(tpc_segments_bubbles_fetch_rows(ctx_, 0, info[0], out.source.data(), out.armA.data(), out.armB.data(), out.sink.data()), "segments_bubbles_fetch_rows");
-				Check(tpc_segments_bubbles_fetch_hist(ctx_, out.hist), "segments_bubbles_fetch_hist");
-				timer.Lap("segment bubbles fetch");
-			}
-
-			// --links / the compact graph: the distinct links of the table on the device found there (csrc/tpc_links.hip); fetched are
-			// the rows (for the link file) and the first bits (for the compact text).  The rows' names come from name[], fetched
-			// here when nothing else fetched it (--graph-text device keeps the table on the device).
-			void LinksFromDevice(uint64_t events, bool rows, bool bits, std::vector<int64_t> & name, GraphFormat::LinkTable & out, PhaseTimer & timer)
-			{
-				Check(tpc_segments_links_build(ctx_), "segments_links_build");
-				timer.Lap("segment links");
-				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   links_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_LINKS) << " ms" << std::endl;
-				uint64_t info[4] = {0, 0, 0, 0};
-				Check(tpc_segments_links_info(ctx_, info), "segments_links_info");
-				out.occurrences = info[1];
-				if (rows)
-				{
-					out.firstEvent.resize(info[0]); out.count.resize(info[0]); out.same.resize(info[0]);
-					Check(tpc_segments_links_fetch_rows(ctx_, 0, info[0], out.firstEvent.data(), out.count.data(), out.same.data()), "segments_links_fetch_rows");
-					if (name.empty() && events)
-					{
-						name.resize(events);
-						Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
-					}
-				}
-
-				if (bits)
-				{
-					out.linkFirst.assign(std::max<size_t>(1, size_t((events + 31) / 32)), 0);
-					Check(tpc_segments_links_fetch_first(ctx_, 0, (events + 31) / 32, out.linkFirst.data()), "segments_links_fetch_first");
-				}
-
-				timer.Lap("segment links fetch");
-			}
-
-			void WriteGraphFromTable(uint64_t events, const std::vector<int64_t> & name, const std::vector<uint32_t> & first, const std::vector<uint32_t> & begin,
-				const std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin, const uint32_t * linkFirst, const EnumeratorOptions & options,
-				const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, size_t k, size_t threads, PhaseTimer & timer)
-			{
-				GraphFormat::EventTable table;
-				table.events = events;
-				table.name = name.data(); table.first = first.data(); table.begin = begin.data(); table.end = end.data();
-				table.sequences = seqEventBegin.size() - 1;
-				table.seqEventBegin = seqEventBegin.data();
-				table.linkFirst = linkFirst;   // given: the compact gfa1
-				GraphFormat::CheckEventTable(table, loaded, k, threads);
-				GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
-				timer.Lap("graph formatting + writing");
-			}
-
-			// what --colors fetched from the device, until its file is written
-			struct DeviceColors
-			{
-				GraphFormat::ColorMap map;
-				GraphFormat::ColorTable table;
-				GraphFormat::EventTable events;
-			};
-
-			void FetchEventTable(uint64_t events, std::vector<int64_t> & name, std::vector<uint32_t> & first, std::vector<uint32_t> & begin, std::vector<uint32_t> & end,
-				std::vector<uint32_t> & seqEventBegin, PhaseTimer & timer)
-			{
-				name.resize(events); first.resize((events + 31) / 32); begin.resize(events); end.resize(events);
-				Check(tpc_segments_fetch_names(ctx_, 0, events, name.data()), "segments_fetch_names");
-				Check(tpc_segments_fetch_first(ctx_, 0, first.size(), first.data()), "segments_fetch_first");
-				Check(tpc_segments_fetch_events(ctx_, 0, events, begin.data(), end.data()), "segments_fetch_events");
-				Check(tpc_segments_fetch_sequences(ctx_, 0, seqEventBegin.size(), seqEventBegin.data()), "segments_fetch_sequences");
-				timer.Lap("segment table fetch");
-			}
-
-			// --colors: the events of the table on the device grouped by segment there (csrc/tpc_colors.hip); fetched are the rows,
-			// their presence words and the histogram.  The names and lengths of the rows come from the fetched event table (`out`
-			// points into name / begin / end / seqEventBegin).  The file is the caller's to write.
-			void ColorsFromDevice(bool bySequence, const std::vector<std::string> & fileName, const GraphFormat::InputSequences & seq,
-				const uint64_t * counts, std::vector<int64_t> & name, std::vector<uint32_t> & begin, std::vector<uint32_t> & end, const std::vector<uint32_t> & seqEventBegin,
-				DeviceColors & out, PhaseTimer & timer)
-			{
-				GraphFormat::ColorMap & map = out.map;
-				GraphFormat::ColorTable & table = out.table;
-				GraphFormat::EventTable & events = out.events;
-				const bool keptTable = !name.empty() || counts[0] == 0;
-				if (!keptTable)
-				{
-					// (--graph-text device fetches no table: the names and positions alone are fetched here)
-					name.resize(counts[0]); begin.resize(counts[0]); end.resize(counts[0]);
-					Check(tpc_segments_fetch_names(ctx_, 0, counts[0], name.data()), "segments_fetch_names");
-					Check(tpc_segments_fetch_events(ctx_, 0, counts[0], begin.data(), end.data()), "segments_fetch_events");
-				}
-
-				GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-				if (map.colorOfSequence.size() + 1 != seqEventBegin.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
-				Check(tpc_segments_colors_build(ctx_, map.colorOfSequence.data(), uint32_t(map.label.size())), "segments_colors_build");
-				timer.Lap("segment colours");
-				if (std::getenv("TWOPACO_TIMING")) std::cerr << "[timing]   colors_kernel_ms: " << tpc_kernel_ms(ctx_, TPC_K_COLORS) << " ms" << std::endl;
-				table.colors = map.label.size();
-				const uint64_t rows = counts[1];
-				table.firstEvent.resize(rows); table.occurrences.resize(rows); table.forward.resize(rows); table.nColors.resize(rows);
-				table.presence.resize(rows * table.Words());
-				table.histSegments.resize(table.colors + 1); table.histBases.resize(table.colors + 1);
-				Check(tpc_segments_colors_fetch_rows(ctx_, 0, rows, table.firstEvent.data(), table.occurrences.data(), table.forward.data(), table.nColors.data()), "segments_colors_fetch_rows");
-				Check(tpc_segments_colors_fetch_presence(ctx_, 0, rows, table.presence.data()), "segments_colors_fetch_presence");
-				Check(tpc_segments_colors_fetch_hist(ctx_, table.histSegments.data(), table.histBases.data()), "segments_colors_fetch_hist");
-				timer.Lap("segment colours fetch");
-				events.events = counts[0];
-				events.name = name.data(); events.begin = begin.data(); events.end = end.data();
-				events.sequences = seqEventBegin.size() - 1;
-				events.seqEventBegin = seqEventBegin.data();
+				DeviceGraph::Api api;
+#define X(name) api.name = &tpc_##name;
+				TPC_DEVICE_GRAPH_ENTRY_POINTS(X)
+#undef X
+				api.ctx = ctx_;
+				api.check = [this](int rc, const char * what) { Check(rc, what); };
+				return api;
 			}
 
 			// --graph-text device: the table stays where it was built.  The header lines are written here, the events' text is
