@@ -63,7 +63,8 @@ enum {
     TPC_K_LINKS = 19,       /* tpc_segments_links_build: the device hash set of the distinct links, their counts and first bits (no counterpart in the reference) */
     TPC_K_BUBBLES = 20,     /* tpc_segments_bubbles_build: arcs, degrees, the simple bubbles and the degree histogram (no counterpart in the reference) */
     TPC_K_DISTANCES = 21,   /* tpc_segments_distances_build: bit columns, weight planes and the two colour x colour matrices (no counterpart in the reference) */
-    TPC_K_COUNT = 22
+    TPC_K_COMPONENTS = 22,  /* tpc_segments_components_build: the union-find over the link rows, the numbering and the per-component sums (no counterpart in the reference) */
+    TPC_K_COUNT = 23
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -662,6 +663,54 @@ int tpc_segments_distances_build(tpc_ctx *ctx);
 int tpc_segments_distances_info(tpc_ctx *ctx, uint64_t *info /* [4]: colours, rows, planes used, peak device bytes */);
 int tpc_segments_distances_fetch(tpc_ctx *ctx, uint64_t i0, uint64_t n_rows, uint64_t *segments_host /* [n_rows x C] */, uint64_t *edges_host /* [n_rows x C] */);
 
+/* The CONNECTED COMPONENTS of the compacted graph (csrc/tpc_components.hip): which pieces hang together.  No counterpart in the
+ * reference; ComputeComponents of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The
+ * definition, over the link table of the last tpc_segments_links_build and the colour table of the last tpc_segments_colors_build,
+ * both over one segment table:
+ *   ROW              a segment.  The rows are the colour table's, in the order of gfa1's S lines with a body.
+ *   JOINED           the rows of `from` and `to` of a link row are joined.  Strands do not matter.  A self-loop and a link that is its
+ *                    own reverse join a row to itself.  'N'-named segments are segments like any other.
+ *   COMPONENT        a class of the transitive closure of JOINED.  A segment that no link touches is a component of one.  Its ROOT
+ *                    is its smallest row.
+ *   COMPONENT ID     components are numbered from 0, ascending by root: the order in which gfa1 first prints a segment of each.
+ *   PER ROW          component[r].
+ *   PER COMPONENT p  root[p]; segments[p]; links[p], the link rows whose ends lie in it (every link row lies in exactly one);
+ *                    length[p], the sum of its segments' lengths in bases; edges[p], the sum of their weights, end - begin of the
+ *                    row's first event, the weight of the distance matrices (length - k per segment); occurrences[p], the sum of the
+ *                    colour rows' occurrences; presence[p], the OR of the colour rows' presence words; n_colors[p], its popcount.
+ *                    The sums are 64-bit.
+ *   CONSEQUENCES     every input sequence with an event lies in exactly one component, because consecutive segments of a sequence
+ *                    are linked; with one colour per sequence presence[p] therefore says which contigs make up component p.  The sum
+ *                    of segments[p] is the number of rows and the sum of links[p] the number of link rows.
+ *   EXACT            integers, commutative sums and ORs, and a root that is the smallest row whatever the order of the atomics: the
+ *                    result does not depend on the schedule.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this; tpc_segments_counts and the colour, link,
+ * bubble and distance outputs are what they were, in any order of the builds.
+ *   tpc_segments_components_build          a lock-free union-find over parent[S] (one thread per link row hooks the larger root under
+ *                                          the smaller with a compare-and-swap), one flatten pass, a scan for the ids, then the sums.
+ *                                          Every loop is counted: a find ends within S steps and a link retries at most S times;
+ *                                          reaching the bound (only with the option test_components_step_limit) is an error text
+ *                                          ("segment components: gave up ...").  Also refused with an error text: no segment table,
+ *                                          a table whose tpc_segments_error kind is not TPC_SEG_OK, no link table, no colour table,
+ *                                          2^31 segments or more, buffers beyond the free device memory; the context stays usable.
+ *                                          Kept until the next segment, link, colour or component build: 4 B per row, per component
+ *                                          4 B of root, 40 B of sums and 4 W B of presence.  During the call 12 B per row of parent,
+ *                                          label and flags and the row index of the link stage.  TPC_K_COMPONENTS times the stage on
+ *                                          the stream from its first kernel to its last, the host's one wait for the component count
+ *                                          included, as TPC_K_BUBBLES times the bubble stage.
+ *   tpc_segments_components_info           info[0] components, [1] rows, [2] the segments of the largest component, [3] the stage's
+ *                                          device bytes at their peak
+ *   tpc_segments_components_fetch_members  component[r] of rows [r0, r0 + n) to the host
+ *   tpc_segments_components_fetch_rows     root / segments / links / length / edges / occurrences of components [p0, p0 + n)
+ *   tpc_segments_components_fetch_presence the n x W presence words of components [p0, p0 + n), row-major (n_colors is their popcount)
+ * A range outside a table is refused with an error text. */
+int tpc_segments_components_build(tpc_ctx *ctx);
+int tpc_segments_components_info(tpc_ctx *ctx, uint64_t *info /* [4]: components, rows, segments of the largest component, peak device bytes */);
+int tpc_segments_components_fetch_members(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *component_host);
+int tpc_segments_components_fetch_rows(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *root_host, uint64_t *segments_host, uint64_t *links_host,
+                                       uint64_t *length_host, uint64_t *edges_host, uint64_t *occurrences_host);
+int tpc_segments_components_fetch_presence(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *words_host /* [n x W] */);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -708,6 +757,9 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *   test_distances_chunk_words  tests only: the next tpc_segments_distances_build stages n column words (64 rows each) per chunk
  *                      instead of its own 64 (0 = its own; more than 64 is refused), so that a table of a few hundred rows crosses
  *                      chunk borders and ends in a partial chunk
+ *   test_components_step_limit  tests only: the next tpc_segments_components_build gives a find n steps and a hook n retries instead
+ *                      of segments + 1 (0 = segments + 1), so that the give-up path -- an error return from kernels that end
+ *                      normally -- can be reached
  *   part_budget_bytes  partition buffers per tile batch (0 = automatic: 40 GiB, or 60 % of the free device
  *                      memory when that is more; any number of batches, not only powers of two); part_min_tiles  smallest batch */
 /*   replicate_filter   1 (before tpc_shard_config / tpc_set_params): a sharded context keeps the whole filter; tpc_pass1_insert / tpc_pass1_query

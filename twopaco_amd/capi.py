@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21}
+           "distances": 21, "components": 22}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -35,7 +35,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_colors_build", "tpc_segments_colors_info", "tpc_segments_colors_fetch_rows", "tpc_segments_colors_fetch_presence", "tpc_segments_colors_fetch_hist",
                "tpc_segments_links_build", "tpc_segments_links_info", "tpc_segments_links_fetch_rows", "tpc_segments_links_fetch_first",
                "tpc_segments_bubbles_build", "tpc_segments_bubbles_info", "tpc_segments_bubbles_fetch_rows", "tpc_segments_bubbles_fetch_sides", "tpc_segments_bubbles_fetch_hist",
-               "tpc_segments_distances_build", "tpc_segments_distances_info", "tpc_segments_distances_fetch"]
+               "tpc_segments_distances_build", "tpc_segments_distances_info", "tpc_segments_distances_fetch",
+               "tpc_segments_components_build", "tpc_segments_components_info", "tpc_segments_components_fetch_members", "tpc_segments_components_fetch_rows",
+               "tpc_segments_components_fetch_presence"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -176,6 +178,11 @@ def hip():
         L.tpc_segments_distances_build.argtypes = [p]
         L.tpc_segments_distances_info.argtypes = [p, p]
         L.tpc_segments_distances_fetch.argtypes = [p, u64, u64, p, p]
+        L.tpc_segments_components_build.argtypes = [p]
+        L.tpc_segments_components_info.argtypes = [p, p]
+        L.tpc_segments_components_fetch_members.argtypes = [p, u64, u64, p]
+        L.tpc_segments_components_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p, p]
+        L.tpc_segments_components_fetch_presence.argtypes = [p, u64, u64, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -223,6 +230,10 @@ def host():
         L.tpch_create_enumerator_distances.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
                                                        ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.c_char_p, ctypes.c_char_p,
                                                        ctypes.c_char_p, ci, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ci, ctypes.POINTER(p)]
+        L.tpch_create_enumerator_components.restype = p
+        L.tpch_create_enumerator_components.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, u64, ctypes.c_char_p,
+                                                        ctypes.c_char_p, ci, u64, ci, ci, ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.c_char_p, ctypes.c_char_p,
+                                                        ctypes.c_char_p, ci, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(p)]
         L.tpch_create_enumerator_auto.restype = p
         L.tpch_create_enumerator_auto.argtypes = [ctypes.POINTER(ctypes.c_char_p), ci, u64, u64, u64, u64, u64, ctypes.c_char_p, ctypes.c_char_p, ci, u64, ci,
                                                   ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(p)]
@@ -382,6 +393,8 @@ class Context:
             raise RuntimeError("twopaco_hip: %s (%d)" % (hip().tpc_last_error(self._h).decode(), rc))
 
     def set_option(self, name, value):
+        """tpc_set_option: the tuning knobs and the tests-only options of include/twopaco_hip.h, among them test_links_slots_log2,
+        test_distances_chunk_words and test_components_step_limit (the step bound of the next segments_components_build, 0 = its own)."""
         self._ck(hip().tpc_set_option(self._h, name.encode(), int(value)))
 
     def stat(self, name):
@@ -726,6 +739,39 @@ class Context:
         self._ck(hip().tpc_segments_distances_fetch(self._h, i0, n, *[a.ctypes.data for a in out]))
         return tuple(out)
 
+    def segments_components_build(self):
+        """The connected components (csrc/tpc_components.hip) over the link table of the last segments_links_build and the colour table
+        of the last segments_colors_build.  Returns segments_components_info()."""
+        self._ck(hip().tpc_segments_components_build(self._h))
+        return self.segments_components_info()
+
+    def segments_components_info(self):
+        """dict: components, rows, largest (segments of the largest component), peak_bytes (device memory of the stage)."""
+        c = np.zeros(4, dtype=np.uint64)
+        self._ck(hip().tpc_segments_components_info(self._h, c.ctypes.data))
+        return dict(zip(("components", "rows", "largest", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_components_fetch_members(self, r0=0, n=None):
+        """component[r] of rows [r0, r0 + n) as uint32; n = None: to the last row."""
+        n = self.segments_components_info()["rows"] - r0 if n is None else n
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_components_fetch_members(self._h, r0, n, out.ctypes.data))
+        return out
+
+    def segments_components_fetch_rows(self, p0=0, n=None):
+        """(root as uint32; segments, links, length, edges, occurrences as uint64) of components [p0, p0 + n); n = None: to the last."""
+        n = self.segments_components_info()["components"] - p0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32)] + [np.zeros(max(n, 0), dtype=np.uint64) for _ in range(5)]
+        self._ck(hip().tpc_segments_components_fetch_rows(self._h, p0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_components_fetch_presence(self, p0=0, n=None):
+        """uint32 [n, W] presence words of components [p0, p0 + n), W as of the colour table; n = None: to the last."""
+        n = self.segments_components_info()["components"] - p0 if n is None else n
+        out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
+        self._ck(hip().tpc_segments_components_fetch_presence(self._h, p0, n, out.ctypes.data))
+        return out
+
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))
 
@@ -918,7 +964,8 @@ class Enumerator:
     def __init__(self, files, k, filter_bits, q=5, rounds=1, threads=1, abundance=(1 << 64) - 1, tmpdir=".",
                  out=None, seed=None, device=0, test_first=False, gpus=1, rccl=True, emulate_ranks=False, force_sharded=False,
                  graph=None, graph_out=None, graph_prefix=False, graph_threads=16, colors=None, colors_out=None,
-                 links=False, links_out=None, graph_compact=False, distances=None, distances_out=None, distances_phylip=None):
+                 links=False, links_out=None, graph_compact=False, distances=None, distances_out=None, distances_phylip=None,
+                 components=None, components_out=None, components_members=None):
         """out: the junction stream's file, default de_bruijn.bin.  graph = gfa1 | gfa2 | fasta: `twopaco --graph` -- the
         compacted graph's text goes to graph_out (default de_bruijn.<graph>) and the junction stream is written only when
         `out` is given.  colors = file | sequence: `twopaco --colors` -- the segment colour table goes to colors_out (default
@@ -926,12 +973,35 @@ class Enumerator:
         de_bruijn.links.tsv); graph_compact: `--graph-compact`, with graph = gfa1.  Both combine with graph, colors and out.
         distances = file | sequence: `twopaco --distances` -- the genome distance table goes to distances_out (default
         de_bruijn.distances.tsv) and, when distances_phylip names a file, the PHYLIP matrix goes there; combines with all of the above and
-        with filter_bits = "auto"."""
+        with filter_bits = "auto".  components = file | sequence: `twopaco --components` -- the component table goes to components_out
+        (default de_bruijn.components.tsv) and, when components_members names a file, the component of every segment goes there; combines
+        with graph, colors, links, graph_compact and out, not with distances (use the program for both)."""
         arr = (ctypes.c_char_p * len(files))(*[f.encode() for f in files])
         log = ctypes.c_void_p()
         if distances is None and (distances_out is not None or distances_phylip is not None):
             raise ValueError("distances_out / distances_phylip: only with distances = file | sequence")
-        if distances is not None:
+        if components is None and (components_out is not None or components_members is not None):
+            raise ValueError("components_out / components_members: only with components = file | sequence")
+        if components is not None:
+            if gpus > 1 or force_sharded or filter_bits == "auto" or distances is not None:
+                raise ValueError("components: one GPU, a given filter size, not with distances")
+            if graph is not None:
+                graph_out = "de_bruijn." + graph if graph_out is None else graph_out
+            elif out is None:
+                out = "de_bruijn.bin"
+            links_out = ("de_bruijn.links.tsv" if links_out is None else links_out) if links else None
+            if colors is not None:
+                colors_out = "de_bruijn.colors.tsv" if colors_out is None else colors_out
+            components_out = "de_bruijn.components.tsv" if components_out is None else components_out
+            self._h = host().tpch_create_enumerator_components(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),
+                                                               b"" if out is None else out.encode(), 0 if seed is None else 1, 0 if seed is None else seed,
+                                                               device, 1 if test_first else 0, None if graph is None else graph.encode(),
+                                                               None if graph is None else os.fsencode(graph_out), 1 if graph_prefix else 0, graph_threads,
+                                                               None if colors is None else colors.encode(), None if colors is None else os.fsencode(colors_out),
+                                                               None if links_out is None else os.fsencode(links_out), 1 if graph_compact else 0,
+                                                               components.encode(), os.fsencode(components_out),
+                                                               None if components_members is None else os.fsencode(components_members), ctypes.byref(log))
+        elif distances is not None:
             if gpus > 1 or force_sharded or (filter_bits == "auto" and test_first):
                 raise ValueError("distances: one GPU; filter_bits='auto' with the plain insert")
             if graph is not None:
@@ -999,7 +1069,7 @@ class Enumerator:
                                                           1 if graph_prefix else 0, graph_threads, ctypes.byref(log))
             out = ""
         out = "de_bruijn.bin" if out is None else out
-        if graph is not None or filter_bits == "auto" or colors is not None or links or graph_compact or distances is not None:
+        if graph is not None or filter_bits == "auto" or colors is not None or links or graph_compact or distances is not None or components is not None:
             pass
         elif gpus > 1 or force_sharded:  # host/multigpu.h: the filter sharded by bit address over `gpus` ranks
             self._h = host().tpch_create_enumerator_mgpu(arr, len(files), k, filter_bits, q, rounds, threads, abundance, tmpdir.encode(),

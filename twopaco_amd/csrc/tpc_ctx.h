@@ -8,8 +8,9 @@
 //   tpc_links.hip         the link table of the compacted graph (tpc_segments_links_*), kernels and entry points
 //   tpc_bubbles.hip       the simple bubbles of the compacted graph (tpc_segments_bubbles_*), kernels and entry points
 //   tpc_distances.hip     the genome distance matrices over the colour table (tpc_segments_distances_*), kernels and entry points
-//   tpc_stage.h           what the four stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
-//   tpc_segrows.h         the row of every event, rebuilt by the colour, link and bubble stages: its owner and the device helpers over it
+//   tpc_components.hip    the connected components over the link and colour tables (tpc_segments_components_*), kernels and entry points
+//   tpc_stage.h           what the five stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
+//   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
 #pragma once
@@ -95,7 +96,7 @@ struct tpc_ctx {
     uint64_t *sp_rec = nullptr, *sp_vscan = nullptr, *sp_cnt = nullptr, *sp_lo = nullptr;
     uint32_t *sp_flags = nullptr;
     uint32_t sp_n_rec = 0;
-    // The tables of the compacted graph, one group each.  A group's drop (tpc_capi_segments.hip: segments_drop ... distances_drop) frees
+    // The tables of the compacted graph, one group each.  A group's drop (tpc_capi_segments.hip: segments_drop ... components_drop) frees
     // its pointers, assigns {} and drops what was built over it.
     // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed and the event table, of the last build
     struct Segments {
@@ -154,6 +155,17 @@ struct tpc_ctx {
         uint64_t n_colors = 0, n_rows = 0, planes = 0, peak_bytes = 0;
         bool valid = false;
     } dst;
+    // connected components (tpc_segments_components_*, tpc_components.hip) of the last tpc_segments_components_build
+    struct Components {
+        uint32_t *component = nullptr;       // device, [n_rows]: the component id of every row
+        uint32_t *root = nullptr;            // device, [n_comp]: the smallest row of every component
+        unsigned long long *sums = nullptr;  // device, [5][n_comp]: segments, links, length, edges, occurrences
+        uint32_t *presence = nullptr;        // device, [n_comp][words]
+        uint64_t n_comp = 0, n_rows = 0, largest = 0, peak_bytes = 0;
+        uint32_t words = 0;
+        bool valid = false;
+    } cmp;
+    int opt_components_step_limit = 0;       // option test_components_step_limit (tests only): steps of a find and retries of a hook, 0 = segments + 1
     int opt_distances_chunk_words = 0;       // option test_distances_chunk_words (tests only): column words a block stages at once, 0 = the kernel's own
     // scalars
     unsigned long long *counters = nullptr;  // device, 8 words
@@ -269,10 +281,11 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these four and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these five and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
+void components_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -29,7 +29,12 @@
 // segments and the edges ((k+1)-mers) two colours both hold -- as TSV of integers, byte for byte what `graphdump --distances` writes,
 // and asked for, the Jaccard distances over edges as a PHYLIP square matrix (csrc/tpc_distances.hip sums the matrices on the device
 // over the colour build; combines with everything above from one segment build and one colour build; --colors and --bubbles must
-// name the same colours; its file is written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// name the same colours; its file is written last);
+// --components file|sequence [--components-out F] [--components-members F]: the connected components of the same graph -- which
+// segments hang together -- as TSV of integers, byte for byte what `graphdump --components` writes, and asked for, the component of
+// every segment (csrc/tpc_components.hip finds them on the device over the link build and the colour build; combines with everything
+// above from one segment, colour and link build; --colors, --bubbles and --distances must name the same colours; its files are
+// written after the distance files).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -88,6 +93,7 @@ namespace
 			<< "               [--links] [--links-out <file name>] [--graph-compact]" << std::endl
 			<< "               [--bubbles <file|sequence>] [--bubbles-out <file name>]" << std::endl
 			<< "               [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>]" << std::endl
+			<< "               [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -116,7 +122,13 @@ namespace
 			<< "               --distances-out (default de_bruijn.distances.tsv): per colour its own segments and edges ((k+1)-mers), then for" << std::endl
 			<< "               every pair i < j the segments and the edges both hold; integers only, Jaccard = e_ij / (e_ii + e_jj - e_ij)." << std::endl
 			<< "               --distances-phylip: also the Jaccard distances over edges as a relaxed PHYLIP square matrix." << std::endl
-			<< "               Combines with --graph, --graph-compact, --colors and --bubbles (the same colours), --links and -o.  One GPU only." << std::endl;
+			<< "               Combines with --graph, --graph-compact, --colors and --bubbles (the same colours), --links and -o.  One GPU only." << std::endl
+			<< "       --components: also write the connected components of the graph as TSV to --components-out (default" << std::endl
+			<< "               de_bruijn.components.tsv): which segments hang together, a segment that no link touches being a component of one." << std::endl
+			<< "               Per component the name of its first segment, its segments, links, bases, edges, occurrences and colours (by file" << std::endl
+			<< "               or by sequence, as --colors).  --components-members: also the component of every segment, one line per segment." << std::endl
+			<< "               Combines with --graph, --graph-compact, --colors, --bubbles and --distances (the same colours), --links and -o." << std::endl
+			<< "               One GPU only." << std::endl;
 	}
 }
 
@@ -157,7 +169,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -250,6 +262,14 @@ int main(int argc, char * argv[])
 			}
 			else if (Match(a, 0, "distances-out")) { options.distancesFile = value("(--distances-out)"); distancesOutSet = true; }
 			else if (Match(a, 0, "distances-phylip")) { options.distancesPhylipFile = value("(--distances-phylip)"); distancesPhylipSet = true; }
+			else if (Match(a, 0, "components"))
+			{
+				options.componentsBy = value("(--components)");
+				if (options.componentsBy != "file" && options.componentsBy != "sequence") throw ArgError("Value '" + options.componentsBy + "' does not meet constraint: file|sequence", "(--components)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "components-out")) { options.componentsFile = value("(--components-out)"); componentsOutSet = true; }
+			else if (Match(a, 0, "components-members")) { options.componentsMembersFile = value("(--components-members)"); componentsMembersSet = true; }
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -338,6 +358,21 @@ int main(int argc, char * argv[])
 		else if (distancesOutSet || distancesPhylipSet)
 		{
 			throw ArgError("This argument needs --distances <file|sequence>", distancesOutSet ? "(--distances-out)" : "(--distances-phylip)");
+		}
+
+		if (!options.componentsBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The component table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--components)");
+			if (!options.colorsBy.empty() && options.colorsBy != options.componentsBy) throw ArgError("The component table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --components " + options.componentsBy, "(--components)");
+			if (!options.bubblesBy.empty() && options.bubblesBy != options.componentsBy) throw ArgError("The component table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --components " + options.componentsBy, "(--components)");
+			if (!options.distancesBy.empty() && options.distancesBy != options.componentsBy) throw ArgError("The component table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --components " + options.componentsBy, "(--components)");
+			if (!componentsOutSet) options.componentsFile = "de_bruijn.components.tsv";
+			if (options.componentsFile.empty()) throw ArgError("The component table needs a file name", "(--components-out)");
+			if (componentsMembersSet && options.componentsMembersFile.empty()) throw ArgError("The component members need a file name", "(--components-members)");
+		}
+		else if (componentsOutSet || componentsMembersSet)
+		{
+			throw ArgError("This argument needs --components <file|sequence>", componentsOutSet ? "(--components-out)" : "(--components-members)");
 		}
 
 		if (runTests)

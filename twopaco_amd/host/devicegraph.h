@@ -22,7 +22,9 @@
 	X(segments_colors_build) X(segments_colors_fetch_rows) X(segments_colors_fetch_presence) X(segments_colors_fetch_hist) \
 	X(segments_links_build) X(segments_links_info) X(segments_links_fetch_rows) X(segments_links_fetch_first) \
 	X(segments_bubbles_build) X(segments_bubbles_info) X(segments_bubbles_fetch_rows) X(segments_bubbles_fetch_hist) \
-	X(segments_distances_build) X(segments_distances_info) X(segments_distances_fetch)
+	X(segments_distances_build) X(segments_distances_info) X(segments_distances_fetch) \
+	X(segments_components_build) X(segments_components_info) X(segments_components_fetch_members) X(segments_components_fetch_rows) \
+	X(segments_components_fetch_presence)
 
 namespace TwoPaCo
 {
@@ -182,6 +184,35 @@ namespace TwoPaCo
 			out.segments.resize(size_t(info[0] * info[0]));
 			out.edges.resize(size_t(info[0] * info[0]));
 			api.check(api.segments_distances_fetch(api.ctx, 0, info[0], out.segments.data(), out.edges.data()), "segments_distances_fetch");
+			return true;
+		}
+
+		// The connected components (csrc/tpc_components.hip), found over the link rows and summed over the colour rows where they lie.
+		inline void BuildComponents(const Api & api)
+		{
+			api.check(api.segments_components_build(api.ctx), "segments_components_build");
+		}
+
+		// ... fetched: the members, the rows and their presence words.  false, and nothing fetched, when the stage saw other segments
+		// than the caller
+		inline bool FetchComponents(const Api & api, uint64_t rows, size_t words, GraphFormat::ComponentTable & out)
+		{
+			uint64_t info[4] = {0, 0, 0, 0};
+			api.check(api.segments_components_info(api.ctx, info), "segments_components_info");
+			if (info[1] != rows) return false;
+			const size_t n = size_t(info[0]);
+			out.component.resize(rows);
+			out.root.resize(n);
+			out.segments.resize(n);
+			out.links.resize(n);
+			out.length.resize(n);
+			out.edges.resize(n);
+			out.occurrences.resize(n);
+			out.presence.resize(n * words);
+			api.check(api.segments_components_fetch_members(api.ctx, 0, rows, out.component.data()), "segments_components_fetch_members");
+			api.check(api.segments_components_fetch_rows(api.ctx, 0, n, out.root.data(), out.segments.data(), out.links.data(), out.length.data(), out.edges.data(),
+				out.occurrences.data()), "segments_components_fetch_rows");
+			api.check(api.segments_components_fetch_presence(api.ctx, 0, n, out.presence.data()), "segments_components_fetch_presence");
 			return true;
 		}
 	}

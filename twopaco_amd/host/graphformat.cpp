@@ -865,6 +865,209 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeComponents(const EventTable & t, size_t k, const LinkTable & links, const ColorTable & colors, ComponentTable & out)
+		{
+			out = ComponentTable();
+			const size_t rows = colors.Rows(), words = colors.Words();
+			if (colors.occurrences.size() != rows || colors.presence.size() != rows * words) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			// the row of every segment: the order of the first sights, as ComputeColors numbers them
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			std::vector<uint32_t> rowOfEvent(size_t(t.events), 0);
+			uint64_t seen = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator at = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				if (at == rowOf.end())
+				{
+					if (name < FRESH) rowOf[name] = uint32_t(seen);
+					rowOfEvent[e] = uint32_t(seen++);
+				}
+				else rowOfEvent[e] = at->second;
+			}
+
+			if (seen != rows) throw std::runtime_error("component table: the colour table's rows are not the segments of the event table");
+			if (rows >= (uint64_t(1) << 31)) throw std::runtime_error("component table: " + std::to_string(rows) + " segments, a row holds at most 2147483647");
+			// union-find: the smaller root stays the root, so a tree's root is its smallest row
+			std::vector<uint32_t> parent(rows);
+			for (size_t r = 0; r < rows; r++) parent[r] = uint32_t(r);
+			auto find = [&](uint32_t x)
+			{
+				while (parent[x] != x) x = parent[x] = parent[parent[x]];
+				return x;
+			};
+
+			for (uint32_t e0 : links.firstEvent)
+			{
+				if (e0 == 0 || e0 >= t.events) throw std::runtime_error("link table: a row's first event lies outside the event table");
+				const uint32_t a = find(rowOfEvent[e0 - 1]), b = find(rowOfEvent[e0]);
+				if (a != b) parent[std::max(a, b)] = std::min(a, b);
+			}
+
+			// ids ascend by root: a root is met before every other row of its component
+			out.component.assign(rows, 0);
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t root = find(uint32_t(r));
+				if (root == r)
+				{
+					out.component[r] = uint32_t(out.root.size());
+					out.root.push_back(uint32_t(r));
+				}
+				else out.component[r] = out.component[root];
+			}
+
+			const size_t n = out.Rows();
+			out.segments.assign(n, 0);
+			out.links.assign(n, 0);
+			out.length.assign(n, 0);
+			out.edges.assign(n, 0);
+			out.occurrences.assign(n, 0);
+			out.presence.assign(n * words, 0);
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t p = out.component[r], e0 = colors.firstEvent[r];
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				out.segments[p] += 1;
+				out.length[p] += uint64_t(t.end[e0]) - t.begin[e0] + k;
+				out.edges[p] += uint64_t(t.end[e0]) - t.begin[e0];
+				out.occurrences[p] += colors.occurrences[r];
+				for (size_t w = 0; w < words; w++) out.presence[p * words + w] |= colors.presence[r * words + w];
+			}
+
+			for (uint32_t e0 : links.firstEvent) out.links[out.component[rowOfEvent[e0]]] += 1;
+		}
+
+		namespace
+		{
+			void CheckComponents(const EventTable & t, const ColorTable & colors, const ComponentTable & c)
+			{
+				const size_t rows = colors.Rows(), words = colors.Words(), n = c.Rows();
+				if (c.component.size() != rows || c.segments.size() != n || c.links.size() != n || c.length.size() != n || c.edges.size() != n || c.occurrences.size() != n ||
+					c.presence.size() != n * words)
+				{
+					throw std::runtime_error("component table: the arrays do not agree about the rows, the components and the colours");
+				}
+
+				for (uint32_t e0 : colors.firstEvent)
+				{
+					if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				}
+
+				for (uint32_t p : c.component)
+				{
+					if (p >= n) throw std::runtime_error("component table: a row lies in no component");
+				}
+
+				for (uint32_t r : c.root)
+				{
+					if (r >= rows) throw std::runtime_error("component table: a root lies outside the segments");
+				}
+			}
+
+			// the text `lines` appends to, written whenever it has grown past 1 MiB and at the end
+			void WriteStreamed(const std::string & path, const char * what, const std::function<void(std::string & buf, const std::function<void()> & flushIfLarge)> & lines)
+			{
+				std::FILE * f = path.empty() ? stdout : std::fopen(path.c_str(), "wb");
+				if (!f) throw std::runtime_error(std::string("Can't create the ") + what + " " + path);
+				std::string buf;
+				bool good = true;
+				auto flush = [&]() { good = good && std::fwrite(buf.data(), 1, buf.size(), f) == buf.size(); buf.clear(); };
+				lines(buf, [&]() { if (buf.size() > (size_t(1) << 20)) flush(); });
+				flush();
+				good = good && std::fflush(f) == 0;
+				if (f != stdout) good = (std::fclose(f) == 0) && good;
+				if (!good)
+				{
+					if (f != stdout) ::unlink(path.c_str());
+					throw std::runtime_error(std::string("Can't write the ") + what);
+				}
+			}
+		}
+
+		void WriteComponents(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & c, const std::string & path)
+		{
+			CheckComponents(t, colors, c);
+			if (map.label.size() != colors.colors) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			const size_t words = colors.Words(), n = c.Rows(), digits = size_t((colors.colors + 3) / 4);
+			// components and their segments by floor(log2(segments)): computed here from the rows, whichever source they have
+			uint64_t sizeComponents[64] = {0}, sizeSegments[64] = {0};
+			for (uint64_t s : c.segments)
+			{
+				if (s == 0) throw std::runtime_error("component table: a component holds no segment");
+				const int b = 63 - __builtin_clzll(static_cast<unsigned long long>(s));
+				sizeComponents[b] += 1;
+				sizeSegments[b] += s;
+			}
+
+			WriteStreamed(path, "component table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-components\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(colors.colors) +
+					"\tsegments=" + std::to_string(colors.Rows()) + "\tlinks=" + std::to_string(links) + "\tcomponents=" + std::to_string(n) + "\n";
+				for (uint64_t col = 0; col < colors.colors; col++) buf += "#color\t" + std::to_string(col) + "\t" + map.label[col] + "\n";
+				for (int b = 0; b < 64; b++)
+				{
+					if (sizeComponents[b]) buf += "#size\t" + std::to_string(b) + "\t" + std::to_string(sizeComponents[b]) + "\t" + std::to_string(sizeSegments[b]) + "\n";
+				}
+
+				for (size_t p = 0; p < n; p++)
+				{
+					buf += std::to_string(p);
+					buf += '\t';
+					buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[c.root[p]]])));
+					for (uint64_t value : {c.segments[p], c.links[p], c.length[p], c.edges[p], c.occurrences[p]})
+					{
+						buf += '\t';
+						buf += std::to_string(value);
+					}
+
+					const uint32_t * bits = &c.presence[p * words];
+					uint32_t held = 0;
+					for (size_t w = 0; w < words; w++) held += uint32_t(__builtin_popcount(bits[w]));
+					buf += '\t';
+					buf += std::to_string(held);
+					buf += '\t';
+					for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(bits[j >> 3] >> (4 * (j & 7))) & 15u];
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteComponentMembers(const EventTable & t, size_t k, const ColorTable & colors, const ComponentTable & c, const std::string & path)
+		{
+			CheckComponents(t, colors, c);
+			if (path.empty()) throw std::runtime_error("The component members need a file name");
+			WriteStreamed(path, "component members", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-component-members\t1\tk=" + std::to_string(k) + "\tsegments=" + std::to_string(colors.Rows()) + "\tcomponents=" + std::to_string(c.Rows()) + "\n";
+				for (size_t r = 0; r < colors.Rows(); r++)
+				{
+					buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[r]])));
+					buf += '\t';
+					buf += std::to_string(c.component[r]);
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteComponentFiles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & c,
+			const std::string & path, const std::string & membersPath)
+		{
+			if (!membersPath.empty()) WriteComponentMembers(t, k, colors, c, membersPath);
+			try
+			{
+				WriteComponents(t, k, map, colors, links, c, path);
+			}
+			catch (...)
+			{
+				if (!membersPath.empty()) ::unlink(membersPath.c_str());
+				throw;
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{

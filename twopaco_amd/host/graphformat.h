@@ -456,6 +456,52 @@ namespace TwoPaCo
 		// path is empty); when the TSV cannot be written the PHYLIP file is removed again before the error is thrown.
 		void WriteDistanceFiles(size_t k, const ColorMap & map, uint64_t rows, const DistanceTable & distances, const std::string & path, const std::string & phylipPath);
 
+		// ---------------------------------------------------------------------------------------- the connected components
+		// Which pieces of the graph hang together (include/twopaco_hip.h, the tpc_segments_components_* group, states the definition
+		// in the same words).  ROW: a segment, the rows are the colour table's.  JOINED: the rows of `from` and `to` of a link row
+		// are joined; strands do not matter, a self-loop and a link that is its own reverse join a row to itself, 'N'-named segments
+		// are segments like any other.  COMPONENT: a class of the transitive closure of JOINED; a segment that no link touches is a
+		// component of one; its ROOT is its smallest row.  COMPONENT ID: components are numbered from 0, ascending by root, the
+		// order in which gfa1 first prints a segment of each.  Per component: root, segments, links (the link rows whose ends lie in
+		// it; every link row lies in exactly one), length (the sum of its segments' lengths in bases), edges (the sum of their
+		// weights, end - begin of the row's first event: length - k per segment), occurrences (the sum of the colour rows'
+		// occurrences), presence (the OR of the colour rows' presence words) and n_colors, its popcount.  The sums are 64-bit.
+		// Every input sequence with an event lies in exactly one component, because consecutive segments of a sequence are linked:
+		// with one colour per sequence, presence says which contigs make up a component.  The segments of all components sum to
+		// the rows, their links to the link rows.  The arrays come from ComputeComponents below -- the serial statement -- or from
+		// the device (csrc/tpc_components.hip); WriteComponents and WriteComponentMembers print either as the same bytes.
+		struct ComponentTable
+		{
+			std::vector<uint32_t> component;                                   // [rows]
+			std::vector<uint32_t> root;                                        // [components]
+			std::vector<uint64_t> segments, links, length, edges, occurrences; // [components]
+			std::vector<uint32_t> presence;                                    // [components][colors.Words()]
+			size_t Rows() const { return root.size(); }
+			uint64_t Largest() const { return segments.empty() ? 0 : *std::max_element(segments.begin(), segments.end()); }
+		};
+
+		// The definition stated with std:: containers: the row of every segment by a hash map from |name|, a plain union-find over
+		// the link rows, the ids by one pass over the rows, then the sums.  The table must be one whose walk did not fail, `links`
+		// its link rows and `colors` its colour table.
+		void ComputeComponents(const EventTable & table, size_t k, const LinkTable & links, const ColorTable & colors, ComponentTable & out);
+
+		// The TSV text: "#twopaco-components\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tlinks=<N>\tcomponents=<P>", the
+		// colour table's "#color" lines, "#size\t<b>\t<components>\t<segments>" for every b = floor(log2(segments[p])) that occurs,
+		// ascending, then one line per component: id, the name of the root segment, segments, links, length, edges, occurrences,
+		// n_colors and presence as hex (as the colour table prints it).  To stdout (path empty) or into the file `path` (removed again
+		// when writing fails).
+		void WriteComponents(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & components,
+			const std::string & path);
+
+		// The members: "#twopaco-component-members\t1\tk=<k>\tsegments=<S>\tcomponents=<P>", then "<name>\t<id>" per row in row order,
+		// into the file `path`.
+		void WriteComponentMembers(const EventTable & table, size_t k, const ColorTable & colors, const ComponentTable & components, const std::string & path);
+
+		// Both files of the component table, or neither: the members first when membersPath is given, then the TSV (to stdout when
+		// path is empty); when the TSV cannot be written the members file is removed again before the error is thrown.
+		void WriteComponentFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & components,
+			const std::string & path, const std::string & membersPath);
+
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
 		// the table carries linkFirst.
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

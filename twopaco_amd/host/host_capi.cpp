@@ -247,6 +247,26 @@ extern "C"
 		});
 	}
 
+	// the same as tpch_create_enumerator_distances with --components instead (EnumeratorOptions::componentsBy, componentsFile,
+	// componentsMembersFile): componentsBy file | sequence into componentsFile, membersFile NULL or empty: no members file
+	void * tpch_create_enumerator_components(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
+		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
+		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile,
+		const char * linksFile, int graphCompact, const char * componentsBy, const char * componentsFile, const char * membersFile, char ** log)
+	{
+		return Create(files, nfiles, k, filterBits, q, rounds, threads, abundance, tmpDir, outFile, pinned, seed, device, log, [&](TwoPaCo::EnumeratorOptions & opt)
+		{
+			opt.insertTestFirst = testFirst != 0;
+			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
+			SetColors(opt, colorsBy, colorsFile);
+			SetLinks(opt, linksFile, graphCompact);
+			opt.componentsBy = componentsBy ? componentsBy : "";
+			opt.componentsFile = componentsFile ? componentsFile : "";
+			opt.componentsMembersFile = membersFile ? membersFile : "";
+			if (opt.componentsBy.empty() || opt.componentsFile.empty()) throw std::runtime_error("The component table needs its colours, one of file, sequence, and a file name");
+		});
+	}
+
 	// The text of the compacted graph from an EVENT TABLE (include/twopaco_hip.h: name / first bits / begin / end per event,
 	// seq_event_begin[0 .. n_seq] per sequence) and the FASTA files, into out_path: graphformat.h without any device.  format
 	// gfa1 | gfa2 | fasta, prefix = graphdump's --prefix.  0, or nonzero with tpch_last_error.

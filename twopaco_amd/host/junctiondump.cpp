@@ -5,7 +5,8 @@
 //   graphdump <infile> -f seq|group|dot|gfa1|gfa2|fasta -k <k> [-s <fasta>]... [--prefix] [--gpu [<device>]] [--threads <n>] [--text host|device]
 //             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]
 //             |  --bubbles file|sequence [--bubbles-out <path>]
-//             |  --distances file|sequence [--distances-out <path>] [--distances-phylip <path>]   (the last four instead of -f)
+//             |  --distances file|sequence [--distances-out <path>] [--distances-phylip <path>]
+//             |  --components file|sequence [--components-out <path>] [--components-members <path>]   (the last five instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -55,6 +56,13 @@
 // as TSV of integers (graphformat.h: WriteDistances) and, asked for, as a PHYLIP square matrix of Jaccard distances over edges.
 // Without --gpu the serial walk, then ComputeColors and ComputeDistances; with --gpu the colour stage and the distance stage over one
 // segment build (csrc/tpc_distances.hip); the bytes are the same.  A stream the walk refuses prints the walk's error and nothing else.
+// --components file|sequence [--components-out <path>] [--components-members <path>] (an addition; instead of -f): the connected
+// components of the graph -- which segments hang together, a segment that no link touches being a component of one;
+// include/twopaco_hip.h defines them -- as TSV of integers with every component's segments, links, bases, edges, occurrences and
+// colours (graphformat.h: WriteComponents) and, asked for, the component of every segment (WriteComponentMembers).  Without --gpu the
+// serial walk, then ComputeColors, ComputeLinks and ComputeComponents; with --gpu the colour stage, the link stage and the component
+// stage over one segment build (csrc/tpc_components.hip); the bytes are the same.  Beside --colors, --bubbles or --distances of the
+// same colours it is written after them.  A stream the walk refuses prints the walk's error and nothing else.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -451,6 +459,37 @@ namespace
 		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
 	}
 
+	// --components beside another table of the same colours, or alone: the file names of the component table (out empty: stdout)
+	struct ComponentsWanted
+	{
+		bool on;
+		std::string out, members;
+		ComponentsWanted() : on(false) {}
+	};
+
+	// --components, serial, alone or beside --colors / --bubbles / --distances of the same colours: one walk, the serial statements one
+	// after the other, then the tables in the order colours or bubbles, distances, components
+	void DumpComponents(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const ComponentsWanted & want,
+		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo)
+	{
+		SerialTable t;
+		WalkLinks(binFile, fasta, k, prefix, false, t);
+		ColorMap map;
+		MakeColorMap(t.seq, fasta, bySequence, map);
+		ColorTable colors;
+		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
+		BubbleTable bubbles;
+		if (bubblesToo) ComputeBubbles(t.table, t.links, bubbles);
+		DistanceTable distances;
+		if (distancesToo) ComputeDistances(t.table, colors, distances);
+		ComponentTable components;
+		ComputeComponents(t.table, k, t.links, colors, components);
+		if (colorsToo) WriteColors(t.table, k, map, colors, firstOut);
+		if (bubblesToo) WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, firstOut);
+		if (distancesToo) WriteDistanceFiles(k, map, colors.Rows(), distances, distancesTo.out, distancesTo.phylip);
+		WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
+	}
+
 	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
 	void DumpDistances(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
 		const std::string & phylipPath)
@@ -482,12 +521,12 @@ namespace
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
-		uint64_t links, linkOccurrences, bubbles;
-		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs;
+		uint64_t links, linkOccurrences, bubbles, components, largestComponent;
+		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
-			threads(1) {}
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
+			componentsKernelMs(0), componentsMs(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -500,10 +539,12 @@ namespace
 				"\"pack_ms\": %.3f, \"index_ms\": %.3f, \"format_ms\": %.3f, \"threads\": %llu, \"device_bytes\": %llu, \"stream_bytes\": %llu, \"text_bytes\": %llu, "
 				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f, "
 				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu, "
-				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f, "
+				"\"components_kernel_ms\": %.3f, \"components_ms\": %.3f, \"components\": %llu, \"largest_component\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
-				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs);
+				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs,
+				(unsigned long long)components, (unsigned long long)largestComponent);
 			std::fclose(f);
 		}
 	};
@@ -643,29 +684,30 @@ namespace
 		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] %s on device: %.3f ms (kernels %.3f ms)\n", what, ms, kernelMs);
 	}
 
-	// The link table of the table on the device (csrc/tpc_links.hip), fetched: the rows, or else the first bits.
-	void LinksOnDevice(DeviceLibrary & lib, uint64_t events, bool rows, LinkTable & links, DumpStats & stats)
+	// The link table of the table on the device (csrc/tpc_links.hip), fetched: the rows, the first bits, or the number of rows alone.
+	void LinksOnDevice(DeviceLibrary & lib, uint64_t events, bool rows, bool bits, LinkTable & links, DumpStats & stats)
 	{
 		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 		BuildLinks(lib);
 		stats.linksKernelMs = lib.kernel_ms(lib.ctx, TPC_K_LINKS);
-		stats.links = FetchLinks(lib, events, rows, !rows, links);
+		stats.links = FetchLinks(lib, events, rows, bits, links);
 		stats.linkOccurrences = links.occurrences;
 		stats.linksMs = MsSince(t0);
 		TimingLine("link table", stats.linksMs, stats.linksKernelMs);
 	}
 
-	// What a --gpu run instead of -f writes: one of the colour, link and bubble tables into `out`, and / or the distance table
-	// (alone, or beside the colour or the bubble table of the same colours, written after it).
+	// What a --gpu run instead of -f writes: one of the colour, link and bubble tables into `out`, and / or the distance table and the
+	// component table (alone, or beside the colour or the bubble table of the same colours, written after it).
 	struct TablesWanted
 	{
-		bool colors, links, bubbles, distances, bySequence;
-		std::string out, distancesOut, distancesPhylip;
+		bool colors, links, bubbles, distances, components, bySequence;
+		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers;
 	};
 
 	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
 	// wanted run there in this order: colours (csrc/tpc_colors.hip), distances over their presence bits (csrc/tpc_distances.hip), links
-	// (csrc/tpc_links.hip), bubbles over the link rows (csrc/tpc_bubbles.hip).  Fetched is what the files print and no more: the event
+	// (csrc/tpc_links.hip), bubbles over the link rows (csrc/tpc_bubbles.hip), components over the link rows and the colour rows
+	// (csrc/tpc_components.hip).  Fetched is what the files print and no more: the event
 	// table for the names and lengths of any rows; --distances alone fetches the two matrices, neither colour rows nor event table.
 	void DumpTablesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
 		const InputSequences & seq, const LoadedSequences & loaded, const TablesWanted & want, DumpStats & stats)
@@ -676,14 +718,14 @@ namespace
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		ColorMap map;
 		ColorTable colors;
-		if (want.colors || want.bubbles || want.distances)
+		if (want.colors || want.bubbles || want.distances || want.components)
 		{
 			MakeColorMap(seq, fasta, want.bySequence, map);
 			if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
 			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
 			BuildColors(lib, map);
 			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
-			if (want.colors || want.bubbles) FetchColors(lib, map, counts[1], colors);
+			if (want.colors || want.bubbles || want.components) FetchColors(lib, map, counts[1], colors);
 			stats.colorsMs = MsSince(c0);
 		}
 
@@ -699,7 +741,7 @@ namespace
 		}
 
 		LinkTable links;
-		if (want.links || want.bubbles) LinksOnDevice(lib, counts[0], true, links, stats);
+		if (want.links || want.bubbles || want.components) LinksOnDevice(lib, counts[0], want.links || want.bubbles, false, links, stats);
 		BubbleTable bubbles;
 		if (want.bubbles)
 		{
@@ -712,14 +754,28 @@ namespace
 			TimingLine("bubble table", stats.bubblesMs, stats.bubblesKernelMs);
 		}
 
+		ComponentTable components;
+		if (want.components)
+		{
+			const std::chrono::steady_clock::time_point p0 = std::chrono::steady_clock::now();
+			BuildComponents(lib);
+			stats.componentsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COMPONENTS);
+			if (!FetchComponents(lib, counts[1], colors.Words(), components)) throw std::runtime_error("--gpu: the component stage and the segment table disagree about the segments");
+			stats.components = components.Rows();
+			stats.largestComponent = components.Largest();
+			stats.componentsMs = MsSince(p0);
+			TimingLine("component table", stats.componentsMs, stats.componentsKernelMs);
+		}
+
 		Events held(counts[0], sequences);
-		if (want.colors || want.links || want.bubbles) FetchTable(lib, held);
+		if (want.colors || want.links || want.bubbles || want.components) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
 		if (want.links) WriteLinks(held.table, k, counts[1], links, want.out);
 		if (want.bubbles) WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, want.out);
 		if (want.distances) WriteDistanceFiles(k, map, counts[1], distances, want.distancesOut, want.distancesPhylip);
+		if (want.components) WriteComponentFiles(held.table, k, map, colors, stats.links, components, want.componentsOut, want.componentsMembers);
 		stats.formatMs = MsSince(t0);
 		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
 	}
@@ -768,7 +824,7 @@ namespace
 		LinkTable links;
 		if (compact)
 		{
-			LinksOnDevice(lib, counts[0], false, links, stats);
+			LinksOnDevice(lib, counts[0], false, true, links, stats);
 			table.linkFirst = links.linkFirst.data();
 		}
 
@@ -797,7 +853,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -836,6 +892,14 @@ namespace
 			"     same colours (one walk and one colour table for both; that table is written first, this one after it); not with --links, --compact or --text.\n\n"
 			"   --distances-out <file name>\n     with --distances: write the table there instead of to the standard output\n\n"
 			"   --distances-phylip <file name>\n     with --distances: also write the Jaccard distances over edges as a relaxed PHYLIP square matrix there\n\n"
+			"   --components <file|sequence>\n     instead of -f: the connected components of the graph as TSV of integers -- which segments hang together, a segment\n"
+			"     that no link touches being a component of one.  Per component, numbered in the order gfa1 first prints a segment of\n"
+			"     each: the name of its first segment, its segments, links, bases, edges ((k+1)-mers), occurrences, number of colours\n"
+			"     and presence bits of --colors; in front the colours and the components by floor(log2(segments)).  Needs -k and -s.\n"
+			"     With --gpu the components are found on the device.  Goes with --colors, --bubbles or --distances of the same colours\n"
+			"     (one walk for all; this table is written last); not with --links, --compact or --text.\n\n"
+			"   --components-out <file name>\n     with --components: write the table there instead of to the standard output\n\n"
+			"   --components-members <file name>\n     with --components: also write the component of every segment there, one line per segment\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -845,9 +909,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false;
+		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -914,6 +978,13 @@ int main(int argc, char * argv[])
 			}
 			else if (a == "--distances-out") { distancesOut = value("(--distances-out)"); distancesOutSet = true; }
 			else if (a == "--distances-phylip") { distancesPhylip = value("(--distances-phylip)"); distancesPhylipSet = true; }
+			else if (a == "--components")
+			{
+				componentsBy = value("(--components)");
+				if (componentsBy != "file" && componentsBy != "sequence") throw ArgError("Value '" + componentsBy + "' does not meet constraint: file|sequence", "Argument: (--components)");
+			}
+			else if (a == "--components-out") { componentsOut = value("(--components-out)"); componentsOutSet = true; }
+			else if (a == "--components-members") { componentsMembers = value("(--components-members)"); componentsMembersSet = true; }
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -934,7 +1005,17 @@ int main(int argc, char * argv[])
 			else throw ArgError("Couldn't find match for argument", "(" + a + ")");
 		}
 
-		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty();
+		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty(), components = !componentsBy.empty();
+		if (components && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--components)");
+		if (components && colors && colorsBy != componentsBy) throw ArgError("The component table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --components " + componentsBy, "(--components)");
+		if (components && bubbles && bubblesBy != componentsBy) throw ArgError("The component table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --components " + componentsBy, "(--components)");
+		if (components && distances && distancesBy != componentsBy) throw ArgError("The component table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --components " + componentsBy, "(--components)");
+		if (components && links) throw ArgError("The component table and the link table are written one at a time: not with --links", "(--components)");
+		if (components && compact) throw ArgError("The component table and the compact text are written one at a time: not with --compact", "(--components)");
+		if (components && textSet) throw ArgError("The component table is formatted by the host: not with --components", "(--text)");
+		if (componentsOutSet && !components) throw ArgError("This argument needs --components <file|sequence>", "(--components-out)");
+		if (componentsMembersSet && !components) throw ArgError("This argument needs --components <file|sequence>", "(--components-members)");
+		if (componentsMembersSet && componentsMembers.empty()) throw ArgError("The component members need a file name", "(--components-members)");
 		if (distances && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--distances)");
 		// one set of colours per run: the modes are compared before anything else is said about the combination
 		if (distances && colors && colorsBy != distancesBy) throw ArgError("The distance table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --distances " + distancesBy, "(--distances)");
@@ -961,10 +1042,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles && !distances) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles && !distances && !components) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || distances || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || distances || components || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -980,7 +1061,7 @@ int main(int argc, char * argv[])
 		also.on = distances && (colors || bubbles);
 		also.out = distancesOut;
 		also.phylip = distancesPhylip;
-		if ((colors || links || bubbles || distances) && lib)
+		if ((colors || links || bubbles || distances || components) && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
@@ -992,11 +1073,22 @@ int main(int argc, char * argv[])
 			want.links = links;
 			want.bubbles = bubbles;
 			want.distances = distances;
-			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distancesBy) == "sequence";
+			want.components = components;
+			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : componentsBy) == "sequence";
+			want.componentsOut = componentsOut;
+			want.componentsMembers = componentsMembers;
 			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
 			want.distancesOut = distancesOut;
 			want.distancesPhylip = distancesPhylip;
 			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
+		}
+		else if (components)
+		{
+			ComponentsWanted wanted;
+			wanted.on = true;
+			wanted.out = componentsOut;
+			wanted.members = componentsMembers;
+			DumpComponents(binFile, fasta, k, prefix, componentsBy == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);

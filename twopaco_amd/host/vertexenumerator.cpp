@@ -357,6 +357,13 @@ namespace TwoPaCo
 				if (distances && bubbles && options.distancesBy != options.bubblesBy) throw std::runtime_error("The distance table and the bubble table share one set of colours: both by file or both by sequence");
 				if (distances && sharded) throw std::runtime_error("The distance table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				if (!distances && !options.distancesPhylipFile.empty()) throw std::runtime_error("The PHYLIP matrix is written with the distance table only");
+				const bool components = !options.componentsFile.empty();
+				if (components && options.componentsBy != "file" && options.componentsBy != "sequence") throw std::runtime_error("The component table's colours must be one of file, sequence");
+				if (components && colors && options.componentsBy != options.colorsBy) throw std::runtime_error("The component table and the colour table share one set of colours: both by file or both by sequence");
+				if (components && bubbles && options.componentsBy != options.bubblesBy) throw std::runtime_error("The component table and the bubble table share one set of colours: both by file or both by sequence");
+				if (components && distances && options.componentsBy != options.distancesBy) throw std::runtime_error("The component table and the distance table share one set of colours: both by file or both by sequence");
+				if (components && sharded) throw std::runtime_error("The component table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (!components && !options.componentsMembersFile.empty()) throw std::runtime_error("The component members are written with the component table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -491,7 +498,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles || distances)
+				if (graph || colors || links || bubbles || distances || components)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -989,7 +996,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles || distances) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles || distances || components) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -1004,12 +1011,16 @@ namespace TwoPaCo
 			// --distances: the colour build of the same table, then the distance stage (csrc/tpc_distances.hip) over the presence bits
 			// where they lie; options.distancesFile and the PHYLIP file are written last of all, both or neither (WriteDistanceFiles), so that
 			// a step that throws leaves no file of theirs.
+			// --components: the colour build and the link build of the same table, then the component stage (csrc/tpc_components.hip) over
+			// the link rows and the colour rows where they lie; options.componentsFile and the members file are written after the
+			// distance files, both or neither (WriteComponentFiles).
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
-				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), colorRows = colors || bubbles || distances;
-				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : options.distancesBy) == "sequence";
+				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), components = !options.componentsFile.empty();
+				const bool colorRows = colors || bubbles || distances || components;
+				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : options.componentsBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1026,6 +1037,7 @@ namespace TwoPaCo
 				GraphFormat::LinkTable linkTable;
 				GraphFormat::BubbleTable bubbleTable;
 				GraphFormat::DistanceTable distanceTable;
+				GraphFormat::ComponentTable componentTable;
 				uint64_t segments = 0, linkRows = 0;
 				DeviceGraph::Events held(0, sequences);
 				const std::vector<uint32_t> noBits(1, 0);
@@ -1040,9 +1052,10 @@ namespace TwoPaCo
 						GraphFormat::ComputeColors(held.table, k, map.colorOfSequence, map.label.size(), colorTable);
 					}
 
-					if (links || bubbles) GraphFormat::ComputeLinks(held.table, linkTable);
+					if (links || bubbles || components) GraphFormat::ComputeLinks(held.table, linkTable);
 					if (bubbles) GraphFormat::ComputeBubbles(held.table, linkTable, bubbleTable);
 					if (distances) GraphFormat::ComputeDistances(held.table, colorTable, distanceTable);
+					if (components) GraphFormat::ComputeComponents(held.table, k, linkTable, colorTable, componentTable);
 				}
 				else
 				{
@@ -1104,9 +1117,9 @@ namespace TwoPaCo
 					}
 
 					if ((links || compact) && !fetched && !onDevice) fetchTable();
-					if (links || compact || bubbles)
+					if (links || compact || bubbles || components)
 					{
-						// --links / the compact graph / --bubbles: the distinct links found on the device (csrc/tpc_links.hip), before the graph
+						// --links / the compact graph / --bubbles / --components: the distinct links found on the device (csrc/tpc_links.hip), before the graph
 						// is written (the compact text needs their first bits); the rows' names come from name[]
 						DeviceGraph::BuildLinks(api);
 						timer.Lap("segment links");
@@ -1139,6 +1152,20 @@ namespace TwoPaCo
 						}
 
 						timer.Lap("segment distances fetch");
+					}
+
+					if (components)
+					{
+						// over the link rows and the colour rows where they lie (csrc/tpc_components.hip); the roots' names are --colors'
+						DeviceGraph::BuildComponents(api);
+						timer.Lap("segment components");
+						kernelLine("components_kernel_ms", TPC_K_COMPONENTS);
+						if (!DeviceGraph::FetchComponents(api, segments, colorTable.Words(), componentTable))
+						{
+							throw std::runtime_error("The component stage and the segment table disagree about the segments");
+						}
+
+						timer.Lap("segment components fetch");
 					}
 
 					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
@@ -1179,6 +1206,12 @@ namespace TwoPaCo
 				{
 					GraphFormat::WriteDistanceFiles(k, map, segments, distanceTable, options.distancesFile, options.distancesPhylipFile);
 					timer.Lap("distance table writing");
+				}
+
+				if (components)
+				{
+					GraphFormat::WriteComponentFiles(held.table, k, map, colorTable, linkRows, componentTable, options.componentsFile, options.componentsMembersFile);
+					timer.Lap("component table writing");
 				}
 			}
 

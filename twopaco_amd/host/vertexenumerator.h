@@ -96,6 +96,14 @@ namespace TwoPaCo
 		std::string distancesBy;
 		std::string distancesFile;
 		std::string distancesPhylipFile;
+		// The connected components of the graph (graphformat.h: WriteComponents; `graphdump --components` writes the same bytes for the
+		// junction stream of this run): componentsFile (empty: off), componentsBy = "file" | "sequence" -- the same as colorsBy,
+		// bubblesBy and distancesBy when those are given -- and componentsMembersFile (empty: off) for the component of every segment.
+		// Found on the device (tpc_segments_components_build) over the link build and the colour build of the same segment table.
+		// One GPU.
+		std::string componentsBy;
+		std::string componentsFile;
+		std::string componentsMembersFile;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
