@@ -64,7 +64,8 @@ enum {
     TPC_K_BUBBLES = 20,     /* tpc_segments_bubbles_build: arcs, degrees, the simple bubbles and the degree histogram (no counterpart in the reference) */
     TPC_K_DISTANCES = 21,   /* tpc_segments_distances_build: bit columns, weight planes and the two colour x colour matrices (no counterpart in the reference) */
     TPC_K_COMPONENTS = 22,  /* tpc_segments_components_build: the union-find over the link rows, the numbering and the per-component sums (no counterpart in the reference) */
-    TPC_K_COUNT = 23
+    TPC_K_SUPERBUBBLES = 23, /* tpc_segments_superbubbles_build: the adjacency lists, the bounded search per entrance and the report (no counterpart in the reference) */
+    TPC_K_COUNT = 24
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -710,6 +711,65 @@ int tpc_segments_components_fetch_members(tpc_ctx *ctx, uint64_t r0, uint64_t n,
 int tpc_segments_components_fetch_rows(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *root_host, uint64_t *segments_host, uint64_t *links_host,
                                        uint64_t *length_host, uint64_t *edges_host, uint64_t *occurrences_host);
 int tpc_segments_components_fetch_presence(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *words_host /* [n x W] */);
+
+/* The SUPERBUBBLES of the compacted graph (csrc/tpc_superbubbles.hip), after Onodera, Sadakane and Shibuya 2013 and bounded to 64
+ * sides: where the genomes differ, beyond the two-allele case of the simple bubbles above.  No counterpart in the reference.  The
+ * definition, over the link table of the last tpc_segments_links_build and the colour table of the last tpc_segments_colors_build,
+ * both over one segment table:
+ *   ROW, SIDE, ARC   as of the tpc_segments_bubbles_* group: code = row * 2 + minus, rev(code) = code ^ 1, a link row gives the arcs
+ *                    from -> to and rev(to) -> rev(from), out(u) is the set of heads of the arcs that leave u, deg(u) its size.
+ *                    in(v) = { rev(w) : w in out(rev(v)) }.
+ *   U(s, t)          for sides s != t, the set of sides reachable from s along arcs without leaving t: s and t are included, a path
+ *                    may end at t but not continue through it.
+ *   SUPERBUBBLE      (s, t) with ENTRANCE s, EXIT t and INSIDE U \ {s, t} when all of the following hold:
+ *                    1. deg(s) >= 2 and t is in U.
+ *                    2. MATCHING.  U equals the set of sides from which t is reachable along arcs without entering s.  Equivalently, where 3 holds:
+ *                       every side of U other than t has all its out-neighbours in U and at least one; every side of U other than s has
+ *                       all its in-neighbours in U.
+ *                    3. ACYCLIC.  The arcs with both ends in U form no cycle.  This includes no arc t -> s and no self-loop.
+ *                    4. ONE STRAND PER SEGMENT.  No two sides of U have the same row.  This excludes hairpins and inversions read as
+ *                       bubbles, as the "four different rows" of the simple bubbles does.
+ *                    5. MINIMAL.  No side t' of the inside makes (s, t') satisfy 1-4.
+ *                    6. BOUNDED.  |inside| <= max_inside, a parameter with default 62 and allowed range 2 .. 62, so a superbubble is at
+ *                       most 64 sides and one 64-bit mask covers it.
+ *                    A side is the entrance of at most one superbubble; exit(s) is that superbubble's exit, or none.  Nested
+ *                    superbubbles are each reported at their own entrance.
+ *   REPORTED         (s, t) when exit(s) = t and either code(s) < code(rev(t)) or exit(rev(t)) != rev(s): a structure found from both
+ *                    ends appears once, under the smaller entrance; one found from one end only still appears.  Rows ascend by
+ *                    entrance code.
+ *   PER ROW          entrance, exit; inside, the number of sides of the inside; arcs, the arcs with both ends in U; paths, the distinct
+ *                    arc paths from s to t (64 bits: at most 2^60 are possible); min_edges and max_edges, the smallest and largest sum
+ *                    over an s-t path of the weights of its inside segments, the weight being that of the distance matrices and the
+ *                    components, length - k (64 bits; an indel shows as min != max); presence, the OR of the inside rows' colour
+ *                    words, and n_colors, its popcount; its MEMBERS, the inside sides in ascending code.
+ *   EXACT            integers with commutative or order-free results: the arrays do not depend on the schedule.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this, and the segment, colour, link, bubble,
+ * distance and component outputs are what they were, in any order of the builds.
+ *   tpc_segments_superbubbles_build            the adjacency lists (CSR over sides, every list ascending), one bounded search per side of
+ *                                              degree 2 or more, the reporting rule, and one more walk per reported row for its
+ *                                              numbers.  Refused with an error text: no segment table, a table whose tpc_segments_error
+ *                                              kind is not TPC_SEG_OK, no link table, no colour table, max_inside outside 2 .. 62, 2^31
+ *                                              segments or more, 2^31 links or more, buffers beyond the free device memory; the context
+ *                                              stays usable.  Kept until the next segment, link, colour or superbubble build.
+ *                                              TPC_K_SUPERBUBBLES times the stage on the stream from its first kernel to its last, the
+ *                                              host's one wait for the row and member counts included.
+ *   tpc_segments_superbubbles_info             info[0] superbubbles, [1] sides, [2] members in total, [3] entrances without a mirror
+ *                                              (exit(s) = t but exit(rev(t)) != rev(s)), [4] the stage's device bytes at their peak,
+ *                                              [5] arcs, [6] max_inside of the build
+ *   tpc_segments_superbubbles_fetch_adjacency  the CSR offsets [sides + 1] and the heads [arcs]
+ *   tpc_segments_superbubbles_fetch_exits      exit[] of sides [c0, c0 + n), all ones standing for none
+ *   tpc_segments_superbubbles_fetch_rows       the planes of rows [b0, b0 + n)
+ *   tpc_segments_superbubbles_fetch_members    the member offsets [superbubbles + 1] and the member sides [members]
+ *   tpc_segments_superbubbles_fetch_presence   the n x W presence words of rows [b0, b0 + n), row-major
+ * A range outside a table is refused with an error text. */
+int tpc_segments_superbubbles_build(tpc_ctx *ctx, uint32_t max_inside);
+int tpc_segments_superbubbles_info(tpc_ctx *ctx, uint64_t *info /* [7] */);
+int tpc_segments_superbubbles_fetch_adjacency(tpc_ctx *ctx, uint32_t *offsets_host /* [sides + 1] */, uint32_t *heads_host /* [arcs] */);
+int tpc_segments_superbubbles_fetch_exits(tpc_ctx *ctx, uint64_t c0, uint64_t n, uint32_t *exit_host);
+int tpc_segments_superbubbles_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *entrance_host, uint32_t *exit_host, uint32_t *inside_host, uint32_t *arcs_host,
+                                         uint32_t *n_colors_host, uint64_t *paths_host, uint64_t *min_edges_host, uint64_t *max_edges_host);
+int tpc_segments_superbubbles_fetch_members(tpc_ctx *ctx, uint32_t *offsets_host /* [superbubbles + 1] */, uint32_t *sides_host /* [members] */);
+int tpc_segments_superbubbles_fetch_presence(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *words_host /* [n x W] */);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22}
+           "distances": 21, "components": 22, "superbubbles": 23}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -37,7 +37,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_bubbles_build", "tpc_segments_bubbles_info", "tpc_segments_bubbles_fetch_rows", "tpc_segments_bubbles_fetch_sides", "tpc_segments_bubbles_fetch_hist",
                "tpc_segments_distances_build", "tpc_segments_distances_info", "tpc_segments_distances_fetch",
                "tpc_segments_components_build", "tpc_segments_components_info", "tpc_segments_components_fetch_members", "tpc_segments_components_fetch_rows",
-               "tpc_segments_components_fetch_presence"]
+               "tpc_segments_components_fetch_presence",
+               "tpc_segments_superbubbles_build", "tpc_segments_superbubbles_info", "tpc_segments_superbubbles_fetch_adjacency", "tpc_segments_superbubbles_fetch_exits",
+               "tpc_segments_superbubbles_fetch_rows", "tpc_segments_superbubbles_fetch_members", "tpc_segments_superbubbles_fetch_presence"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -183,6 +185,13 @@ def hip():
         L.tpc_segments_components_fetch_members.argtypes = [p, u64, u64, p]
         L.tpc_segments_components_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p, p]
         L.tpc_segments_components_fetch_presence.argtypes = [p, u64, u64, p]
+        L.tpc_segments_superbubbles_build.argtypes = [p, ctypes.c_uint32]
+        L.tpc_segments_superbubbles_info.argtypes = [p, p]
+        L.tpc_segments_superbubbles_fetch_adjacency.argtypes = [p, p, p]
+        L.tpc_segments_superbubbles_fetch_exits.argtypes = [p, u64, u64, p]
+        L.tpc_segments_superbubbles_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p, p, p, p]
+        L.tpc_segments_superbubbles_fetch_members.argtypes = [p, p, p]
+        L.tpc_segments_superbubbles_fetch_presence.argtypes = [p, u64, u64, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -770,6 +779,53 @@ class Context:
         n = self.segments_components_info()["components"] - p0 if n is None else n
         out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
         self._ck(hip().tpc_segments_components_fetch_presence(self._h, p0, n, out.ctypes.data))
+        return out
+
+    def segments_superbubbles_build(self, max_inside=62):
+        """The bounded superbubbles (csrc/tpc_superbubbles.hip) over the link table of the last segments_links_build and the colour table
+        of the last segments_colors_build; max_inside 2 .. 62.  Returns segments_superbubbles_info()."""
+        self._ck(hip().tpc_segments_superbubbles_build(self._h, max_inside))
+        return self.segments_superbubbles_info()
+
+    def segments_superbubbles_info(self):
+        """dict: superbubbles, sides, members (in total), unmirrored (entrances whose mirror is missing), peak_bytes, arcs, max_inside."""
+        c = np.zeros(7, dtype=np.uint64)
+        self._ck(hip().tpc_segments_superbubbles_info(self._h, c.ctypes.data))
+        return dict(zip(("superbubbles", "sides", "members", "unmirrored", "peak_bytes", "arcs", "max_inside"), (int(x) for x in c)))
+
+    def segments_superbubbles_fetch_adjacency(self):
+        """(offsets uint32 [sides + 1], heads uint32 [arcs]): the arcs that leave every side, every list ascending."""
+        info = self.segments_superbubbles_info()
+        off, heads = np.zeros(info["sides"] + 1, dtype=np.uint32), np.zeros(info["arcs"], dtype=np.uint32)
+        self._ck(hip().tpc_segments_superbubbles_fetch_adjacency(self._h, off.ctypes.data, heads.ctypes.data))
+        return off, heads
+
+    def segments_superbubbles_fetch_exits(self, c0=0, n=None):
+        """exit[] of sides [c0, c0 + n) as uint32, all ones for none; n = None: to the last side."""
+        n = self.segments_superbubbles_info()["sides"] - c0 if n is None else n
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_superbubbles_fetch_exits(self._h, c0, n, out.ctypes.data))
+        return out
+
+    def segments_superbubbles_fetch_rows(self, b0=0, n=None):
+        """(entrance, exit, inside, arcs, n_colors as uint32; paths, min_edges, max_edges as uint64) of rows [b0, b0 + n); n = None: to the last."""
+        n = self.segments_superbubbles_info()["superbubbles"] - b0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(5)] + [np.zeros(max(n, 0), dtype=np.uint64) for _ in range(3)]
+        self._ck(hip().tpc_segments_superbubbles_fetch_rows(self._h, b0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_superbubbles_fetch_members(self):
+        """(offsets uint32 [superbubbles + 1], sides uint32 [members]): the inside sides of every row, ascending."""
+        info = self.segments_superbubbles_info()
+        off, sides = np.zeros(info["superbubbles"] + 1, dtype=np.uint32), np.zeros(info["members"], dtype=np.uint32)
+        self._ck(hip().tpc_segments_superbubbles_fetch_members(self._h, off.ctypes.data, sides.ctypes.data))
+        return off, sides
+
+    def segments_superbubbles_fetch_presence(self, b0=0, n=None):
+        """uint32 [n, W] presence words of rows [b0, b0 + n), W as of the colour table; n = None: to the last."""
+        n = self.segments_superbubbles_info()["superbubbles"] - b0 if n is None else n
+        out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
+        self._ck(hip().tpc_segments_superbubbles_fetch_presence(self._h, b0, n, out.ctypes.data))
         return out
 
     def filter_words(self):

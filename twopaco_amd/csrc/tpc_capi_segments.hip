@@ -27,6 +27,7 @@ void text_plan_drop(tpc_ctx *c)
 //   segments <- colours <- distances        (the matrices were summed over the colour table)
 //   segments <- links   <- bubbles          (the bubbles were found over the link table)
 //   colours, links      <- components       (joined by the link rows, summed over the colour rows)
+//   colours, links      <- superbubbles     (searched over the link rows' arcs, presence ORed over the colour rows)
 //   segments <- the graph text's plan
 void free_all(std::initializer_list<const void *> ps) { for (const void *p : ps) if (p) (void)hipFree(const_cast<void *>(p)); }
 
@@ -36,9 +37,14 @@ namespace tpch {
 
 void distances_drop(tpc_ctx *c) { free_all({c->dst.mat}); c->dst = {}; }
 void components_drop(tpc_ctx *c) { free_all({c->cmp.component, c->cmp.root, c->cmp.sums, c->cmp.presence}); c->cmp = {}; }
+void superbubbles_drop(tpc_ctx *c)
+{
+    free_all({c->sbb.off, c->sbb.heads, c->sbb.exit_of, c->sbb.u32, c->sbb.u64, c->sbb.presence, c->sbb.member_off, c->sbb.members});
+    c->sbb = {};
+}
 void bubbles_drop(tpc_ctx *c) { free_all({c->bub.rows, c->bub.sides, c->bub.hist}); c->bub = {}; }
-void colors_drop(tpc_ctx *c) { distances_drop(c); components_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
-void links_drop(tpc_ctx *c) { bubbles_drop(c); components_drop(c); free_all({c->lnk.rows, c->lnk.first}); c->lnk = {}; }
+void colors_drop(tpc_ctx *c) { distances_drop(c); components_drop(c); superbubbles_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
+void links_drop(tpc_ctx *c) { bubbles_drop(c); components_drop(c); superbubbles_drop(c); free_all({c->lnk.rows, c->lnk.first}); c->lnk = {}; }
 
 }  // namespace tpch
 

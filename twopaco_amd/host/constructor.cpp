@@ -34,7 +34,12 @@
 // segments hang together -- as TSV of integers, byte for byte what `graphdump --components` writes, and asked for, the component of
 // every segment (csrc/tpc_components.hip finds them on the device over the link build and the colour build; combines with everything
 // above from one segment, colour and link build; --colors, --bubbles and --distances must name the same colours; its files are
-// written after the distance files).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// written after the distance files);
+// --superbubbles file|sequence [--superbubbles-out F] [--superbubbles-members F] [--superbubbles-max N]: the superbubbles of the same
+// graph, bounded to N sides inside (2 .. 62, default 62) -- where the genomes differ beyond two alleles -- as TSV of integers, byte
+// for byte what `graphdump --superbubbles` writes, and asked for, the inside sides of every row (csrc/tpc_superbubbles.hip finds them
+// on the device over the link build and the colour build; combines with everything above from one segment, colour and link build;
+// the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -94,6 +99,7 @@ namespace
 			<< "               [--bubbles <file|sequence>] [--bubbles-out <file name>]" << std::endl
 			<< "               [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>]" << std::endl
 			<< "               [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>]" << std::endl
+			<< "               [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -128,7 +134,14 @@ namespace
 			<< "               Per component the name of its first segment, its segments, links, bases, edges, occurrences and colours (by file" << std::endl
 			<< "               or by sequence, as --colors).  --components-members: also the component of every segment, one line per segment." << std::endl
 			<< "               Combines with --graph, --graph-compact, --colors, --bubbles and --distances (the same colours), --links and -o." << std::endl
-			<< "               One GPU only." << std::endl;
+			<< "               One GPU only." << std::endl
+			<< "       --superbubbles: also write the superbubbles of the graph as TSV to --superbubbles-out (default" << std::endl
+			<< "               de_bruijn.superbubbles.tsv): where the paths that leave one side of a segment meet again at one side of another" << std::endl
+			<< "               and touch nothing else -- three alleles, substitutions closer than k, a substitution beside an indel, nested ones." << std::endl
+			<< "               Per row entrance and exit, the sides inside, arcs, paths, the smallest and largest path weight in edges and the" << std::endl
+			<< "               colours over the inside (by file or by sequence, as --colors).  --superbubbles-members: also the inside sides of" << std::endl
+			<< "               every row.  --superbubbles-max: the largest inside reported, 2 .. 62 (default 62).  Combines with --graph," << std::endl
+			<< "               --graph-compact, --colors, --bubbles, --distances and --components (the same colours), --links and -o.  One GPU only." << std::endl;
 	}
 }
 
@@ -169,7 +182,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -270,6 +283,23 @@ int main(int argc, char * argv[])
 			}
 			else if (Match(a, 0, "components-out")) { options.componentsFile = value("(--components-out)"); componentsOutSet = true; }
 			else if (Match(a, 0, "components-members")) { options.componentsMembersFile = value("(--components-members)"); componentsMembersSet = true; }
+			else if (Match(a, 0, "superbubbles"))
+			{
+				options.superbubblesBy = value("(--superbubbles)");
+				if (options.superbubblesBy != "file" && options.superbubblesBy != "sequence") throw ArgError("Value '" + options.superbubblesBy + "' does not meet constraint: file|sequence", "(--superbubbles)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "superbubbles-out")) { options.superbubblesFile = value("(--superbubbles-out)"); superbubblesOutSet = true; }
+			else if (Match(a, 0, "superbubbles-members")) { options.superbubblesMembersFile = value("(--superbubbles-members)"); superbubblesMembersSet = true; }
+			else if (Match(a, 0, "superbubbles-max"))
+			{
+				const std::string v = value("(--superbubbles-max)");
+				char * end = 0;
+				const long n = std::strtol(v.c_str(), &end, 10);
+				if (v.empty() || *end || n < 2 || n > 62) throw ArgError("Value '" + v + "' does not meet constraint: an integer 2 .. 62", "(--superbubbles-max)");
+				options.superbubblesMax = uint32_t(n);
+				superbubblesMaxSet = true;
+			}
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -373,6 +403,22 @@ int main(int argc, char * argv[])
 		else if (componentsOutSet || componentsMembersSet)
 		{
 			throw ArgError("This argument needs --components <file|sequence>", componentsOutSet ? "(--components-out)" : "(--components-members)");
+		}
+
+		if (!options.superbubblesBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The superbubble table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--superbubbles)");
+			if (!options.colorsBy.empty() && options.colorsBy != options.superbubblesBy) throw ArgError("The superbubble table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
+			if (!options.bubblesBy.empty() && options.bubblesBy != options.superbubblesBy) throw ArgError("The superbubble table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
+			if (!options.distancesBy.empty() && options.distancesBy != options.superbubblesBy) throw ArgError("The superbubble table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
+			if (!options.componentsBy.empty() && options.componentsBy != options.superbubblesBy) throw ArgError("The superbubble table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
+			if (!superbubblesOutSet) options.superbubblesFile = "de_bruijn.superbubbles.tsv";
+			if (options.superbubblesFile.empty()) throw ArgError("The superbubble table needs a file name", "(--superbubbles-out)");
+			if (superbubblesMembersSet && options.superbubblesMembersFile.empty()) throw ArgError("The superbubble members need a file name", "(--superbubbles-members)");
+		}
+		else if (superbubblesOutSet || superbubblesMembersSet || superbubblesMaxSet)
+		{
+			throw ArgError("This argument needs --superbubbles <file|sequence>", superbubblesOutSet ? "(--superbubbles-out)" : superbubblesMembersSet ? "(--superbubbles-members)" : "(--superbubbles-max)");
 		}
 
 		if (runTests)

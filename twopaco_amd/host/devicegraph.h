@@ -24,7 +24,9 @@
 	X(segments_bubbles_build) X(segments_bubbles_info) X(segments_bubbles_fetch_rows) X(segments_bubbles_fetch_hist) \
 	X(segments_distances_build) X(segments_distances_info) X(segments_distances_fetch) \
 	X(segments_components_build) X(segments_components_info) X(segments_components_fetch_members) X(segments_components_fetch_rows) \
-	X(segments_components_fetch_presence)
+	X(segments_components_fetch_presence) \
+	X(segments_superbubbles_build) X(segments_superbubbles_info) X(segments_superbubbles_fetch_rows) X(segments_superbubbles_fetch_members) \
+	X(segments_superbubbles_fetch_presence)
 
 namespace TwoPaCo
 {
@@ -213,6 +215,42 @@ namespace TwoPaCo
 			api.check(api.segments_components_fetch_rows(api.ctx, 0, n, out.root.data(), out.segments.data(), out.links.data(), out.length.data(), out.edges.data(),
 				out.occurrences.data()), "segments_components_fetch_rows");
 			api.check(api.segments_components_fetch_presence(api.ctx, 0, n, out.presence.data()), "segments_components_fetch_presence");
+			return true;
+		}
+
+		// The bounded superbubbles (csrc/tpc_superbubbles.hip), searched over the link rows' arcs, presence ORed over the colour rows.
+		inline void BuildSuperbubbles(const Api & api, uint32_t maxInside)
+		{
+			api.check(api.segments_superbubbles_build(api.ctx, maxInside), "segments_superbubbles_build");
+		}
+
+		// ... fetched: the rows, their members and presence words; the adjacency and exit[] stay on the device.  false, and nothing
+		// fetched, when the stage saw other segments than the caller
+		inline bool FetchSuperbubbles(const Api & api, uint64_t rows, size_t words, GraphFormat::SuperbubbleTable & out)
+		{
+			uint64_t info[7] = {0, 0, 0, 0, 0, 0, 0};
+			api.check(api.segments_superbubbles_info(api.ctx, info), "segments_superbubbles_info");
+			if (info[1] != 2 * rows) return false;
+			const size_t n = size_t(info[0]);
+			out.sides = info[1];
+			out.unmirrored = info[3];
+			out.arcs = info[5];
+			out.maxInside = uint32_t(info[6]);
+			out.entrance.resize(n);
+			out.exit.resize(n);
+			out.inside.resize(n);
+			out.arcsIn.resize(n);
+			out.nColors.resize(n);
+			out.paths.resize(n);
+			out.minEdges.resize(n);
+			out.maxEdges.resize(n);
+			out.presence.resize(n * words);
+			out.memberOffset.resize(n + 1);
+			out.members.resize(size_t(info[2]));
+			api.check(api.segments_superbubbles_fetch_rows(api.ctx, 0, n, out.entrance.data(), out.exit.data(), out.inside.data(), out.arcsIn.data(), out.nColors.data(),
+				out.paths.data(), out.minEdges.data(), out.maxEdges.data()), "segments_superbubbles_fetch_rows");
+			api.check(api.segments_superbubbles_fetch_members(api.ctx, out.memberOffset.data(), out.members.data()), "segments_superbubbles_fetch_members");
+			api.check(api.segments_superbubbles_fetch_presence(api.ctx, 0, n, out.presence.data()), "segments_superbubbles_fetch_presence");
 			return true;
 		}
 	}

@@ -1068,6 +1068,281 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeSuperbubbles(const EventTable & t, size_t k, const LinkTable & links, const ColorTable & colors, uint32_t maxInside, SuperbubbleTable & out)
+		{
+			(void)k;
+			out = SuperbubbleTable();
+			if (maxInside < 2 || maxInside > 62) throw std::runtime_error("superbubble table: max_inside = " + std::to_string(maxInside) + ", allowed are 2 .. 62");
+			out.maxInside = maxInside;
+			const size_t words = colors.Words();
+			if (colors.presence.size() != colors.Rows() * words) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			// the row of every segment: the order of the first sights, as ComputeColors numbers them
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			std::vector<uint32_t> rowOfEvent(size_t(t.events), 0);
+			uint64_t rows = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator seen = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				if (seen == rowOf.end())
+				{
+					if (name < FRESH) rowOf[name] = uint32_t(rows);
+					rowOfEvent[e] = uint32_t(rows++);
+				}
+				else rowOfEvent[e] = seen->second;
+			}
+
+			if (rows != colors.Rows()) throw std::runtime_error("superbubble table: the colour table's rows are not the segments of the event table");
+			if (rows >= (uint64_t(1) << 31)) throw std::runtime_error("superbubble table: " + std::to_string(rows) + " segments, a side holds at most 2147483647");
+			out.sides = 2 * rows;
+			auto side = [&](uint64_t e) { return uint32_t(rowOfEvent[e] << 1 | (t.name[e] < 0 ? 1u : 0u)); };
+			auto rev = [](uint32_t code) { return code ^ 1u; };
+			std::vector<std::set<uint32_t> > outSet(size_t(out.sides));
+			for (uint32_t e0 : links.firstEvent)
+			{
+				if (e0 == 0 || e0 >= t.events) throw std::runtime_error("link table: a row's first event lies outside the event table");
+				const uint32_t from = side(e0 - 1), to = side(e0);
+				outSet[from].insert(to);
+				outSet[rev(to)].insert(rev(from));   // the same arc once more when the link is its own reverse: a set holds it once
+			}
+
+			for (const std::set<uint32_t> & heads : outSet) out.arcs += heads.size();
+			for (uint32_t e0 : colors.firstEvent)
+			{
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+			}
+
+			const uint32_t NONE = 0xFFFFFFFFu;
+			// the walk from s: the sides seen in `list`, those visited in `order` (a topological order of U without the exit); the exit or NONE
+			std::vector<uint32_t> list, pending, order;
+			std::vector<bool> visited;
+			auto walk = [&](uint32_t s) -> uint32_t
+			{
+				list.assign(1, s);
+				pending.assign(1, 0);
+				visited.assign(1, false);
+				order.clear();
+				if (outSet[s].size() < 2) return NONE;
+				std::vector<size_t> ready(1, 0);
+				while (!ready.empty())
+				{
+					const size_t i = ready.back();
+					ready.pop_back();
+					visited[i] = true;
+					order.push_back(uint32_t(i));
+					const uint32_t v = list[i];
+					if (outSet[v].empty()) return NONE;                                  // a dead end
+					for (uint32_t u : outSet[v])
+					{
+						if (u == s) return NONE;                                         // an arc back to the entrance
+						size_t j = list.size();
+						for (size_t q = 0; q < list.size(); q++)
+						{
+							if (list[q] == rev(u)) return NONE;                          // both strands of a row
+							if (list[q] == u) j = q;
+						}
+
+						if (j == list.size())
+						{
+							if (list.size() == size_t(maxInside) + 2) return NONE;      // one entry too many
+							list.push_back(u);
+							pending.push_back(uint32_t(outSet[rev(u)].size()));          // in(u) = rev(out(rev(u)))
+							visited.push_back(false);
+						}
+
+						if (visited[j] || pending[j] == 0) return NONE;
+						if (--pending[j] == 0) ready.push_back(j);
+					}
+
+					if (list.size() - order.size() == 1 && ready.size() == 1)            // one side left, and all its in-neighbours visited
+					{
+						const uint32_t exit = list[ready[0]];
+						return outSet[exit].count(s) ? NONE : exit;                      // an arc from exit to entrance closes a cycle
+					}
+				}
+
+				return NONE;   // sides are seen that wait for an in-neighbour outside: no matching
+			};
+
+			std::vector<uint32_t> exitOf(size_t(out.sides), NONE);
+			for (uint64_t code = 0; code < out.sides; code++) exitOf[code] = walk(uint32_t(code));
+			out.memberOffset.push_back(0);
+			for (uint64_t code = 0; code < out.sides; code++)
+			{
+				const uint32_t s = uint32_t(code), exit = exitOf[code];
+				if (exit == NONE) continue;
+				const bool mirrored = exitOf[rev(exit)] == rev(s);
+				if (!mirrored) out.unmirrored += 1;
+				if (!(s < rev(exit) || !mirrored)) continue;
+				if (walk(s) != exit) throw std::runtime_error("superbubble table: a walk did not repeat itself");
+				const size_t n = list.size();
+				std::vector<uint64_t> paths(n, 0), low(n, ~uint64_t(0)), high(n, 0);
+				paths[0] = 1;
+				low[0] = 0;
+				uint32_t arcsIn = 0;
+				for (uint32_t i : order)
+				{
+					arcsIn += uint32_t(outSet[list[i]].size());   // every arc that leaves a side of U other than the exit ends in U
+					for (uint32_t u : outSet[list[i]])
+					{
+						const size_t j = size_t(std::find(list.begin(), list.end(), u) - list.begin());
+						const uint32_t e0 = colors.firstEvent[u >> 1];
+						const uint64_t weight = u == exit ? 0 : uint64_t(t.end[e0]) - t.begin[e0];
+						paths[j] += paths[i];
+						low[j] = std::min(low[j], low[i] + weight);
+						high[j] = std::max(high[j], high[i] + weight);
+					}
+				}
+
+				const size_t at = size_t(std::find(list.begin(), list.end(), exit) - list.begin());
+				std::vector<uint32_t> inside;
+				for (uint32_t u : list)
+				{
+					if (u != s && u != exit) inside.push_back(u);
+				}
+
+				std::sort(inside.begin(), inside.end());
+				std::vector<uint32_t> bits(words, 0);
+				for (uint32_t u : inside)
+				{
+					for (size_t w = 0; w < words; w++) bits[w] |= colors.presence[size_t(u >> 1) * words + w];
+				}
+
+				uint32_t held = 0;
+				for (uint32_t w : bits) held += uint32_t(__builtin_popcount(w));
+				out.entrance.push_back(s);
+				out.exit.push_back(exit);
+				out.inside.push_back(uint32_t(inside.size()));
+				out.arcsIn.push_back(arcsIn);
+				out.nColors.push_back(held);
+				out.paths.push_back(paths[at]);
+				out.minEdges.push_back(low[at]);
+				out.maxEdges.push_back(high[at]);
+				out.presence.insert(out.presence.end(), bits.begin(), bits.end());
+				out.members.insert(out.members.end(), inside.begin(), inside.end());
+				out.memberOffset.push_back(uint32_t(out.members.size()));
+			}
+		}
+
+		namespace
+		{
+			void CheckSuperbubbles(const EventTable & t, const ColorTable & colors, const SuperbubbleTable & b)
+			{
+				const size_t n = b.Rows(), words = colors.Words();
+				if (b.exit.size() != n || b.inside.size() != n || b.arcsIn.size() != n || b.nColors.size() != n || b.paths.size() != n || b.minEdges.size() != n ||
+					b.maxEdges.size() != n || b.presence.size() != n * words || b.memberOffset.size() != n + 1 || b.memberOffset[0] != 0 || b.memberOffset[n] != b.members.size())
+				{
+					throw std::runtime_error("superbubble table: the arrays do not agree about the rows, the members and the colours");
+				}
+
+				if (b.sides != 2 * uint64_t(colors.Rows())) throw std::runtime_error("superbubble table: its sides are not those of the colour table's rows");
+				for (uint32_t e0 : colors.firstEvent)
+				{
+					if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				}
+
+				for (const std::vector<uint32_t> * codes : {&b.entrance, &b.exit, &b.members})
+				{
+					for (uint32_t code : *codes)
+					{
+						if (code >= b.sides) throw std::runtime_error("superbubble table: a side lies outside the segments");
+					}
+				}
+
+				for (size_t r = 0; r < n; r++)
+				{
+					if (b.memberOffset[r + 1] < b.memberOffset[r] || b.memberOffset[r + 1] - b.memberOffset[r] != b.inside[r] || b.inside[r] > b.maxInside)
+					{
+						throw std::runtime_error("superbubble table: a row's members are not its inside");
+					}
+				}
+			}
+
+			void AppendSide(std::string & buf, const EventTable & t, const ColorTable & colors, uint32_t code)
+			{
+				buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[code >> 1]])));
+				buf += '\t';
+				buf += (code & 1u) ? '-' : '+';
+			}
+		}
+
+		void WriteSuperbubbles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & b, const std::string & path)
+		{
+			CheckSuperbubbles(t, colors, b);
+			if (map.label.size() != colors.colors) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			const size_t words = colors.Words(), n = b.Rows(), digits = size_t((colors.colors + 3) / 4);
+			uint64_t bySize[63] = {0};
+			for (uint32_t inside : b.inside) bySize[inside] += 1;
+			WriteStreamed(path, "superbubble table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-superbubbles\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(colors.colors) +
+					"\tsegments=" + std::to_string(colors.Rows()) + "\tlinks=" + std::to_string(links) + "\tmax_inside=" + std::to_string(b.maxInside) + "\tsuperbubbles=" +
+					std::to_string(n) + "\n";
+				for (uint64_t col = 0; col < colors.colors; col++) buf += "#color\t" + std::to_string(col) + "\t" + map.label[col] + "\n";
+				for (int size = 0; size < 63; size++)
+				{
+					if (bySize[size]) buf += "#inside\t" + std::to_string(size) + "\t" + std::to_string(bySize[size]) + "\n";
+				}
+
+				for (size_t r = 0; r < n; r++)
+				{
+					AppendSide(buf, t, colors, b.entrance[r]);
+					buf += '\t';
+					AppendSide(buf, t, colors, b.exit[r]);
+					for (uint64_t value : {uint64_t(b.inside[r]), uint64_t(b.arcsIn[r]), b.paths[r], b.minEdges[r], b.maxEdges[r], uint64_t(b.nColors[r])})
+					{
+						buf += '\t';
+						buf += std::to_string(value);
+					}
+
+					const uint32_t * bits = &b.presence[r * words];
+					buf += '\t';
+					for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(bits[j >> 3] >> (4 * (j & 7))) & 15u];
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteSuperbubbleMembers(const EventTable & t, size_t k, const ColorTable & colors, const SuperbubbleTable & b, const std::string & path)
+		{
+			CheckSuperbubbles(t, colors, b);
+			if (path.empty()) throw std::runtime_error("The superbubble members need a file name");
+			WriteStreamed(path, "superbubble members", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-superbubble-members\t1\tk=" + std::to_string(k) + "\tsegments=" + std::to_string(colors.Rows()) + "\tmax_inside=" + std::to_string(b.maxInside) +
+					"\tsuperbubbles=" + std::to_string(b.Rows()) + "\tmembers=" + std::to_string(b.members.size()) + "\n";
+				for (size_t r = 0; r < b.Rows(); r++)
+				{
+					for (uint32_t m = b.memberOffset[r]; m < b.memberOffset[r + 1]; m++)
+					{
+						buf += std::to_string(r);
+						buf += '\t';
+						AppendSide(buf, t, colors, b.members[m]);
+						buf += '\n';
+					}
+
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteSuperbubbleFiles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & b,
+			const std::string & path, const std::string & membersPath)
+		{
+			if (!membersPath.empty()) WriteSuperbubbleMembers(t, k, colors, b, membersPath);
+			try
+			{
+				WriteSuperbubbles(t, k, map, colors, links, b, path);
+			}
+			catch (...)
+			{
+				if (!membersPath.empty()) ::unlink(membersPath.c_str());
+				throw;
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{

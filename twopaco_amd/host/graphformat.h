@@ -399,7 +399,8 @@ namespace TwoPaCo
 		// ---------------------------------------------------------------------------------------- the simple bubbles
 		// Where the genomes differ: two segments leave one side of a segment, touch nothing else and meet again at one side of
 		// another (include/twopaco_hip.h, the tpc_segments_bubbles_* group, defines side, arc, degree, bubble, canonical orientation
-		// and the orders; simple bubbles only -- three alleles at one place, nested bubbles and superbubbles are not reported).  The
+		// and the orders; simple bubbles only -- three alleles at one place, nested bubbles and superbubbles are in the superbubble
+		// table below).  The
 		// arrays come from ComputeBubbles below -- the serial statement -- or from the device (csrc/tpc_bubbles.hip); WriteBubbles
 		// prints either as the same bytes.  A side is row * 2 + (1 when the strand is '-'), the rows being the colour table's.
 		struct BubbleTable
@@ -500,6 +501,57 @@ namespace TwoPaCo
 		// Both files of the component table, or neither: the members first when membersPath is given, then the TSV (to stdout when
 		// path is empty); when the TSV cannot be written the members file is removed again before the error is thrown.
 		void WriteComponentFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & components,
+			const std::string & path, const std::string & membersPath);
+
+		// ---------------------------------------------------------------------------------------- the superbubbles
+		// Where the genomes differ, beyond two alleles (include/twopaco_hip.h, the tpc_segments_superbubbles_* group, states the
+		// definition in the same words; Onodera, Sadakane and Shibuya 2013).  Rows, sides (code = row * 2 + minus, rev(code) = code ^ 1),
+		// arcs, out(u) and deg(u) are those of the simple bubbles; in(v) = { rev(w) : w in out(rev(v)) }.  For sides s != t, U(s, t) is
+		// the set of sides reachable from s along arcs without leaving t (s and t included; a path may end at t but not continue
+		// through it).  (s, t) is a SUPERBUBBLE with entrance s, exit t and inside U \ {s, t} when: 1. deg(s) >= 2 and t is in U;
+		// 2. MATCHING: U equals the set of sides from which t is reachable along arcs without entering s (where 3 holds: every side of
+		// U other than t has all its out-neighbours in U and at least one, every side of U other than s has all its in-neighbours in
+		// U); 3. ACYCLIC: the arcs with both ends in U form no cycle, which includes no arc t -> s and no self-loop; 4. ONE STRAND PER
+		// SEGMENT: no two sides of U have the same row; 5. MINIMAL: no side t' of the inside makes (s, t') satisfy 1-4; 6. BOUNDED:
+		// |inside| <= maxInside, 2 .. 62, so a superbubble is at most 64 sides.  A side is the entrance of at most one superbubble,
+		// exit(s).  (s, t) is REPORTED when exit(s) = t and either code(s) < code(rev(t)) or exit(rev(t)) != rev(s); rows ascend by
+		// entrance code.  Per row: entrance, exit, inside (the number of sides inside), arcs (both ends in U), paths (the distinct arc
+		// paths from s to t), minEdges and maxEdges (the smallest and largest sum over an s-t path of the weights, length - k, of its
+		// inside segments), presence (the OR of the inside rows' colour words), nColors, and the members: the inside sides ascending.
+		// The arrays come from ComputeSuperbubbles below -- the serial statement -- or from the device (csrc/tpc_superbubbles.hip);
+		// the writers print either as the same bytes.
+		struct SuperbubbleTable
+		{
+			uint64_t sides, arcs, unmirrored;                        // arcs of the whole graph; entrances whose mirror is missing
+			uint32_t maxInside;
+			std::vector<uint32_t> entrance, exit, inside, arcsIn, nColors;   // [superbubbles]
+			std::vector<uint64_t> paths, minEdges, maxEdges;                   // [superbubbles]
+			std::vector<uint32_t> presence;                                    // [superbubbles][colors.Words()]
+			std::vector<uint32_t> memberOffset, members;                       // [superbubbles + 1], [members]: side codes
+			SuperbubbleTable() : sides(0), arcs(0), unmirrored(0), maxInside(62) {}
+			size_t Rows() const { return entrance.size(); }
+		};
+
+		// The definition's procedure stated with std:: containers: the arcs of every link row into one std::set of heads per side,
+		// then per side of degree 2 or more Onodera's walk -- a list of the sides seen with their unvisited in-neighbours counted down,
+		// failing on a dead end, an arc back to the entrance, the other strand of a listed side and an entry beyond maxInside + 2 --
+		// the reporting rule, and per reported row the sums over the walk's own topological order.  No device dependency.
+		void ComputeSuperbubbles(const EventTable & table, size_t k, const LinkTable & links, const ColorTable & colors, uint32_t maxInside, SuperbubbleTable & out);
+
+		// The TSV text: "#twopaco-superbubbles\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tlinks=<N>\tmax_inside=<M>\t
+		// superbubbles=<B>", the colour table's "#color" lines, "#inside\t<n>\t<count>" for every inside size that occurs, ascending,
+		// then one line per row: entrance and exit each as |name| and strand, inside, arcs, paths, min_edges, max_edges, n_colors and
+		// presence as hex.  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteSuperbubbles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & superbubbles,
+			const std::string & path);
+
+		// The members: "#twopaco-superbubble-members\t1\tk=<k>\tsegments=<S>\tmax_inside=<M>\tsuperbubbles=<B>\tmembers=<T>", then
+		// "<row of the table, from 0>\t<name>\t<strand>" per member, into the file `path`.
+		void WriteSuperbubbleMembers(const EventTable & table, size_t k, const ColorTable & colors, const SuperbubbleTable & superbubbles, const std::string & path);
+
+		// Both files, or neither: the members first when membersPath is given, then the TSV (to stdout when path is empty); when the
+		// TSV cannot be written the members file is removed again before the error is thrown.
+		void WriteSuperbubbleFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & superbubbles,
 			const std::string & path, const std::string & membersPath);
 
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when

@@ -6,7 +6,9 @@
 //             [--compact]  |  --colors file|sequence [--colors-out <path>]  |  --links [--links-out <path>]
 //             |  --bubbles file|sequence [--bubbles-out <path>]
 //             |  --distances file|sequence [--distances-out <path>] [--distances-phylip <path>]
-//             |  --components file|sequence [--components-out <path>] [--components-members <path>]   (the last five instead of -f)
+//             |  --components file|sequence [--components-out <path>] [--components-members <path>]
+//             |  --superbubbles file|sequence [--superbubbles-out <path>] [--superbubbles-members <path>] [--superbubbles-max <n>]
+//             (the last six instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -63,6 +65,13 @@
 // serial walk, then ComputeColors, ComputeLinks and ComputeComponents; with --gpu the colour stage, the link stage and the component
 // stage over one segment build (csrc/tpc_components.hip); the bytes are the same.  Beside --colors, --bubbles or --distances of the
 // same colours it is written after them.  A stream the walk refuses prints the walk's error and nothing else.
+// --superbubbles file|sequence [--superbubbles-out <path>] [--superbubbles-members <path>] [--superbubbles-max <n>] (an addition;
+// instead of -f): the superbubbles of the graph, bounded to n sides inside (2 .. 62, default 62) -- where the genomes differ beyond
+// two alleles; include/twopaco_hip.h defines them -- as TSV of integers (graphformat.h: WriteSuperbubbles) and, asked for, the inside
+// sides of every row (WriteSuperbubbleMembers).  Without --gpu the serial walk, then ComputeColors, ComputeLinks and
+// ComputeSuperbubbles; with --gpu the colour stage, the link stage and the superbubble stage over one segment build
+// (csrc/tpc_superbubbles.hip); the bytes are the same.  Beside --colors, --bubbles, --distances or --components of the same colours it
+// is written after them.  Its refusals are those of --bubbles.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -467,10 +476,19 @@ namespace
 		ComponentsWanted() : on(false) {}
 	};
 
-	// --components, serial, alone or beside --colors / --bubbles / --distances of the same colours: one walk, the serial statements one
-	// after the other, then the tables in the order colours or bubbles, distances, components
+	// --superbubbles beside another table of the same colours, or alone: the file names (out empty: stdout) and the bound
+	struct SuperbubblesWanted
+	{
+		bool on;
+		std::string out, members;
+		uint32_t maxInside;
+		SuperbubblesWanted() : on(false), maxInside(62) {}
+	};
+
+	// --components and / or --superbubbles, serial, alone or beside --colors / --bubbles / --distances of the same colours: one walk, the
+	// serial statements one after the other, then the tables in the order colours or bubbles, distances, components, superbubbles
 	void DumpComponents(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const ComponentsWanted & want,
-		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo)
+		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo, const SuperbubblesWanted & super)
 	{
 		SerialTable t;
 		WalkLinks(binFile, fasta, k, prefix, false, t);
@@ -483,11 +501,14 @@ namespace
 		DistanceTable distances;
 		if (distancesToo) ComputeDistances(t.table, colors, distances);
 		ComponentTable components;
-		ComputeComponents(t.table, k, t.links, colors, components);
+		if (want.on) ComputeComponents(t.table, k, t.links, colors, components);
+		SuperbubbleTable superbubbles;
+		if (super.on) ComputeSuperbubbles(t.table, k, t.links, colors, super.maxInside, superbubbles);
 		if (colorsToo) WriteColors(t.table, k, map, colors, firstOut);
 		if (bubblesToo) WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, firstOut);
 		if (distancesToo) WriteDistanceFiles(k, map, colors.Rows(), distances, distancesTo.out, distancesTo.phylip);
-		WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
+		if (want.on) WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
+		if (super.on) WriteSuperbubbleFiles(t.table, k, map, colors, t.links.Rows(), superbubbles, super.out, super.members);
 	}
 
 	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
@@ -521,12 +542,12 @@ namespace
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
-		uint64_t links, linkOccurrences, bubbles, components, largestComponent;
-		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs;
+		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored;
+		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs, superbubblesKernelMs, superbubblesMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
 			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
-			componentsKernelMs(0), componentsMs(0), threads(1) {}
+			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), superbubblesKernelMs(0), superbubblesMs(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -540,11 +561,13 @@ namespace
 				"\"table_bytes\": %llu, \"text\": \"%s\", \"text_kernel_ms\": %.3f, \"colors_kernel_ms\": %.3f, \"colors_ms\": %.3f, "
 				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu, "
 				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f, "
-				"\"components_kernel_ms\": %.3f, \"components_ms\": %.3f, \"components\": %llu, \"largest_component\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"components_kernel_ms\": %.3f, \"components_ms\": %.3f, \"components\": %llu, \"largest_component\": %llu, "
+				"\"superbubbles_kernel_ms\": %.3f, \"superbubbles_ms\": %.3f, \"superbubbles\": %llu, \"superbubble_members\": %llu, \"superbubbles_unmirrored\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
 				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs,
-				(unsigned long long)components, (unsigned long long)largestComponent);
+				(unsigned long long)components, (unsigned long long)largestComponent, superbubblesKernelMs, superbubblesMs, (unsigned long long)superbubbles,
+				(unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored);
 			std::fclose(f);
 		}
 	};
@@ -700,8 +723,9 @@ namespace
 	// component table (alone, or beside the colour or the bubble table of the same colours, written after it).
 	struct TablesWanted
 	{
-		bool colors, links, bubbles, distances, components, bySequence;
-		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers;
+		bool colors, links, bubbles, distances, components, superbubbles, bySequence;
+		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers, superbubblesOut, superbubblesMembers;
+		uint32_t superbubblesMax;
 	};
 
 	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
@@ -718,14 +742,14 @@ namespace
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		ColorMap map;
 		ColorTable colors;
-		if (want.colors || want.bubbles || want.distances || want.components)
+		if (want.colors || want.bubbles || want.distances || want.components || want.superbubbles)
 		{
 			MakeColorMap(seq, fasta, want.bySequence, map);
 			if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
 			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
 			BuildColors(lib, map);
 			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
-			if (want.colors || want.bubbles || want.components) FetchColors(lib, map, counts[1], colors);
+			if (want.colors || want.bubbles || want.components || want.superbubbles) FetchColors(lib, map, counts[1], colors);
 			stats.colorsMs = MsSince(c0);
 		}
 
@@ -741,7 +765,7 @@ namespace
 		}
 
 		LinkTable links;
-		if (want.links || want.bubbles || want.components) LinksOnDevice(lib, counts[0], want.links || want.bubbles, false, links, stats);
+		if (want.links || want.bubbles || want.components || want.superbubbles) LinksOnDevice(lib, counts[0], want.links || want.bubbles, false, links, stats);
 		BubbleTable bubbles;
 		if (want.bubbles)
 		{
@@ -767,8 +791,22 @@ namespace
 			TimingLine("component table", stats.componentsMs, stats.componentsKernelMs);
 		}
 
+		SuperbubbleTable superbubbles;
+		if (want.superbubbles)
+		{
+			const std::chrono::steady_clock::time_point p0 = std::chrono::steady_clock::now();
+			BuildSuperbubbles(lib, want.superbubblesMax);
+			stats.superbubblesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_SUPERBUBBLES);
+			if (!FetchSuperbubbles(lib, counts[1], colors.Words(), superbubbles)) throw std::runtime_error("--gpu: the superbubble stage and the segment table disagree about the segments");
+			stats.superbubbles = superbubbles.Rows();
+			stats.superbubbleMembers = superbubbles.members.size();
+			stats.superbubblesUnmirrored = superbubbles.unmirrored;
+			stats.superbubblesMs = MsSince(p0);
+			TimingLine("superbubble table", stats.superbubblesMs, stats.superbubblesKernelMs);
+		}
+
 		Events held(counts[0], sequences);
-		if (want.colors || want.links || want.bubbles || want.components) FetchTable(lib, held);
+		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
@@ -776,6 +814,7 @@ namespace
 		if (want.bubbles) WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, want.out);
 		if (want.distances) WriteDistanceFiles(k, map, counts[1], distances, want.distancesOut, want.distancesPhylip);
 		if (want.components) WriteComponentFiles(held.table, k, map, colors, stats.links, components, want.componentsOut, want.componentsMembers);
+		if (want.superbubbles) WriteSuperbubbleFiles(held.table, k, map, colors, stats.links, superbubbles, want.superbubblesOut, want.superbubblesMembers);
 		stats.formatMs = MsSince(t0);
 		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
 	}
@@ -853,7 +892,7 @@ namespace
 
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -900,6 +939,17 @@ namespace
 			"     (one walk for all; this table is written last); not with --links, --compact or --text.\n\n"
 			"   --components-out <file name>\n     with --components: write the table there instead of to the standard output\n\n"
 			"   --components-members <file name>\n     with --components: also write the component of every segment there, one line per segment\n\n"
+			"   --superbubbles <file|sequence>\n     instead of -f: the superbubbles of the graph as TSV of integers -- the places where the paths that leave one side of a\n"
+			"     segment (the entrance) meet again at one side of another (the exit) and touch nothing else: three alleles, substitutions\n"
+			"     closer than k, a substitution beside an indel, nested ones each at its own entrance, and the simple bubbles.  Per row the\n"
+			"     entrance and the exit as name and strand, the sides inside, the arcs, the paths, the smallest and largest path weight\n"
+			"     in edges ((k+1)-mers), the number of colours and the presence bits of --colors over the inside; in front the colours and\n"
+			"     the rows by their inside.  Needs -k and -s.  With --gpu they are found on the device.  Goes with --colors, --bubbles,\n"
+			"     --distances or --components of the same colours (one walk for all; this table is written last); not with --links,\n"
+			"     --compact or --text.\n\n"
+			"   --superbubbles-out <file name>\n     with --superbubbles: write the table there instead of to the standard output\n\n"
+			"   --superbubbles-members <file name>\n     with --superbubbles: also write the inside sides of every row there, one line per side\n\n"
+			"   --superbubbles-max <integer>\n     with --superbubbles: the largest inside reported, 2 .. 62 (default 62)\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -909,9 +959,10 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false;
+		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
+		uint32_t superbubblesMax = 62;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -985,6 +1036,22 @@ int main(int argc, char * argv[])
 			}
 			else if (a == "--components-out") { componentsOut = value("(--components-out)"); componentsOutSet = true; }
 			else if (a == "--components-members") { componentsMembers = value("(--components-members)"); componentsMembersSet = true; }
+			else if (a == "--superbubbles")
+			{
+				superbubblesBy = value("(--superbubbles)");
+				if (superbubblesBy != "file" && superbubblesBy != "sequence") throw ArgError("Value '" + superbubblesBy + "' does not meet constraint: file|sequence", "Argument: (--superbubbles)");
+			}
+			else if (a == "--superbubbles-out") { superbubblesOut = value("(--superbubbles-out)"); superbubblesOutSet = true; }
+			else if (a == "--superbubbles-members") { superbubblesMembers = value("(--superbubbles-members)"); superbubblesMembersSet = true; }
+			else if (a == "--superbubbles-max")
+			{
+				const std::string v = value("(--superbubbles-max)");
+				char * end = 0;
+				const long n = std::strtol(v.c_str(), &end, 10);
+				if (v.empty() || *end || n < 2 || n > 62) throw ArgError("Value '" + v + "' does not meet constraint: an integer 2 .. 62", "Argument: (--superbubbles-max)");
+				superbubblesMax = uint32_t(n);
+				superbubblesMaxSet = true;
+			}
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -1006,6 +1073,19 @@ int main(int argc, char * argv[])
 		}
 
 		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty(), components = !componentsBy.empty();
+		const bool superbubbles = !superbubblesBy.empty();
+		if (superbubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--superbubbles)");
+		if (superbubbles && colors && colorsBy != superbubblesBy) throw ArgError("The superbubble table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
+		if (superbubbles && bubbles && bubblesBy != superbubblesBy) throw ArgError("The superbubble table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
+		if (superbubbles && distances && distancesBy != superbubblesBy) throw ArgError("The superbubble table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
+		if (superbubbles && components && componentsBy != superbubblesBy) throw ArgError("The superbubble table and the component table share one set of colours: --components " + componentsBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
+		if (superbubbles && links) throw ArgError("The superbubble table and the link table are written one at a time: not with --links", "(--superbubbles)");
+		if (superbubbles && compact) throw ArgError("The superbubble table and the compact text are written one at a time: not with --compact", "(--superbubbles)");
+		if (superbubbles && textSet) throw ArgError("The superbubble table is formatted by the host: not with --superbubbles", "(--text)");
+		if (superbubblesOutSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-out)");
+		if (superbubblesMembersSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-members)");
+		if (superbubblesMaxSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-max)");
+		if (superbubblesMembersSet && superbubblesMembers.empty()) throw ArgError("The superbubble members need a file name", "(--superbubbles-members)");
 		if (components && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--components)");
 		if (components && colors && colorsBy != componentsBy) throw ArgError("The component table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --components " + componentsBy, "(--components)");
 		if (components && bubbles && bubblesBy != componentsBy) throw ArgError("The component table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --components " + componentsBy, "(--components)");
@@ -1042,10 +1122,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles && !distances && !components) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || distances || components || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -1061,7 +1141,7 @@ int main(int argc, char * argv[])
 		also.on = distances && (colors || bubbles);
 		also.out = distancesOut;
 		also.phylip = distancesPhylip;
-		if ((colors || links || bubbles || distances || components) && lib)
+		if ((colors || links || bubbles || distances || components || superbubbles) && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
@@ -1074,7 +1154,11 @@ int main(int argc, char * argv[])
 			want.bubbles = bubbles;
 			want.distances = distances;
 			want.components = components;
-			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : componentsBy) == "sequence";
+			want.superbubbles = superbubbles;
+			want.superbubblesOut = superbubblesOut;
+			want.superbubblesMembers = superbubblesMembers;
+			want.superbubblesMax = superbubblesMax;
+			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubblesBy) == "sequence";
 			want.componentsOut = componentsOut;
 			want.componentsMembers = componentsMembers;
 			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
@@ -1082,13 +1166,18 @@ int main(int argc, char * argv[])
 			want.distancesPhylip = distancesPhylip;
 			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
 		}
-		else if (components)
+		else if (components || superbubbles)
 		{
 			ComponentsWanted wanted;
-			wanted.on = true;
+			wanted.on = components;
 			wanted.out = componentsOut;
 			wanted.members = componentsMembers;
-			DumpComponents(binFile, fasta, k, prefix, componentsBy == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also);
+			SuperbubblesWanted super;
+			super.on = superbubbles;
+			super.out = superbubblesOut;
+			super.members = superbubblesMembers;
+			super.maxInside = superbubblesMax;
+			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubblesBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);

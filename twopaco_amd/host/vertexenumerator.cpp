@@ -364,6 +364,15 @@ namespace TwoPaCo
 				if (components && distances && options.componentsBy != options.distancesBy) throw std::runtime_error("The component table and the distance table share one set of colours: both by file or both by sequence");
 				if (components && sharded) throw std::runtime_error("The component table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				if (!components && !options.componentsMembersFile.empty()) throw std::runtime_error("The component members are written with the component table only");
+				const bool superbubbles = !options.superbubblesFile.empty();
+				if (superbubbles && options.superbubblesBy != "file" && options.superbubblesBy != "sequence") throw std::runtime_error("The superbubble table's colours must be one of file, sequence");
+				if (superbubbles && colors && options.superbubblesBy != options.colorsBy) throw std::runtime_error("The superbubble table and the colour table share one set of colours: both by file or both by sequence");
+				if (superbubbles && bubbles && options.superbubblesBy != options.bubblesBy) throw std::runtime_error("The superbubble table and the bubble table share one set of colours: both by file or both by sequence");
+				if (superbubbles && distances && options.superbubblesBy != options.distancesBy) throw std::runtime_error("The superbubble table and the distance table share one set of colours: both by file or both by sequence");
+				if (superbubbles && components && options.superbubblesBy != options.componentsBy) throw std::runtime_error("The superbubble table and the component table share one set of colours: both by file or both by sequence");
+				if (superbubbles && sharded) throw std::runtime_error("The superbubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (superbubbles && (options.superbubblesMax < 2 || options.superbubblesMax > 62)) throw std::runtime_error("The superbubble table's largest inside must be 2 .. 62");
+				if (!superbubbles && !options.superbubblesMembersFile.empty()) throw std::runtime_error("The superbubble members are written with the superbubble table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -498,7 +507,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles || distances || components)
+				if (graph || colors || links || bubbles || distances || components || superbubbles)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -996,7 +1005,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles || distances || components) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles || distances || components || superbubbles) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -1014,13 +1023,16 @@ namespace TwoPaCo
 			// --components: the colour build and the link build of the same table, then the component stage (csrc/tpc_components.hip) over
 			// the link rows and the colour rows where they lie; options.componentsFile and the members file are written after the
 			// distance files, both or neither (WriteComponentFiles).
+			// --superbubbles: the same two builds, then the superbubble stage (csrc/tpc_superbubbles.hip) over the link rows' arcs and the
+			// colour rows; options.superbubblesFile and the members file are written last of all, both or neither (WriteSuperbubbleFiles).
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
 				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), components = !options.componentsFile.empty();
-				const bool colorRows = colors || bubbles || distances || components;
-				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : options.componentsBy) == "sequence";
+				const bool superbubbles = !options.superbubblesFile.empty();
+				const bool colorRows = colors || bubbles || distances || components || superbubbles;
+				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : components ? options.componentsBy : options.superbubblesBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1038,6 +1050,7 @@ namespace TwoPaCo
 				GraphFormat::BubbleTable bubbleTable;
 				GraphFormat::DistanceTable distanceTable;
 				GraphFormat::ComponentTable componentTable;
+				GraphFormat::SuperbubbleTable superbubbleTable;
 				uint64_t segments = 0, linkRows = 0;
 				DeviceGraph::Events held(0, sequences);
 				const std::vector<uint32_t> noBits(1, 0);
@@ -1052,10 +1065,11 @@ namespace TwoPaCo
 						GraphFormat::ComputeColors(held.table, k, map.colorOfSequence, map.label.size(), colorTable);
 					}
 
-					if (links || bubbles || components) GraphFormat::ComputeLinks(held.table, linkTable);
+					if (links || bubbles || components || superbubbles) GraphFormat::ComputeLinks(held.table, linkTable);
 					if (bubbles) GraphFormat::ComputeBubbles(held.table, linkTable, bubbleTable);
 					if (distances) GraphFormat::ComputeDistances(held.table, colorTable, distanceTable);
 					if (components) GraphFormat::ComputeComponents(held.table, k, linkTable, colorTable, componentTable);
+					if (superbubbles) GraphFormat::ComputeSuperbubbles(held.table, k, linkTable, colorTable, options.superbubblesMax, superbubbleTable);
 				}
 				else
 				{
@@ -1117,7 +1131,7 @@ namespace TwoPaCo
 					}
 
 					if ((links || compact) && !fetched && !onDevice) fetchTable();
-					if (links || compact || bubbles || components)
+					if (links || compact || bubbles || components || superbubbles)
 					{
 						// --links / the compact graph / --bubbles / --components: the distinct links found on the device (csrc/tpc_links.hip), before the graph
 						// is written (the compact text needs their first bits); the rows' names come from name[]
@@ -1168,6 +1182,20 @@ namespace TwoPaCo
 						timer.Lap("segment components fetch");
 					}
 
+					if (superbubbles)
+					{
+						// over the link rows' arcs and the colour rows where they lie (csrc/tpc_superbubbles.hip); the sides' names are --colors'
+						DeviceGraph::BuildSuperbubbles(api, options.superbubblesMax);
+						timer.Lap("segment superbubbles");
+						kernelLine("superbubbles_kernel_ms", TPC_K_SUPERBUBBLES);
+						if (!DeviceGraph::FetchSuperbubbles(api, segments, colorTable.Words(), superbubbleTable))
+						{
+							throw std::runtime_error("The superbubble stage and the segment table disagree about the segments");
+						}
+
+						timer.Lap("segment superbubbles fetch");
+					}
+
 					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph && !fetched) fetchTable();
 				}
@@ -1212,6 +1240,12 @@ namespace TwoPaCo
 				{
 					GraphFormat::WriteComponentFiles(held.table, k, map, colorTable, linkRows, componentTable, options.componentsFile, options.componentsMembersFile);
 					timer.Lap("component table writing");
+				}
+
+				if (superbubbles)
+				{
+					GraphFormat::WriteSuperbubbleFiles(held.table, k, map, colorTable, linkRows, superbubbleTable, options.superbubblesFile, options.superbubblesMembersFile);
+					timer.Lap("superbubble table writing");
 				}
 			}
 

@@ -104,6 +104,15 @@ namespace TwoPaCo
 		std::string componentsBy;
 		std::string componentsFile;
 		std::string componentsMembersFile;
+		// The bounded superbubbles of the graph (graphformat.h: WriteSuperbubbles; `graphdump --superbubbles` writes the same bytes for
+		// the junction stream of this run): superbubblesFile (empty: off), superbubblesBy = "file" | "sequence" -- the same as the
+		// other tables' when those are given --, superbubblesMembersFile (empty: off) for the inside sides of every row and
+		// superbubblesMax, the largest inside reported (2 .. 62).  Found on the device (tpc_segments_superbubbles_build) over the link
+		// build and the colour build of the same segment table.  One GPU.
+		std::string superbubblesBy;
+		std::string superbubblesFile;
+		std::string superbubblesMembersFile;
+		uint32_t superbubblesMax = 62;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
