@@ -152,6 +152,10 @@ def hip():
         L.tpc_mask_import.argtypes = [p, p]
         L.tpc_emit_stream.argtypes = [p, p, p, u32, p, p]
         L.tpc_emit_stream_fetch.argtypes = [p, u64, u64, p]
+        L.tpc_emit_import.argtypes = [p, p, p, u64]
+        L.tpc_shard_chunk.argtypes = [p, p, p]
+        L.tpc_emit_stream_partial.argtypes = [p, p, p, u32, p, p]
+        L.tpc_emit_stream_part.argtypes = [p, p, p, u32, p, p, p, p, u32, u64, u64, u64, u64, p]
         L.tpc_segments_build_host.argtypes = [p, p, u64, ci, p, p, u32, p, u64]
         L.tpc_segments_build_resident.argtypes = [p, ci, p, p, u32, p, u64]
         L.tpc_segments_counts.argtypes = [p, p]
@@ -553,6 +557,45 @@ class Context:
         if hip().tpc_emit_stream_fetch(self._h, 0, nb.value, buf.ctypes.data) != 0:
             raise RuntimeError("tpc_emit_stream_fetch failed")
         return buf.tobytes(), nr.value
+
+    def emit_import(self, g_dev_ptr, id_dev_ptr, n):
+        """Installs n (position, id) pairs from device buffers (uint64 / int64, positions ascending) as the lists emit() would have left."""
+        self._ck(hip().tpc_emit_import(self._h, g_dev_ptr, id_dev_ptr, n))
+        self.n_marked = n
+
+    def shard_chunk(self):
+        """(chunk_lo, chunk_hi): this rank's chunk of text positions (after shard_config and seq_upload); the last rank's end is 2^64 - 1."""
+        lo, hi = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if hip().tpc_shard_chunk(self._h, ctypes.byref(lo), ctypes.byref(hi)) != 0:
+            raise RuntimeError("tpc_shard_chunk failed: seq_upload first")
+        return lo.value, hi.value
+
+    def emit_stream_partial(self, rec_start, rec_len):
+        """Step 1 of the stream cut over ranks: (cnt uint64 [n_rec], flags uint32 [n_rec]) -- per sequence the real-id records among THIS
+        context's marks, and bit 0 / 1: it holds the first / last k-mer with a real id."""
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        cnt, flags = np.zeros(rs.size, dtype=np.uint64), np.zeros(rs.size, dtype=np.uint32)
+        self._ck(hip().tpc_emit_stream_partial(self._h, rs.ctypes.data, rl.ctypes.data, rs.size, cnt.ctypes.data, flags.ctypes.data))
+        return cnt, flags
+
+    def emit_stream_part(self, rec_start, rec_len, gflags, e_scan, s_scan, before, r_last, chunk_lo, chunk_hi, slot0, n_slots):
+        """Step 2, after emit_stream_partial and the add-up over the ranks (include/twopaco_hip.h: tpc_emit_stream_part): the bytes of this
+        rank's n_slots slots, the file's [12 slot0, 12 (slot0 + n_slots))."""
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        gf = np.ascontiguousarray(gflags, dtype=np.uint32)
+        es, ss = np.ascontiguousarray(e_scan, dtype=np.uint64), np.ascontiguousarray(s_scan, dtype=np.uint64)
+        bf = np.ascontiguousarray(before, dtype=np.uint64)
+        if not (rl.size == gf.size == bf.size == rs.size and es.size == ss.size == rs.size + 1):
+            raise ValueError("emit_stream_part: n_rec entries in rec_len, gflags, before; n_rec + 1 in e_scan, s_scan")
+        nb = ctypes.c_uint64(0)
+        self._ck(hip().tpc_emit_stream_part(self._h, rs.ctypes.data, rl.ctypes.data, rs.size, gf.ctypes.data, es.ctypes.data, ss.ctypes.data, bf.ctypes.data,
+                                            r_last, chunk_lo, chunk_hi, slot0, n_slots, ctypes.byref(nb)))
+        buf = np.zeros(nb.value, dtype=np.uint8)
+        if hip().tpc_emit_stream_fetch(self._h, 0, nb.value, buf.ctypes.data) != 0:
+            raise RuntimeError("tpc_emit_stream_fetch failed")
+        return buf.tobytes()
 
     def segments_build(self, stream, k, rec_start, rec_len, ambiguous=()):
         """The segment table of graphdump's gfa1 / gfa2 / fasta walk (csrc/tpc_segments.hip) over the text of seq_upload.

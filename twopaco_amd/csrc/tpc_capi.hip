@@ -468,6 +468,10 @@ int tpc_set_params(tpc_ctx *c, int k, int L, int q, const uint64_t *seed_table)
         return fail(c, -1, "The value of K is too big. Please refer to documentaion how to increase the max supported value of K.");
     HIPCHK(c, hipSetDevice(c->device));
     c->P.k = k; c->P.L = L; c->P.q = q; c->P.rk = k % L; c->P.lmask = (1ull << L) - 1ull;
+    if (C != c->C && c->keys) {  // keys_cap counts keys of the old width: a wider key would be written past the buffer's end
+        (void)hipFree(c->keys);
+        c->keys = nullptr; c->keys_cap = 0;
+    }
     c->C = C;
     memset(c->tab_host, 0, sizeof c->tab_host);
     for (int i = 0; i < q; i++)
