@@ -43,7 +43,7 @@ def event_table(data, seqs, k):
                 n = "ACGT".index(nxt) if nxt in "ACGT" else -1
                 if n >= 0:
                     n |= (4 | abs(start) << 3) if start < 0 else start << 3
-                n = n if forward else -n
+                n = -n if start != lid else n   # reverse, but not between two ids of 0 (graphdump.cpp:88-91)
             name.append(n)
             begin.append(lp)
             end.append(pos)

@@ -199,7 +199,7 @@ def segment_table(data, seqs, k):
         name = "ACGT".index(nxt) if nxt in "ACGT" else -1
         if name >= 0:
             name |= (4 | abs(start) << 3) if start < 0 else start << 3
-        names.append(name if forward else -name)
+        names.append(-name if start != lid else name)   # reverse, but not between two ids of 0 (graphdump.cpp:88-91)
     seen, first = set(), []
     for n in names:
         first.append(abs(n) not in seen)

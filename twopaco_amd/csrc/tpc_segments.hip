@@ -115,7 +115,7 @@ __global__ void k_seg_name(const uint32_t *__restrict__ slots, uint64_t n, int k
                 } else {
                     if (!forward) code = 3u - code;
                     const int64_t v = (int64_t)code | (start < 0 ? (int64_t)(4ull | (seg_mag(start) << 3)) : (int64_t)((uint64_t)start << 3));
-                    nm = forward ? v : -v;
+                    nm = start != lid ? -v : v;  // graphdump.cpp:88-91: reverse, but not between two ids of 0 (start = -0 is the left id)
                 }
                 if (!fresh) my_max = max(my_max, (unsigned long long)seg_mag(nm));
             }

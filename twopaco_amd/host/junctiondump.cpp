@@ -178,7 +178,8 @@ namespace
 	// ---------------------------------------------------------------------------------------- segments
 	// Segment naming, reference graphdump.cpp:44-113.  The segment between junctions a (left) and b (right) is
 	// oriented from its end with the smaller |id| (ties: forward unless both ids are 0); `next` is the character
-	// that follows the start junction's k-mer in that orientation.
+	// that follows the start junction's k-mer in that orientation.  The name of a reverse segment is negative, except
+	// between two ids of 0, where the reference keeps it positive.
 	class SegmentNamer
 	{
 	public:
@@ -187,11 +188,13 @@ namespace
 		int64_t Name(int64_t leftId, int64_t rightId, char afterLeft, char beforeRightComplemented)
 		{
 			const int64_t LIMIT = int64_t(1) << 31;  // MAX_JUNCTION_ID
-			const int64_t l = Magnitude(leftId), r = Magnitude(rightId);
-			if (l >= LIMIT || r >= LIMIT)
+			// compared as they stand: the magnitude of INT64_MIN does not exist (the reference negates it all the same)
+			if (leftId >= LIMIT || leftId <= -LIMIT || rightId >= LIMIT || rightId <= -LIMIT)
 			{
 				throw std::runtime_error("A vertex id is too large, cannot generate GFA");
 			}
+
+			const int64_t l = Magnitude(leftId), r = Magnitude(rightId);
 
 			const bool forward = l < r || (l == r && l > 0);
 			const char next = forward ? afterLeft : beforeRightComplemented;
@@ -212,7 +215,9 @@ namespace
 				name |= start << 3;
 			}
 
-			return forward ? name : -name;
+			// negated when the start is not the left junction as it stands (graphdump.cpp:88-91): every reverse segment but the one
+			// between two ids of 0, whose start -0 is the left id
+			return start != leftId ? -name : name;
 		}
 
 	private:
