@@ -802,6 +802,13 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      positions into the candidate mask through LDS, in whole lines (k_mark_split, k_mark_apply); 0: it marks with
  *                      one device atomic per passing survivor.  TPC_VERIFY_MARKS=0 / 1 in the environment overrides the option
  *                      (measurements; read once per process).  The sharded first pass always marks with atomics
+ *   qhash_pushes       process-wide, 6 (default): k_q_hash2 compacts the 3 + 3 unknown edges of a position per lane and pushes them
+ *                      with every lane active; 8: the 4 + 4 candidates as predicated pushes.  TPC_QHASH_PUSHES=6 / 8 in the
+ *                      environment overrides the option (measurements; read once per process)
+ *   qhash_roll_scalars process-wide, 1 (default): k_q_hash2 rolls its hash with letter hashes selected from scalar registers; 0: with
+ *                      two 16-byte LDS reads per position.  TPC_QHASH_ROLL_SCALARS=0 / 1 overrides it.  A sharded context (more
+ *                      than one rank) with qhash_pushes = 8 always takes the LDS reads, whatever this option says: one of its
+ *                      instantiations spilled with the selects.  "query_hash_form" tells which roll ran
  *   mark_bucket_bits / mark_region_cap / mark_slice_bits   tests only, process-wide (0 = automatic): log2 positions of a bucket of the
  *                      mark lists (14..21), entries of a (workgroup, bucket) region (tiny: most entries take the atomic fallback),
  *                      log2 bits of the LDS slice k_mark_apply holds (10..20: a larger bucket is cut into sub-slices)
@@ -839,6 +846,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "insert_hash_kernel" = 0 none (the direct rolling kernel), 1 the instruction-lean hash with its seed table in LDS, 2 the same
  * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);
  * "query_hash_kernel" = 0 none (direct), 1 the lean k_q_hash2, 2 k_q_hash, 4 the closed form;
+ * "query_hash_form" = of the last k_q_hash2 launch (0 after another hash kernel): 1 = six compacted pushes per position (option
+ * qhash_pushes), + 2 = the roll from scalar registers (option qhash_roll_scalars), + 4 = its gated instantiation (a range [lo, hi] that
+ * is not the whole hash space);
  * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify;
  * "query_mark_path" = how the last query set the marks of its mask: 1 the write-combined lists, 0 device atomics (option verify_marks, a
  * plan whose lists do not fit the level-1 buffer) or the direct kernel (also when it completed an overflowed partitioned pass);

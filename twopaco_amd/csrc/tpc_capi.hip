@@ -370,6 +370,8 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "mark_bucket_bits")) { tpc_test_mark_bucket_bits = (int)value; return 0; }  // process-wide, tests only
     if (!strcmp(name, "mark_region_cap")) { tpc_test_mark_region_cap = (int)value; return 0; }    // process-wide, tests only
     if (!strcmp(name, "mark_slice_bits")) { tpc_test_mark_slice_bits = (int)value; return 0; }    // process-wide, tests only
+    if (!strcmp(name, "qhash_pushes")) { tpc_opt_qhash_pushes = value == 8 ? 8 : 6; return 0; }          // process-wide (tpc_internal.h)
+    if (!strcmp(name, "qhash_roll_scalars")) { tpc_opt_qhash_roll = value != 0; return 0; }               // process-wide (tpc_internal.h)
     if (!strcmp(name, "fuse_apply_lookup")) { c->opt_fuse = value != 0; return 0; }
     if (!strcmp(name, "test_q6_pb2")) { tpc_test_q6_pb2 = (int)value; return 0; }  // process-wide, tests only
     if (!strcmp(name, "insert_entry_fmt")) { tpc_test_insert_p3 = value == 3; return 0; }  // process-wide; 3 = blocked 24-bit level-2 insert entries (off by default: tpc_partition.hip)
@@ -423,6 +425,7 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "insert_hash_kernel")) return c->stat_kernel[0];
     if (!strcmp(name, "query_hash_kernel")) return c->stat_kernel[1];
     if (!strcmp(name, "query_verify_kernel")) return c->stat_kernel[2];
+    if (!strcmp(name, "query_hash_form")) return c->stat_kernel[3];
     if (!strcmp(name, "query_mark_path")) return c->stat_mark_path;
     if (!strcmp(name, "query_mark_fallback")) return c->stat_mark_fallback;
     if (!strcmp(name, "insert_batches")) return c->stat_batches[0];

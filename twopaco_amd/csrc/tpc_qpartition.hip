@@ -41,6 +41,7 @@
 
 #if TPC_QPARTITION_PART == 0
 int tpc_test_q6_pb2 = 0;  // option "test_q6_pb2" (tests)
+int tpc_opt_qhash_pushes = 6, tpc_opt_qhash_roll = 1;  // options "qhash_pushes", "qhash_roll_scalars" (tpc_internal.h)
 int tpc_test_mark_bucket_bits = 0, tpc_test_mark_region_cap = 0, tpc_test_mark_slice_bits = 0;  // options "mark_bucket_bits", "mark_region_cap", "mark_slice_bits" (tests)
 #endif
 
@@ -245,6 +246,9 @@ k_q_hash(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const ui
 // 16-byte pairs, and the bins are Bins3.  Used whenever the geometry allows (launch_qhash); entries, masks and overflow
 // entries are those of k_q_hash (order inside a region differs: nothing downstream depends on it).
 constexpr int QT_MAXK = 64;  // seed table: k x 5 letters x 16 bytes
+// k_q_hash2's mode bits (uniform).  The kernel is bound by the LDS pipe, and the two per-lane-indexed 16-byte reads of the roll
+// turned out to hold it for ~0.6 G of its 2.0 G busy cycles (profiles/r09_qhash_lds.md):
+constexpr uint32_t QH_ROLL_S = 1u;  // the roll selects its letter hashes from scalar registers instead of reading them from s_roll
 
 // every mask bit doubled: bit i -> bits 2i, 2i+1
 __device__ __forceinline__ uint64_t q_spread2(uint32_t m)
@@ -258,13 +262,16 @@ __device__ __forceinline__ uint64_t q_spread2(uint32_t m)
     return x | (x << 1);
 }
 
-template <bool GATED, bool SHARDED, bool HALF, bool LHI>
+template <bool GATED, bool SHARDED, bool HALF, bool LHI, bool PUSH6>
 __global__ void __launch_bounds__(QH_THREADS)
 k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__restrict__ bases,
           const uint32_t *__restrict__ nmask, uint64_t n_text, uint64_t tile0, uint64_t n_tiles, int pos_per_round,
           uint64_t lo, uint64_t hi, uint64_t *buf1, uint32_t *cnt1, uint64_t cap1, QOverflow ovf, PtPerm perm, PtShard sh,
-          uint64_t gbase, uint32_t *__restrict__ rmask, uint32_t tiles_per_wg, const uint16_t *__restrict__ skip16)
-{   // LHI: L > 32; L-bit values on two separate 32-bit registers (LeanV, tpc_lean.h: round 4)
+          uint64_t gbase, uint32_t *__restrict__ rmask, uint32_t tiles_per_wg, const uint16_t *__restrict__ skip16, uint32_t mode)
+{   // PUSH6: the 3 + 3 unknown edges of a position are compacted per lane and pushed with every lane active -- 6 LDS claims and 6
+    // stores per wave and position instead of 8 predicated ones of each (a compile-time switch: as a uniform branch the two forms
+    // together spilled 40-60 bytes per lane; option "qhash_pushes").  mode: QH_* bits
+    // LHI: L > 32; L-bit values on two separate 32-bit registers (LeanV, tpc_lean.h: round 4)
     // skip16 (k_periodic_build's per_qs, or nullptr): positions whose k + 2 characters repeat those of the position 1 .. 63 before
     // them send no probes -- k_periodic_copy gives them that position's verdict after the verification
     // tiles_per_wg > 0: workgroup w takes the tiles [w T, (w + 1) T) of the batch instead of w, w + nwg, ...: its regions then hold
@@ -303,12 +310,19 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
     const int xw = (k + 1) / 32 + 2;
     uint16_t *rmask16 = reinterpret_cast<uint16_t *>(rmask);
     // function 0's table entries of the four letters as scalars: the eight candidate edges use them with constant letters
-    uint32_t h0l[4], h0h[4], hk0l[4], hk0h[4];
+    uint32_t h0l[5], h0h[5], hk0l[5], hk0h[5];  // ([4]: the N row, for the roll from scalars)
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
+    for (int c = 0; c < 5; c++) {
         const uint64_t h = tab[c], hk = tab[TPC_TAB_HK + c];
         h0l[c] = (uint32_t)h; h0h[c] = (uint32_t)(h >> 32); hk0l[c] = (uint32_t)hk; hk0h[c] = (uint32_t)(hk >> 32);
     }
+    // letter c (0..4) -> {x[c], y[rc c]} on 32-bit halves: two selects on the letter's bits, one on its N bit
+    auto pick = [](uint32_t c, const uint32_t (&x)[5], const uint32_t (&y)[5], uint32_t &ox, uint32_t &oy) {
+        const bool b0 = (c & 1u) != 0u, b1 = (c & 2u) != 0u, n = c >= 4u;
+        const uint32_t x01 = b0 ? x[1] : x[0], x23 = b0 ? x[3] : x[2], y32 = b0 ? y[2] : y[3], y10 = b0 ? y[0] : y[1];
+        const uint32_t xv = b1 ? x23 : x01, yv = b1 ? y10 : y32;
+        ox = n ? x[4] : xv; oy = n ? y[4] : yv;
+    };
     const uint32_t ppr_mask = (uint32_t)pos_per_round - 1u;  // a power of two <= 16
     constexpr bool half_rounds = HALF;                       // 512 bins: see the push below
     const uint32_t p0 = 32u + tid * (uint32_t)QH_RUN;        // my first position, relative to the first staged word (the one before the tile)
@@ -373,6 +387,9 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
             uint32_t eb[8];
             uint64_t ev[8];
             bool eok[8];
+            uint32_t b6[6];  // (PUSH6) the unknown edges: in-edges 0..2, out-edges 3..5
+            uint64_t v6[6];
+            constexpr bool all3[3] = {true, true, true}, all6[6] = {true, true, true, true, true, true};
             bool probing = false;
             if (check && !nadj && !__builtin_amdgcn_ubfe(sk, (uint32_t)s, 1u)) {
                 const uint32_t hi_s = sid0 + (uint32_t)(s << 2);  // (survivor id >> 1) without the edge: position << 2
@@ -388,7 +405,25 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
                     ev[4 + c] = ((uint64_t)(hi_s | (uint32_t)((4 + c) >> 1)) << 32) | (rem | ((uint32_t)(c & 1) << 31));
                     eok[4 + c] = (uint32_t)c != cn;
                 }
-                if constexpr (!half_rounds) bins.template push_batch<8>(eb, ev, eok, lost);
+                if constexpr (PUSH6) {
+                    // cp, cn < 4 here.  The unknown letters are 0..3 without cp (cn): slot j takes candidate j, or candidate j + 1 when
+                    // the known letter is at or below j.  An entry keeps the edge number of its own letter (the verification recomputes
+                    // the edge from it), so the selects move whole {bin, value} pairs.
+#pragma unroll
+                    for (int j = 0; j < 3; j++) {
+                        const bool ui = cp <= (uint32_t)j, uo = cn <= (uint32_t)j;
+                        b6[j] = ui ? eb[j + 1] : eb[j];
+                        v6[j] = ui ? ev[j + 1] : ev[j];
+                        b6[3 + j] = uo ? eb[4 + j + 1] : eb[4 + j];
+                        v6[3 + j] = uo ? ev[4 + j + 1] : ev[4 + j];
+                    }
+                    if constexpr (!half_rounds) bins.template push_batch<6>(b6, v6, all6, lost);
+                    else {
+                        const uint32_t b3[3] = {b6[0], b6[1], b6[2]};
+                        const uint64_t v3[3] = {v6[0], v6[1], v6[2]};
+                        bins.template push_batch<3>(b3, v3, all3, lost);
+                    }
+                } else if constexpr (!half_rounds) bins.template push_batch<8>(eb, ev, eok, lost);
                 else {  // 512 bins: a ring holds 32 entries, so the in-edges and the out-edges of a position go in two rounds
                     uint32_t b4[4];
                     uint64_t v4[4];
@@ -402,16 +437,29 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
             if constexpr (half_rounds) {  // (uniform: every lane reaches both flushes of the position)
                 bins.template flush<false>(lost);
                 if (probing) {
-                    uint32_t b4[4];
-                    uint64_t v4[4];
-                    bool o4[4];
+                    if constexpr (PUSH6) {
+                        const uint32_t b3[3] = {b6[3], b6[4], b6[5]};
+                        const uint64_t v3[3] = {v6[3], v6[4], v6[5]};
+                        bins.template push_batch<3>(b3, v3, all3, lost);
+                    } else {
+                        uint32_t b4[4];
+                        uint64_t v4[4];
+                        bool o4[4];
 #pragma unroll
-                    for (int c = 0; c < 4; c++) { b4[c] = eb[4 + c]; v4[c] = ev[4 + c]; o4[c] = eok[4 + c]; }
-                    bins.template push_batch<4>(b4, v4, o4, lost);
+                        for (int c = 0; c < 4; c++) { b4[c] = eb[4 + c]; v4[c] = ev[4 + c]; o4[c] = eok[4 + c]; }
+                        bins.template push_batch<4>(b4, v4, o4, lost);
+                    }
                 }
             }
             if (s + 1 < QH_RUN) {  // roll: VertexRollingHash::Update (vertexrollinghash.h:104-113), function 0
-                const uint4 en = reinterpret_cast<const uint4 *>(s_roll)[cn], ef = reinterpret_cast<const uint4 *>(s_roll)[5 + cf];
+                uint4 en, ef;  // {h[cn], hk[rc cn]}, {hk[cf], h[rc cf]}
+                if ((PUSH6 || !SHARDED) && (mode & QH_ROLL_S)) {  // (every sharded eight-push instantiation keeps the reads: its !HALF, LHI form spilled 8 more bytes with the selects; launch_qhash clears the bit)
+                    pick(cn, h0l, hk0l, en.x, en.z); pick(cf, hk0l, h0l, ef.x, ef.z);
+                    en.y = en.w = ef.y = ef.w = 0u;
+                    if constexpr (LHI) { pick(cn, h0h, hk0h, en.y, en.w); pick(cf, hk0h, h0h, ef.y, ef.w); }
+                } else {
+                    en = reinterpret_cast<const uint4 *>(s_roll)[cn]; ef = reinterpret_cast<const uint4 *>(s_roll)[5 + cf];
+                }
                 pos = lv_xor<LHI>(lv_xor<LHI>(r1p, en.x, en.y), ef.x, ef.y);
                 neg = R.rotr1(lv_xor<LHI>(lv_xor<LHI>(neg, en.z, en.w), ef.z, ef.w));
                 ncnt += (int)(cn >> 2) - (int)(cf >> 2);
@@ -1532,24 +1580,32 @@ void launch_qhash(const TpcLaunch &a, const TpcQPlan &pl, bool gated, uint64_t l
     const bool rb = q_use_rbins(pl.b1);
     // the instruction-lean kernel: flush-per-round bins (two rounds per position at 512 bins), a 24-bit slice index
     const bool lean = pl.b1 <= 9 && pl.sub_rounds <= 2 && perm.F <= 24 && !TpcEnv::get().no_lean && !(rb && TpcEnv::get().rb_hash);
-    if (a.stat_kernel) a.stat_kernel[1] = lean ? 1 : 2;
+    if (a.stat_kernel) { a.stat_kernel[1] = lean ? 1 : 2; a.stat_kernel[3] = 0; }
     if (lean) {
         const size_t lds = Bins3<uint64_t, QH_THREADS>::lds_bytes(pl.b1) + (size_t)(PT_THREADS + 1 + TPC_XW_MAX) * 12 + 160 + (size_t)QT_MAXK * 80 + 64;
-#define TPC_QHASH2_GO(G, S, H, X)                                                                                                           \
+        const uint32_t mode = tpc_qhash_roll_scalars() && (tpc_qhash_compact() || pl.world == 1) ? QH_ROLL_S : 0u;
+        if (a.stat_kernel) a.stat_kernel[3] = (tpc_qhash_compact() ? 1 : 0) | (mode & QH_ROLL_S ? 2 : 0) | (gated ? 4 : 0);  // "query_hash_form"
+#define TPC_QHASH2_GO(G, S, H, X, C)                                                                                                          \
     do {                                                                                                                                    \
-        (void)hipFuncSetAttribute((const void *)k_q_hash2<G, S, H, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
-        hipLaunchKernelGGL((k_q_hash2<G, S, H, X>), dim3(pl.nwg1), dim3(QH_THREADS), lds, a.stream, pl.b1, a.P, a.tab, a.bases, a.nmask, a.n_text, \
+        (void)hipFuncSetAttribute((const void *)k_q_hash2<G, S, H, X, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
+        hipLaunchKernelGGL((k_q_hash2<G, S, H, X, C>), dim3(pl.nwg1), dim3(QH_THREADS), lds, a.stream, pl.b1, a.P, a.tab, a.bases, a.nmask, a.n_text, \
                            pl.tile0, pl.n_tiles, pl.pos_per_round, lo, hi, pl.buf1, pl.cnt1, pl.cap1, ovf, perm, sh,                          \
                            pl.tile0_global * (uint64_t)(PT_THREADS * TPC_RUN), rmask, pl.fmt == 6 ? pl.tiles_per_wg : 0u,                  \
-                           reinterpret_cast<const uint16_t *>(a.per_qs));  /* (global word index: the sharded variants skip too) */          \
+                           reinterpret_cast<const uint16_t *>(a.per_qs), /* (global word index: the sharded variants skip too) */           \
+                           mode);                                                                                                          \
     } while (0)
-#define TPC_QHASH2_GS(H, X)                                                                                                                 \
+#define TPC_QHASH2_GS(H, X, C)                                                                                                              \
     do {                                                                                                                                    \
-        if (pl.world > 1) { if (gated) TPC_QHASH2_GO(true, true, H, X); else TPC_QHASH2_GO(false, true, H, X); }                            \
-        else { if (gated) TPC_QHASH2_GO(true, false, H, X); else TPC_QHASH2_GO(false, false, H, X); }                                       \
+        if (pl.world > 1) { if (gated) TPC_QHASH2_GO(true, true, H, X, C); else TPC_QHASH2_GO(false, true, H, X, C); }                      \
+        else { if (gated) TPC_QHASH2_GO(true, false, H, X, C); else TPC_QHASH2_GO(false, false, H, X, C); }                                 \
     } while (0)
-        if (a.P.L > 32) { if (pl.b1 >= 9) TPC_QHASH2_GS(true, true); else TPC_QHASH2_GS(false, true); }
-        else { if (pl.b1 >= 9) TPC_QHASH2_GS(true, false); else TPC_QHASH2_GS(false, false); }
+#define TPC_QHASH2_HX(C)                                                                                                                    \
+    do {                                                                                                                                    \
+        if (a.P.L > 32) { if (pl.b1 >= 9) TPC_QHASH2_GS(true, true, C); else TPC_QHASH2_GS(false, true, C); }                               \
+        else { if (pl.b1 >= 9) TPC_QHASH2_GS(true, false, C); else TPC_QHASH2_GS(false, false, C); }                                        \
+    } while (0)
+        if (tpc_qhash_compact()) TPC_QHASH2_HX(true); else TPC_QHASH2_HX(false);
+#undef TPC_QHASH2_HX
 #undef TPC_QHASH2_GS
 #undef TPC_QHASH2_GO
         return;
