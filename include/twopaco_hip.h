@@ -324,7 +324,8 @@ int tpc_periodic_download(tpc_ctx *ctx, uint32_t *qs_host, uint32_t *planes_host
  *   tpc_shard_probe           answer probes against this rank's shard (hit_dev[i] = 0/1)
  *   tpc_shard_mark            set the candidate mark of every id in sid_dev (all q probes hit)
  *   tpc_shard_route           owner-major send order for `n` probes: perm_dev[i] = slot of item i, counts_host[r] =
- *                             items for rank r (the grouping a host language would do with a sort; world <= 64)
+ *                             items for rank r (the grouping a host language would do with a sort; world <= 64).  An owner
+ *                             outside [0, world) is an error ("counted x of n items"): perm_dev is then not written
  *   tpc_shard_permute64       dst[perm[i]] = src[i] (the addresses into send order)
  *   tpc_shard_select          the ids of sid_dev whose fn_count answers are all 1; hit_dev holds the answers in SEND
  *                             order (owners answer in the order they were asked), sid_out_dev / *n_out the kept ids
@@ -376,7 +377,11 @@ int tpc_shard_survivors(tpc_ctx *ctx, uint64_t *sid_dev);
  *                             natural order is the send order; tmp_dev and perm_dev are not used (pass perm_dev = NULL on)
  *   tpc_shard_finish          last round of a batch: the candidate mark of every survivor whose fn_count answers (hit_dev, in send
  *                             order; perm_dev NULL = natural order) are all 1 -- tpc_shard_select + tpc_shard_mark without the list
- *                             in between; *n_marked = how many passed.  tpc_shard_select takes perm_dev = NULL the same way. */
+ *                             in between; *n_marked = how many passed (survivors, not bits: an id given twice counts twice).
+ *                             tpc_shard_select takes perm_dev = NULL the same way.
+ *   Alignment: with perm_dev = NULL and fn_count = 4, tpc_shard_select and tpc_shard_finish read the four answers of a survivor as
+ *   one 32-bit word, so hit_dev must then be 4-byte aligned (any device allocation is; a pointer INTO a buffer of answers must be
+ *   taken at a multiple of four), and the answers must be the bytes 0 and 1 that tpc_shard_probe writes. */
 int tpc_shard_survivors_home(tpc_ctx *ctx, uint64_t *tmp_dev, uint64_t *send_dev, uint64_t *counts_host);
 int tpc_shard_verify_send(tpc_ctx *ctx, int fn, int fn_count, const uint64_t *sid_dev, uint64_t n, uint64_t *tmp_dev, uint64_t *send_dev, uint32_t *perm_dev,
                           uint64_t *counts_host);

@@ -627,8 +627,10 @@ int tpc_shard_route(tpc_ctx *c, const int32_t *owner_dev, uint64_t n, uint32_t *
     unsigned long long h[64], cur[64];
     HIPCHK(c, hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    unsigned long long acc = 0;
-    for (int i = 0; i < 64; i++) { cur[i] = acc; acc += h[i]; if ((uint32_t)i < c->sh_world) counts_host[i] = h[i]; }
+    unsigned long long acc = 0, inside = 0;
+    for (int i = 0; i < 64; i++) { cur[i] = acc; acc += h[i]; if ((uint32_t)i < c->sh_world) { counts_host[i] = h[i]; inside += h[i]; } }
+    // (the kernels take an owner mod 64: one outside the world would get slots no count reports)
+    if (inside != n) return fail(c, -1, "owner routing: counted %llu of %llu items (an owner outside the %u ranks)", inside, (unsigned long long)n, c->sh_world);
     HIPCHK(c, hipMemcpyAsync(d + 64, cur, sizeof cur, hipMemcpyHostToDevice, c->stream));
     tpc_launch_route(c->stream, owner_dev, n, d, d + 64, perm_dev, 1);
     HIPCHK(c, hipGetLastError());
