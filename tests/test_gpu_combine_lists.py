@@ -11,14 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from lists_reference import PERM_INV, PERM_MULT, WINDOW_BITS, assert_bits_are_filter, decode_export  # noqa: F401 (the wire format, stated once)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 LETTERS = np.frombuffer(b"ACGTN", dtype=np.uint8)
-# the slice permutation of the partitioned passes (csrc/tpc_bins.h:pt_make_perm): permuted slice sp lives at (sp * inverse) mod 2^F
-PERM_MULT = 0x9E3779B1
-PERM_INV = pow(PERM_MULT, -1, 1 << 32)
-WINDOW_BITS = 16
 
 
 @pytest.fixture(scope="module")
@@ -51,52 +48,6 @@ def _setup(capi, recs, k, L, q, seed, slice_bits, **opts):
     ctx.set_params(k, L, q, capi.seed_table(q, L, seed=seed))
     ctx.seq_upload(capi.PackedText.from_codes(recs))
     return ctx, o
-
-
-def decode_export(info, n_dest, L, payload, dirs, units):
-    """Filter addresses of every entry of an export, after checking the block layout: lists inside the used prefix of their block,
-    no two lists sharing a unit, offsets inside their window."""
-    sb, log_nb2, n_win, cap = info["slice_bits"], info["b2"], info["windows"], info["cap_units"]
-    F = L - sb
-    spd = info["slices"] // n_dest
-    assert dirs.size == info["slices"] * n_win
-    idx = np.arange(dirs.size, dtype=np.int64)
-    dest = idx // (spd * n_win)
-    key = (idx // n_win) % spd
-    win = idx % n_win
-    b1 = (key >> log_nb2) * n_dest + dest  # (the block of destination d holds the slices of the level-1 buckets b1 = d mod n_dest)
-    sp = (b1 << log_nb2) | (key & ((1 << log_nb2) - 1))
-    n = (dirs & 0xFFFFFF).astype(np.int64)
-    base = (dirs >> 24).astype(np.int64)
-    assert n.max(initial=0) <= 1 << min(sb, WINDOW_BITS)
-    live = n > 0
-    dest, win, sp, n, base = dest[live], win[live], sp[live], n[live], base[live]
-    ulen = (n + 7) // 8
-    used = np.asarray(units, dtype=np.int64)
-    assert (base + ulen <= used[dest]).all(), "a list beyond its block's used units"
-    order = np.lexsort((base, dest))
-    d_s, b_s, e_s = dest[order], base[order], (base + ulen)[order]
-    same = d_s[1:] == d_s[:-1]
-    assert (b_s[1:][same] >= e_s[:-1][same]).all(), "two lists share a unit"
-    total = int(n.sum())
-    first = np.cumsum(n) - n
-    at = np.repeat((dest * cap + base) * 8 - first, n) + np.arange(total, dtype=np.int64)
-    vals = payload[at].astype(np.int64)
-    assert (vals < (1 << min(sb, WINDOW_BITS))).all()
-    phys = (np.repeat(sp, n).astype(np.uint64) * np.uint64(PERM_INV)) & np.uint64((1 << F) - 1)
-    return (phys << np.uint64(sb)) | (np.repeat(win, n) * (1 << WINDOW_BITS) + vals).astype(np.uint64)
-
-
-def assert_bits_are_filter(addr, filt):
-    """The addresses, one per entry, are exactly the set bits of filt: per word, as many entries as set bits and their powers of two
-    summing to the word -- which also rules out any address listed twice (a sum of c powers of two has c bits only when they differ)."""
-    words = (addr >> np.uint64(5)).astype(np.int64)
-    bits = np.left_shift(np.uint64(1), addr & np.uint64(31)).astype(np.float64)
-    assert words.max(initial=0) < filt.size
-    cnt = np.bincount(words, minlength=filt.size)
-    sums = np.bincount(words, weights=bits, minlength=filt.size)
-    assert (cnt == np.bitwise_count(filt)).all(), "entries per filter word differ from its set bits"
-    assert (sums.astype(np.uint64) == filt.astype(np.uint64)).all(), "the lists are not the oracle's filter"
 
 
 def export_and_check(ctx, o, n_dest, L):
