@@ -65,7 +65,8 @@ enum {
     TPC_K_DISTANCES = 21,   /* tpc_segments_distances_build: bit columns, weight planes and the two colour x colour matrices (no counterpart in the reference) */
     TPC_K_COMPONENTS = 22,  /* tpc_segments_components_build: the union-find over the link rows, the numbering and the per-component sums (no counterpart in the reference) */
     TPC_K_SUPERBUBBLES = 23, /* tpc_segments_superbubbles_build: the adjacency lists, the bounded search per entrance and the report (no counterpart in the reference) */
-    TPC_K_COUNT = 24
+    TPC_K_ANCHORS = 24,     /* tpc_segments_anchors_build: the keys, their sort, mates, heads and tails, the blocks and the per-colour sums (no counterpart in the reference) */
+    TPC_K_COUNT = 25
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -775,6 +776,55 @@ int tpc_segments_superbubbles_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, 
                                          uint32_t *n_colors_host, uint64_t *paths_host, uint64_t *min_edges_host, uint64_t *max_edges_host);
 int tpc_segments_superbubbles_fetch_members(tpc_ctx *ctx, uint32_t *offsets_host /* [superbubbles + 1] */, uint32_t *sides_host /* [members] */);
 int tpc_segments_superbubbles_fetch_presence(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *words_host /* [n x W] */);
+
+/* The ANCHOR BLOCKS of the compacted graph (csrc/tpc_anchors.hip): where the sequence that a colour shares with a reference colour
+ * lies in both, in which order, on which strand, and where the match breaks -- a dot plot, a synteny view, a set of liftover
+ * anchors.  A block is an exact match, or an exact reverse-complement match, between two intervals in which every (k+1)-mer is unique
+ * on both sides: the kind of object MUMmer's maximal unique matches are, read off the graph.  No counterpart in the reference;
+ * ComputeAnchors of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The definition, over the
+ * event table of the last tpc_segments_build_*:
+ *   EVENT, ROW, COLOUR  those of the colour table: an event is one occurrence of a segment, a row one segment in first-sight order,
+ *                    the caller gives color_of_seq[s].  R is the reference colour.
+ *   COUNT            count[r][c] is the number of events of row r that lie in sequences of colour c.
+ *   ANCHOR           an event e of row r in colour c != R is an anchor when count[r][R] == 1 and count[r][c] == 1.
+ *   MATE             mate[e] of an anchor is the one event of r in colour R.  Events of colour R have no mate, non-anchors have none.
+ *   REVERSE          the anchor is reverse when name[e] and name[mate[e]] have different signs.
+ *   'N'-named segments (names >= 2^34) are rows of their own, so they are never anchors.
+ *   CONTINUES        an anchor e continues e - 1 when all of these hold: both events lie in the same sequence; e - 1 is an anchor with
+ *                    the same reverse flag; mate[e] == mate[e - 1] + 1 when forward, mate[e] == mate[e - 1] - 1 when reverse; both
+ *                    mates lie in the same reference sequence.  (Consecutive events of one sequence share their junction:
+ *                    end[e - 1] == begin[e].)
+ *   BLOCK            a maximal run query_first .. query_last of anchors in which each one continues the one before it.  Its reference
+ *                    events ref_first .. ref_last ascend: forward they are mate[query_first] .. mate[query_last], reverse they are
+ *                    mate[query_last] .. mate[query_first].  Query interval [begin[query_first], end[query_last] + k), reference
+ *                    interval [begin[ref_first], end[ref_last] + k): both have the same length.  anchors = query_last - query_first
+ *                    + 1, edges = end[query_last] - begin[query_first].  Blocks are reported ascending by query_first.
+ *   PER COLOUR c != R  blocks[c], anchors[c], edges[c] and reverse_edges[c], the edges of the reverse blocks; colour R's entries are 0.
+ *                    The edge sums are 64-bit.
+ *   REF EDGES        the sum of end - begin over all events of colour R.
+ *   SELF-REVERSE-COMPLEMENT segments are treated like any other: their strand is what the names say.
+ *   EXACT            integers with commutative sums: the arrays do not depend on the schedule.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this, tpc_segments_counts reports what it
+ * reported before, and the other tables are what they were, in any order of the builds.
+ *   tpc_segments_anchors_build         one key row << bits | colour per event, one radix sort over the key bits in use, the runs of
+ *                                      equal keys give count == 1 on both sides and the mates, one thread per event evaluates the
+ *                                      continue rule, one scan numbers the blocks.  Refused with an error text: no segment table, a
+ *                                      table whose tpc_segments_error kind is not TPC_SEG_OK, n_colors == 0, a colour >= n_colors,
+ *                                      ref_color >= n_colors, buffers beyond the free device memory; the context stays usable.  Kept
+ *                                      until the next segment build or anchor build: 4 B per event of mates, 16 B per block, 32 B per
+ *                                      colour.  TPC_K_ANCHORS times the stage on the stream from its first kernel to its last, the
+ *                                      host's one wait for the block count included.
+ *   tpc_segments_anchors_info          info[0] blocks, [1] anchors, [2] colours, [3] the reference colour, [4] ref_edges, [5] the
+ *                                      stage's device bytes at their peak
+ *   tpc_segments_anchors_fetch_mates   mate[] of events [e0, e0 + n), 0xFFFFFFFF standing for none
+ *   tpc_segments_anchors_fetch_rows    query_first / query_last / ref_first / ref_last of blocks [b0, b0 + n)
+ *   tpc_segments_anchors_fetch_shared  the four per-colour sums, n_colors entries each
+ * A range outside a table is refused with an error text. */
+int tpc_segments_anchors_build(tpc_ctx *ctx, const uint32_t *color_of_seq /* [n_rec] */, uint32_t n_colors, uint32_t ref_color);
+int tpc_segments_anchors_info(tpc_ctx *ctx, uint64_t *info /* [6] */);
+int tpc_segments_anchors_fetch_mates(tpc_ctx *ctx, uint64_t e0, uint64_t n, uint32_t *mate_host);
+int tpc_segments_anchors_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *query_first, uint32_t *query_last, uint32_t *ref_first, uint32_t *ref_last);
+int tpc_segments_anchors_fetch_shared(tpc_ctx *ctx, uint64_t *blocks, uint64_t *anchors, uint64_t *edges, uint64_t *reverse_edges /* [n_colors] each */);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

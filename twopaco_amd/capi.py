@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22, "superbubbles": 23}
+           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -39,7 +39,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_components_build", "tpc_segments_components_info", "tpc_segments_components_fetch_members", "tpc_segments_components_fetch_rows",
                "tpc_segments_components_fetch_presence",
                "tpc_segments_superbubbles_build", "tpc_segments_superbubbles_info", "tpc_segments_superbubbles_fetch_adjacency", "tpc_segments_superbubbles_fetch_exits",
-               "tpc_segments_superbubbles_fetch_rows", "tpc_segments_superbubbles_fetch_members", "tpc_segments_superbubbles_fetch_presence"]
+               "tpc_segments_superbubbles_fetch_rows", "tpc_segments_superbubbles_fetch_members", "tpc_segments_superbubbles_fetch_presence",
+               "tpc_segments_anchors_build", "tpc_segments_anchors_info", "tpc_segments_anchors_fetch_mates", "tpc_segments_anchors_fetch_rows",
+               "tpc_segments_anchors_fetch_shared"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -196,6 +198,11 @@ def hip():
         L.tpc_segments_superbubbles_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p, p, p, p]
         L.tpc_segments_superbubbles_fetch_members.argtypes = [p, p, p]
         L.tpc_segments_superbubbles_fetch_presence.argtypes = [p, u64, u64, p]
+        L.tpc_segments_anchors_build.argtypes = [p, p, ctypes.c_uint32, ctypes.c_uint32]
+        L.tpc_segments_anchors_info.argtypes = [p, p]
+        L.tpc_segments_anchors_fetch_mates.argtypes = [p, u64, u64, p]
+        L.tpc_segments_anchors_fetch_rows.argtypes = [p, u64, u64, p, p, p, p]
+        L.tpc_segments_anchors_fetch_shared.argtypes = [p, p, p, p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -870,6 +877,39 @@ class Context:
         out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
         self._ck(hip().tpc_segments_superbubbles_fetch_presence(self._h, b0, n, out.ctypes.data))
         return out
+
+    def segments_anchors_build(self, color_of_seq, n_colors, ref_color=0):
+        """The anchor blocks (csrc/tpc_anchors.hip) of every other colour against ref_color, over the table of the last segments_build,
+        whose error must be None: color_of_seq[s] in [0, n_colors) for every sequence of that build.  Returns segments_anchors_info()."""
+        col = np.ascontiguousarray(color_of_seq, dtype=np.uint32)
+        self._ck(hip().tpc_segments_anchors_build(self._h, col.ctypes.data if col.size else None, n_colors, ref_color))
+        return self.segments_anchors_info()
+
+    def segments_anchors_info(self):
+        """dict: blocks, anchors, colors, ref_color, ref_edges, peak_bytes (device memory of the stage)."""
+        c = np.zeros(6, dtype=np.uint64)
+        self._ck(hip().tpc_segments_anchors_info(self._h, c.ctypes.data))
+        return dict(zip(("blocks", "anchors", "colors", "ref_color", "ref_edges", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_anchors_fetch_mates(self, e0=0, n=None):
+        """mate[] of events [e0, e0 + n) as uint32, all ones for none; n = None: to the last event."""
+        n = self.segments_counts()["events"] - e0 if n is None else n
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_anchors_fetch_mates(self._h, e0, n, out.ctypes.data))
+        return out
+
+    def segments_anchors_fetch_rows(self, b0=0, n=None):
+        """(query_first, query_last, ref_first, ref_last) of blocks [b0, b0 + n) as uint32 event indices; n = None: to the last block."""
+        n = self.segments_anchors_info()["blocks"] - b0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(4)]
+        self._ck(hip().tpc_segments_anchors_fetch_rows(self._h, b0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_anchors_fetch_shared(self):
+        """(blocks, anchors, edges, reverse_edges) per colour as uint64 [colors]; the reference colour's entries are 0."""
+        out = [np.zeros(self.segments_anchors_info()["colors"], dtype=np.uint64) for _ in range(4)]
+        self._ck(hip().tpc_segments_anchors_fetch_shared(self._h, *[a.ctypes.data for a in out]))
+        return tuple(out)
 
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))

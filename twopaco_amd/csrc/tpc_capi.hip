@@ -339,6 +339,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
     stream_part_release(c);
     colors_drop(c);
     links_drop(c);
+    anchors_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);

@@ -10,7 +10,8 @@
 //   tpc_distances.hip     the genome distance matrices over the colour table (tpc_segments_distances_*), kernels and entry points
 //   tpc_components.hip    the connected components over the link and colour tables (tpc_segments_components_*), kernels and entry points
 //   tpc_superbubbles.hip  the bounded superbubbles over the link and colour tables (tpc_segments_superbubbles_*), kernels and entry points
-//   tpc_stage.h           what the six stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
+//   tpc_anchors.hip       the anchor blocks against a reference colour (tpc_segments_anchors_*), kernels and entry points
+//   tpc_stage.h           what the seven stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
 //   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
@@ -97,7 +98,7 @@ struct tpc_ctx {
     uint64_t *sp_rec = nullptr, *sp_vscan = nullptr, *sp_cnt = nullptr, *sp_lo = nullptr;
     uint32_t *sp_flags = nullptr;
     uint32_t sp_n_rec = 0;
-    // The tables of the compacted graph, one group each.  A group's drop (tpc_capi_segments.hip: segments_drop ... superbubbles_drop) frees
+    // The tables of the compacted graph, one group each.  A group's drop (tpc_capi_segments.hip: segments_drop ... anchors_drop) frees
     // its pointers, assigns {} and drops what was built over it.
     // segment table (tpc_segments_*, tpc_capi_segments.hip): name[e], first[] bit-packed and the event table, of the last build
     struct Segments {
@@ -180,6 +181,15 @@ struct tpc_ctx {
         uint32_t words = 0, max_inside = 0;
         bool valid = false;
     } sbb;
+    // anchor blocks (tpc_segments_anchors_*, tpc_anchors.hip) of the last tpc_segments_anchors_build
+    struct Anchors {
+        uint32_t *mate = nullptr;            // device, [n_events]: the mate of every anchor, all ones for none
+        uint32_t *rows = nullptr;            // device, [4][n_blocks]: query_first, query_last, ref_first, ref_last
+        unsigned long long *sums = nullptr;  // device, [4][n_colors]: blocks, anchors, edges, reverse_edges; then ref_edges
+        uint64_t n_blocks = 0, n_anchors = 0, n_events = 0, ref_edges = 0, peak_bytes = 0;
+        uint32_t n_colors = 0, ref_color = 0;
+        bool valid = false;
+    } anc;
     int opt_components_step_limit = 0;       // option test_components_step_limit (tests only): steps of a find and retries of a hook, 0 = segments + 1
     int opt_distances_chunk_words = 0;       // option test_distances_chunk_words (tests only): column words a block stages at once, 0 = the kernel's own
     // scalars
@@ -296,12 +306,13 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these six and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these seven and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
 void components_drop(tpc_ctx *c);
 void superbubbles_drop(tpc_ctx *c);
+void anchors_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -39,7 +39,11 @@
 // graph, bounded to N sides inside (2 .. 62, default 62) -- where the genomes differ beyond two alleles -- as TSV of integers, byte
 // for byte what `graphdump --superbubbles` writes, and asked for, the inside sides of every row (csrc/tpc_superbubbles.hip finds them
 // on the device over the link build and the colour build; combines with everything above from one segment, colour and link build;
-// the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// the other tables must name the same colours; its files are written after the component files);
+// --anchors file|sequence [--anchors-ref N] [--anchors-out F] [--anchors-paf F]: the anchor blocks of every other colour against the
+// reference colour N (default 0) -- unique collinear matches, forward or reverse-complement -- as TSV, byte for byte what `graphdump
+// --anchors` writes, and asked for, as PAF (csrc/tpc_anchors.hip finds them on the device over the event table of the same segment
+// build; combines with everything above; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -100,6 +104,7 @@ namespace
 			<< "               [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>]" << std::endl
 			<< "               [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>]" << std::endl
 			<< "               [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>]" << std::endl
+			<< "               [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -141,7 +146,13 @@ namespace
 			<< "               Per row entrance and exit, the sides inside, arcs, paths, the smallest and largest path weight in edges and the" << std::endl
 			<< "               colours over the inside (by file or by sequence, as --colors).  --superbubbles-members: also the inside sides of" << std::endl
 			<< "               every row.  --superbubbles-max: the largest inside reported, 2 .. 62 (default 62).  Combines with --graph," << std::endl
-			<< "               --graph-compact, --colors, --bubbles, --distances and --components (the same colours), --links and -o.  One GPU only." << std::endl;
+			<< "               --graph-compact, --colors, --bubbles, --distances and --components (the same colours), --links and -o.  One GPU only." << std::endl
+			<< "       --anchors: also write the anchor blocks against the reference colour --anchors-ref (default 0) as TSV to --anchors-out (default" << std::endl
+			<< "               de_bruijn.anchors.tsv): a segment that occurs exactly once in the reference and exactly once in another colour (by" << std::endl
+			<< "               file or by sequence, as --colors) is an anchor, anchors that follow each other in both are chained into maximal" << std::endl
+			<< "               collinear blocks, exact matches or exact reverse-complement matches between two intervals.  --anchors-paf: also the" << std::endl
+			<< "               blocks as PAF.  Combines with --graph, --graph-compact, --colors, --bubbles, --distances, --components and" << std::endl
+			<< "               --superbubbles (the same colours), --links and -o.  One GPU only." << std::endl;
 	}
 }
 
@@ -182,7 +193,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false, anchorsOutSet = false, anchorsPafSet = false, anchorsRefSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -299,6 +310,23 @@ int main(int argc, char * argv[])
 				if (v.empty() || *end || n < 2 || n > 62) throw ArgError("Value '" + v + "' does not meet constraint: an integer 2 .. 62", "(--superbubbles-max)");
 				options.superbubblesMax = uint32_t(n);
 				superbubblesMaxSet = true;
+			}
+			else if (Match(a, 0, "anchors"))
+			{
+				options.anchorsBy = value("(--anchors)");
+				if (options.anchorsBy != "file" && options.anchorsBy != "sequence") throw ArgError("Value '" + options.anchorsBy + "' does not meet constraint: file|sequence", "(--anchors)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "anchors-out")) { options.anchorsFile = value("(--anchors-out)"); anchorsOutSet = true; }
+			else if (Match(a, 0, "anchors-paf")) { options.anchorsPafFile = value("(--anchors-paf)"); anchorsPafSet = true; }
+			else if (Match(a, 0, "anchors-ref"))
+			{
+				const std::string v = value("(--anchors-ref)");
+				char * end = 0;
+				const long long n = std::strtoll(v.c_str(), &end, 10);
+				if (v.empty() || *end || n < 0 || n > 0x7FFFFFFFll) throw ArgError("Value '" + v + "' does not meet constraint: a colour index", "(--anchors-ref)");
+				options.anchorsRef = uint32_t(n);
+				anchorsRefSet = true;
 			}
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
@@ -419,6 +447,24 @@ int main(int argc, char * argv[])
 		else if (superbubblesOutSet || superbubblesMembersSet || superbubblesMaxSet)
 		{
 			throw ArgError("This argument needs --superbubbles <file|sequence>", superbubblesOutSet ? "(--superbubbles-out)" : superbubblesMembersSet ? "(--superbubbles-members)" : "(--superbubbles-max)");
+		}
+
+		if (!options.anchorsBy.empty())
+		{
+			if (options.gpus > 1) throw ArgError("The anchor table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--anchors)");
+			if (!options.colorsBy.empty() && options.colorsBy != options.anchorsBy) throw ArgError("The anchor table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
+			if (!options.bubblesBy.empty() && options.bubblesBy != options.anchorsBy) throw ArgError("The anchor table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
+			if (!options.distancesBy.empty() && options.distancesBy != options.anchorsBy) throw ArgError("The anchor table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
+			if (!options.componentsBy.empty() && options.componentsBy != options.anchorsBy) throw ArgError("The anchor table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
+			if (!options.superbubblesBy.empty() && options.superbubblesBy != options.anchorsBy) throw ArgError("The anchor table and the superbubble table share one set of colours: --superbubbles " + options.superbubblesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
+			if (!anchorsOutSet) options.anchorsFile = "de_bruijn.anchors.tsv";
+			if (options.anchorsFile.empty()) throw ArgError("The anchor table needs a file name", "(--anchors-out)");
+			if (anchorsPafSet && options.anchorsPafFile.empty()) throw ArgError("The anchor PAF needs a file name", "(--anchors-paf)");
+			if (options.anchorsBy == "file" && options.anchorsRef >= fileName.size()) throw ArgError("Value '" + std::to_string(options.anchorsRef) + "' does not meet constraint: a colour index below " + std::to_string(fileName.size()), "(--anchors-ref)");
+		}
+		else if (anchorsOutSet || anchorsPafSet || anchorsRefSet)
+		{
+			throw ArgError("This argument needs --anchors <file|sequence>", anchorsOutSet ? "(--anchors-out)" : anchorsPafSet ? "(--anchors-paf)" : "(--anchors-ref)");
 		}
 
 		if (runTests)

@@ -26,7 +26,8 @@
 	X(segments_components_build) X(segments_components_info) X(segments_components_fetch_members) X(segments_components_fetch_rows) \
 	X(segments_components_fetch_presence) \
 	X(segments_superbubbles_build) X(segments_superbubbles_info) X(segments_superbubbles_fetch_rows) X(segments_superbubbles_fetch_members) \
-	X(segments_superbubbles_fetch_presence)
+	X(segments_superbubbles_fetch_presence) \
+	X(segments_anchors_build) X(segments_anchors_info) X(segments_anchors_fetch_mates) X(segments_anchors_fetch_rows) X(segments_anchors_fetch_shared)
 
 namespace TwoPaCo
 {
@@ -251,6 +252,39 @@ namespace TwoPaCo
 				out.paths.data(), out.minEdges.data(), out.maxEdges.data()), "segments_superbubbles_fetch_rows");
 			api.check(api.segments_superbubbles_fetch_members(api.ctx, out.memberOffset.data(), out.members.data()), "segments_superbubbles_fetch_members");
 			api.check(api.segments_superbubbles_fetch_presence(api.ctx, 0, n, out.presence.data()), "segments_superbubbles_fetch_presence");
+			return true;
+		}
+
+		// The anchor blocks (csrc/tpc_anchors.hip): the events of the table on the device paired with the reference colour's and chained there.
+		inline void BuildAnchors(const Api & api, const GraphFormat::ColorMap & map, uint32_t ref)
+		{
+			api.check(api.segments_anchors_build(api.ctx, map.colorOfSequence.data(), uint32_t(map.label.size()), ref), "segments_anchors_build");
+		}
+
+		// ... fetched: the mates, the blocks and the per-colour sums.  false, and nothing fetched, when the stage saw other colours than
+		// the caller
+		inline bool FetchAnchors(const Api & api, const GraphFormat::ColorMap & map, uint64_t events, uint64_t segments, GraphFormat::AnchorTable & out)
+		{
+			uint64_t info[6] = {0, 0, 0, 0, 0, 0};
+			api.check(api.segments_anchors_info(api.ctx, info), "segments_anchors_info");
+			if (info[2] != map.label.size()) return false;
+			const size_t n = size_t(info[0]);
+			out.colors = info[2];
+			out.ref = uint32_t(info[3]);
+			out.refEdges = info[4];
+			out.segments = segments;
+			out.mate.resize(size_t(events));
+			out.queryFirst.resize(n);
+			out.queryLast.resize(n);
+			out.refFirst.resize(n);
+			out.refLast.resize(n);
+			out.blocks.resize(size_t(out.colors));
+			out.anchors.resize(size_t(out.colors));
+			out.edges.resize(size_t(out.colors));
+			out.reverseEdges.resize(size_t(out.colors));
+			api.check(api.segments_anchors_fetch_mates(api.ctx, 0, events, out.mate.data()), "segments_anchors_fetch_mates");
+			api.check(api.segments_anchors_fetch_rows(api.ctx, 0, n, out.queryFirst.data(), out.queryLast.data(), out.refFirst.data(), out.refLast.data()), "segments_anchors_fetch_rows");
+			api.check(api.segments_anchors_fetch_shared(api.ctx, out.blocks.data(), out.anchors.data(), out.edges.data(), out.reverseEdges.data()), "segments_anchors_fetch_shared");
 			return true;
 		}
 	}

@@ -1343,6 +1343,206 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeAnchors(const EventTable & t, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t colors, uint32_t ref, AnchorTable & out)
+		{
+			(void)k;
+			if (colors == 0) throw std::runtime_error("anchor table: at least one colour is required");
+			if (ref >= colors) throw std::runtime_error("anchor table: the reference colour is " + std::to_string(ref) + ", there are " + std::to_string(colors) + " colours");
+			if (colorOfSequence.size() != t.sequences) throw std::runtime_error("anchor table: the colour of every sequence is required");
+			for (uint32_t c : colorOfSequence)
+			{
+				if (c >= colors) throw std::runtime_error("anchor table: a sequence has the colour " + std::to_string(c) + ", there are " + std::to_string(colors) + " colours");
+			}
+
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			out = AnchorTable();
+			out.colors = colors;
+			out.ref = ref;
+			const uint32_t NONE = AnchorTable::NONE;
+			const int64_t FRESH = int64_t(1) << 34;
+			// the row, the sequence and the colour of every event; count[row][colour] with the last event counted
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			std::vector<uint32_t> rowOfEvent(size_t(t.events)), seqOfEvent(size_t(t.events));
+			std::map<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint32_t> > count;
+			uint32_t sequence = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator seen = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				if (seen == rowOf.end())
+				{
+					if (name < FRESH) rowOf[name] = uint32_t(out.segments);
+					rowOfEvent[e] = uint32_t(out.segments++);
+				}
+				else rowOfEvent[e] = seen->second;
+
+				seqOfEvent[e] = sequence;
+				std::pair<uint64_t, uint32_t> & held = count[std::make_pair(rowOfEvent[e], colorOfSequence[sequence])];
+				held.first += 1;
+				held.second = uint32_t(e);
+				if (colorOfSequence[sequence] == ref) out.refEdges += uint64_t(t.end[e]) - t.begin[e];
+			}
+
+			out.mate.assign(size_t(t.events), NONE);
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				const uint32_t c = colorOfSequence[seqOfEvent[e]];
+				if (c == ref || count[std::make_pair(rowOfEvent[e], c)].first != 1) continue;
+				std::map<std::pair<uint32_t, uint32_t>, std::pair<uint64_t, uint32_t> >::const_iterator inRef = count.find(std::make_pair(rowOfEvent[e], ref));
+				if (inRef != count.end() && inRef->second.first == 1) out.mate[e] = inRef->second.second;
+			}
+
+			auto reverse = [&](uint64_t e) { return (t.name[e] < 0) != (t.name[out.mate[e]] < 0); };
+			auto continues = [&](uint64_t e)
+			{
+				if (e == 0 || out.mate[e] == NONE || out.mate[e - 1] == NONE || seqOfEvent[e] != seqOfEvent[e - 1] || reverse(e) != reverse(e - 1)) return false;
+				const uint64_t m = out.mate[e], before = out.mate[e - 1];
+				return (reverse(e) ? m + 1 == before : m == before + 1) && seqOfEvent[m] == seqOfEvent[before];
+			};
+
+			out.blocks.assign(colors, 0);
+			out.anchors.assign(colors, 0);
+			out.edges.assign(colors, 0);
+			out.reverseEdges.assign(colors, 0);
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				if (out.mate[e] == NONE || continues(e)) continue;
+				uint64_t last = e;
+				while (last + 1 < t.events && continues(last + 1)) ++last;
+				const bool rev = reverse(e);
+				out.queryFirst.push_back(uint32_t(e));
+				out.queryLast.push_back(uint32_t(last));
+				out.refFirst.push_back(rev ? out.mate[last] : out.mate[e]);
+				out.refLast.push_back(rev ? out.mate[e] : out.mate[last]);
+				const uint32_t c = colorOfSequence[seqOfEvent[e]];
+				const uint64_t edges = uint64_t(t.end[last]) - t.begin[e];
+				out.blocks[c] += 1;
+				out.anchors[c] += last - e + 1;
+				out.edges[c] += edges;
+				if (rev) out.reverseEdges[c] += edges;
+			}
+		}
+
+		namespace
+		{
+			// one block as the writers print it: colour, strand, and on each side the sequence and the half-open interval
+			struct AnchorLine
+			{
+				uint32_t color, refSeq, querySeq;
+				uint64_t refBegin, refEnd, queryBegin, queryEnd, anchors;
+				bool reverse;
+			};
+
+			void CheckAnchors(const EventTable & t, const ColorMap & map, const InputSequences & seq, const AnchorTable & a)
+			{
+				const size_t n = a.Rows();
+				if (a.queryLast.size() != n || a.refFirst.size() != n || a.refLast.size() != n || a.mate.size() != t.events || a.blocks.size() != a.colors ||
+					a.anchors.size() != a.colors || a.edges.size() != a.colors || a.reverseEdges.size() != a.colors || map.label.size() != a.colors || a.ref >= a.colors)
+				{
+					throw std::runtime_error("anchor table: the arrays do not agree about the blocks, the events and the colours");
+				}
+
+				if (map.colorOfSequence.size() != t.sequences || seq.name.size() != t.sequences || seq.length.size() != t.sequences)
+				{
+					throw std::runtime_error("anchor table: the colour, the name and the length of every sequence are required");
+				}
+
+				if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+				for (size_t b = 0; b < n; b++)
+				{
+					if (a.queryFirst[b] > a.queryLast[b] || a.queryLast[b] >= t.events || a.refFirst[b] > a.refLast[b] || a.refLast[b] >= t.events ||
+						a.refLast[b] - a.refFirst[b] != a.queryLast[b] - a.queryFirst[b] || a.mate[a.queryFirst[b]] >= t.events)
+					{
+						throw std::runtime_error("anchor table: a block lies outside the event table");
+					}
+				}
+			}
+
+			AnchorLine MakeAnchorLine(const EventTable & t, size_t k, const ColorMap & map, const AnchorTable & a, size_t b)
+			{
+				auto sequenceOf = [&](uint32_t e) { return uint32_t(std::upper_bound(t.seqEventBegin, t.seqEventBegin + t.sequences + 1, e) - t.seqEventBegin - 1); };
+				AnchorLine line;
+				const uint32_t qf = a.queryFirst[b], ql = a.queryLast[b], rf = a.refFirst[b], rl = a.refLast[b];
+				line.querySeq = sequenceOf(qf);
+				line.refSeq = sequenceOf(rf);
+				line.color = map.colorOfSequence[line.querySeq];
+				line.reverse = (t.name[qf] < 0) != (t.name[a.mate[qf]] < 0);
+				line.queryBegin = t.begin[qf];
+				line.queryEnd = uint64_t(t.end[ql]) + k;
+				line.refBegin = t.begin[rf];
+				line.refEnd = uint64_t(t.end[rl]) + k;
+				line.anchors = uint64_t(ql) - qf + 1;
+				return line;
+			}
+		}
+
+		void WriteAnchors(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & a, const std::string & path)
+		{
+			CheckAnchors(t, map, seq, a);
+			WriteStreamed(path, "anchor table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-anchors\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(a.colors) +
+					"\tsegments=" + std::to_string(a.segments) + "\tref=" + std::to_string(a.ref) + "\tref_edges=" + std::to_string(a.refEdges) + "\tblocks=" +
+					std::to_string(a.Rows()) + "\n";
+				for (uint64_t c = 0; c < a.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+				for (size_t s = 0; s < seq.name.size(); s++)
+				{
+					buf += "#sequence\t" + std::to_string(s) + "\t" + std::to_string(map.colorOfSequence[s]) + "\t" + std::to_string(seq.length[s]) + "\t" + seq.name[s] + "\n";
+					flushIfLarge();
+				}
+
+				for (uint64_t c = 0; c < a.colors; c++)
+				{
+					if (c == a.ref) continue;
+					buf += "#shared\t" + std::to_string(c) + "\t" + std::to_string(a.blocks[c]) + "\t" + std::to_string(a.anchors[c]) + "\t" + std::to_string(a.edges[c]) + "\t" +
+						std::to_string(a.reverseEdges[c]) + "\n";
+				}
+
+				for (size_t b = 0; b < a.Rows(); b++)
+				{
+					const AnchorLine line = MakeAnchorLine(t, k, map, a, b);
+					buf += std::to_string(line.color) + "\t" + std::to_string(line.refSeq) + "\t" + std::to_string(line.refBegin) + "\t" + std::to_string(line.refEnd) + "\t" +
+						(line.reverse ? "-" : "+") + "\t" + std::to_string(line.querySeq) + "\t" + std::to_string(line.queryBegin) + "\t" + std::to_string(line.queryEnd) + "\t" +
+						std::to_string(line.anchors) + "\n";
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteAnchorsPaf(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & a, const std::string & path)
+		{
+			CheckAnchors(t, map, seq, a);
+			if (path.empty()) throw std::runtime_error("The anchor PAF needs a file name");
+			WriteStreamed(path, "anchor PAF", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				for (size_t b = 0; b < a.Rows(); b++)
+				{
+					const AnchorLine line = MakeAnchorLine(t, k, map, a, b);
+					const std::string length = std::to_string(line.queryEnd - line.queryBegin);
+					buf += seq.name[line.querySeq] + "\t" + std::to_string(seq.length[line.querySeq]) + "\t" + std::to_string(line.queryBegin) + "\t" + std::to_string(line.queryEnd) + "\t" +
+						(line.reverse ? "-" : "+") + "\t" + seq.name[line.refSeq] + "\t" + std::to_string(seq.length[line.refSeq]) + "\t" + std::to_string(line.refBegin) + "\t" +
+						std::to_string(line.refEnd) + "\t" + length + "\t" + length + "\t255\ttp:A:P\tcg:Z:" + length + "=\tan:i:" + std::to_string(line.anchors) + "\n";
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteAnchorFiles(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & a, const std::string & path,
+			const std::string & pafPath)
+		{
+			if (!pafPath.empty()) WriteAnchorsPaf(t, k, map, seq, a, pafPath);
+			try
+			{
+				WriteAnchors(t, k, map, seq, a, path);
+			}
+			catch (...)
+			{
+				if (!pafPath.empty()) ::unlink(pafPath.c_str());
+				throw;
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{

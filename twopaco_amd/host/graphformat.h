@@ -554,6 +554,53 @@ namespace TwoPaCo
 		void WriteSuperbubbleFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & superbubbles,
 			const std::string & path, const std::string & membersPath);
 
+		// ---------------------------------------------------------------------------------------- the anchor blocks
+		// Where the sequence a colour shares with a reference colour lies in both (include/twopaco_hip.h, the tpc_segments_anchors_*
+		// group, states the definition in the same words).  count[r][c]: the events of row r in sequences of colour c.  An event e of
+		// row r in colour c != ref is an ANCHOR when count[r][ref] == 1 and count[r][c] == 1; mate[e] is the one event of r in the
+		// reference colour; the anchor is REVERSE when name[e] and name[mate[e]] differ in sign.  An anchor e CONTINUES e - 1 when both
+		// lie in one sequence, e - 1 is an anchor with the same reverse flag, mate[e] == mate[e - 1] + 1 (forward) or - 1 (reverse),
+		// and both mates lie in one reference sequence.  A BLOCK is a maximal run queryFirst .. queryLast of anchors each continuing
+		// the one before; its reference events refFirst .. refLast ascend (reverse: mate[queryLast] .. mate[queryFirst]).  Blocks
+		// ascend by queryFirst.  Per colour other than ref: blocks, anchors, edges (end[queryLast] - begin[queryFirst] summed) and
+		// reverseEdges; refEdges is the sum of end - begin over the reference colour's events.  The arrays come from ComputeAnchors
+		// below -- the serial statement -- or from the device (csrc/tpc_anchors.hip); the writers print either as the same bytes.
+		struct AnchorTable
+		{
+			static const uint32_t NONE = 0xFFFFFFFFu;                      // mate[]: no mate
+			uint64_t colors, segments, refEdges;
+			uint32_t ref;
+			std::vector<uint32_t> mate;                                    // [events]
+			std::vector<uint32_t> queryFirst, queryLast, refFirst, refLast; // [blocks], events
+			std::vector<uint64_t> blocks, anchors, edges, reverseEdges;     // [colors], 0 for ref
+			AnchorTable() : colors(0), segments(0), refEdges(0), ref(0) {}
+			size_t Rows() const { return queryFirst.size(); }
+			uint64_t Anchors() const { uint64_t n = 0; for (uint64_t a : anchors) n += a; return n; }
+		};
+
+		// The definition stated with std:: containers: the row of every event by a hash map from |name|, count[][] as one std::map from
+		// (row, colour) to the number of events and the last of them, the mates, then one pass over the events for the blocks.  The
+		// table must be one whose walk did not fail; every sequence needs a colour below `colors`, and ref < colors
+		// (std::runtime_error otherwise).  No device dependency.
+		void ComputeAnchors(const EventTable & table, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t colors, uint32_t ref, AnchorTable & out);
+
+		// The TSV text: "#twopaco-anchors\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tref=<R>\tref_edges=<T>\tblocks=<B>", the
+		// colour table's "#color" lines, "#sequence\t<s>\t<colour>\t<length>\t<name>" for every input sequence, "#shared\t<c>\t<blocks>\t
+		// <anchors>\t<edges>\t<reverse_edges>" for every colour other than R, zeros included, then one line per block: colour, ref_seq,
+		// ref_begin, ref_end, + or -, query_seq, query_begin, query_end, anchors.  Sequences are 0-based input indices, intervals
+		// half-open, all coordinates on each sequence's forward strand.  To stdout (path empty) or into the file `path` (removed again
+		// when writing fails).
+		void WriteAnchors(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & anchors, const std::string & path);
+
+		// PAF, one line per block in the table's order, into the file `path`: query name, length, begin, end, strand, reference name,
+		// length, begin, end, matches (= the block length), the block length, 255, tp:A:P, cg:Z:<len>=, an:i:<anchors>.
+		void WriteAnchorsPaf(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & anchors, const std::string & path);
+
+		// Both files, or neither: the PAF first when pafPath is given, then the TSV (to stdout when path is empty); when the TSV cannot
+		// be written the PAF file is removed again before the error is thrown.
+		void WriteAnchorFiles(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & anchors, const std::string & path,
+			const std::string & pafPath);
+
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
 		// the table carries linkFirst.
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,

@@ -8,7 +8,8 @@
 //             |  --distances file|sequence [--distances-out <path>] [--distances-phylip <path>]
 //             |  --components file|sequence [--components-out <path>] [--components-members <path>]
 //             |  --superbubbles file|sequence [--superbubbles-out <path>] [--superbubbles-members <path>] [--superbubbles-max <n>]
-//             (the last six instead of -f)
+//             |  --anchors file|sequence [--anchors-ref <colour>] [--anchors-out <path>] [--anchors-paf <path>]
+//             (the last seven instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -72,6 +73,12 @@
 // ComputeSuperbubbles; with --gpu the colour stage, the link stage and the superbubble stage over one segment build
 // (csrc/tpc_superbubbles.hip); the bytes are the same.  Beside --colors, --bubbles, --distances or --components of the same colours it
 // is written after them.  Its refusals are those of --bubbles.
+// --anchors file|sequence [--anchors-ref <colour>] [--anchors-out <path>] [--anchors-paf <path>] (an addition; instead of -f): the
+// anchor blocks against the reference colour (default 0) -- where every other colour matches it uniquely, in which order and on
+// which strand; include/twopaco_hip.h defines them -- as TSV (graphformat.h: WriteAnchors) and, asked for, as PAF
+// (WriteAnchorsPaf).  Without --gpu the serial walk, then ComputeAnchors; with --gpu the anchor stage over the segment build
+// (csrc/tpc_anchors.hip); the bytes are the same.  Beside --colors, --bubbles, --distances, --components or --superbubbles of the
+// same colours it is written after them; not with --links.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -473,6 +480,30 @@ namespace
 		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
 	}
 
+	struct ArgError
+	{
+		std::string what, arg;
+		ArgError(const std::string & w, const std::string & a) : what(w), arg(a) {}
+	};
+
+	// --anchors beside another table of the same colours, or alone: the reference colour and the file names (out empty: stdout)
+	struct AnchorsWanted
+	{
+		bool on;
+		uint32_t ref;
+		std::string out, paf;
+		AnchorsWanted() : on(false), ref(0) {}
+	};
+
+	// the reference colour must be one of the map's: known only once the input's files and sequences are
+	void CheckAnchorsRef(const AnchorsWanted & anchors, const ColorMap & map)
+	{
+		if (anchors.on && anchors.ref >= map.label.size())
+		{
+			throw ArgError("Value '" + std::to_string(anchors.ref) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--anchors-ref)");
+		}
+	}
+
 	// --components beside another table of the same colours, or alone: the file names of the component table (out empty: stdout)
 	struct ComponentsWanted
 	{
@@ -490,15 +521,18 @@ namespace
 		SuperbubblesWanted() : on(false), maxInside(62) {}
 	};
 
-	// --components and / or --superbubbles, serial, alone or beside --colors / --bubbles / --distances of the same colours: one walk, the
-	// serial statements one after the other, then the tables in the order colours or bubbles, distances, components, superbubbles
+	// --components, --superbubbles and / or --anchors, serial, alone or beside --colors / --bubbles / --distances of the same colours: one
+	// walk, the serial statements one after the other, then the tables in the order colours or bubbles, distances, components,
+	// superbubbles, anchors
 	void DumpComponents(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const ComponentsWanted & want,
-		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo, const SuperbubblesWanted & super)
+		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo, const SuperbubblesWanted & super,
+		const AnchorsWanted & anchorsTo = AnchorsWanted())
 	{
 		SerialTable t;
 		WalkLinks(binFile, fasta, k, prefix, false, t);
 		ColorMap map;
 		MakeColorMap(t.seq, fasta, bySequence, map);
+		CheckAnchorsRef(anchorsTo, map);
 		ColorTable colors;
 		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
 		BubbleTable bubbles;
@@ -509,11 +543,14 @@ namespace
 		if (want.on) ComputeComponents(t.table, k, t.links, colors, components);
 		SuperbubbleTable superbubbles;
 		if (super.on) ComputeSuperbubbles(t.table, k, t.links, colors, super.maxInside, superbubbles);
+		AnchorTable anchors;
+		if (anchorsTo.on) ComputeAnchors(t.table, k, map.colorOfSequence, map.label.size(), anchorsTo.ref, anchors);
 		if (colorsToo) WriteColors(t.table, k, map, colors, firstOut);
 		if (bubblesToo) WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, firstOut);
 		if (distancesToo) WriteDistanceFiles(k, map, colors.Rows(), distances, distancesTo.out, distancesTo.phylip);
 		if (want.on) WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
 		if (super.on) WriteSuperbubbleFiles(t.table, k, map, colors, t.links.Rows(), superbubbles, super.out, super.members);
+		if (anchorsTo.on) WriteAnchorFiles(t.table, k, map, t.seq, anchors, anchorsTo.out, anchorsTo.paf);
 	}
 
 	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
@@ -547,12 +584,12 @@ namespace
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
-		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored;
-		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs, superbubblesKernelMs, superbubblesMs;
+		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored, anchorBlocks, anchors;
+		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs, superbubblesKernelMs, superbubblesMs, anchorsKernelMs, anchorsMs;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
 			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
-			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), superbubblesKernelMs(0), superbubblesMs(0), threads(1) {}
+			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), superbubblesKernelMs(0), superbubblesMs(0), anchorsKernelMs(0), anchorsMs(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -567,12 +604,14 @@ namespace
 				"\"links_kernel_ms\": %.3f, \"links_ms\": %.3f, \"links\": %llu, \"link_occurrences\": %llu, "
 				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f, "
 				"\"components_kernel_ms\": %.3f, \"components_ms\": %.3f, \"components\": %llu, \"largest_component\": %llu, "
-				"\"superbubbles_kernel_ms\": %.3f, \"superbubbles_ms\": %.3f, \"superbubbles\": %llu, \"superbubble_members\": %llu, \"superbubbles_unmirrored\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"superbubbles_kernel_ms\": %.3f, \"superbubbles_ms\": %.3f, \"superbubbles\": %llu, \"superbubble_members\": %llu, \"superbubbles_unmirrored\": %llu, "
+				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
 				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs,
 				(unsigned long long)components, (unsigned long long)largestComponent, superbubblesKernelMs, superbubblesMs, (unsigned long long)superbubbles,
-				(unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored);
+				(unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, anchorsKernelMs, anchorsMs, (unsigned long long)anchorBlocks,
+				(unsigned long long)anchors);
 			std::fclose(f);
 		}
 	};
@@ -731,6 +770,7 @@ namespace
 		bool colors, links, bubbles, distances, components, superbubbles, bySequence;
 		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers, superbubblesOut, superbubblesMembers;
 		uint32_t superbubblesMax;
+		AnchorsWanted anchors;
 	};
 
 	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
@@ -747,10 +787,16 @@ namespace
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		ColorMap map;
 		ColorTable colors;
-		if (want.colors || want.bubbles || want.distances || want.components || want.superbubbles)
+		const bool colorTable = want.colors || want.bubbles || want.distances || want.components || want.superbubbles;
+		if (colorTable || want.anchors.on)
 		{
 			MakeColorMap(seq, fasta, want.bySequence, map);
 			if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
+			CheckAnchorsRef(want.anchors, map);
+		}
+
+		if (colorTable)
+		{
 			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
 			BuildColors(lib, map);
 			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
@@ -810,8 +856,22 @@ namespace
 			TimingLine("superbubble table", stats.superbubblesMs, stats.superbubblesKernelMs);
 		}
 
+		AnchorTable anchors;
+		if (want.anchors.on)
+		{
+			// over the event table alone (csrc/tpc_anchors.hip): neither the colour rows nor the link rows are read
+			const std::chrono::steady_clock::time_point a0 = std::chrono::steady_clock::now();
+			BuildAnchors(lib, map, want.anchors.ref);
+			stats.anchorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_ANCHORS);
+			if (!FetchAnchors(lib, map, counts[0], counts[1], anchors)) throw std::runtime_error("--gpu: the anchor stage and the colour map disagree about the colours");
+			stats.anchorBlocks = anchors.Rows();
+			stats.anchors = anchors.Anchors();
+			stats.anchorsMs = MsSince(a0);
+			TimingLine("anchor table", stats.anchorsMs, stats.anchorsKernelMs);
+		}
+
 		Events held(counts[0], sequences);
-		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles) FetchTable(lib, held);
+		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles || want.anchors.on) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
@@ -820,6 +880,7 @@ namespace
 		if (want.distances) WriteDistanceFiles(k, map, counts[1], distances, want.distancesOut, want.distancesPhylip);
 		if (want.components) WriteComponentFiles(held.table, k, map, colors, stats.links, components, want.componentsOut, want.componentsMembers);
 		if (want.superbubbles) WriteSuperbubbleFiles(held.table, k, map, colors, stats.links, superbubbles, want.superbubblesOut, want.superbubblesMembers);
+		if (want.anchors.on) WriteAnchorFiles(held.table, k, map, seq, anchors, want.anchors.out, want.anchors.paf);
 		stats.formatMs = MsSince(t0);
 		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
 	}
@@ -889,15 +950,9 @@ namespace
 	}
 
 	// ---------------------------------------------------------------------------------------- command line
-	struct ArgError
-	{
-		std::string what, arg;
-		ArgError(const std::string & w, const std::string & a) : what(w), arg(a) {}
-	};
-
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -955,6 +1010,16 @@ namespace
 			"   --superbubbles-out <file name>\n     with --superbubbles: write the table there instead of to the standard output\n\n"
 			"   --superbubbles-members <file name>\n     with --superbubbles: also write the inside sides of every row there, one line per side\n\n"
 			"   --superbubbles-max <integer>\n     with --superbubbles: the largest inside reported, 2 .. 62 (default 62)\n\n"
+			"   --anchors <file|sequence>\n     instead of -f: the anchor blocks against a reference colour as TSV -- every segment that occurs exactly once in the\n"
+			"     reference and exactly once in another colour is an anchor, anchors that follow each other in both are chained into maximal\n"
+			"     collinear blocks: exact matches, or exact reverse-complement matches, between two intervals.  Per block the colour, the\n"
+			"     reference sequence and interval, the strand, the query sequence and interval and the number of anchors; in front the\n"
+			"     colours, the input sequences and per colour the blocks, anchors, edges and reverse edges it shares with the reference.\n"
+			"     Needs -k and -s.  With --gpu they are found on the device.  Goes with --colors, --bubbles, --distances, --components or\n"
+			"     --superbubbles of the same colours (one walk for all; this table is written last); not with --links, --compact or --text.\n\n"
+			"   --anchors-ref <integer>\n     with --anchors: the index of the reference colour (default 0)\n\n"
+			"   --anchors-out <file name>\n     with --anchors: write the table there instead of to the standard output\n\n"
+			"   --anchors-paf <file name>\n     with --anchors: also write the blocks there as PAF, one line per block\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -964,10 +1029,11 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers, anchorsBy, anchorsOut, anchorsPaf;
 		std::vector<std::string> fasta;
 		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
-		uint32_t superbubblesMax = 62;
+		uint32_t superbubblesMax = 62, anchorsRef = 0;
+		bool anchorsRefSet = false, anchorsOutSet = false, anchorsPafSet = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -1057,6 +1123,22 @@ int main(int argc, char * argv[])
 				superbubblesMax = uint32_t(n);
 				superbubblesMaxSet = true;
 			}
+			else if (a == "--anchors")
+			{
+				anchorsBy = value("(--anchors)");
+				if (anchorsBy != "file" && anchorsBy != "sequence") throw ArgError("Value '" + anchorsBy + "' does not meet constraint: file|sequence", "Argument: (--anchors)");
+			}
+			else if (a == "--anchors-out") { anchorsOut = value("(--anchors-out)"); anchorsOutSet = true; }
+			else if (a == "--anchors-paf") { anchorsPaf = value("(--anchors-paf)"); anchorsPafSet = true; }
+			else if (a == "--anchors-ref")
+			{
+				const std::string v = value("(--anchors-ref)");
+				char * end = 0;
+				const long long n = std::strtoll(v.c_str(), &end, 10);
+				if (v.empty() || *end || n < 0 || n > 0x7FFFFFFFll) throw ArgError("Value '" + v + "' does not meet constraint: a colour index", "Argument: (--anchors-ref)");
+				anchorsRef = uint32_t(n);
+				anchorsRefSet = true;
+			}
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -1079,6 +1161,20 @@ int main(int argc, char * argv[])
 
 		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty(), components = !componentsBy.empty();
 		const bool superbubbles = !superbubblesBy.empty();
+		const bool anchors = !anchorsBy.empty();
+		if (anchors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--anchors)");
+		if (anchors && colors && colorsBy != anchorsBy) throw ArgError("The anchor table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
+		if (anchors && bubbles && bubblesBy != anchorsBy) throw ArgError("The anchor table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
+		if (anchors && distances && distancesBy != anchorsBy) throw ArgError("The anchor table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
+		if (anchors && components && componentsBy != anchorsBy) throw ArgError("The anchor table and the component table share one set of colours: --components " + componentsBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
+		if (anchors && superbubbles && superbubblesBy != anchorsBy) throw ArgError("The anchor table and the superbubble table share one set of colours: --superbubbles " + superbubblesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
+		if (anchors && links) throw ArgError("The anchor table and the link table are written one at a time: not with --links", "(--anchors)");
+		if (anchors && compact) throw ArgError("The anchor table and the compact text are written one at a time: not with --compact", "(--anchors)");
+		if (anchors && textSet) throw ArgError("The anchor table is formatted by the host: not with --anchors", "(--text)");
+		if (anchorsOutSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-out)");
+		if (anchorsPafSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-paf)");
+		if (anchorsRefSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-ref)");
+		if (anchorsPafSet && anchorsPaf.empty()) throw ArgError("The anchor PAF needs a file name", "(--anchors-paf)");
 		if (superbubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--superbubbles)");
 		if (superbubbles && colors && colorsBy != superbubblesBy) throw ArgError("The superbubble table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
 		if (superbubbles && bubbles && bubblesBy != superbubblesBy) throw ArgError("The superbubble table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
@@ -1127,10 +1223,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles && !anchors) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || anchors || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -1146,7 +1242,12 @@ int main(int argc, char * argv[])
 		also.on = distances && (colors || bubbles);
 		also.out = distancesOut;
 		also.phylip = distancesPhylip;
-		if ((colors || links || bubbles || distances || components || superbubbles) && lib)
+		AnchorsWanted anchorsTo;
+		anchorsTo.on = anchors;
+		anchorsTo.ref = anchorsRef;
+		anchorsTo.out = anchorsOut;
+		anchorsTo.paf = anchorsPaf;
+		if ((colors || links || bubbles || distances || components || superbubbles || anchors) && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
@@ -1163,7 +1264,8 @@ int main(int argc, char * argv[])
 			want.superbubblesOut = superbubblesOut;
 			want.superbubblesMembers = superbubblesMembers;
 			want.superbubblesMax = superbubblesMax;
-			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubblesBy) == "sequence";
+			want.anchors = anchorsTo;
+			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubbles ? superbubblesBy : anchorsBy) == "sequence";
 			want.componentsOut = componentsOut;
 			want.componentsMembers = componentsMembers;
 			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
@@ -1171,7 +1273,7 @@ int main(int argc, char * argv[])
 			want.distancesPhylip = distancesPhylip;
 			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
 		}
-		else if (components || superbubbles)
+		else if (components || superbubbles || anchors)
 		{
 			ComponentsWanted wanted;
 			wanted.on = components;
@@ -1182,7 +1284,7 @@ int main(int argc, char * argv[])
 			super.out = superbubblesOut;
 			super.members = superbubblesMembers;
 			super.maxInside = superbubblesMax;
-			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubblesBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super);
+			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubbles ? superbubblesBy : anchorsBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super, anchorsTo);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);

@@ -373,6 +373,15 @@ namespace TwoPaCo
 				if (superbubbles && sharded) throw std::runtime_error("The superbubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				if (superbubbles && (options.superbubblesMax < 2 || options.superbubblesMax > 62)) throw std::runtime_error("The superbubble table's largest inside must be 2 .. 62");
 				if (!superbubbles && !options.superbubblesMembersFile.empty()) throw std::runtime_error("The superbubble members are written with the superbubble table only");
+				const bool anchors = !options.anchorsFile.empty();
+				if (anchors && options.anchorsBy != "file" && options.anchorsBy != "sequence") throw std::runtime_error("The anchor table's colours must be one of file, sequence");
+				if (anchors && colors && options.anchorsBy != options.colorsBy) throw std::runtime_error("The anchor table and the colour table share one set of colours: both by file or both by sequence");
+				if (anchors && bubbles && options.anchorsBy != options.bubblesBy) throw std::runtime_error("The anchor table and the bubble table share one set of colours: both by file or both by sequence");
+				if (anchors && distances && options.anchorsBy != options.distancesBy) throw std::runtime_error("The anchor table and the distance table share one set of colours: both by file or both by sequence");
+				if (anchors && components && options.anchorsBy != options.componentsBy) throw std::runtime_error("The anchor table and the component table share one set of colours: both by file or both by sequence");
+				if (anchors && superbubbles && options.anchorsBy != options.superbubblesBy) throw std::runtime_error("The anchor table and the superbubble table share one set of colours: both by file or both by sequence");
+				if (anchors && sharded) throw std::runtime_error("The anchor table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (!anchors && !options.anchorsPafFile.empty()) throw std::runtime_error("The anchor PAF is written with the anchor table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -507,7 +516,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles || distances || components || superbubbles)
+				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -1005,7 +1014,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles || distances || components || superbubbles) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -1024,15 +1033,19 @@ namespace TwoPaCo
 			// the link rows and the colour rows where they lie; options.componentsFile and the members file are written after the
 			// distance files, both or neither (WriteComponentFiles).
 			// --superbubbles: the same two builds, then the superbubble stage (csrc/tpc_superbubbles.hip) over the link rows' arcs and the
-			// colour rows; options.superbubblesFile and the members file are written last of all, both or neither (WriteSuperbubbleFiles).
+			// colour rows; options.superbubblesFile and the members file are written after the component files, both or neither
+			// (WriteSuperbubbleFiles).
+			// --anchors: the anchor stage (csrc/tpc_anchors.hip) over the event table of the same build and the colour map alone;
+			// options.anchorsFile and the PAF file are written last of all, both or neither (WriteAnchorFiles).
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
 				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), components = !options.componentsFile.empty();
-				const bool superbubbles = !options.superbubblesFile.empty();
+				const bool superbubbles = !options.superbubblesFile.empty(), anchors = !options.anchorsFile.empty();
 				const bool colorRows = colors || bubbles || distances || components || superbubbles;
-				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : components ? options.componentsBy : options.superbubblesBy) == "sequence";
+				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : components ? options.componentsBy :
+					superbubbles ? options.superbubblesBy : options.anchorsBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1051,6 +1064,17 @@ namespace TwoPaCo
 				GraphFormat::DistanceTable distanceTable;
 				GraphFormat::ComponentTable componentTable;
 				GraphFormat::SuperbubbleTable superbubbleTable;
+				GraphFormat::AnchorTable anchorTable;
+				auto anchorColors = [&]()
+				{
+					if (!colorRows) GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
+					if (map.colorOfSequence.size() != sequences) throw std::runtime_error("The packer and the parser disagree about the input sequences");
+					if (options.anchorsRef >= map.label.size())
+					{
+						throw std::runtime_error("The anchor table's reference colour is " + std::to_string(options.anchorsRef) + ", there are " + std::to_string(map.label.size()) + " colours");
+					}
+				};
+
 				uint64_t segments = 0, linkRows = 0;
 				DeviceGraph::Events held(0, sequences);
 				const std::vector<uint32_t> noBits(1, 0);
@@ -1070,6 +1094,11 @@ namespace TwoPaCo
 					if (distances) GraphFormat::ComputeDistances(held.table, colorTable, distanceTable);
 					if (components) GraphFormat::ComputeComponents(held.table, k, linkTable, colorTable, componentTable);
 					if (superbubbles) GraphFormat::ComputeSuperbubbles(held.table, k, linkTable, colorTable, options.superbubblesMax, superbubbleTable);
+					if (anchors)
+					{
+						anchorColors();
+						GraphFormat::ComputeAnchors(held.table, k, map.colorOfSequence, map.label.size(), options.anchorsRef, anchorTable);
+					}
 				}
 				else
 				{
@@ -1196,6 +1225,32 @@ namespace TwoPaCo
 						timer.Lap("segment superbubbles fetch");
 					}
 
+					if (anchors)
+					{
+						// over the event table where it lies (csrc/tpc_anchors.hip); the files print names, positions and sequences of events
+						if (!onDevice)
+						{
+							if (!fetched) fetchTable();
+						}
+						else
+						{
+							if (counts[0] && held.name.empty()) DeviceGraph::FetchNames(api, held);
+							if (counts[0] && held.begin.empty()) DeviceGraph::FetchPositions(api, held);
+							DeviceGraph::FetchSequences(api, held);
+						}
+
+						anchorColors();
+						DeviceGraph::BuildAnchors(api, map, options.anchorsRef);
+						timer.Lap("segment anchors");
+						kernelLine("anchors_kernel_ms", TPC_K_ANCHORS);
+						if (!DeviceGraph::FetchAnchors(api, map, counts[0], segments, anchorTable))
+						{
+							throw std::runtime_error("The anchor stage and the colour map disagree about the colours");
+						}
+
+						timer.Lap("segment anchors fetch");
+					}
+
 					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph && !fetched) fetchTable();
 				}
@@ -1246,6 +1301,12 @@ namespace TwoPaCo
 				{
 					GraphFormat::WriteSuperbubbleFiles(held.table, k, map, colorTable, linkRows, superbubbleTable, options.superbubblesFile, options.superbubblesMembersFile);
 					timer.Lap("superbubble table writing");
+				}
+
+				if (anchors)
+				{
+					GraphFormat::WriteAnchorFiles(held.table, k, map, seq, anchorTable, options.anchorsFile, options.anchorsPafFile);
+					timer.Lap("anchor table writing");
 				}
 			}
 

@@ -113,6 +113,14 @@ namespace TwoPaCo
 		std::string superbubblesFile;
 		std::string superbubblesMembersFile;
 		uint32_t superbubblesMax = 62;
+		// The anchor blocks against a reference colour (graphformat.h: WriteAnchors; `graphdump --anchors` writes the same bytes for the
+		// junction stream of this run): anchorsFile (empty: off), anchorsBy = "file" | "sequence" -- the same as the other tables' when
+		// those are given --, anchorsRef, the index of the reference colour, and anchorsPafFile (empty: off) for the blocks as PAF.
+		// Found on the device (tpc_segments_anchors_build) over the event table of the same segment build.  One GPU.
+		std::string anchorsBy;
+		std::string anchorsFile;
+		std::string anchorsPafFile;
+		uint32_t anchorsRef = 0;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
