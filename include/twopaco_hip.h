@@ -66,7 +66,8 @@ enum {
     TPC_K_COMPONENTS = 22,  /* tpc_segments_components_build: the union-find over the link rows, the numbering and the per-component sums (no counterpart in the reference) */
     TPC_K_SUPERBUBBLES = 23, /* tpc_segments_superbubbles_build: the adjacency lists, the bounded search per entrance and the report (no counterpart in the reference) */
     TPC_K_ANCHORS = 24,     /* tpc_segments_anchors_build: the keys, their sort, mates, heads and tails, the blocks and the per-colour sums (no counterpart in the reference) */
-    TPC_K_COUNT = 25
+    TPC_K_LOCATE = 25,      /* tpc_segments_edges_build / tpc_segments_locate, whichever ran last: the stage on the stream from its first kernel to its last (no counterpart in the reference) */
+    TPC_K_COUNT = 26
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -825,6 +826,62 @@ int tpc_segments_anchors_info(tpc_ctx *ctx, uint64_t *info /* [6] */);
 int tpc_segments_anchors_fetch_mates(tpc_ctx *ctx, uint64_t e0, uint64_t n, uint32_t *mate_host);
 int tpc_segments_anchors_fetch_rows(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *query_first, uint32_t *query_last, uint32_t *ref_first, uint32_t *ref_last);
 int tpc_segments_anchors_fetch_shared(tpc_ctx *ctx, uint64_t *blocks, uint64_t *anchors, uint64_t *edges, uint64_t *reverse_edges /* [n_colors] each */);
+
+/* The EDGE INDEX of the compacted graph and LOCATE (csrc/tpc_locate.hip): is a sequence that was no input in the graph, where, and
+ * in which colours.  No counterpart in the reference.  Definitions; host/graphformat.h states them serially.
+ *   n = k + 1.  T is the text of tpc_seq_upload that the last segment build read.  A WINDOW W_T(g) = T[g, g + n) is VALID when the
+ *   N mask holds none of its positions (letters other than ACGT are N, as in the packed text).  canon(w) = the smaller of w and its
+ *   reverse complement.
+ *   ROWS             the colour table's: the events whose first bit is set, in event order; e0(r) = the first event of row r.  The
+ *                    SPAN of r is the global positions g0(r) + j, 0 <= j < end[e0] - begin[e0], g0(r) = rec_start[seq(e0)] + begin[e0],
+ *                    the sequence of an event from seq_event_begin.
+ *   EDGE INDEX I     one entry for every position g of some row's span with W_T(g) valid: key canon(W_T(g)), value (g, row).  Where
+ *                    several positions share a key the SMALLEST g is the entry and the others are DUPLICATES; span positions with an
+ *                    invalid window are SKIPPED.  The result is exact and does not depend on the schedule.
+ *   QUERY TEXT Q     packed exactly like T (N rec0 N rec1 N ...), with its own rec_start / rec_len, ascending.  Each position p with
+ *                    p + n <= |Q| is INVALID (W_Q(p) holds an N), ABSENT (canon(W_Q(p)) is no key of I) or a HIT (g, row, rev):
+ *                    rev = 0 when W_Q(p) == W_T(g) letter for letter (a palindromic window counts as forward), 1 when it is the
+ *                    reverse complement.  off = g - g0(row).  The LETTERS decide: the hash only finds the slot.
+ *   RUN              the hit at p CONTINUES the one at p - 1 when both are hits of one row with one rev and off[p] == off[p - 1] + 1
+ *                    (forward) or - 1 (reverse).  A run is a maximal chain; runs are numbered by ascending p.  A separator is an N,
+ *                    so no run crosses records.  Per run: q_first, length (windows), row, rev, off_first.  A run of L windows says that
+ *                    the query letters [p, p + L + k) are the row's span letters [off, off + L + k) in text orientation (reverse: the
+ *                    reverse complement of [off_first - L + 1, off_first + 1 + k)).
+ *   PER RECORD       64-bit sums windows (valid), found, forward (hits with rev = 0), runs and, when a colour table is valid at the
+ *                    time of the call, shared[rec][c]: the hits whose row has colour c in its presence.
+ * Device encoding: hit[p] is 64 bits, all ones = invalid, all ones - 1 = absent, else rev << 63 | g (g < 2^40); row[p] is 32 bits, all
+ * ones / all ones - 1 likewise.  Run arrays are 32 bits each: a query text of 2^32 - 2 positions or more is refused (cut it into batches).
+ *   tpc_segments_edges_build           marks the spans in a bit mask over T, counts and then inserts the masked valid positions with the
+ *                                      tile kernel of tpc_distinct_sketch's shape into an open-addressed table of 16-byte slots
+ *                                      {tag:24 | g:40, row:32} at a load factor of at most 0.5 (atomicCAS claims, equal letters take
+ *                                      atomicMin), and writes every slot's row in a pass of its own after all inserts.  Refused: no
+ *                                      segment table or a failed walk, a text that is not the build's or a windowed one, k + 1 beyond
+ *                                      the tile halo (k > 670), a text of 2^40 positions or more, a forced table that is full, buffers
+ *                                      beyond the free device memory.  Kept until the next segment build, edge build or text upload.
+ *                                      Options (tests): test_edges_slots_log2 forces the table size, test_edges_hash_bits keeps that
+ *                                      many bits of the hash (keys then share tag and home slot), test_locate_grid bounds the
+ *                                      workgroups of the tile kernels.
+ *   tpc_segments_edges_info            info[0] entries, [1] duplicates, [2] skipped, [3] slots, [4] the longest probe (slots stepped
+ *                                      over by one insert), [5] the stage's device memory at its peak
+ *   tpc_segments_locate                uploads Q (q_bases / q_nmask of (n_q_text + 31) / 32 words, as tpc_seq_upload takes T) and its
+ *                                      records as temporaries, rolls, probes and compares every position, folds the per-record and
+ *                                      per-colour sums, numbers the runs with one scan.  Uses the colour table that is valid at the
+ *                                      time of the call; none: no shared counts.  TPC_K_LOCATE times the last edge build or locate.
+ *   tpc_segments_locate_info           info[0] positions (|Q| - n + 1, or 0), [1] windows, [2] found, [3] runs, [4] colours used (0 =
+ *                                      none), [5] the call's device memory at its peak
+ *   tpc_segments_locate_fetch_hits     hit[] / row[] of positions [p0, p0 + n)
+ *   tpc_segments_locate_fetch_runs     the five run arrays of runs [r0, r0 + n)
+ *   tpc_segments_locate_fetch_records  the four sums of records [s0, s0 + n)
+ *   tpc_segments_locate_fetch_shared   shared[s][c] of records [s0, s0 + n), n x colours counts; refused without a colour table
+ * Ranges outside a table are refused with an error text. */
+int tpc_segments_edges_build(tpc_ctx *ctx);
+int tpc_segments_edges_info(tpc_ctx *ctx, uint64_t *info /* [6] */);
+int tpc_segments_locate(tpc_ctx *ctx, const uint64_t *q_bases, const uint32_t *q_nmask, uint64_t n_q_text, const uint64_t *rec_start, const uint64_t *rec_len, uint32_t n_rec);
+int tpc_segments_locate_info(tpc_ctx *ctx, uint64_t *info /* [6] */);
+int tpc_segments_locate_fetch_hits(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint64_t *hit_host, uint32_t *row_host);
+int tpc_segments_locate_fetch_runs(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *q_first, uint32_t *length, uint32_t *row, uint32_t *rev, uint32_t *off_first);
+int tpc_segments_locate_fetch_records(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint64_t *windows, uint64_t *found, uint64_t *forward, uint64_t *runs);
+int tpc_segments_locate_fetch_shared(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint64_t *counts_host /* [n x colours] */);
 
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */

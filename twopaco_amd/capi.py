@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24}
+           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -41,7 +41,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_superbubbles_build", "tpc_segments_superbubbles_info", "tpc_segments_superbubbles_fetch_adjacency", "tpc_segments_superbubbles_fetch_exits",
                "tpc_segments_superbubbles_fetch_rows", "tpc_segments_superbubbles_fetch_members", "tpc_segments_superbubbles_fetch_presence",
                "tpc_segments_anchors_build", "tpc_segments_anchors_info", "tpc_segments_anchors_fetch_mates", "tpc_segments_anchors_fetch_rows",
-               "tpc_segments_anchors_fetch_shared"]
+               "tpc_segments_anchors_fetch_shared",
+               "tpc_segments_edges_build", "tpc_segments_edges_info", "tpc_segments_locate", "tpc_segments_locate_info", "tpc_segments_locate_fetch_hits",
+               "tpc_segments_locate_fetch_runs", "tpc_segments_locate_fetch_records", "tpc_segments_locate_fetch_shared"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -203,6 +205,14 @@ def hip():
         L.tpc_segments_anchors_fetch_mates.argtypes = [p, u64, u64, p]
         L.tpc_segments_anchors_fetch_rows.argtypes = [p, u64, u64, p, p, p, p]
         L.tpc_segments_anchors_fetch_shared.argtypes = [p, p, p, p, p]
+        L.tpc_segments_edges_build.argtypes = [p]
+        L.tpc_segments_edges_info.argtypes = [p, p]
+        L.tpc_segments_locate.argtypes = [p, p, p, u64, p, p, ctypes.c_uint32]
+        L.tpc_segments_locate_info.argtypes = [p, p]
+        L.tpc_segments_locate_fetch_hits.argtypes = [p, u64, u64, p, p]
+        L.tpc_segments_locate_fetch_runs.argtypes = [p, u64, u64, p, p, p, p, p]
+        L.tpc_segments_locate_fetch_records.argtypes = [p, u64, u64, p, p, p, p]
+        L.tpc_segments_locate_fetch_shared.argtypes = [p, u64, u64, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -910,6 +920,58 @@ class Context:
         out = [np.zeros(self.segments_anchors_info()["colors"], dtype=np.uint64) for _ in range(4)]
         self._ck(hip().tpc_segments_anchors_fetch_shared(self._h, *[a.ctypes.data for a in out]))
         return tuple(out)
+
+    def segments_edges_build(self):
+        """The edge index (csrc/tpc_locate.hip) over the table of the last segments_build, whose error must be None, and the text it
+        was built over: canonical (k+1)-mer -> (smallest position, row).  Returns segments_edges_info()."""
+        self._ck(hip().tpc_segments_edges_build(self._h))
+        return self.segments_edges_info()
+
+    def segments_edges_info(self):
+        """dict: entries, duplicates, skipped, slots, longest_probe, peak_bytes."""
+        c = np.zeros(6, dtype=np.uint64)
+        self._ck(hip().tpc_segments_edges_info(self._h, c.ctypes.data))
+        return dict(zip(("entries", "duplicates", "skipped", "slots", "longest_probe", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_locate(self, text):
+        """Every window of the PackedText `text` through the edge index.  Returns segments_locate_info()."""
+        bases, nmask = np.ascontiguousarray(text.bases), np.ascontiguousarray(text.nmask)
+        start, length = np.ascontiguousarray(text.rec_start, dtype=np.uint64), np.ascontiguousarray(text.rec_length, dtype=np.uint64)
+        self._ck(hip().tpc_segments_locate(self._h, bases.ctypes.data, nmask.ctypes.data, text.length, start.ctypes.data if start.size else None,
+                                           length.ctypes.data if length.size else None, start.size))
+        return self.segments_locate_info()
+
+    def segments_locate_info(self):
+        """dict: positions, windows, found, runs, colors (0 = no colour table was used), peak_bytes."""
+        c = np.zeros(6, dtype=np.uint64)
+        self._ck(hip().tpc_segments_locate_info(self._h, c.ctypes.data))
+        return dict(zip(("positions", "windows", "found", "runs", "colors", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_locate_fetch_hits(self, p0=0, n=None):
+        """(hit uint64, row uint32) of positions [p0, p0 + n): hit all ones = invalid, all ones - 1 = absent, else rev << 63 | g."""
+        n = self.segments_locate_info()["positions"] - p0 if n is None else n
+        hit, row = np.zeros(max(n, 0), dtype=np.uint64), np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_locate_fetch_hits(self._h, p0, n, hit.ctypes.data, row.ctypes.data))
+        return hit, row
+
+    def segments_locate_fetch_runs(self, r0=0, n=None):
+        """(q_first, length, row, rev, off_first) of runs [r0, r0 + n) as uint32; n = None: to the last run."""
+        n = self.segments_locate_info()["runs"] - r0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(5)]
+        self._ck(hip().tpc_segments_locate_fetch_runs(self._h, r0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_locate_fetch_records(self, s0, n):
+        """(windows, found, forward, runs) of query records [s0, s0 + n) as uint64."""
+        out = [np.zeros(max(n, 0), dtype=np.uint64) for _ in range(4)]
+        self._ck(hip().tpc_segments_locate_fetch_records(self._h, s0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_locate_fetch_shared(self, s0, n):
+        """uint64 [n, colors]: the hits of query records [s0, s0 + n) whose row has the colour."""
+        out = np.zeros((max(n, 0), self.segments_locate_info()["colors"]), dtype=np.uint64)
+        self._ck(hip().tpc_segments_locate_fetch_shared(self._h, s0, n, out.ctypes.data))
+        return out
 
     def filter_words(self):
         return int(hip().tpc_filter_words(self._h))

@@ -340,6 +340,7 @@ void tpc_ctx_destroy(tpc_ctx *c)
     colors_drop(c);
     links_drop(c);
     anchors_drop(c);
+    edges_drop(c);
     for (void *p : c->pbuf) if (p) (void)hipFree(p);
     for (void *p : c->ikeep) if (p) (void)hipFree(p);
     if (c->periodic) (void)hipFree(c->periodic);
@@ -385,6 +386,9 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "test_force_anyq")) { tpc_test_force_anyq = value != 0; return 0; }  // process-wide, tests only
     if (!strcmp(name, "test_sketch_grid")) { tpc_test_sketch_grid = value > 0 ? (int)value : 0; return 0; }  // process-wide, tests only
     if (!strcmp(name, "test_links_slots_log2")) { c->opt_links_slots_log2 = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 64)); return 0; }  // tests only: slots of the next tpc_segments_links_build
+    if (!strcmp(name, "test_edges_slots_log2")) { c->opt_edges_slots_log2 = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 64)); return 0; }  // tests only: slots of the next tpc_segments_edges_build
+    if (!strcmp(name, "test_edges_hash_bits")) { c->opt_edges_hash_bits = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 65)); return 0; }  // tests only: hash bits of the next tpc_segments_edges_build
+    if (!strcmp(name, "test_locate_grid")) { c->opt_locate_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }  // tests only: workgroups of the edge index's tile kernels
     if (!strcmp(name, "test_distances_chunk_words")) { c->opt_distances_chunk_words = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); return 0; }  // tests only: chunk length of the next tpc_segments_distances_build
     if (!strcmp(name, "test_components_step_limit")) { c->opt_components_step_limit = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return 0; }  // tests only: step bound of the next tpc_segments_components_build
     if (!strcmp(name, "test_fail_mallocs")) { tpc_test_fail_mallocs.store(value > 0 ? (int)value : 0); return 0; }  // process-wide, tests only

@@ -29,6 +29,7 @@ void text_plan_drop(tpc_ctx *c)
 //   colours, links      <- components       (joined by the link rows, summed over the colour rows)
 //   colours, links      <- superbubbles     (searched over the link rows' arcs, presence ORed over the colour rows)
 //   segments <- anchors                     (paired and chained over the event table alone)
+//   segments <- edges   <- locate           (the index holds positions of the build's text and rows; a locate holds hits in that index)
 //   segments <- the graph text's plan
 void free_all(std::initializer_list<const void *> ps) { for (const void *p : ps) if (p) (void)hipFree(const_cast<void *>(p)); }
 
@@ -43,6 +44,8 @@ void superbubbles_drop(tpc_ctx *c)
     free_all({c->sbb.off, c->sbb.heads, c->sbb.exit_of, c->sbb.u32, c->sbb.u64, c->sbb.presence, c->sbb.member_off, c->sbb.members});
     c->sbb = {};
 }
+void locate_drop(tpc_ctx *c) { free_all({c->loc.hit, c->loc.row, c->loc.runs, c->loc.recs, c->loc.shared}); c->loc = {}; }
+void edges_drop(tpc_ctx *c) { locate_drop(c); free_all({c->edg.slots, c->edg.g0}); c->edg = {}; }
 void anchors_drop(tpc_ctx *c) { free_all({c->anc.mate, c->anc.rows, c->anc.sums}); c->anc = {}; }
 void bubbles_drop(tpc_ctx *c) { free_all({c->bub.rows, c->bub.sides, c->bub.hist}); c->bub = {}; }
 void colors_drop(tpc_ctx *c) { distances_drop(c); components_drop(c); superbubbles_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
@@ -58,6 +61,7 @@ void segments_drop(tpc_ctx *c)
     colors_drop(c);
     links_drop(c);
     anchors_drop(c);
+    edges_drop(c);
     free_all({c->seg.name, c->seg.first, c->seg.ev[0], c->seg.ev[1], c->seg.ev[2], c->seg.rec, c->seg.amb});
     c->seg = {};
 }

@@ -11,7 +11,9 @@
 //   tpc_components.hip    the connected components over the link and colour tables (tpc_segments_components_*), kernels and entry points
 //   tpc_superbubbles.hip  the bounded superbubbles over the link and colour tables (tpc_segments_superbubbles_*), kernels and entry points
 //   tpc_anchors.hip       the anchor blocks against a reference colour (tpc_segments_anchors_*), kernels and entry points
-//   tpc_stage.h           what the seven stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
+//   tpc_locate.hip        the edge index and the location of a query text in it (tpc_segments_edges_*, tpc_segments_locate_*), kernels and entry points
+//   tpc_edgehash.h        the two-strand rolling hash of an edge, shared by tpc_sketch.hip and tpc_locate.hip
+//   tpc_stage.h           what the eight stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
 //   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
 // No CPU fallback anywhere: every entry point needs a HIP device.
@@ -190,6 +192,28 @@ struct tpc_ctx {
         uint32_t n_colors = 0, ref_color = 0;
         bool valid = false;
     } anc;
+    // edge index (tpc_segments_edges_*, tpc_locate.hip) of the last tpc_segments_edges_build: canonical (k+1)-mer -> (g, row)
+    struct Edges {
+        void *slots = nullptr;               // device, [n_slots] x 16 B: {tag:24 | g:40, row:32, unused:32}, all ones = empty
+        uint64_t *g0 = nullptr;              // device, [n_rows]: the global position of every row's span
+        uint64_t n_slots = 0, n_rows = 0, entries = 0, duplicates = 0, skipped = 0, longest_probe = 0, peak_bytes = 0, hash_mask = 0;
+        uint64_t text_uploads = 0;
+        bool valid = false;
+    } edg;
+    // the last tpc_segments_locate (tpc_locate.hip): per position, per run, per query record
+    struct Locate {
+        unsigned long long *hit = nullptr;   // device, [positions]
+        uint32_t *row = nullptr;             // device, [positions]
+        uint32_t *runs = nullptr;            // device, [5][n_runs]: q_first, length, row, rev, off_first
+        unsigned long long *recs = nullptr;  // device, [4][n_rec]: windows, found, forward, runs
+        unsigned long long *shared = nullptr;  // device, [n_rec][n_colors], or none
+        uint64_t positions = 0, windows = 0, found = 0, n_runs = 0, n_rec = 0, peak_bytes = 0;
+        uint32_t n_colors = 0;
+        bool valid = false;
+    } loc;
+    int opt_edges_slots_log2 = 0;            // option test_edges_slots_log2 (tests only): slots of the edge index, 0 = by the edges
+    int opt_edges_hash_bits = 0;             // option test_edges_hash_bits (tests only): bits of the edge's hash that are kept, 0 = all 64
+    int opt_locate_grid = 0;                 // option test_locate_grid (tests only): at most this many workgroups of the tile kernels, 0 = by the CUs
     int opt_components_step_limit = 0;       // option test_components_step_limit (tests only): steps of a find and retries of a hook, 0 = segments + 1
     int opt_distances_chunk_words = 0;       // option test_distances_chunk_words (tests only): column words a block stages at once, 0 = the kernel's own
     // scalars
@@ -306,13 +330,15 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these seven and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these nine and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
 void components_drop(tpc_ctx *c);
 void superbubbles_drop(tpc_ctx *c);
 void anchors_drop(tpc_ctx *c);
+void edges_drop(tpc_ctx *c);
+void locate_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -1,6 +1,6 @@
 // tpc_segrows.h -- the ROW of every event of the segment table: the index of its segment among the first bits in event order.
 // Shared by the stages that group the events of the last tpc_segments_build_* by segment (tpc_colors.hip, tpc_links.hip,
-// tpc_bubbles.hip, tpc_components.hip, tpc_superbubbles.hip, tpc_anchors.hip).  The build's first-sight table is gone by the time they run, so it is made again:
+// tpc_bubbles.hip, tpc_components.hip, tpc_superbubbles.hip, tpc_anchors.hip) and by the edge index (tpc_locate.hip: the rank of a first event alone).  The build's first-sight table is gone by the time they run, so it is made again:
 //   k_col_flags    rank[e] = first bit of e; one exclusive scan makes it the row of every first event (the total is the row count)
 //   k_col_min      table[|name[e]|] = min(e), as k_seg_min of tpc_segments.hip ('N'-named events, names >= 2^34, are their own row)
 // and the row of event e is rank[table[|name[e]|]], or rank[e] for an 'N'-named one.  Every including unit gets its own copy of

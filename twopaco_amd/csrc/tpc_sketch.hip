@@ -17,6 +17,7 @@
 // almost every position is then one LDS byte read.  Each workgroup merges once, at its end, into the 16384 32-bit registers in
 // global memory: read first there too, atomicMax when larger.  max is order independent, so the result is bit-exact.
 #include "tpc_ctx.h"
+#include "tpc_edgehash.h"
 
 #define TPC_HLL_P 14
 #define TPC_HLL_M (1 << TPC_HLL_P)
@@ -25,16 +26,6 @@
 int tpc_test_sketch_grid = 0;  // option "test_sketch_grid": at most this many workgroups (0 = TPC_SKETCH_WG_PER_CU per CU)
 
 namespace {
-
-struct SketchTab {
-    uint64_t h[4];    // h[c]
-    uint64_t hn[4];   // rotl64(h[c], n mod 64): what the letter leaving the window contributes to F after one more rotation
-    uint64_t hc[4];   // h[3 - c]
-    uint64_t hcr[4];  // rotl64(h[3 - c], (n - 1) mod 64): what the letter entering the window contributes to R
-};
-
-__device__ __forceinline__ uint64_t rotl1_64(uint64_t x) { return tpc_rotl1(x, 64, ~0ull); }
-__device__ __forceinline__ uint64_t rotr1_64(uint64_t x) { return tpc_rotr1(x, 64); }
 
 // reg[idx] = max(reg[idx], rank) on the packed LDS registers
 __device__ __forceinline__ void reg_max(uint32_t *s_reg, uint32_t idx, uint32_t rank)
@@ -61,7 +52,7 @@ k_distinct_sketch(SketchTab tab, int n, const uint64_t *__restrict__ bases, cons
     __shared__ uint32_t s_w[4];
     const int tid = threadIdx.x;
     for (int i = tid; i < TPC_HLL_M / 4; i += TPC_TILE_THREADS) s_reg[i] = 0;
-    if (tid < 4) { s_t[tid] = tab.h[tid]; s_t[4 + tid] = tab.hn[tid]; s_t[8 + tid] = tab.hc[tid]; s_t[12 + tid] = tab.hcr[tid]; }
+    tpc_edge_stage_tab(s_t, tab, tid);
     const int xw = n / 32 + 2;  // the last thread's last window ends (31 + n) / 32 words behind its own
     unsigned counted = 0;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -72,33 +63,20 @@ k_distinct_sketch(SketchTab tab, int n, const uint64_t *__restrict__ bases, cons
         __syncthreads();
         const uint64_t g0 = (wfirst + tid) * TPC_RUN;
         if (g0 >= n_text) continue;
-        // eat the first window: F left to right, R right to left ('N' hashes as code 0 -- such a window is never used, it only
-        // has to leave the way it came in)
-        uint64_t F = 0, R = 0;
-        int ncnt = 0;
-        for (int t = 0; t < n; t++) {
-            const int c = tpc_tile_char(s_b, s_n, g0 + t, wbase);
-            const int cr = tpc_tile_char(s_b, s_n, g0 + n - 1 - t, wbase);
-            ncnt += c == TPC_CODE_N;
-            F = rotl1_64(F) ^ s_t[c & 3];
-            R = rotl1_64(R) ^ s_t[8 + (cr & 3)];
-        }
+        uint64_t F, R;
+        int ncnt;
+        tpc_edge_eat(s_t, s_b, s_n, g0, wbase, n, F, R, ncnt);
         for (int s = 0; s < TPC_RUN; s++) {
             const uint64_t g = g0 + s;
             if (ncnt == 0) {
-                const uint64_t x = tpc_mix64(tpc_min(F, R));
+                const uint64_t x = tpc_edge_hash(F, R);
                 const uint32_t idx = (uint32_t)(x >> (64 - TPC_HLL_P));
                 const uint64_t v = x << TPC_HLL_P;
                 const uint32_t rank = v ? (uint32_t)__builtin_clzll(v) + 1u : (uint32_t)(64 - TPC_HLL_P + 1);
                 reg_max(s_reg, idx, rank);
                 counted++;
             }
-            // the edge extends the window by one letter on the positive strand and prepends its complement on the negative one
-            const int c_out = tpc_tile_char(s_b, s_n, g, wbase);
-            const int c_in = tpc_tile_char(s_b, s_n, g + n, wbase);
-            ncnt += (c_in == TPC_CODE_N) - (c_out == TPC_CODE_N);
-            F = rotl1_64(F) ^ s_t[4 + (c_out & 3)] ^ s_t[c_in & 3];
-            R = rotr1_64(R ^ s_t[8 + (c_out & 3)]) ^ s_t[12 + (c_in & 3)];
+            tpc_edge_roll(s_t, s_b, s_n, g, wbase, n, F, R, ncnt);
         }
     }
     __syncthreads();
@@ -123,8 +101,6 @@ k_distinct_sketch(SketchTab tab, int n, const uint64_t *__restrict__ bases, cons
     }
 }
 
-uint64_t rotl64_host(uint64_t x, int r) { r &= 63; return r ? (x << r) | (x >> (64 - r)) : x; }
-
 }  // namespace
 
 extern "C" int tpc_distinct_sketch(tpc_ctx *c, int k, uint8_t *registers_host, uint64_t *n_windows)
@@ -140,20 +116,7 @@ extern "C" int tpc_distinct_sketch(tpc_ctx *c, int k, uint8_t *registers_host, u
     memset(registers_host, 0, TPC_HLL_M);
     if (n_windows) *n_windows = 0;
     if (c->n_text < (uint64_t)n) return 0;  // no window at all
-    SketchTab tab;
-    uint64_t state = 0x5457504143ull;
-    for (int i = 0; i < 4; i++) {  // splitmix64: the state steps by the golden gamma, tpc_mix64 is its finaliser
-        state += 0x9E3779B97F4A7C15ull;
-        uint64_t z = state;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        tab.h[i] = z ^ (z >> 31);
-    }
-    for (int i = 0; i < 4; i++) {
-        tab.hn[i] = rotl64_host(tab.h[i], n);
-        tab.hc[i] = tab.h[3 - i];
-        tab.hcr[i] = rotl64_host(tab.h[3 - i], n - 1);
-    }
+    const SketchTab tab = tpc_edge_tab(n);
     uint32_t *reg_dev = nullptr;
     HIPCHK(c, dev_malloc(c, (void **)&reg_dev, TPC_HLL_M * sizeof(uint32_t)));
     int n_cu = 0;

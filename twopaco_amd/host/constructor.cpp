@@ -43,7 +43,11 @@
 // --anchors file|sequence [--anchors-ref N] [--anchors-out F] [--anchors-paf F]: the anchor blocks of every other colour against the
 // reference colour N (default 0) -- unique collinear matches, forward or reverse-complement -- as TSV, byte for byte what `graphdump
 // --anchors` writes, and asked for, as PAF (csrc/tpc_anchors.hip finds them on the device over the event table of the same segment
-// build; combines with everything above; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// build; combines with everything above; the other tables must name the same colours; its files are written after the superbubble files);
+// --locate file|sequence --locate-in Q.fa [--locate-in ...] [--locate-out F] [--locate-walks F]: the records of the query files looked
+// up in the graph window by window -- found, where, on which strand, in which colours -- as TSV, byte for byte what `graphdump
+// --locate` writes, and asked for, the runs as a walks file (csrc/tpc_locate.hip builds the edge index and looks the queries up on
+// the device; combines with everything above; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -105,6 +109,7 @@ namespace
 			<< "               [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>]" << std::endl
 			<< "               [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>]" << std::endl
 			<< "               [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>]" << std::endl
+			<< "               [--locate <file|sequence> --locate-in <file name> ... [--locate-out <file name>] [--locate-walks <file name>]]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -152,7 +157,11 @@ namespace
 			<< "               file or by sequence, as --colors) is an anchor, anchors that follow each other in both are chained into maximal" << std::endl
 			<< "               collinear blocks, exact matches or exact reverse-complement matches between two intervals.  --anchors-paf: also the" << std::endl
 			<< "               blocks as PAF.  Combines with --graph, --graph-compact, --colors, --bubbles, --distances, --components and" << std::endl
-			<< "               --superbubbles (the same colours), --links and -o.  One GPU only." << std::endl;
+			<< "               --superbubbles (the same colours), --links and -o.  One GPU only." << std::endl
+			<< "       --locate: also look every (k+1)-mer of the records of the --locate-in FASTA files up in the graph and write per record its valid" << std::endl
+			<< "               windows, those found, those found forward, the runs they form and per colour (by file or by sequence, as --colors) the" << std::endl
+			<< "               hits in segments of that colour as TSV to --locate-out (default de_bruijn.locate.tsv).  --locate-walks: also the runs," << std::endl
+			<< "               one line each: the query's interval and the segment's.  Combines with all tables above (the same colours).  One GPU only." << std::endl;
 	}
 }
 
@@ -193,7 +202,7 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false, anchorsOutSet = false, anchorsPafSet = false, anchorsRefSet = false;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false, anchorsOutSet = false, anchorsPafSet = false, anchorsRefSet = false, locateOutSet = false, locateWalksSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -317,6 +326,15 @@ int main(int argc, char * argv[])
 				if (options.anchorsBy != "file" && options.anchorsBy != "sequence") throw ArgError("Value '" + options.anchorsBy + "' does not meet constraint: file|sequence", "(--anchors)");
 				optionsSet = true;
 			}
+			else if (Match(a, 0, "locate"))
+			{
+				options.locateBy = value("(--locate)");
+				if (options.locateBy != "file" && options.locateBy != "sequence") throw ArgError("Value '" + options.locateBy + "' does not meet constraint: file|sequence", "(--locate)");
+				optionsSet = true;
+			}
+			else if (Match(a, 0, "locate-in")) options.locateIn.push_back(value("(--locate-in)"));
+			else if (Match(a, 0, "locate-out")) { options.locateFile = value("(--locate-out)"); locateOutSet = true; }
+			else if (Match(a, 0, "locate-walks")) { options.locateWalksFile = value("(--locate-walks)"); locateWalksSet = true; }
 			else if (Match(a, 0, "anchors-out")) { options.anchorsFile = value("(--anchors-out)"); anchorsOutSet = true; }
 			else if (Match(a, 0, "anchors-paf")) { options.anchorsPafFile = value("(--anchors-paf)"); anchorsPafSet = true; }
 			else if (Match(a, 0, "anchors-ref"))
@@ -465,6 +483,26 @@ int main(int argc, char * argv[])
 		else if (anchorsOutSet || anchorsPafSet || anchorsRefSet)
 		{
 			throw ArgError("This argument needs --anchors <file|sequence>", anchorsOutSet ? "(--anchors-out)" : anchorsPafSet ? "(--anchors-paf)" : "(--anchors-ref)");
+		}
+
+		if (!options.locateBy.empty())
+		{
+			const std::string & by = options.locateBy;
+			if (options.gpus > 1) throw ArgError("The locate table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--locate)");
+			if (!options.colorsBy.empty() && options.colorsBy != by) throw ArgError("The locate table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --locate " + by, "(--locate)");
+			if (!options.bubblesBy.empty() && options.bubblesBy != by) throw ArgError("The locate table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --locate " + by, "(--locate)");
+			if (!options.distancesBy.empty() && options.distancesBy != by) throw ArgError("The locate table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --locate " + by, "(--locate)");
+			if (!options.componentsBy.empty() && options.componentsBy != by) throw ArgError("The locate table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --locate " + by, "(--locate)");
+			if (!options.superbubblesBy.empty() && options.superbubblesBy != by) throw ArgError("The locate table and the superbubble table share one set of colours: --superbubbles " + options.superbubblesBy + " does not go with --locate " + by, "(--locate)");
+			if (!options.anchorsBy.empty() && options.anchorsBy != by) throw ArgError("The locate table and the anchor table share one set of colours: --anchors " + options.anchorsBy + " does not go with --locate " + by, "(--locate)");
+			if (options.locateIn.empty()) throw ArgError("The locate table needs a query: --locate-in <fasta file>", "(--locate)");
+			if (!locateOutSet) options.locateFile = "de_bruijn.locate.tsv";
+			if (options.locateFile.empty()) throw ArgError("The locate table needs a file name", "(--locate-out)");
+			if (locateWalksSet && options.locateWalksFile.empty()) throw ArgError("The locate walks need a file name", "(--locate-walks)");
+		}
+		else if (locateOutSet || locateWalksSet || !options.locateIn.empty())
+		{
+			throw ArgError("This argument needs --locate <file|sequence>", locateOutSet ? "(--locate-out)" : locateWalksSet ? "(--locate-walks)" : "(--locate-in)");
 		}
 
 		if (runTests)

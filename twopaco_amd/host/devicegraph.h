@@ -7,10 +7,12 @@
 
 #include <algorithm>
 #include <functional>
+#include <stdexcept>
 #include <vector>
 
 #include "../../include/twopaco_hip.h"
 #include "graphformat.h"
+#include "textpack.h"
 
 // The entry points both programs reach through Api, each as tpc_<name>: the one list behind the members, graphdump's dlsym loads
 // (Api::Load) and twopaco's direct addresses (filled where the symbols are linked: vertexenumerator.cpp).
@@ -27,7 +29,9 @@
 	X(segments_components_fetch_presence) \
 	X(segments_superbubbles_build) X(segments_superbubbles_info) X(segments_superbubbles_fetch_rows) X(segments_superbubbles_fetch_members) \
 	X(segments_superbubbles_fetch_presence) \
-	X(segments_anchors_build) X(segments_anchors_info) X(segments_anchors_fetch_mates) X(segments_anchors_fetch_rows) X(segments_anchors_fetch_shared)
+	X(segments_anchors_build) X(segments_anchors_info) X(segments_anchors_fetch_mates) X(segments_anchors_fetch_rows) X(segments_anchors_fetch_shared) \
+	X(segments_edges_build) X(segments_edges_info) X(segments_locate) X(segments_locate_info) X(segments_locate_fetch_runs) X(segments_locate_fetch_records) \
+	X(segments_locate_fetch_shared)
 
 namespace TwoPaCo
 {
@@ -286,6 +290,80 @@ namespace TwoPaCo
 			api.check(api.segments_anchors_fetch_rows(api.ctx, 0, n, out.queryFirst.data(), out.queryLast.data(), out.refFirst.data(), out.refLast.data()), "segments_anchors_fetch_rows");
 			api.check(api.segments_anchors_fetch_shared(api.ctx, out.blocks.data(), out.anchors.data(), out.edges.data(), out.reverseEdges.data()), "segments_anchors_fetch_shared");
 			return true;
+		}
+
+		// The edge index over the table and the text on the device (csrc/tpc_locate.hip); info: tpc_segments_edges_info
+		inline void BuildEdges(const Api & api, uint64_t * info)
+		{
+			api.check(api.segments_edges_build(api.ctx), "segments_edges_build");
+			api.check(api.segments_edges_info(api.ctx, info), "segments_edges_info");
+		}
+
+		// The query records through the edge index in BATCHES of whole records of at most batchPositions positions of packed text (a
+		// longer record is a batch of its own): the sums are per record and the runs ascend, so the batches only concatenate.  The
+		// colour table on the device at the time must be the caller's (`colors` colours).  edges: what BuildEdges reported; kernelMs:
+		// TPC_K_LOCATE summed over the batches.  Returns the number of batches.
+		inline uint64_t LocateOnDevice(const Api & api, const uint64_t * edges, uint64_t colors, uint64_t segments, const GraphFormat::LoadedSequences & queries, uint64_t batchPositions,
+			GraphFormat::LocateTable & out, double & kernelMs)
+		{
+			kernelMs = 0;
+			uint64_t info[6] = {0, 0, 0, 0, 0, 0};
+			out = GraphFormat::LocateTable();
+			out.colors = colors;
+			out.segments = segments;
+			out.entries = edges[0];
+			out.duplicates = edges[1];
+			const size_t records = queries.body.size();
+			out.windows.assign(records, 0);
+			out.found.assign(records, 0);
+			out.forward.assign(records, 0);
+			out.runs.assign(records, 0);
+			out.shared.assign(records * size_t(colors), 0);
+			std::vector<uint8_t> codes;
+			uint64_t batches = 0;
+			for (size_t first = 0; first < records; ++batches)
+			{
+				TwoPaCo::PackedText text;
+				text.BeginText();
+				size_t last = first;
+				while (last < records && (last == first || text.length + queries.body[last].size() + 1 <= batchPositions))
+				{
+					const std::string & body = queries.body[last];
+					codes.resize(body.size());
+					for (size_t i = 0; i < body.size(); i++) codes[i] = body[i] == 'A' ? 0 : body[i] == 'C' ? 1 : body[i] == 'G' ? 2 : body[i] == 'T' ? 3 : 4;
+					text.AppendCodes(codes.data(), codes.size());
+					text.EndRecord(codes.size());
+					++last;
+				}
+
+				const size_t n = last - first;
+				api.check(api.segments_locate(api.ctx, text.bases.data(), text.nmask.data(), text.length, text.recStart.data(), text.recLength.data(), uint32_t(n)), "segments_locate");
+				kernelMs += api.kernel_ms(api.ctx, TPC_K_LOCATE);
+				api.check(api.segments_locate_info(api.ctx, info), "segments_locate_info");
+				if (info[4] != colors) throw std::runtime_error("the locate stage and the colour map disagree about the colours");
+				api.check(api.segments_locate_fetch_records(api.ctx, 0, n, &out.windows[first], &out.found[first], &out.forward[first], &out.runs[first]), "segments_locate_fetch_records");
+				if (colors) api.check(api.segments_locate_fetch_shared(api.ctx, 0, n, &out.shared[first * size_t(colors)]), "segments_locate_fetch_shared");
+				const size_t runs = size_t(info[3]), at = out.Runs();
+				std::vector<uint32_t> qFirst(runs);
+				out.runLength.resize(at + runs);
+				out.runRow.resize(at + runs);
+				out.runRev.resize(at + runs);
+				out.runOff.resize(at + runs);
+				api.check(api.segments_locate_fetch_runs(api.ctx, 0, runs, qFirst.data(), out.runLength.data() + at, out.runRow.data() + at, out.runRev.data() + at, out.runOff.data() + at),
+					"segments_locate_fetch_runs");
+				for (size_t i = 0; i < runs; i++)
+				{
+					// the record of a run: the last one that starts at or before its first window
+					const size_t r = size_t(std::upper_bound(text.recStart.begin(), text.recStart.end(), uint64_t(qFirst[i])) - text.recStart.begin());
+					if (r == 0 || r > n) throw std::runtime_error("the locate stage reports a run outside the query records");
+					out.runQuery.push_back(first + r - 1);
+					out.runBegin.push_back(qFirst[i] - text.recStart[r - 1]);
+				}
+
+				first = last;
+			}
+
+			return batches;
 		}
 	}
 }

@@ -1543,6 +1543,208 @@ namespace TwoPaCo
 			}
 		}
 
+		namespace
+		{
+			char LocateLetter(char ch)
+			{
+				return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' ? ch : 'N';
+			}
+
+			std::string ReverseComplement(const std::string & w)
+			{
+				std::string r(w.rbegin(), w.rend());
+				for (char & ch : r) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : 'N';
+				return r;
+			}
+
+			void CheckLocate(const ColorMap & map, size_t queries, const LocateTable & l)
+			{
+				const size_t runs = l.Runs();
+				if (l.found.size() != queries || l.forward.size() != queries || l.runs.size() != queries || l.windows.size() != queries || l.shared.size() != queries * l.colors ||
+					map.label.size() != l.colors || l.runBegin.size() != runs || l.runLength.size() != runs || l.runRow.size() != runs || l.runRev.size() != runs || l.runOff.size() != runs)
+				{
+					throw std::runtime_error("locate table: the arrays do not agree about the queries, the runs and the colours");
+				}
+			}
+		}
+
+		void BuildEdgeIndex(const EventTable & t, const LoadedSequences & loaded, size_t k, EdgeIndex & out)
+		{
+			if (loaded.body.size() != t.sequences) throw std::runtime_error("edge index: the letters of every sequence are required");
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			out = EdgeIndex();
+			out.k = k;
+			const size_t n = k + 1;
+			std::vector<uint64_t> start;
+			out.text = "N";
+			for (const std::string & body : loaded.body)
+			{
+				start.push_back(out.text.size());
+				for (char ch : body) out.text += LocateLetter(ch);
+				out.text += 'N';
+			}
+
+			size_t sequence = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+				if (!((t.first[e >> 5] >> (e & 31)) & 1u)) continue;
+				if (t.end[e] < t.begin[e] || t.end[e] > loaded.body[sequence].size()) throw std::runtime_error("edge index: an event lies outside its sequence");
+				const uint32_t row = uint32_t(out.g0.size());
+				const uint64_t g0 = start[sequence] + t.begin[e];
+				out.g0.push_back(g0);
+				for (uint64_t g = g0; g < g0 + (t.end[e] - t.begin[e]); g++)
+				{
+					if (g + n > out.text.size()) { ++out.skipped; continue; }
+					std::string w = out.text.substr(size_t(g), n);
+					if (w.find('N') != std::string::npos) { ++out.skipped; continue; }
+					const std::string r = ReverseComplement(w);
+					if (r < w) w = r;
+					auto seen = out.entry.find(w);
+					if (seen == out.entry.end()) out.entry.emplace(w, std::make_pair(g, row));
+					else
+					{
+						++out.duplicates;
+						if (g < seen->second.first) seen->second = std::make_pair(g, row);
+					}
+				}
+			}
+		}
+
+		void ComputeLocate(const EdgeIndex & index, const ColorTable & colors, const LoadedSequences & queries, LocateTable & out)
+		{
+			if (colors.Rows() != index.g0.size()) throw std::runtime_error("locate table: the colour table and the edge index disagree about the segments");
+			out = LocateTable();
+			out.colors = colors.colors;
+			out.segments = index.g0.size();
+			out.entries = index.entry.size();
+			out.duplicates = index.duplicates;
+			const size_t n = index.k + 1, words = colors.Words(), records = queries.body.size();
+			out.windows.assign(records, 0);
+			out.found.assign(records, 0);
+			out.forward.assign(records, 0);
+			out.runs.assign(records, 0);
+			out.shared.assign(records * size_t(out.colors), 0);
+			for (size_t q = 0; q < records; q++)
+			{
+				std::string body;
+				for (char ch : queries.body[q]) body += LocateLetter(ch);
+				bool open = false;           // the window before this one was a hit: (row, rev, off) below are its
+				uint32_t lastRow = 0, lastRev = 0;
+				uint64_t lastOff = 0;
+				for (size_t p = 0; p + n <= body.size(); p++)
+				{
+					const std::string w = body.substr(p, n);
+					if (w.find('N') != std::string::npos) { open = false; continue; }
+					++out.windows[q];
+					const std::string r = ReverseComplement(w);
+					auto seen = index.entry.find(r < w ? r : w);
+					if (seen == index.entry.end()) { open = false; continue; }
+					const uint64_t g = seen->second.first;
+					const uint32_t row = seen->second.second;
+					const uint32_t rev = index.text.compare(size_t(g), n, w) == 0 ? 0u : 1u;
+					const uint64_t off = g - index.g0[row];
+					++out.found[q];
+					if (!rev) ++out.forward[q];
+					for (uint64_t c = 0; c < out.colors; c++)
+					{
+						if ((colors.presence[size_t(row) * words + size_t(c >> 5)] >> (c & 31)) & 1u) ++out.shared[q * size_t(out.colors) + size_t(c)];
+					}
+
+					if (open && row == lastRow && rev == lastRev && (rev ? off + 1 == lastOff : off == lastOff + 1)) ++out.runLength.back();
+					else
+					{
+						++out.runs[q];
+						out.runQuery.push_back(q);
+						out.runBegin.push_back(p);
+						out.runLength.push_back(1);
+						out.runRow.push_back(row);
+						out.runRev.push_back(rev);
+						out.runOff.push_back(uint32_t(off));
+					}
+
+					open = true;
+					lastRow = row;
+					lastRev = rev;
+					lastOff = off;
+				}
+			}
+		}
+
+		void WriteLocate(size_t k, const ColorMap & map, const InputSequences & queries, const LocateTable & l, const std::string & path)
+		{
+			CheckLocate(map, queries.name.size(), l);
+			if (queries.length.size() != queries.name.size()) throw std::runtime_error("locate table: the name and the length of every query are required");
+			WriteStreamed(path, "locate table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-locate\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(l.colors) +
+					"\tsegments=" + std::to_string(l.segments) + "\tentries=" + std::to_string(l.entries) + "\tduplicates=" + std::to_string(l.duplicates) + "\tqueries=" +
+					std::to_string(l.Queries()) + "\n";
+				for (uint64_t c = 0; c < l.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+				uint64_t total[4] = {0, 0, 0, 0};
+				for (size_t q = 0; q < l.Queries(); q++)
+				{
+					buf += queries.name[q] + "\t" + std::to_string(queries.length[q]) + "\t" + std::to_string(l.windows[q]) + "\t" + std::to_string(l.found[q]) + "\t" +
+						std::to_string(l.forward[q]) + "\t" + std::to_string(l.runs[q]);
+					for (uint64_t c = 0; c < l.colors; c++) buf += "\t" + std::to_string(l.shared[q * size_t(l.colors) + size_t(c)]);
+					buf += "\n";
+					total[0] += l.windows[q]; total[1] += l.found[q]; total[2] += l.forward[q]; total[3] += l.runs[q];
+					flushIfLarge();
+				}
+
+				buf += "#total\t" + std::to_string(total[0]) + "\t" + std::to_string(total[1]) + "\t" + std::to_string(total[2]) + "\t" + std::to_string(total[3]) + "\n";
+			});
+		}
+
+		void WriteLocateWalks(const EventTable & t, size_t k, const ColorTable & colors, const LocateTable & l, const std::string & path)
+		{
+			if (path.empty()) throw std::runtime_error("The locate walks need a file name");
+			for (size_t i = 0; i < l.Runs(); i++)
+			{
+				if (l.runRow[i] >= colors.Rows() || colors.firstEvent[l.runRow[i]] >= t.events) throw std::runtime_error("locate table: a run lies outside the segments");
+			}
+
+			WriteStreamed(path, "locate walks", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-locate-walks\t1\tk=" + std::to_string(k) + "\n";
+				for (size_t i = 0; i < l.Runs(); i++)
+				{
+					const uint32_t e0 = colors.firstEvent[l.runRow[i]];
+					const uint64_t length = l.runLength[i], body = uint64_t(t.end[e0]) - t.begin[e0] + k;
+					// the span's letters the run covers, in text orientation
+					uint64_t sBegin = l.runRev[i] ? uint64_t(l.runOff[i]) + 1 - length : uint64_t(l.runOff[i]), sEnd = sBegin + length + k;
+					bool minus = l.runRev[i] != 0;
+					if (t.name[e0] < 0)
+					{
+						const uint64_t b = body - sEnd;
+						sEnd = body - sBegin;
+						sBegin = b;
+						minus = !minus;
+					}
+
+					buf += std::to_string(l.runQuery[i]) + "\t" + std::to_string(l.runBegin[i]) + "\t" + std::to_string(l.runBegin[i] + length + k) + "\t" +
+						std::to_string(static_cast<long long>(Magnitude(t.name[e0]))) + "\t" + (minus ? "-" : "+") + "\t" + std::to_string(sBegin) + "\t" + std::to_string(sEnd) + "\n";
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteLocateFiles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, const InputSequences & queries, const LocateTable & l,
+			const std::string & path, const std::string & walksPath)
+		{
+			CheckLocate(map, queries.name.size(), l);
+			if (!walksPath.empty()) WriteLocateWalks(t, k, colors, l, walksPath);
+			try
+			{
+				WriteLocate(k, map, queries, l, path);
+			}
+			catch (...)
+			{
+				if (!walksPath.empty()) ::unlink(walksPath.c_str());
+				throw;
+			}
+		}
+
 		void WriteGraphFile(const EventTable & table, const InputSequences & seq, const LoadedSequences & loaded, size_t k, const std::string & format,
 			size_t threads, const std::string & outPath)
 		{

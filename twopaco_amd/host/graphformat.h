@@ -19,6 +19,8 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "dnachar.h"
@@ -600,6 +602,61 @@ namespace TwoPaCo
 		// be written the PAF file is removed again before the error is thrown.
 		void WriteAnchorFiles(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const AnchorTable & anchors, const std::string & path,
 			const std::string & pafPath);
+
+		// ---------------------------------------------------------------------------------------- the edge index and locate
+		// Is a sequence that was no input in the graph, where, and in which colours (include/twopaco_hip.h, the tpc_segments_edges_* and
+		// tpc_segments_locate_* groups, state the definition in the same words).  n = k + 1; T = N seq0 N seq1 N ... with every letter
+		// other than A C G T an N; a window T[g, g + n) is valid when it holds no N; canon(w) is the smaller of w and its reverse
+		// complement.  The SPAN of row r (the colour table's rows: first events in event order) is T[g0, g0 + end - begin) of its first
+		// event, g0 = the sequence's start in T + begin.  The index holds canon(window) -> (g, row) for every span position with a valid
+		// window, the SMALLEST g where positions share a key (the others are duplicates; span positions with an invalid window are
+		// skipped).  ComputeLocate below is the serial statement: an unordered_map of canonical windows, no device.
+		struct EdgeIndex
+		{
+			size_t k;
+			std::string text;                                              // T
+			std::vector<uint64_t> g0;                                      // [rows]
+			std::unordered_map<std::string, std::pair<uint64_t, uint32_t> > entry;
+			uint64_t duplicates, skipped;
+			EdgeIndex() : k(0), duplicates(0), skipped(0) {}
+		};
+
+		// The table must be one whose walk did not fail and must have passed CheckEventTable against `loaded`.
+		void BuildEdgeIndex(const EventTable & table, const LoadedSequences & loaded, size_t k, EdgeIndex & out);
+
+		// Every window of every query record: invalid (it holds an N), absent (no key of the index) or a hit (g, row, rev), rev = 0 when
+		// the window equals T's letter for letter (a palindrome counts as forward).  off = g - g0(row).  A hit CONTINUES the one before it
+		// when both lie in one row with one rev and off steps by + 1 (forward) or - 1 (reverse); a RUN is a maximal chain, runs ascend by
+		// query position.  Per record: windows (valid), found, forward (hits with rev = 0), runs, shared[c] (hits whose row has colour c).
+		// The arrays come from ComputeLocate or from the device (csrc/tpc_locate.hip, devicegraph.h); the writers print either as the same bytes.
+		struct LocateTable
+		{
+			uint64_t colors, segments, entries, duplicates;
+			std::vector<uint64_t> windows, found, forward, runs;           // [queries]
+			std::vector<uint64_t> shared;                                  // [queries][colors]
+			std::vector<uint64_t> runQuery, runBegin;                      // [runs]: the record and the 0-based position of the first window on it
+			std::vector<uint32_t> runLength, runRow, runRev, runOff;       // [runs]: windows, row, rev, off of the first window
+			LocateTable() : colors(0), segments(0), entries(0), duplicates(0) {}
+			size_t Queries() const { return windows.size(); }
+			size_t Runs() const { return runQuery.size(); }
+		};
+
+		void ComputeLocate(const EdgeIndex & index, const ColorTable & colors, const LoadedSequences & queries, LocateTable & out);
+
+		// The TSV text: "#twopaco-locate\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tentries=<E>\tduplicates=<D>\tqueries=<Q>", the
+		// colour table's "#color" lines, one line per query record (name, length, windows, found, forward, runs, then C integers: the hits
+		// in rows of each colour), "#total\t<windows>\t<found>\t<forward>\t<runs>".  To stdout (path empty) or into the file `path`.
+		void WriteLocate(size_t k, const ColorMap & map, const InputSequences & queries, const LocateTable & locate, const std::string & path);
+
+		// "#twopaco-locate-walks\t1\tk=<k>", then one line per run: query_index, q_begin, q_end (half-open, 0-based on the record, q_end =
+		// q_begin + length + k), the segment as gfa1 names it, the strand, s_begin, s_end on the S line's body: where name[e0] < 0 the body
+		// is the reverse complement of the span, so the offsets and the strand are flipped.
+		void WriteLocateWalks(const EventTable & table, size_t k, const ColorTable & colors, const LocateTable & locate, const std::string & path);
+
+		// Both files, or neither: the walks first when walksPath is given, then the TSV; when the TSV cannot be written the walks file is
+		// removed again before the error is thrown.
+		void WriteLocateFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const InputSequences & queries, const LocateTable & locate,
+			const std::string & path, const std::string & walksPath);
 
 		// Header lines and events into the file outPath (created or truncated; removed again when anything fails); compact when
 		// the table carries linkFirst.

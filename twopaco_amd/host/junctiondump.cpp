@@ -9,6 +9,7 @@
 //             |  --components file|sequence [--components-out <path>] [--components-members <path>]
 //             |  --superbubbles file|sequence [--superbubbles-out <path>] [--superbubbles-members <path>] [--superbubbles-max <n>]
 //             |  --anchors file|sequence [--anchors-ref <colour>] [--anchors-out <path>] [--anchors-paf <path>]
+//             |  --locate file|sequence --locate-in <q.fa> [--locate-in ...] [--locate-out <path>] [--locate-walks <path>]
 //             (the last seven instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
@@ -79,6 +80,13 @@
 // (WriteAnchorsPaf).  Without --gpu the serial walk, then ComputeAnchors; with --gpu the anchor stage over the segment build
 // (csrc/tpc_anchors.hip); the bytes are the same.  Beside --colors, --bubbles, --distances, --components or --superbubbles of the
 // same colours it is written after them; not with --links.
+// --locate file|sequence --locate-in <q.fa> [--locate-in ...] [--locate-out <path>] [--locate-walks <path>] (an addition; instead of
+// -f): the records of the query files looked up in the graph, window by window -- is a sequence that was no input in the graph,
+// where, and in which colours; include/twopaco_hip.h defines index, hit, run and sums -- as TSV (graphformat.h: WriteLocate) and,
+// asked for, the runs as a walks file (WriteLocateWalks).  Without --gpu the serial walk, then BuildEdgeIndex and ComputeLocate;
+// with --gpu the edge index over the segment build and the queries through it in batches of whole records of at most 2^28
+// positions (csrc/tpc_locate.hip); the bytes are the same.  Beside the other tables of the same colours it is written last; not
+// with -f, --links, --compact or --text.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -504,6 +512,24 @@ namespace
 		}
 	}
 
+	// --locate beside another table of the same colours, or alone: the query files and the file names (out empty: stdout, walks empty: none)
+	struct LocateWanted
+	{
+		bool on;
+		std::vector<std::string> in;
+		std::string out, walks;
+		LocateWanted() : on(false) {}
+	};
+
+	// Positions of packed query text per device call, whole records: 2^28, or what TWOPACO_LOCATE_BATCH says (tests: a small query in
+	// several batches)
+	uint64_t LocateBatchPositions()
+	{
+		const char * e = std::getenv("TWOPACO_LOCATE_BATCH");
+		const long long n = e && *e ? std::atoll(e) : 0;
+		return n > 0 ? uint64_t(n) : uint64_t(1) << 28;
+	}
+
 	// --components beside another table of the same colours, or alone: the file names of the component table (out empty: stdout)
 	struct ComponentsWanted
 	{
@@ -526,10 +552,10 @@ namespace
 	// superbubbles, anchors
 	void DumpComponents(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const ComponentsWanted & want,
 		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo, const SuperbubblesWanted & super,
-		const AnchorsWanted & anchorsTo = AnchorsWanted())
+		const AnchorsWanted & anchorsTo = AnchorsWanted(), const LocateWanted & locateTo = LocateWanted())
 	{
 		SerialTable t;
-		WalkLinks(binFile, fasta, k, prefix, false, t);
+		WalkLinks(binFile, fasta, k, prefix, locateTo.on, t);   // (the edge index reads the letters)
 		ColorMap map;
 		MakeColorMap(t.seq, fasta, bySequence, map);
 		CheckAnchorsRef(anchorsTo, map);
@@ -545,12 +571,25 @@ namespace
 		if (super.on) ComputeSuperbubbles(t.table, k, t.links, colors, super.maxInside, superbubbles);
 		AnchorTable anchors;
 		if (anchorsTo.on) ComputeAnchors(t.table, k, map.colorOfSequence, map.label.size(), anchorsTo.ref, anchors);
+		InputSequences queries;
+		LocateTable locate;
+		if (locateTo.on)
+		{
+			LoadedSequences queryLetters;
+			LoadSequences(locateTo.in, false, 1, queries, queryLetters);
+			CheckEventTable(t.table, t.loaded, k, 1);
+			EdgeIndex index;
+			BuildEdgeIndex(t.table, t.loaded, k, index);
+			ComputeLocate(index, colors, queryLetters, locate);
+		}
+
 		if (colorsToo) WriteColors(t.table, k, map, colors, firstOut);
 		if (bubblesToo) WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, firstOut);
 		if (distancesToo) WriteDistanceFiles(k, map, colors.Rows(), distances, distancesTo.out, distancesTo.phylip);
 		if (want.on) WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
 		if (super.on) WriteSuperbubbleFiles(t.table, k, map, colors, t.links.Rows(), superbubbles, super.out, super.members);
 		if (anchorsTo.on) WriteAnchorFiles(t.table, k, map, t.seq, anchors, anchorsTo.out, anchorsTo.paf);
+		if (locateTo.on) WriteLocateFiles(t.table, k, map, colors, queries, locate, locateTo.out, locateTo.walks);
 	}
 
 	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
@@ -586,10 +625,12 @@ namespace
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
 		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored, anchorBlocks, anchors;
 		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs, superbubblesKernelMs, superbubblesMs, anchorsKernelMs, anchorsMs;
+		double edgesKernelMs, edgesMs, locateKernelMs, locateMs;
+		uint64_t locateRuns, locateBatches;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
 			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
-			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), superbubblesKernelMs(0), superbubblesMs(0), anchorsKernelMs(0), anchorsMs(0), threads(1) {}
+			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), superbubblesKernelMs(0), superbubblesMs(0), anchorsKernelMs(0), anchorsMs(0), edgesKernelMs(0), edgesMs(0), locateKernelMs(0), locateMs(0), locateRuns(0), locateBatches(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -605,13 +646,14 @@ namespace
 				"\"bubbles_kernel_ms\": %.3f, \"bubbles_ms\": %.3f, \"bubbles\": %llu, \"distances_kernel_ms\": %.3f, \"distances_ms\": %.3f, "
 				"\"components_kernel_ms\": %.3f, \"components_ms\": %.3f, \"components\": %llu, \"largest_component\": %llu, "
 				"\"superbubbles_kernel_ms\": %.3f, \"superbubbles_ms\": %.3f, \"superbubbles\": %llu, \"superbubble_members\": %llu, \"superbubbles_unmirrored\": %llu, "
-				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu, "
+				"\"edges_kernel_ms\": %.3f, \"edges_ms\": %.3f, \"locate_kernel_ms\": %.3f, \"locate_ms\": %.3f, \"locate_runs\": %llu, \"locate_batches\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
 				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs,
 				(unsigned long long)components, (unsigned long long)largestComponent, superbubblesKernelMs, superbubblesMs, (unsigned long long)superbubbles,
 				(unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, anchorsKernelMs, anchorsMs, (unsigned long long)anchorBlocks,
-				(unsigned long long)anchors);
+				(unsigned long long)anchors, edgesKernelMs, edgesMs, locateKernelMs, locateMs, (unsigned long long)locateRuns, (unsigned long long)locateBatches);
 			std::fclose(f);
 		}
 	};
@@ -771,6 +813,7 @@ namespace
 		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers, superbubblesOut, superbubblesMembers;
 		uint32_t superbubblesMax;
 		AnchorsWanted anchors;
+		LocateWanted locate;
 	};
 
 	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
@@ -787,7 +830,7 @@ namespace
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
 		ColorMap map;
 		ColorTable colors;
-		const bool colorTable = want.colors || want.bubbles || want.distances || want.components || want.superbubbles;
+		const bool colorTable = want.colors || want.bubbles || want.distances || want.components || want.superbubbles || want.locate.on;
 		if (colorTable || want.anchors.on)
 		{
 			MakeColorMap(seq, fasta, want.bySequence, map);
@@ -800,7 +843,7 @@ namespace
 			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
 			BuildColors(lib, map);
 			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
-			if (want.colors || want.bubbles || want.components || want.superbubbles) FetchColors(lib, map, counts[1], colors);
+			if (want.colors || want.bubbles || want.components || want.superbubbles || want.locate.on) FetchColors(lib, map, counts[1], colors);
 			stats.colorsMs = MsSince(c0);
 		}
 
@@ -870,8 +913,28 @@ namespace
 			TimingLine("anchor table", stats.anchorsMs, stats.anchorsKernelMs);
 		}
 
+		InputSequences queries;
+		LocateTable locate;
+		if (want.locate.on)
+		{
+			// the edge index over the table and the text where they are, the colour rows of the build above (csrc/tpc_locate.hip)
+			const std::chrono::steady_clock::time_point l0 = std::chrono::steady_clock::now();
+			LoadedSequences queryLetters;
+			LoadSequences(want.locate.in, false, threads, queries, queryLetters);
+			uint64_t edges[6] = {0, 0, 0, 0, 0, 0};
+			BuildEdges(lib, edges);
+			stats.edgesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_LOCATE);
+			stats.edgesMs = MsSince(l0);
+			TimingLine("edge index", stats.edgesMs, stats.edgesKernelMs);
+			const std::chrono::steady_clock::time_point l1 = std::chrono::steady_clock::now();
+			stats.locateBatches = LocateOnDevice(lib, edges, map.label.size(), counts[1], queryLetters, LocateBatchPositions(), locate, stats.locateKernelMs);
+			stats.locateRuns = locate.Runs();
+			stats.locateMs = MsSince(l1);
+			TimingLine("locate", stats.locateMs, stats.locateKernelMs);
+		}
+
 		Events held(counts[0], sequences);
-		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles || want.anchors.on) FetchTable(lib, held);
+		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles || want.anchors.on || want.locate.on) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
 		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
@@ -881,6 +944,7 @@ namespace
 		if (want.components) WriteComponentFiles(held.table, k, map, colors, stats.links, components, want.componentsOut, want.componentsMembers);
 		if (want.superbubbles) WriteSuperbubbleFiles(held.table, k, map, colors, stats.links, superbubbles, want.superbubblesOut, want.superbubblesMembers);
 		if (want.anchors.on) WriteAnchorFiles(held.table, k, map, seq, anchors, want.anchors.out, want.anchors.paf);
+		if (want.locate.on) WriteLocateFiles(held.table, k, map, colors, queries, locate, want.locate.out, want.locate.walks);
 		stats.formatMs = MsSince(t0);
 		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
 	}
@@ -1017,6 +1081,12 @@ namespace
 			"     colours, the input sequences and per colour the blocks, anchors, edges and reverse edges it shares with the reference.\n"
 			"     Needs -k and -s.  With --gpu they are found on the device.  Goes with --colors, --bubbles, --distances, --components or\n"
 			"     --superbubbles of the same colours (one walk for all; this table is written last); not with --links, --compact or --text.\n\n"
+			"   --locate <file|sequence>\n     instead of -f: every (k+1)-mer of the records of the --locate-in files looked up in the graph -- per query record its\n"
+			"     valid windows, those found, those found on the forward strand, the runs they form and, per colour, the hits in segments of\n"
+			"     that colour, as TSV; the colours as of --colors.  Beside the other tables of the same colours it is written last.\n\n"
+			"   --locate-in <file name>  (accepted multiple times)\n     with --locate: a FASTA file of query records\n\n"
+			"   --locate-out <file name>\n     with --locate: write the table there instead of to the standard output\n\n"
+			"   --locate-walks <file name>\n     with --locate: also write the runs there, one line per run: the query's interval and the segment's\n\n"
 			"   --anchors-ref <integer>\n     with --anchors: the index of the reference colour (default 0)\n\n"
 			"   --anchors-out <file name>\n     with --anchors: write the table there instead of to the standard output\n\n"
 			"   --anchors-paf <file name>\n     with --anchors: also write the blocks there as PAF, one line per block\n\n"
@@ -1029,7 +1099,9 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers, anchorsBy, anchorsOut, anchorsPaf;
+		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers, anchorsBy, anchorsOut, anchorsPaf, locateBy, locateOut, locateWalks;
+		std::vector<std::string> locateIn;
+		bool locateOutSet = false, locateWalksSet = false;
 		std::vector<std::string> fasta;
 		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
 		uint32_t superbubblesMax = 62, anchorsRef = 0;
@@ -1128,6 +1200,14 @@ int main(int argc, char * argv[])
 				anchorsBy = value("(--anchors)");
 				if (anchorsBy != "file" && anchorsBy != "sequence") throw ArgError("Value '" + anchorsBy + "' does not meet constraint: file|sequence", "Argument: (--anchors)");
 			}
+			else if (a == "--locate")
+			{
+				locateBy = value("(--locate)");
+				if (locateBy != "file" && locateBy != "sequence") throw ArgError("Value '" + locateBy + "' does not meet constraint: file|sequence", "Argument: (--locate)");
+			}
+			else if (a == "--locate-in") locateIn.push_back(value("(--locate-in)"));
+			else if (a == "--locate-out") { locateOut = value("(--locate-out)"); locateOutSet = true; }
+			else if (a == "--locate-walks") { locateWalks = value("(--locate-walks)"); locateWalksSet = true; }
 			else if (a == "--anchors-out") { anchorsOut = value("(--anchors-out)"); anchorsOutSet = true; }
 			else if (a == "--anchors-paf") { anchorsPaf = value("(--anchors-paf)"); anchorsPafSet = true; }
 			else if (a == "--anchors-ref")
@@ -1162,6 +1242,22 @@ int main(int argc, char * argv[])
 		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty(), components = !componentsBy.empty();
 		const bool superbubbles = !superbubblesBy.empty();
 		const bool anchors = !anchorsBy.empty();
+		const bool locate = !locateBy.empty();
+		if (locate && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--locate)");
+		if (locate && colors && colorsBy != locateBy) throw ArgError("The locate table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && bubbles && bubblesBy != locateBy) throw ArgError("The locate table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && distances && distancesBy != locateBy) throw ArgError("The locate table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && components && componentsBy != locateBy) throw ArgError("The locate table and the component table share one set of colours: --components " + componentsBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && superbubbles && superbubblesBy != locateBy) throw ArgError("The locate table and the superbubble table share one set of colours: --superbubbles " + superbubblesBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && anchors && anchorsBy != locateBy) throw ArgError("The locate table and the anchor table share one set of colours: --anchors " + anchorsBy + " does not go with --locate " + locateBy, "(--locate)");
+		if (locate && links) throw ArgError("The locate table and the link table are written one at a time: not with --links", "(--locate)");
+		if (locate && compact) throw ArgError("The locate table and the compact text are written one at a time: not with --compact", "(--locate)");
+		if (locate && textSet) throw ArgError("The locate table is formatted by the host: not with --locate", "(--text)");
+		if (locate && locateIn.empty()) throw ArgError("The locate table needs a query: --locate-in <fasta file>", "(--locate)");
+		if (!locateIn.empty() && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-in)");
+		if (locateOutSet && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-out)");
+		if (locateWalksSet && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-walks)");
+		if (locateWalksSet && locateWalks.empty()) throw ArgError("The locate walks need a file name", "(--locate-walks)");
 		if (anchors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--anchors)");
 		if (anchors && colors && colorsBy != anchorsBy) throw ArgError("The anchor table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
 		if (anchors && bubbles && bubblesBy != anchorsBy) throw ArgError("The anchor table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
@@ -1223,10 +1319,10 @@ int main(int argc, char * argv[])
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles && !anchors) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles && !anchors && !locate) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || anchors || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || anchors || locate || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -1247,7 +1343,12 @@ int main(int argc, char * argv[])
 		anchorsTo.ref = anchorsRef;
 		anchorsTo.out = anchorsOut;
 		anchorsTo.paf = anchorsPaf;
-		if ((colors || links || bubbles || distances || components || superbubbles || anchors) && lib)
+		LocateWanted locateTo;
+		locateTo.on = locate;
+		locateTo.in = locateIn;
+		locateTo.out = locateOut;
+		locateTo.walks = locateWalks;
+		if ((colors || links || bubbles || distances || components || superbubbles || anchors || locate) && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
@@ -1265,7 +1366,8 @@ int main(int argc, char * argv[])
 			want.superbubblesMembers = superbubblesMembers;
 			want.superbubblesMax = superbubblesMax;
 			want.anchors = anchorsTo;
-			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubbles ? superbubblesBy : anchorsBy) == "sequence";
+			want.locate = locateTo;
+			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubbles ? superbubblesBy : anchors ? anchorsBy : locateBy) == "sequence";
 			want.componentsOut = componentsOut;
 			want.componentsMembers = componentsMembers;
 			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
@@ -1273,7 +1375,7 @@ int main(int argc, char * argv[])
 			want.distancesPhylip = distancesPhylip;
 			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
 		}
-		else if (components || superbubbles || anchors)
+		else if (components || superbubbles || anchors || locate)
 		{
 			ComponentsWanted wanted;
 			wanted.on = components;
@@ -1284,7 +1386,7 @@ int main(int argc, char * argv[])
 			super.out = superbubblesOut;
 			super.members = superbubblesMembers;
 			super.maxInside = superbubblesMax;
-			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubbles ? superbubblesBy : anchorsBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super, anchorsTo);
+			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubbles ? superbubblesBy : anchors ? anchorsBy : locateBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super, anchorsTo, locateTo);
 		}
 		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
 		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);

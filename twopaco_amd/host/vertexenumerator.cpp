@@ -382,6 +382,16 @@ namespace TwoPaCo
 				if (anchors && superbubbles && options.anchorsBy != options.superbubblesBy) throw std::runtime_error("The anchor table and the superbubble table share one set of colours: both by file or both by sequence");
 				if (anchors && sharded) throw std::runtime_error("The anchor table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				if (!anchors && !options.anchorsPafFile.empty()) throw std::runtime_error("The anchor PAF is written with the anchor table only");
+				const bool locate = !options.locateFile.empty();
+				if (locate && options.locateBy != "file" && options.locateBy != "sequence") throw std::runtime_error("The locate table's colours must be one of file, sequence");
+				if (locate && options.locateIn.empty()) throw std::runtime_error("The locate table needs the FASTA files of the queries");
+				for (const std::string * by : { &options.colorsBy, &options.bubblesBy, &options.distancesBy, &options.componentsBy, &options.superbubblesBy, &options.anchorsBy })
+				{
+					if (locate && !by->empty() && *by != options.locateBy) throw std::runtime_error("The locate table and the other tables share one set of colours: all by file or all by sequence");
+				}
+
+				if (locate && sharded) throw std::runtime_error("The locate table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+				if (!locate && !options.locateWalksFile.empty()) throw std::runtime_error("The locate walks are written with the locate table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -516,7 +526,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors)
+				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors || locate)
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -1014,7 +1024,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors || locate) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -1036,16 +1046,19 @@ namespace TwoPaCo
 			// colour rows; options.superbubblesFile and the members file are written after the component files, both or neither
 			// (WriteSuperbubbleFiles).
 			// --anchors: the anchor stage (csrc/tpc_anchors.hip) over the event table of the same build and the colour map alone;
-			// options.anchorsFile and the PAF file are written last of all, both or neither (WriteAnchorFiles).
+			// options.anchorsFile and the PAF file are written after the superbubble files, both or neither (WriteAnchorFiles).
+			// --locate: the edge index and the lookups (csrc/tpc_locate.hip) over the event table, the text and the colour rows of the same
+			// build, the queries in batches of whole records; options.locateFile and the walks file are written last of all, both or
+			// neither (WriteLocateFiles).
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
 				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
 				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), components = !options.componentsFile.empty();
-				const bool superbubbles = !options.superbubblesFile.empty(), anchors = !options.anchorsFile.empty();
-				const bool colorRows = colors || bubbles || distances || components || superbubbles;
+				const bool superbubbles = !options.superbubblesFile.empty(), anchors = !options.anchorsFile.empty(), locate = !options.locateFile.empty();
+				const bool colorRows = colors || bubbles || distances || components || superbubbles || locate;
 				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : components ? options.componentsBy :
-					superbubbles ? options.superbubblesBy : options.anchorsBy) == "sequence";
+					superbubbles ? options.superbubblesBy : anchors ? options.anchorsBy : options.locateBy) == "sequence";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
 				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
@@ -1065,6 +1078,10 @@ namespace TwoPaCo
 				GraphFormat::ComponentTable componentTable;
 				GraphFormat::SuperbubbleTable superbubbleTable;
 				GraphFormat::AnchorTable anchorTable;
+				GraphFormat::LocateTable locateTable;
+				GraphFormat::InputSequences querySeq;
+				GraphFormat::LoadedSequences queryLetters;
+				if (locate) GraphFormat::LoadSequences(options.locateIn, false, threads, querySeq, queryLetters);
 				auto anchorColors = [&]()
 				{
 					if (!colorRows) GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
@@ -1098,6 +1115,13 @@ namespace TwoPaCo
 					{
 						anchorColors();
 						GraphFormat::ComputeAnchors(held.table, k, map.colorOfSequence, map.label.size(), options.anchorsRef, anchorTable);
+					}
+
+					if (locate)
+					{
+						GraphFormat::EdgeIndex index;
+						GraphFormat::BuildEdgeIndex(held.table, loaded, k, index);
+						GraphFormat::ComputeLocate(index, colorTable, queryLetters, locateTable);
 					}
 				}
 				else
@@ -1251,6 +1275,19 @@ namespace TwoPaCo
 						timer.Lap("segment anchors fetch");
 					}
 
+					if (locate)
+					{
+						// over the event table, the text and the colour rows where they lie (csrc/tpc_locate.hip); the walks print the rows' names
+						uint64_t edges[6] = {0, 0, 0, 0, 0, 0};
+						DeviceGraph::BuildEdges(api, edges);
+						timer.Lap("edge index");
+						kernelLine("edges_kernel_ms", TPC_K_LOCATE);
+						double kernelMs = 0;
+						DeviceGraph::LocateOnDevice(api, edges, map.label.size(), segments, queryLetters, uint64_t(1) << 28, locateTable, kernelMs);
+						timer.Lap("locate");
+						if (timing) std::cerr << "[timing]   locate_kernel_ms: " << kernelMs << " ms" << std::endl;
+					}
+
 					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
 					else if (graph && !fetched) fetchTable();
 				}
@@ -1307,6 +1344,12 @@ namespace TwoPaCo
 				{
 					GraphFormat::WriteAnchorFiles(held.table, k, map, seq, anchorTable, options.anchorsFile, options.anchorsPafFile);
 					timer.Lap("anchor table writing");
+				}
+
+				if (locate)
+				{
+					GraphFormat::WriteLocateFiles(held.table, k, map, colorTable, querySeq, locateTable, options.locateFile, options.locateWalksFile);
+					timer.Lap("locate table writing");
 				}
 			}
 

@@ -121,6 +121,15 @@ namespace TwoPaCo
 		std::string anchorsFile;
 		std::string anchorsPafFile;
 		uint32_t anchorsRef = 0;
+		// The query records of locateIn looked up in the graph window by window (graphformat.h: WriteLocate; `graphdump --locate` writes
+		// the same bytes for the junction stream of this run): locateFile (empty: off), locateBy = "file" | "sequence" -- the same as the
+		// other tables' when those are given --, locateIn, the FASTA files of the queries, and locateWalksFile (empty: off) for the
+		// runs.  The edge index and the lookups run on the device (tpc_segments_edges_build, tpc_segments_locate) over the event table
+		// and the colour rows of the same segment build.  One GPU.
+		std::string locateBy;
+		std::string locateFile;
+		std::string locateWalksFile;
+		std::vector<std::string> locateIn;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
