@@ -917,10 +917,15 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *   qhash_pushes       process-wide, 6 (default): k_q_hash2 compacts the 3 + 3 unknown edges of a position per lane and pushes them
  *                      with every lane active; 8: the 4 + 4 candidates as predicated pushes.  TPC_QHASH_PUSHES=6 / 8 in the
  *                      environment overrides the option (measurements; read once per process)
- *   qhash_roll_scalars process-wide, 1 (default): k_q_hash2 rolls its hash with letter hashes selected from scalar registers; 0: with
+ *   qhash_roll_scalars process-wide, 1 (default): k_q_hash2 rolls its hash with letter hashes taken from scalar registers by lane masks; 0: with
  *                      two 16-byte LDS reads per position.  TPC_QHASH_ROLL_SCALARS=0 / 1 overrides it.  A sharded context (more
  *                      than one rank) with qhash_pushes = 8 always takes the LDS reads, whatever this option says: one of its
  *                      instantiations spilled with the selects.  "query_hash_form" tells which roll ran
+ *   qhash_seed_scalars process-wide, 1 (default): k_q_hash2 seeds a thread's run of 16 positions from function 0's pre-rotated letter
+ *                      rows [k][5] x 16 bytes that tpc_set_params keeps in device memory: the five rows of a character are loaded at a
+ *                      uniform index and XORed in under one-hot lane masks of the letter; 0: from the same rows in LDS, one 16-byte read per character at
+ *                      a per-lane index.  TPC_QHASH_SEED_SCALARS=0 / 1 overrides it.  k > "query_hash_seed_maxk" (64) has no such rows and seeds by rolling
+ *                      whatever the option says.  "query_hash_seed" tells which seeding ran
  *   mark_bucket_bits / mark_region_cap / mark_slice_bits   tests only, process-wide (0 = automatic): log2 positions of a bucket of the
  *                      mark lists (14..21), entries of a (workgroup, bucket) region (tiny: most entries take the atomic fallback),
  *                      log2 bits of the LDS slice k_mark_apply holds (10..20: a larger bucket is cut into sub-slices)
@@ -961,6 +966,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "query_hash_form" = of the last k_q_hash2 launch (0 after another hash kernel): 1 = six compacted pushes per position (option
  * qhash_pushes), + 2 = the roll from scalar registers (option qhash_roll_scalars), + 4 = its gated instantiation (a range [lo, hi] that
  * is not the whole hash space);
+ * "query_hash_seed" = 1 when the last k_q_hash2 launch seeded its runs from the uniform rows (option qhash_seed_scalars), 0 when it read
+ * them from LDS or rolled (k > 64), and after another hash kernel -- a stat of its own and not a bit of "query_hash_form", whose values
+ * 0..7 callers compare as they stand; "query_hash_seed_maxk" = the longest k that has such rows (a constant);
  * "query_verify_kernel" = 0 none (the direct kernels verify in place), 1 k_q_verify2 lazy, 2 k_q_verify2 eager (TPC_VERIFY_LAZY=0), 3 k_q_verify;
  * "query_mark_path" = how the last query set the marks of its mask: 1 the write-combined lists, 0 device atomics (option verify_marks, a
  * plan whose lists do not fit the level-1 buffer) or the direct kernel (also when it completed an overflowed partitioned pass);

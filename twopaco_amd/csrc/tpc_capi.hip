@@ -25,6 +25,7 @@ TpcLaunch make_launch(const tpc_ctx *c)
     a.P = c->P; a.tab = c->tab; a.bases = c->bases; a.nmask = c->nmask; a.n_text = c->n_text;
     a.n_tiles = c->n_tiles; a.filter = c->filter; a.stream = c->stream;
     a.stat_kernel = c->stat_kernel;
+    if (c->P.k <= TPC_QSEED_MAXK) a.qseed = c->tab + TPC_TAB_WORDS;
     return a;
 }
 
@@ -320,7 +321,7 @@ int tpc_ctx_create(int device, tpc_ctx **out)
     for (int i = 0; i < TPC_K_COUNT; i++) {
         if (hipEventCreate(&c->ev0[i]) != hipSuccess || hipEventCreate(&c->ev1[i]) != hipSuccess) { delete c; return -5; }
     }
-    if (hipMalloc((void **)&c->tab, TPC_TAB_WORDS * sizeof(uint64_t)) != hipSuccess ||
+    if (hipMalloc((void **)&c->tab, sizeof c->tab_host) != hipSuccess ||
         hipMalloc((void **)&c->counters, 8 * sizeof(unsigned long long)) != hipSuccess ||
         hipMalloc((void **)&c->route_scratch, 128 * sizeof(unsigned long long)) != hipSuccess) { delete c; return -6; }
     *out = c;
@@ -374,6 +375,7 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "mark_slice_bits")) { tpc_test_mark_slice_bits = (int)value; return 0; }    // process-wide, tests only
     if (!strcmp(name, "qhash_pushes")) { tpc_opt_qhash_pushes = value == 8 ? 8 : 6; return 0; }          // process-wide (tpc_internal.h)
     if (!strcmp(name, "qhash_roll_scalars")) { tpc_opt_qhash_roll = value != 0; return 0; }               // process-wide (tpc_internal.h)
+    if (!strcmp(name, "qhash_seed_scalars")) { tpc_opt_qhash_seed = value != 0; return 0; }               // process-wide (tpc_internal.h)
     if (!strcmp(name, "fuse_apply_lookup")) { c->opt_fuse = value != 0; return 0; }
     if (!strcmp(name, "test_q6_pb2")) { tpc_test_q6_pb2 = (int)value; return 0; }  // process-wide, tests only
     if (!strcmp(name, "insert_entry_fmt")) { tpc_test_insert_p3 = value == 3; return 0; }  // process-wide; 3 = blocked 24-bit level-2 insert entries (off by default: tpc_partition.hip)
@@ -431,6 +433,8 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "query_hash_kernel")) return c->stat_kernel[1];
     if (!strcmp(name, "query_verify_kernel")) return c->stat_kernel[2];
     if (!strcmp(name, "query_hash_form")) return c->stat_kernel[3];
+    if (!strcmp(name, "query_hash_seed")) return c->stat_kernel[4];
+    if (!strcmp(name, "query_hash_seed_maxk")) return TPC_QSEED_MAXK;
     if (!strcmp(name, "query_mark_path")) return c->stat_mark_path;
     if (!strcmp(name, "query_mark_fallback")) return c->stat_mark_fallback;
     if (!strcmp(name, "insert_batches")) return c->stat_batches[0];
@@ -489,6 +493,15 @@ int tpc_set_params(tpc_ctx *c, int k, int L, int q, const uint64_t *seed_table)
             c->tab_host[i * 5 + ch] = h;
             c->tab_host[TPC_TAB_HK + i * 5 + ch] = rotln_host(h, L, c->P.rk);
         }
+    // k_q_hash2's seed rows, function 0: H(w) = XOR_t rotl(h[w_t], k-1-t), H'(w) = XOR_t rotl(h[rc w_t], t) (cyclichash.h:106-109 folded).
+    // They depend on k, L and the seed table, all three set here and nowhere else.
+    if (k <= TPC_QSEED_MAXK)
+        for (int t = 0; t < k; t++)
+            for (int ch = 0; ch < 5; ch++) {
+                const int rc = ch == 4 ? 4 : 3 - ch;
+                c->tab_host[TPC_TAB_WORDS + (t * 5 + ch) * 2] = rotln_host(c->tab_host[ch], L, (k - 1 - t) % L);
+                c->tab_host[TPC_TAB_WORDS + (t * 5 + ch) * 2 + 1] = rotln_host(c->tab_host[rc], L, t % L);
+            }
     HIPCHK(c, hipMemcpy(c->tab, c->tab_host, sizeof c->tab_host, hipMemcpyHostToDevice));
     const uint64_t fw = filter_words_for(L, c->opt_replicate ? 1 : c->sh_world);
     c->sh_have[0] = c->sh_have[1] = false;

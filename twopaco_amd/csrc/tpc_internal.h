@@ -9,11 +9,12 @@
 // on every pass).  TPC_NO_LEAN: the generic hash kernels; TPC_RB_HASH: the barrier-free rings in the 512-bin hash; TPC_VERIFY_LAZY=0:
 // all q - 1 probes at once; TPC_GATED_FULL_REGIONS: gated rounds sized for all entries; TPC_PPR_INSERT / TPC_GATED_LOADS: round sizes;
 // TPC_VERIFY_MARKS=0 / 1: the verification's marks as device atomics / as write-combined lists, whatever option "verify_marks" says.
-// TPC_QHASH_PUSHES=6 / 8 and TPC_QHASH_ROLL_SCALARS=0 / 1: the same for the options "qhash_pushes" and "qhash_roll_scalars" (below).
+// TPC_QHASH_PUSHES=6 / 8, TPC_QHASH_ROLL_SCALARS=0 / 1 and TPC_QHASH_SEED_SCALARS=0 / 1: the same for the options "qhash_pushes", "qhash_roll_scalars"
+// and "qhash_seed_scalars" (below).
 struct TpcEnv {
     bool no_lean, rb_hash, verify_eager, gated_full;
     int verify_marks;  // -1: not set
-    int qhash_pushes, qhash_roll;  // 0 / -1: not set
+    int qhash_pushes, qhash_roll, qhash_seed;  // 0 / -1 / -1: not set
     int ppr_insert, gated_loads, split_loads9;  // 0: not set
     int slice_grid;  // workgroups of a one-slice-at-a-time kernel (tpc_slice_grid); 0: one per slice
     static const TpcEnv &get()
@@ -31,6 +32,8 @@ struct TpcEnv {
             v.qhash_pushes = qp && (atoi(qp) == 6 || atoi(qp) == 8) ? atoi(qp) : 0;  // (anything else: as if not set)
             const char *qr = getenv("TPC_QHASH_ROLL_SCALARS");
             v.qhash_roll = qr && qr[0] ? (qr[0] != '0' ? 1 : 0) : -1;
+            const char *qs = getenv("TPC_QHASH_SEED_SCALARS");
+            v.qhash_seed = qs && qs[0] ? (qs[0] != '0' ? 1 : 0) : -1;
             const char *p = getenv("TPC_PPR_INSERT"), *g = getenv("TPC_GATED_LOADS");
             v.ppr_insert = p ? atoi(p) : 0;
             v.gated_loads = g ? atoi(g) : 0;
@@ -56,22 +59,29 @@ inline uint32_t tpc_slice_grid(uint32_t n_slices)
     return g > 0 ? std::min<uint32_t>(n_slices, (uint32_t)g) : n_slices;
 }
 
-// LDS instructions of k_q_hash2 that the result does not need (profiles/r09_qhash_lds.md); both process-wide, for A/B:
+// LDS instructions of k_q_hash2 that the result does not need (profiles/r09_qhash_lds.md, r10_qhash_seed.md); all process-wide, for A/B:
 //   option "qhash_pushes" = 6 (default): the 3 + 3 unknown edges of a position are compacted per lane and pushed with every lane
 //     active; 8: the four in- and four out-edge candidates as predicated pushes.
-//   option "qhash_roll_scalars" = 1 (default): the roll selects its letter hashes from scalar registers; 0: two 16-byte LDS reads.
-extern int tpc_opt_qhash_pushes, tpc_opt_qhash_roll;  // tpc_qpartition.hip
+//   option "qhash_roll_scalars" = 1 (default): the roll takes its letter hashes from scalar registers, by one-hot lane masks; 0: two 16-byte LDS reads.
+//   option "qhash_seed_scalars" = 1 (default): a run is seeded from the rows of TpcLaunch::qseed, loaded at uniform indices and
+//     XORed in under one-hot lane masks of the letter; 0: from the same rows in LDS, one 16-byte read per character at a per-lane index.  k > TPC_QSEED_MAXK: neither (rolled).
+extern int tpc_opt_qhash_pushes, tpc_opt_qhash_roll, tpc_opt_qhash_seed;  // tpc_qpartition.hip
 inline bool tpc_qhash_roll_scalars() { const int e = TpcEnv::get().qhash_roll; return (e >= 0 ? e : tpc_opt_qhash_roll) != 0; }
+inline bool tpc_qhash_seed_scalars() { const int e = TpcEnv::get().qhash_seed; return (e >= 0 ? e : tpc_opt_qhash_seed) != 0; }
 inline bool tpc_qhash_compact() { const int e = TpcEnv::get().qhash_pushes; return (e ? e : tpc_opt_qhash_pushes) != 8; }
 
 #define TPC_TAB_MAXQ 64                // = TPC_MAX_Q (include/twopaco_hip.h)
 #define TPC_KERNEL_MAXQ 16             // the rolling kernels are instantiated for 1..16 functions; beyond that tpc_pass1_anyq.hip
 #define TPC_TAB_HK (TPC_TAB_MAXQ * 5)  // device table layout: h[64][5] then hk[64][5]
 #define TPC_TAB_WORDS (2 * TPC_TAB_MAXQ * 5)
+// behind them, function 0's seed rows of k_q_hash2 (TpcLaunch::qseed): [k][5] rows {rotl(h[c], (k-1-t) % L), rotl(h[rc c], t % L)}, k <= TPC_QSEED_MAXK
+#define TPC_QSEED_MAXK 64
+#define TPC_QSEED_WORDS (TPC_QSEED_MAXK * 5 * 2)
 
 struct TpcLaunch {
     TpcHashParams P;
     const uint64_t *tab;    // device: character tables
+    const uint64_t *qseed = nullptr;  // device: the seed rows behind them (tpc_set_params), or nullptr when k > TPC_QSEED_MAXK
     const uint64_t *bases;  // device: packed text
     const uint32_t *nmask;  // device: N mask
     uint64_t n_text;
@@ -87,7 +97,8 @@ struct TpcLaunch {
     // measurement: recorded around the k_apply_lookup launch of tpc_launch_query_part_fused_lookup when set (TPC_K_LOOKUP)
     hipEvent_t ev_lookup0 = nullptr, ev_lookup1 = nullptr;
     // when set: the launchers record which hash / verification kernel they chose, [0] insert hash, [1] query hash, [2] query
-    // verification (tpc_ctx::stat_kernel, the values of tpc_get_stat "insert_hash_kernel" / "query_hash_kernel" / "query_verify_kernel" / "query_hash_form")
+    // verification, [3] / [4] the form and the seeding of k_q_hash2 (tpc_ctx::stat_kernel, the values of tpc_get_stat "insert_hash_kernel" /
+    // "query_hash_kernel" / "query_verify_kernel" / "query_hash_form" / "query_hash_seed")
     int *stat_kernel = nullptr;
 };
 constexpr int TPC_PER_MAXP = 63;    // periods of the periodic windows the first pass skips (tpc_qpartition.hip:k_periodic_build)

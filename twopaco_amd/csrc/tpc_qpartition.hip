@@ -41,7 +41,7 @@
 
 #if TPC_QPARTITION_PART == 0
 int tpc_test_q6_pb2 = 0;  // option "test_q6_pb2" (tests)
-int tpc_opt_qhash_pushes = 6, tpc_opt_qhash_roll = 1;  // options "qhash_pushes", "qhash_roll_scalars" (tpc_internal.h)
+int tpc_opt_qhash_pushes = 6, tpc_opt_qhash_roll = 1, tpc_opt_qhash_seed = 1;  // options "qhash_pushes", "qhash_roll_scalars", "qhash_seed_scalars" (tpc_internal.h)
 int tpc_test_mark_bucket_bits = 0, tpc_test_mark_region_cap = 0, tpc_test_mark_slice_bits = 0;  // options "mark_bucket_bits", "mark_region_cap", "mark_slice_bits" (tests)
 #endif
 
@@ -241,14 +241,28 @@ k_q_hash(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const ui
 // ------------------------------------------------------------------------------------------ A, instruction-lean
 // The same level-1 pass as k_q_hash<.., RB = false>, rebuilt around the VALU instruction count (tpc_lean.h): the 16 first and
 // 16 next characters of a thread's run sit in two registers, rotations and the address split work on 32-bit halves, the run
-// is seeded from a table of pre-rotated letter hashes (one 16-byte LDS read per character: H(w) = XOR_t rotl(h[w_t], k-1-t),
-// H'(w) = XOR_t rotl(h[rc w_t], t); cyclichash.h:106-109 folded), the roll reads {h[c], hk[rc c]} / {hk[c], h[rc c]} as
-// 16-byte pairs, and the bins are Bins3.  Used whenever the geometry allows (launch_qhash); entries, masks and overflow
+// is seeded from a table of pre-rotated letter hashes (H(w) = XOR_t rotl(h[w_t], k-1-t), H'(w) = XOR_t rotl(h[rc w_t], t);
+// cyclichash.h:106-109 folded: five 16-byte rows per character, from uniform loads or one LDS read, QH_SEED_S), the roll takes
+// {h[c], hk[rc c]} / {hk[c], h[rc c]} from scalar registers or as 16-byte pairs from LDS (QH_ROLL_S), and the bins are Bins3.  Used whenever the geometry allows (launch_qhash); entries, masks and overflow
 // entries are those of k_q_hash (order inside a region differs: nothing downstream depends on it).
-constexpr int QT_MAXK = 64;  // seed table: k x 5 letters x 16 bytes
+constexpr int QT_MAXK = TPC_QSEED_MAXK;  // seed table: k x 5 letters x 16 bytes
 // k_q_hash2's mode bits (uniform).  The kernel is bound by the LDS pipe, and the two per-lane-indexed 16-byte reads of the roll
 // turned out to hold it for ~0.6 G of its 2.0 G busy cycles (profiles/r09_qhash_lds.md):
-constexpr uint32_t QH_ROLL_S = 1u;  // the roll selects its letter hashes from scalar registers instead of reading them from s_roll
+constexpr uint32_t QH_ROLL_S = 1u;  // the roll takes its letter hashes from scalar registers (by lane masks) instead of reading them from s_roll
+// The seeding read s_seed the same way, k reads per run of 16 positions.  The row index t is the same for every lane and only the
+// letter differs, so the five rows of a character come through uniform loads and the lane takes its own under a one-hot mask (profiles/r10_qhash_seed.md):
+constexpr uint32_t QH_SEED_S = 2u;  // a run is seeded from the rows of `qseed` (tpc_set_params) instead of s_seed; needs k <= QT_MAXK
+
+// v ^ (row & mask) in one instruction: v_bitop3_b32 with the truth table (a & b) ^ c = 0x6A (a = 0xF0, b = 0xCC, c = 0xAA).  The
+// compiler does not form it by itself (it emits the v_and and the v_xor), and with a scalar `row` it needs no move.
+__device__ __forceinline__ uint32_t q_xor_and(uint32_t v, uint32_t row, uint32_t mask)
+{
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(row, mask, v, 0x6Au);
+#else
+    return v ^ (row & mask);
+#endif
+}
 
 // every mask bit doubled: bit i -> bits 2i, 2i+1
 __device__ __forceinline__ uint64_t q_spread2(uint32_t m)
@@ -267,7 +281,8 @@ __global__ void __launch_bounds__(QH_THREADS)
 k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__restrict__ bases,
           const uint32_t *__restrict__ nmask, uint64_t n_text, uint64_t tile0, uint64_t n_tiles, int pos_per_round,
           uint64_t lo, uint64_t hi, uint64_t *buf1, uint32_t *cnt1, uint64_t cap1, QOverflow ovf, PtPerm perm, PtShard sh,
-          uint64_t gbase, uint32_t *__restrict__ rmask, uint32_t tiles_per_wg, const uint16_t *__restrict__ skip16, uint32_t mode)
+          uint64_t gbase, uint32_t *__restrict__ rmask, uint32_t tiles_per_wg, const uint16_t *__restrict__ skip16, uint32_t mode,
+          const uint4 *__restrict__ qseed)
 {   // PUSH6: the 3 + 3 unknown edges of a position are compacted per lane and pushed with every lane active -- 6 LDS claims and 6
     // stores per wave and position instead of 8 predicated ones of each (a compile-time switch: as a uniform branch the two forms
     // together spilled 40-60 bytes per lane; option "qhash_pushes").  mode: QH_* bits
@@ -292,7 +307,7 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
         s_roll[c * 2] = tab[c]; s_roll[c * 2 + 1] = tab[TPC_TAB_HK + rc];
         s_roll[10 + c * 2] = tab[TPC_TAB_HK + c]; s_roll[10 + c * 2 + 1] = tab[rc];
     }
-    if (k <= QT_MAXK)
+    if (k <= QT_MAXK && !(mode & QH_SEED_S))
         for (uint32_t i = tid; i < 5u * (uint32_t)k; i += QH_THREADS) {
             const uint32_t t = i / 5u, c = i % 5u, rc = c == 4 ? 4u : 3u - c;
             s_seed[2 * i] = q_rotl_n(tab[c], L, (k - 1 - (int)t) % L);
@@ -316,12 +331,12 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
         const uint64_t h = tab[c], hk = tab[TPC_TAB_HK + c];
         h0l[c] = (uint32_t)h; h0h[c] = (uint32_t)(h >> 32); hk0l[c] = (uint32_t)hk; hk0h[c] = (uint32_t)(hk >> 32);
     }
-    // letter c (0..4) -> {x[c], y[rc c]} on 32-bit halves: two selects on the letter's bits, one on its N bit
-    auto pick = [](uint32_t c, const uint32_t (&x)[5], const uint32_t (&y)[5], uint32_t &ox, uint32_t &oy) {
-        const bool b0 = (c & 1u) != 0u, b1 = (c & 2u) != 0u, n = c >= 4u;
-        const uint32_t x01 = b0 ? x[1] : x[0], x23 = b0 ? x[3] : x[2], y32 = b0 ? y[2] : y[3], y10 = b0 ? y[0] : y[1];
-        const uint32_t xv = b1 ? x23 : x01, yv = b1 ? y10 : y32;
-        ox = n ? x[4] : xv; oy = n ? y[4] : yv;
+    // character i of 16 packed two-bit letters and their N bits -> five one-hot lane masks (all ones where the lane holds A / C / G / T / N;
+    // an N has letter bits 0 in the staged word)
+    auto hot = [](uint32_t chars, uint32_t nbits, uint32_t i, uint32_t (&m)[5]) {
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)chars, 2u * i, 1u), m1 = (uint32_t)__builtin_amdgcn_sbfe((int)chars, 2u * i + 1u, 1u);
+        m[4] = (uint32_t)__builtin_amdgcn_sbfe((int)nbits, i, 1u);
+        m[0] = ~(m0 | m1 | m[4]); m[1] = m0 & ~m1; m[2] = m1 & ~m0; m[3] = m0 & m1;
     };
     const uint32_t ppr_mask = (uint32_t)pos_per_round - 1u;  // a power of two <= 16
     constexpr bool half_rounds = HALF;                       // 512 bins: see the push below
@@ -353,7 +368,30 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
             ncnt += __popc(bits);
         }
         V pos = lv_make<LHI>(0u, 0u), neg = lv_make<LHI>(0u, 0u);  // VertexRollingHash ctor (vertexrollinghash.h:79-102), function 0
-        if (k <= QT_MAXK) {
+        if (mode & QH_SEED_S) {  // (launch_qhash sets the bit only with k <= QT_MAXK and a table)
+            for (int t0 = 0; t0 < k; t0 += 16) {
+                const uint32_t ch = lean_chars16(s_b, p0 + (uint32_t)t0), nb = lean_nbits32(s_n, p0 + (uint32_t)t0);
+                const int m = min(16, k - t0);
+                const uint4 *row = qseed + t0 * 5;  // uniform: the five rows of a character are scalar loads
+                for (int j = 0; j < m; j++) {
+                    // The lane's letter as one-hot masks: a row then costs one instruction per dword, with the row as its scalar operand.
+                    // Selects between scalars -- two on the letter's bits, one on its N bit -- cost two moves each besides the select:
+                    // 50 vector instructions per character against 27 (profiles/r10_qhash_seed.md).
+                    uint32_t mk[5];
+                    hot(ch, nb, (uint32_t)j, mk);
+                    const uint4 r0 = row[j * 5], r1 = row[j * 5 + 1], r2 = row[j * 5 + 2], r3 = row[j * 5 + 3], r4 = row[j * 5 + 4];
+                    auto mix = [&mk](uint32_t v, uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint32_t x) {
+                        return q_xor_and(q_xor_and(q_xor_and(q_xor_and(q_xor_and(v, a, mk[0]), c, mk[1]), g, mk[2]), t, mk[3]), x, mk[4]);
+                    };
+                    pos.lo = mix(pos.lo, r0.x, r1.x, r2.x, r3.x, r4.x);
+                    neg.lo = mix(neg.lo, r0.z, r1.z, r2.z, r3.z, r4.z);
+                    if constexpr (LHI) {
+                        pos.hi = mix(pos.hi, r0.y, r1.y, r2.y, r3.y, r4.y);
+                        neg.hi = mix(neg.hi, r0.w, r1.w, r2.w, r3.w, r4.w);
+                    }
+                }
+            }
+        } else if (k <= QT_MAXK) {
             for (int t0 = 0; t0 < k; t0 += 16) {
                 uint32_t ch = lean_chars16(s_b, p0 + (uint32_t)t0), nb = lean_nbits32(s_n, p0 + (uint32_t)t0);
                 const int m = min(16, k - t0);
@@ -452,16 +490,28 @@ k_q_hash2(int LOG_NB, TpcHashParams P, const uint64_t *__restrict__ tab, const u
                 }
             }
             if (s + 1 < QH_RUN) {  // roll: VertexRollingHash::Update (vertexrollinghash.h:104-113), function 0
-                uint4 en, ef;  // {h[cn], hk[rc cn]}, {hk[cf], h[rc cf]}
                 if ((PUSH6 || !SHARDED) && (mode & QH_ROLL_S)) {  // (every sharded eight-push instantiation keeps the reads: its !HALF, LHI form spilled 8 more bytes with the selects; launch_qhash clears the bit)
-                    pick(cn, h0l, hk0l, en.x, en.z); pick(cf, hk0l, h0l, ef.x, ef.z);
-                    en.y = en.w = ef.y = ef.w = 0u;
-                    if constexpr (LHI) { pick(cn, h0h, hk0h, en.y, en.w); pick(cf, hk0h, h0h, ef.y, ef.w); }
+                    // h[cn] ^ hk[cf] into pos, hk[rc cn] ^ h[rc cf] into neg: the two letters as one-hot masks, one instruction per
+                    // letter and dword with the table entry as its scalar operand (as the seeding above; selects took about twice as many)
+                    uint32_t mnx[5], mfx[5];
+                    hot(cx, nx, (uint32_t)s, mnx); hot(cw, nw, (uint32_t)s, mfx);
+                    V p = r1p, q = neg;
+#pragma unroll
+                    for (int c = 0; c < 5; c++) {
+                        const int r = c == 4 ? 4 : 3 - c;
+                        p.lo = q_xor_and(q_xor_and(p.lo, h0l[c], mnx[c]), hk0l[c], mfx[c]);
+                        q.lo = q_xor_and(q_xor_and(q.lo, hk0l[r], mnx[c]), h0l[r], mfx[c]);
+                        if constexpr (LHI) {
+                            p.hi = q_xor_and(q_xor_and(p.hi, h0h[c], mnx[c]), hk0h[c], mfx[c]);
+                            q.hi = q_xor_and(q_xor_and(q.hi, hk0h[r], mnx[c]), h0h[r], mfx[c]);
+                        }
+                    }
+                    pos = p; neg = R.rotr1(q);
                 } else {
-                    en = reinterpret_cast<const uint4 *>(s_roll)[cn]; ef = reinterpret_cast<const uint4 *>(s_roll)[5 + cf];
+                    const uint4 en = reinterpret_cast<const uint4 *>(s_roll)[cn], ef = reinterpret_cast<const uint4 *>(s_roll)[5 + cf];  // {h[cn], hk[rc cn]}, {hk[cf], h[rc cf]}
+                    pos = lv_xor<LHI>(lv_xor<LHI>(r1p, en.x, en.y), ef.x, ef.y);
+                    neg = R.rotr1(lv_xor<LHI>(lv_xor<LHI>(neg, en.z, en.w), ef.z, ef.w));
                 }
-                pos = lv_xor<LHI>(lv_xor<LHI>(r1p, en.x, en.y), ef.x, ef.y);
-                neg = R.rotr1(lv_xor<LHI>(lv_xor<LHI>(neg, en.z, en.w), ef.z, ef.w));
                 ncnt += (int)(cn >> 2) - (int)(cf >> 2);
                 cp = cf;
             }
@@ -1580,11 +1630,17 @@ void launch_qhash(const TpcLaunch &a, const TpcQPlan &pl, bool gated, uint64_t l
     const bool rb = q_use_rbins(pl.b1);
     // the instruction-lean kernel: flush-per-round bins (two rounds per position at 512 bins), a 24-bit slice index
     const bool lean = pl.b1 <= 9 && pl.sub_rounds <= 2 && perm.F <= 24 && !TpcEnv::get().no_lean && !(rb && TpcEnv::get().rb_hash);
-    if (a.stat_kernel) { a.stat_kernel[1] = lean ? 1 : 2; a.stat_kernel[3] = 0; }
+    if (a.stat_kernel) { a.stat_kernel[1] = lean ? 1 : 2; a.stat_kernel[3] = 0; a.stat_kernel[4] = 0; }
     if (lean) {
+        // (QT_MAXK * 80: s_seed.  With QH_SEED_S the kernel neither fills nor reads it; the space stays for the other value of the switch,
+        //  and one workgroup per CU is resident either way)
         const size_t lds = Bins3<uint64_t, QH_THREADS>::lds_bytes(pl.b1) + (size_t)(PT_THREADS + 1 + TPC_XW_MAX) * 12 + 160 + (size_t)QT_MAXK * 80 + 64;
-        const uint32_t mode = tpc_qhash_roll_scalars() && (tpc_qhash_compact() || pl.world == 1) ? QH_ROLL_S : 0u;
-        if (a.stat_kernel) a.stat_kernel[3] = (tpc_qhash_compact() ? 1 : 0) | (mode & QH_ROLL_S ? 2 : 0) | (gated ? 4 : 0);  // "query_hash_form"
+        const uint32_t mode = (tpc_qhash_roll_scalars() && (tpc_qhash_compact() || pl.world == 1) ? QH_ROLL_S : 0u) |
+                              (tpc_qhash_seed_scalars() && a.qseed && a.P.k <= QT_MAXK ? QH_SEED_S : 0u);
+        if (a.stat_kernel) {
+            a.stat_kernel[3] = (tpc_qhash_compact() ? 1 : 0) | (mode & QH_ROLL_S ? 2 : 0) | (gated ? 4 : 0);  // "query_hash_form"
+            a.stat_kernel[4] = mode & QH_SEED_S ? 1 : 0;                                                      // "query_hash_seed"
+        }
 #define TPC_QHASH2_GO(G, S, H, X, C)                                                                                                          \
     do {                                                                                                                                    \
         (void)hipFuncSetAttribute((const void *)k_q_hash2<G, S, H, X, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
@@ -1592,7 +1648,7 @@ void launch_qhash(const TpcLaunch &a, const TpcQPlan &pl, bool gated, uint64_t l
                            pl.tile0, pl.n_tiles, pl.pos_per_round, lo, hi, pl.buf1, pl.cnt1, pl.cap1, ovf, perm, sh,                          \
                            pl.tile0_global * (uint64_t)(PT_THREADS * TPC_RUN), rmask, pl.fmt == 6 ? pl.tiles_per_wg : 0u,                  \
                            reinterpret_cast<const uint16_t *>(a.per_qs), /* (global word index: the sharded variants skip too) */           \
-                           mode);                                                                                                          \
+                           mode, reinterpret_cast<const uint4 *>(a.qseed));                                                                \
     } while (0)
 #define TPC_QHASH2_GS(H, X, C)                                                                                                              \
     do {                                                                                                                                    \
