@@ -4,7 +4,8 @@
 // The text is, byte for byte, what the sinks of twopaco_amd/host/graphformat.h (Gfa1Sink, Gfa2Sink, FastaSink fed by
 // FormatChunk) write for the table, in file order; the header lines stay on the host.  Event e of sequence s, size = end + k -
 // begin, owns in this order: the segment line when first[e] (S, or ">id" and the body wrapped at 80 letters), the occurrence
-// line (C / F), the link line (L / E) when e is not the first event of s, and the path line (P / O) of s when e is its last.
+// line (C / F), the link line (L / E) when e is not the first event of s and the event before it is not named 0 (the sinks'
+// prevId_ != 0: 0 is the walk's "no segment yet"), and the path line (P / O) of s when e is its last.
 //   k_text_size     one thread per event: off[e] = bytes of its lines but the path line -- widths are computed (digit counts of
 //                   64-bit values), nothing is printed -- and piece[e] = bytes of its piece of the path line (digits of |name|,
 //                   the strand, one separator or terminator byte).  Sizes and bytes come from ONE template (emit_lines) run
@@ -76,10 +77,14 @@ __device__ __forceinline__ void text_load(const TpcTextPlan &T, uint64_t e, Text
     ev.size = (uint64_t)ev.en + (uint64_t)T.k - ev.b;
     ev.first = (T.first[e >> 5] >> (e & 31)) & 1u;
     ev.s = text_seq_of(T, e);
-    ev.link = e > T.seq_begin[ev.s];
+    ev.link = false;
     ev.last = e + 1 == T.seq_begin[ev.s + 1];
     ev.prev_nm = 0; ev.prev_size = 0;
-    if (ev.link) { ev.prev_nm = T.name[e - 1]; ev.prev_size = (uint64_t)T.end[e - 1] + (uint64_t)T.k - T.begin[e - 1]; }
+    if (e > T.seq_begin[ev.s]) {
+        // GfaSink::Segment prints the link only `if (prevId_ != 0)`: a name of 0 is the walk's "no segment yet"
+        ev.prev_nm = T.name[e - 1]; ev.prev_size = (uint64_t)T.end[e - 1] + (uint64_t)T.k - T.begin[e - 1];
+        ev.link = ev.prev_nm != 0;
+    }
 }
 
 __device__ __forceinline__ uint64_t text_body_bytes(int format, uint64_t size) { return format == TPC_TEXT_FASTA ? size + (size + 79) / 80 : size; }
