@@ -930,6 +930,11 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      mark lists (14..21), entries of a (workgroup, bucket) region (tiny: most entries take the atomic fallback),
  *                      log2 bits of the LDS slice k_mark_apply holds (10..20: a larger bucket is cut into sub-slices)
  *   test_sched_cap     tests only, process-wide: rounds per segment of the split kernels' round schedule (0 = what fits in LDS)
+ *   test_mask_scan     tests only, process-wide: which scan of the block sums the mask compaction (tpc_pass2_marks, tpc_pass2_filter, the
+ *                      partitioned query's counts) takes: 0 = by size (one workgroup up to 4096 block sums of 8192 positions each and
+ *                      beyond 64 x 4096, the segmented pair of kernels between), 1 = always the single workgroup (more than 4096 sums: its
+ *                      loop turns over and carries), 2 = the segmented pair whenever the segments number 1..64 (a small text: one
+ *                      segment with base 0).  "mask_scan_form" tells which one the last count took
  *   test_fail_mallocs  tests only, process-wide: the next N second-pass / output allocations fail at their first attempt, as if
  *                      the device were full (they then give the partition buffers back and try again, see "pbuf_releases")
  *   test_sketch_grid   tests only, process-wide: workgroups of tpc_distinct_sketch's kernel (0 = a few per CU), so that a small text
@@ -975,7 +980,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "query_mark_fallback" = entries of those lists that found a ring or a region full and were ORed straight into the mask (0 on path 0);
  * "text_word_begin" / "text_word_end" = the packed words [begin, end) of the text this context holds ("text_words" is their difference);
  * "periodic_any_query" / "periodic_any_insert" = 1 when the detection-only launch of the periodic-window masks found a position that
- * copies its verdict / drops its insert (0 before the masks of this text and k were asked for, or with the option off).
+ * copies its verdict / drops its insert (0 before the masks of this text and k were asked for, or with the option off);
+ * "mask_scan_form" = process-wide, the scan of the block sums that the last mask count of any context launched: 1 the single
+ * workgroup (k_scan_sums), 2 the segmented pair (k_scan_sums_seg + k_scan_sums_wide), 0 before the first count (option test_mask_scan).
  * -1: unknown name. */
 int64_t tpc_get_stat(const tpc_ctx *ctx, const char *name);
 

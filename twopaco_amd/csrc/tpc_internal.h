@@ -2,6 +2,7 @@
 #pragma once
 #include "tpc_device.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <vector>
 
@@ -299,6 +300,8 @@ int tpc_launch_slice_combine(const TpcLaunch &a, int slice_bits, int b1, int b2,
 // n_words/256+2 uint64; *n_out (device) receives the list length; list must hold it (two-phase:
 // call with list == nullptr to count only).
 int tpc_launch_mask_count(hipStream_t s, const uint32_t *mask, uint64_t n_words, uint64_t *block_sums, unsigned long long *n_out);
+extern int tpc_test_mask_scan;       // tpc_pass2.hip: option "test_mask_scan" (tests: 0 = the scan of the block sums chosen by size, 1 = one workgroup, 2 = the segmented pair; process-wide)
+extern std::atomic<int> tpc_stat_mask_scan_form;  // tpc_pass2.hip: stat "mask_scan_form" (1 / 2: what the last tpc_launch_mask_count launched; process-wide, contexts count from several host threads)
 int tpc_launch_mask_scatter(hipStream_t s, const uint32_t *mask, uint64_t n_words, const uint64_t *block_sums, uint64_t *list);
 int tpc_launch_mask_or(hipStream_t s, uint32_t *dst, const uint32_t *src, uint64_t n_words);
 

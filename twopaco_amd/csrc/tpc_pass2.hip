@@ -771,12 +771,17 @@ __global__ void __launch_bounds__(256) k_scan_sums_wide(uint64_t *block_sums, ui
     if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = all;
 }
 
+int tpc_test_mask_scan = 0;                   // option "test_mask_scan" (tests only, process-wide): 1 = always k_scan_sums, 2 = the segmented pair from one segment on
+std::atomic<int> tpc_stat_mask_scan_form{0};  // stat "mask_scan_form": 1 = k_scan_sums, 2 = the segmented pair
+
 int tpc_launch_mask_count(hipStream_t s, const uint32_t *mask, uint64_t n_words, uint64_t *block_sums, unsigned long long *n_out)
 {   // block_sums: nblk(n_words, 256) sums + 64 words of scratch behind them (TPC_MASK_SUMS_SCRATCH)
     const unsigned nb = nblk(n_words, 256);
     hipLaunchKernelGGL(k_mask_count, dim3(nb), dim3(256), 0, s, mask, n_words, block_sums);
     const unsigned segs = (nb + SCAN_SEG - 1) / SCAN_SEG;
-    if (segs < 2 || segs > 64) { hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, block_sums, (uint64_t)nb, n_out); return 0; }
+    const bool single = tpc_test_mask_scan == 1 || segs < (tpc_test_mask_scan == 2 ? 1u : 2u) || segs > 64;
+    tpc_stat_mask_scan_form.store(single ? 1 : 2, std::memory_order_relaxed);
+    if (single) { hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, block_sums, (uint64_t)nb, n_out); return 0; }
     unsigned long long *seg_tot = reinterpret_cast<unsigned long long *>(block_sums + nb);
     hipLaunchKernelGGL(k_scan_sums_seg, dim3(segs), dim3(256), 0, s, block_sums, (uint64_t)nb, seg_tot);
     hipLaunchKernelGGL(k_scan_sums_wide, dim3(segs), dim3(256), 0, s, block_sums, (uint64_t)nb, seg_tot, n_out);
