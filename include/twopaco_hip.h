@@ -968,6 +968,9 @@ int tpc_set_option(tpc_ctx *ctx, const char *name, int64_t value);
  * "insert_hash_kernel" = 0 none (the direct rolling kernel), 1 the instruction-lean hash with its seed table in LDS, 2 the same
  * without it (k too large for q), 3 the classic k_part_hash, 4 the closed form (q > 16, tpc_pass1_anyq.hip);
  * "query_hash_kernel" = 0 none (direct), 1 the lean k_q_hash2, 2 k_q_hash, 4 the closed form;
+ * "split_kernel" = of the last tpc_pass1_split_hist: 0 the rolling k_split<Q> (q <= 16), 4 the closed form k_split_anyq (q > 16 or option
+ * test_force_anyq); "split_phases" = the ballot launches of that call: min(q, 3) on a sparse scratch filter, q when q x text length
+ * exceeds 2^L / 8 (both 0 before the first call);
  * "query_hash_form" = of the last k_q_hash2 launch (0 after another hash kernel): 1 = six compacted pushes per position (option
  * qhash_pushes), + 2 = the roll from scalar registers (option qhash_roll_scalars), + 4 = its gated instantiation (a range [lo, hi] that
  * is not the whole hash space);

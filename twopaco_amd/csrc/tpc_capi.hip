@@ -25,6 +25,7 @@ TpcLaunch make_launch(const tpc_ctx *c)
     a.P = c->P; a.tab = c->tab; a.bases = c->bases; a.nmask = c->nmask; a.n_text = c->n_text;
     a.n_tiles = c->n_tiles; a.filter = c->filter; a.stream = c->stream;
     a.stat_kernel = c->stat_kernel;
+    a.stat_split = c->stat_split;
     if (c->P.k <= TPC_QSEED_MAXK) a.qseed = c->tab + TPC_TAB_WORDS;
     return a;
 }
@@ -435,6 +436,8 @@ int64_t tpc_get_stat(const tpc_ctx *c, const char *name)
     if (!strcmp(name, "query_verify_kernel")) return c->stat_kernel[2];
     if (!strcmp(name, "query_hash_form")) return c->stat_kernel[3];
     if (!strcmp(name, "query_hash_seed")) return c->stat_kernel[4];
+    if (!strcmp(name, "split_kernel")) return c->stat_split[0];
+    if (!strcmp(name, "split_phases")) return c->stat_split[1];
     if (!strcmp(name, "query_hash_seed_maxk")) return TPC_QSEED_MAXK;
     if (!strcmp(name, "query_mark_path")) return c->stat_mark_path;
     if (!strcmp(name, "query_mark_fallback")) return c->stat_mark_fallback;

@@ -237,6 +237,7 @@ struct tpc_ctx {
     int stat_path[2] = {0, 0};       // 1 direct kernel, 2 / 3 partitioned with that many levels (+10: partitioned, then completed by the direct kernel)
     int64_t stat_batches[2] = {0, 0};
     mutable int stat_kernel[5] = {0, 0, 0, 0, 0};  // hash kernel of the last insert / query, the query's verification kernel, the form and the seeding of k_q_hash2 (TpcLaunch::stat_kernel)
+    mutable int stat_split[2] = {0, 0};  // kernel (0 rolling, 4 closed form) and launches of the last tpc_pass1_split_hist (TpcLaunch::stat_split)
     int stat_fmt[2] = {0, 0};        // entry format of the last partitioned insert (level 2: 0 = 32-bit, 3 = planar 24-bit) / query (0 = 8-byte, 6 = planar 48-bit)
     int64_t stat_filter2_retries = 0;  // exact-filter passes repeated with the full-size table (last tpc_pass2_filter)
     int64_t stat_aggregate_retries = 0;  // ... by the last tpc_pass2_aggregate_records

@@ -101,6 +101,9 @@ struct TpcLaunch {
     // verification, [3] / [4] the form and the seeding of k_q_hash2 (tpc_ctx::stat_kernel, the values of tpc_get_stat "insert_hash_kernel" /
     // "query_hash_kernel" / "query_verify_kernel" / "query_hash_form" / "query_hash_seed")
     int *stat_kernel = nullptr;
+    // when set: the split pass records [0] its kernel (0 rolling k_split<Q>, 4 the closed form k_split_anyq) and [1] the phases it
+    // launched (tpc_ctx::stat_split, tpc_get_stat "split_kernel" / "split_phases")
+    int *stat_split = nullptr;
 };
 constexpr int TPC_PER_MAXP = 63;    // periods of the periodic windows the first pass skips (tpc_qpartition.hip:k_periodic_build)
 constexpr int TPC_PER_PLANES = 6;   // bit planes of the copy distance; the masks of a text are [2 + TPC_PER_PLANES][n_words_alloc]: per_qs, the planes, per_i

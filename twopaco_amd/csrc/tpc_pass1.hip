@@ -239,7 +239,9 @@ k_query(TpcHashParams P, const uint64_t *__restrict__ tab, const uint64_t *__res
 // sequential rule is "unless all q bits are covered by earlier edges".  phases = min(q, 3) while the filter
 // is sparse (the two rules then differ by (fill/q)^3 of the edges), q when it is crowded.  With a scratch
 // filter large enough that no such coverage happens both give the number of distinct edges, bin for bin
-// (tests/test_gpu_parity.py::test_split_histogram_exact_when_collision_free).
+// (tests/test_gpu_split_pass.py: every q, k from 3 to 604, tile edges and mask layouts against tests/split_reference.py, which also
+// states what holds under any schedule when bits ARE covered; tests/test_gpu_parity.py::test_split_histogram_exact_when_collision_free
+// on three goldens).
 // One order dependence survives even then, in the reference as here: for k + 1 > L the cyclic polynomial
 // hash rotates characters L positions apart by the same amount (cyclichash.h:29-35), so two DIFFERENT
 // (k+1)-mers with the same letters in every rotation class (typically windows over the edge of an N run)
@@ -350,6 +352,7 @@ void launch_split_q(const TpcLaunch &a, uint32_t *todo, uint32_t *bins, uint64_t
     dim3 grid((unsigned)a.n_tiles), block(TPC_TILE_THREADS);
     const bool crowded = (double)Q * (double)a.n_text > (double)(a.P.lmask >> 3);  // more than 1/8 of the bits could be set
     const int phases = (Q < 3 || crowded) ? Q : 3;  // see k_split
+    if (a.stat_split) { a.stat_split[0] = 0; a.stat_split[1] = phases; }
     for (int phase = 0; phase < phases; phase++)
         hipLaunchKernelGGL((k_split<Q>), grid, block, 0, a.stream, a.P, a.tab, a.bases, a.nmask, todo, todo, phase, a.n_text, a.filter, bins, bin_size);
 }
