@@ -307,3 +307,90 @@ def test_m2r2_graph_equals_twopaco_then_serial_graphdump(tmp_path):
         os.unlink(out)
     assert not os.path.exists(os.path.join(d, "de_bruijn.bin"))
     no_junction_file_anywhere()
+
+
+# ------------------------------------------------------------------------------------------------ 5. every table from one process
+TABLES = {"colors": None, "links": None, "bubbles": None, "distances": "phylip", "components": "members", "superbubbles": "members", "anchors": "paf", "locate": "walks"}
+TOGETHER = ("colors", "distances", "components", "superbubbles", "anchors", "locate")   # the largest set graphdump writes in one run
+
+
+def table_args(name, by, d, query):
+    """The options of one table with every file it can write, into directory d."""
+    a = ["--links"] if name == "links" else ["--" + name, by]
+    a += ["--%s-out" % name, os.path.join(d, name + ".tsv")]
+    if TABLES[name]:
+        a += ["--%s-%s" % (name, TABLES[name]), os.path.join(d, "%s.%s" % (name, TABLES[name]))]
+    return a + (["--locate-in", query] if name == "locate" else [])
+
+
+def read_all(d, keep):
+    return {f: open(os.path.join(d, f), "rb").read() for f in sorted(os.listdir(d)) if f.split(".")[0] in keep}
+
+
+def all_tables_inputs(d):
+    """name -> (fasta files relative to d, k, the other twopaco arguments, the locate query)."""
+    with open(os.path.join(d, "short_a.fa"), "w") as f:
+        f.write(">a1\nACGTACGTTG\n>a2\nGGATCCAT\n")
+    with open(os.path.join(d, "short_b.fa"), "w") as f:
+        f.write(">b1\nTTG\n")
+    with open(os.path.join(d, "two.fa"), "w") as f:
+        f.write(">r5\nACGTA\n>r7\nGATTACA\n")
+    case = CASES["c2_k29"]
+    with open(os.path.join(d, "c2.fa"), "wb") as f:
+        f.write(open(os.path.join(GOLDEN, case["fasta"]), "rb").read())
+    return {"shorter_than_k": (["short_a.fa", "short_b.fa"], 11, ["-f", "20", "--seed", "7"], "short_a.fa"),
+            "two_records_k9": (["two.fa"], 9, ["-f", "20", "--seed", "7"], "two.fa"),
+            "c2_k29": (["c2.fa"], case["k"], ["-f", str(case["L"]), "-q", str(case["q"]), "-r", str(case["n_rounds"]), "--seed", str(case["seed"])], "c2.fa")}
+
+
+@pytest.mark.parametrize("name", ["shorter_than_k", "two_records_k9", "c2_k29"])
+def test_all_tables_from_one_process_equal_the_serial_graphdump(tmp_path, name):
+    """One `twopaco --graph gfa1` with all eight tables, and one `graphdump --gpu` with the largest set it writes together, by file
+    and by sequence: every file byte for byte what the serial graphdump writes for that table alone.  Inputs: records all shorter
+    than k in two files (nothing is dispatched: the stream is empty), two records of 5 and 7 bases at k = 9, and c2_k29 with its own file as the query."""
+    d = str(tmp_path)
+    files, k, args, query = all_tables_inputs(d)[name]
+
+    def run(exe, argv, into):
+        os.mkdir(os.path.join(d, into))
+        return subprocess.run([exe] + argv, cwd=d, capture_output=True, timeout=300)
+
+    # twopaco: the graph, the junction stream and all eight tables by sequence
+    argv = ["-k", str(k)] + args + ["--tmpdir", d, "-o", "stream.bin", "--graph", "gfa1", "--graph-out", os.path.join("twopaco", "graph.gfa1")]
+    for t in TABLES:
+        argv += table_args(t, "sequence", "twopaco", query)
+    r = run(TWOPACO, argv + files, "twopaco")
+    assert r.returncode == 0 and r.stderr == b"", r.stderr[-800:]
+    if name == "c2_k29":
+        assert open(os.path.join(d, "stream.bin"), "rb").read() == open(os.path.join(GOLDEN, CASES[name]["bin"]), "rb").read()
+    else:
+        assert os.path.getsize(os.path.join(d, "stream.bin")) == 0
+    base = ["stream.bin", "-k", str(k)] + [a for f in files for a in ("-s", f)]
+
+    # the serial graphdump, every table alone
+    want = {}
+    for by in ("file", "sequence"):
+        into = "serial_" + by
+        os.mkdir(os.path.join(d, into))
+        for t in TABLES:
+            r = subprocess.run([GRAPHDUMP] + base + table_args(t, by, into, query), cwd=d, capture_output=True, timeout=300)
+            assert r.returncode == 0 and r.stderr == b"" and r.stdout == b"", (t, r.stderr[-400:])
+        want[by] = read_all(os.path.join(d, into), TABLES)
+        assert len(want[by]) == 13 and all(want[by][t + ".tsv"] for t in TABLES)
+    r = subprocess.run([GRAPHDUMP] + base + ["-f", "gfa1"], cwd=d, capture_output=True, timeout=300)
+    assert r.returncode == 0 and r.stderr == b""
+    want["sequence"]["graph.gfa1"] = r.stdout
+    assert want["file"]["links.tsv"] == want["sequence"]["links.tsv"] and want["file"]["colors.tsv"] != want["sequence"]["colors.tsv"]
+
+    assert read_all(os.path.join(d, "twopaco"), list(TABLES) + ["graph"]) == want["sequence"]
+
+    # graphdump --gpu: the six tables it writes together
+    for by in ("file", "sequence"):
+        into = "gpu_" + by
+        argv = list(base) + ["--gpu"]
+        for t in TOGETHER:
+            argv += table_args(t, by, into, query)
+        r = run(GRAPHDUMP, argv, into)
+        assert r.returncode == 0 and r.stderr == b"" and r.stdout == b"", r.stderr[-800:]
+        got = read_all(os.path.join(d, into), TOGETHER)
+        assert got == {f: b for f, b in want[by].items() if f.split(".")[0] in TOGETHER} and len(got) == 11

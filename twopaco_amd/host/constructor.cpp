@@ -67,11 +67,7 @@
 
 namespace
 {
-	struct ArgError : public std::runtime_error
-	{
-		std::string arg;
-		ArgError(const std::string & msg, const std::string & argId) : std::runtime_error(msg), arg(argId) {}
-	};
+	using TwoPaCo::GraphFormat::ArgError;
 
 	bool Match(const std::string & a, const char * shortName, const char * longName)
 	{
@@ -202,7 +198,8 @@ int main(int argc, char * argv[])
 		std::string tmpDirName = ".", outFileName = "de_bruijn.bin";
 		std::vector<std::string> fileName;
 		TwoPaCo::EnumeratorOptions options;
-		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false, colorsOutSet = false, links = false, linksOutSet = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false, anchorsOutSet = false, anchorsPafSet = false, anchorsRefSet = false, locateOutSet = false, locateWalksSet = false;
+		TwoPaCo::GraphFormat::TableOptions tables;
+		bool optionsSet = false, outFileSet = false, graphOutSet = false, graphTextSet = false;
 		for (int i = 1; i < argc; i++)
 		{
 			std::string a = argv[i];
@@ -266,86 +263,8 @@ int main(int argc, char * argv[])
 				options.graphTextOnDevice = v == "device";
 				graphTextSet = true;
 			}
-			else if (Match(a, 0, "colors"))
-			{
-				options.colorsBy = value("(--colors)");
-				if (options.colorsBy != "file" && options.colorsBy != "sequence")
-				{
-					throw ArgError("Value '" + options.colorsBy + "' does not meet constraint: file|sequence", "(--colors)");
-				}
-
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "colors-out")) { options.colorsFile = value("(--colors-out)"); colorsOutSet = true; }
-			else if (Match(a, 0, "links")) { links = true; optionsSet = true; }
-			else if (Match(a, 0, "links-out")) { options.linksFile = value("(--links-out)"); linksOutSet = true; }
 			else if (Match(a, 0, "graph-compact")) { options.graphCompact = true; optionsSet = true; }
-			else if (Match(a, 0, "bubbles"))
-			{
-				options.bubblesBy = value("(--bubbles)");
-				if (options.bubblesBy != "file" && options.bubblesBy != "sequence") throw ArgError("Value '" + options.bubblesBy + "' does not meet constraint: file|sequence", "(--bubbles)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "bubbles-out")) { options.bubblesFile = value("(--bubbles-out)"); bubblesOutSet = true; }
-			else if (Match(a, 0, "distances"))
-			{
-				options.distancesBy = value("(--distances)");
-				if (options.distancesBy != "file" && options.distancesBy != "sequence") throw ArgError("Value '" + options.distancesBy + "' does not meet constraint: file|sequence", "(--distances)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "distances-out")) { options.distancesFile = value("(--distances-out)"); distancesOutSet = true; }
-			else if (Match(a, 0, "distances-phylip")) { options.distancesPhylipFile = value("(--distances-phylip)"); distancesPhylipSet = true; }
-			else if (Match(a, 0, "components"))
-			{
-				options.componentsBy = value("(--components)");
-				if (options.componentsBy != "file" && options.componentsBy != "sequence") throw ArgError("Value '" + options.componentsBy + "' does not meet constraint: file|sequence", "(--components)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "components-out")) { options.componentsFile = value("(--components-out)"); componentsOutSet = true; }
-			else if (Match(a, 0, "components-members")) { options.componentsMembersFile = value("(--components-members)"); componentsMembersSet = true; }
-			else if (Match(a, 0, "superbubbles"))
-			{
-				options.superbubblesBy = value("(--superbubbles)");
-				if (options.superbubblesBy != "file" && options.superbubblesBy != "sequence") throw ArgError("Value '" + options.superbubblesBy + "' does not meet constraint: file|sequence", "(--superbubbles)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "superbubbles-out")) { options.superbubblesFile = value("(--superbubbles-out)"); superbubblesOutSet = true; }
-			else if (Match(a, 0, "superbubbles-members")) { options.superbubblesMembersFile = value("(--superbubbles-members)"); superbubblesMembersSet = true; }
-			else if (Match(a, 0, "superbubbles-max"))
-			{
-				const std::string v = value("(--superbubbles-max)");
-				char * end = 0;
-				const long n = std::strtol(v.c_str(), &end, 10);
-				if (v.empty() || *end || n < 2 || n > 62) throw ArgError("Value '" + v + "' does not meet constraint: an integer 2 .. 62", "(--superbubbles-max)");
-				options.superbubblesMax = uint32_t(n);
-				superbubblesMaxSet = true;
-			}
-			else if (Match(a, 0, "anchors"))
-			{
-				options.anchorsBy = value("(--anchors)");
-				if (options.anchorsBy != "file" && options.anchorsBy != "sequence") throw ArgError("Value '" + options.anchorsBy + "' does not meet constraint: file|sequence", "(--anchors)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "locate"))
-			{
-				options.locateBy = value("(--locate)");
-				if (options.locateBy != "file" && options.locateBy != "sequence") throw ArgError("Value '" + options.locateBy + "' does not meet constraint: file|sequence", "(--locate)");
-				optionsSet = true;
-			}
-			else if (Match(a, 0, "locate-in")) options.locateIn.push_back(value("(--locate-in)"));
-			else if (Match(a, 0, "locate-out")) { options.locateFile = value("(--locate-out)"); locateOutSet = true; }
-			else if (Match(a, 0, "locate-walks")) { options.locateWalksFile = value("(--locate-walks)"); locateWalksSet = true; }
-			else if (Match(a, 0, "anchors-out")) { options.anchorsFile = value("(--anchors-out)"); anchorsOutSet = true; }
-			else if (Match(a, 0, "anchors-paf")) { options.anchorsPafFile = value("(--anchors-paf)"); anchorsPafSet = true; }
-			else if (Match(a, 0, "anchors-ref"))
-			{
-				const std::string v = value("(--anchors-ref)");
-				char * end = 0;
-				const long long n = std::strtoll(v.c_str(), &end, 10);
-				if (v.empty() || *end || n < 0 || n > 0x7FFFFFFFll) throw ArgError("Value '" + v + "' does not meet constraint: a colour index", "(--anchors-ref)");
-				options.anchorsRef = uint32_t(n);
-				anchorsRefSet = true;
-			}
+			else if (TwoPaCo::GraphFormat::ParseTableOption(a, value, "", tables)) continue;
 			else if (Match(a, "h", "help")) { Usage(); return 0; }
 			else if (a == "--version") { std::cout << argv[0] << "  version: 1.1.0" << std::endl; return 0; }
 			else if (a.size() > 1 && a[0] == '-') throw ArgError("Couldn't find match for argument", "(" + a + ")");
@@ -389,121 +308,13 @@ int main(int argc, char * argv[])
 			throw ArgError("This argument needs --graph <gfa1|gfa2|fasta>", graphOutSet ? "(--graph-out)" : options.graphPrefix ? "(--graph-prefix)" : "(--graph-text)");
 		}
 
-		if (!options.colorsBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The colour table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--colors)");
-			if (!colorsOutSet) options.colorsFile = "de_bruijn.colors.tsv";
-		}
-		else if (colorsOutSet)
-		{
-			throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
-		}
-
-		if (links)
-		{
-			if (options.gpus > 1) throw ArgError("The link table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--links)");
-			if (!linksOutSet) options.linksFile = "de_bruijn.links.tsv";
-			if (options.linksFile.empty()) throw ArgError("The link table needs a file name", "(--links-out)");
-		}
-		else if (linksOutSet)
-		{
-			throw ArgError("This argument needs --links", "(--links-out)");
-		}
-
-		if (!options.bubblesBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The bubble table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--bubbles)");
-			if (!options.colorsBy.empty() && options.colorsBy != options.bubblesBy) throw ArgError("The bubble table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --bubbles " + options.bubblesBy, "(--bubbles)");
-			if (!bubblesOutSet) options.bubblesFile = "de_bruijn.bubbles.tsv";
-			if (options.bubblesFile.empty()) throw ArgError("The bubble table needs a file name", "(--bubbles-out)");
-		}
-		else if (bubblesOutSet)
-		{
-			throw ArgError("This argument needs --bubbles <file|sequence>", "(--bubbles-out)");
-		}
-
-		if (!options.distancesBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The distance table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--distances)");
-			if (!options.colorsBy.empty() && options.colorsBy != options.distancesBy) throw ArgError("The distance table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --distances " + options.distancesBy, "(--distances)");
-			if (!options.bubblesBy.empty() && options.bubblesBy != options.distancesBy) throw ArgError("The distance table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --distances " + options.distancesBy, "(--distances)");
-			if (!distancesOutSet) options.distancesFile = "de_bruijn.distances.tsv";
-			if (options.distancesFile.empty()) throw ArgError("The distance table needs a file name", "(--distances-out)");
-			if (distancesPhylipSet && options.distancesPhylipFile.empty()) throw ArgError("The PHYLIP matrix needs a file name", "(--distances-phylip)");
-		}
-		else if (distancesOutSet || distancesPhylipSet)
-		{
-			throw ArgError("This argument needs --distances <file|sequence>", distancesOutSet ? "(--distances-out)" : "(--distances-phylip)");
-		}
-
-		if (!options.componentsBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The component table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--components)");
-			if (!options.colorsBy.empty() && options.colorsBy != options.componentsBy) throw ArgError("The component table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --components " + options.componentsBy, "(--components)");
-			if (!options.bubblesBy.empty() && options.bubblesBy != options.componentsBy) throw ArgError("The component table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --components " + options.componentsBy, "(--components)");
-			if (!options.distancesBy.empty() && options.distancesBy != options.componentsBy) throw ArgError("The component table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --components " + options.componentsBy, "(--components)");
-			if (!componentsOutSet) options.componentsFile = "de_bruijn.components.tsv";
-			if (options.componentsFile.empty()) throw ArgError("The component table needs a file name", "(--components-out)");
-			if (componentsMembersSet && options.componentsMembersFile.empty()) throw ArgError("The component members need a file name", "(--components-members)");
-		}
-		else if (componentsOutSet || componentsMembersSet)
-		{
-			throw ArgError("This argument needs --components <file|sequence>", componentsOutSet ? "(--components-out)" : "(--components-members)");
-		}
-
-		if (!options.superbubblesBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The superbubble table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--superbubbles)");
-			if (!options.colorsBy.empty() && options.colorsBy != options.superbubblesBy) throw ArgError("The superbubble table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
-			if (!options.bubblesBy.empty() && options.bubblesBy != options.superbubblesBy) throw ArgError("The superbubble table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
-			if (!options.distancesBy.empty() && options.distancesBy != options.superbubblesBy) throw ArgError("The superbubble table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
-			if (!options.componentsBy.empty() && options.componentsBy != options.superbubblesBy) throw ArgError("The superbubble table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --superbubbles " + options.superbubblesBy, "(--superbubbles)");
-			if (!superbubblesOutSet) options.superbubblesFile = "de_bruijn.superbubbles.tsv";
-			if (options.superbubblesFile.empty()) throw ArgError("The superbubble table needs a file name", "(--superbubbles-out)");
-			if (superbubblesMembersSet && options.superbubblesMembersFile.empty()) throw ArgError("The superbubble members need a file name", "(--superbubbles-members)");
-		}
-		else if (superbubblesOutSet || superbubblesMembersSet || superbubblesMaxSet)
-		{
-			throw ArgError("This argument needs --superbubbles <file|sequence>", superbubblesOutSet ? "(--superbubbles-out)" : superbubblesMembersSet ? "(--superbubbles-members)" : "(--superbubbles-max)");
-		}
-
-		if (!options.anchorsBy.empty())
-		{
-			if (options.gpus > 1) throw ArgError("The anchor table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--anchors)");
-			if (!options.colorsBy.empty() && options.colorsBy != options.anchorsBy) throw ArgError("The anchor table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
-			if (!options.bubblesBy.empty() && options.bubblesBy != options.anchorsBy) throw ArgError("The anchor table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
-			if (!options.distancesBy.empty() && options.distancesBy != options.anchorsBy) throw ArgError("The anchor table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
-			if (!options.componentsBy.empty() && options.componentsBy != options.anchorsBy) throw ArgError("The anchor table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
-			if (!options.superbubblesBy.empty() && options.superbubblesBy != options.anchorsBy) throw ArgError("The anchor table and the superbubble table share one set of colours: --superbubbles " + options.superbubblesBy + " does not go with --anchors " + options.anchorsBy, "(--anchors)");
-			if (!anchorsOutSet) options.anchorsFile = "de_bruijn.anchors.tsv";
-			if (options.anchorsFile.empty()) throw ArgError("The anchor table needs a file name", "(--anchors-out)");
-			if (anchorsPafSet && options.anchorsPafFile.empty()) throw ArgError("The anchor PAF needs a file name", "(--anchors-paf)");
-			if (options.anchorsBy == "file" && options.anchorsRef >= fileName.size()) throw ArgError("Value '" + std::to_string(options.anchorsRef) + "' does not meet constraint: a colour index below " + std::to_string(fileName.size()), "(--anchors-ref)");
-		}
-		else if (anchorsOutSet || anchorsPafSet || anchorsRefSet)
-		{
-			throw ArgError("This argument needs --anchors <file|sequence>", anchorsOutSet ? "(--anchors-out)" : anchorsPafSet ? "(--anchors-paf)" : "(--anchors-ref)");
-		}
-
-		if (!options.locateBy.empty())
-		{
-			const std::string & by = options.locateBy;
-			if (options.gpus > 1) throw ArgError("The locate table is written by one GPU only (every rank holds its own piece of the junction stream): not with --gpus above 1", "(--locate)");
-			if (!options.colorsBy.empty() && options.colorsBy != by) throw ArgError("The locate table and the colour table share one set of colours: --colors " + options.colorsBy + " does not go with --locate " + by, "(--locate)");
-			if (!options.bubblesBy.empty() && options.bubblesBy != by) throw ArgError("The locate table and the bubble table share one set of colours: --bubbles " + options.bubblesBy + " does not go with --locate " + by, "(--locate)");
-			if (!options.distancesBy.empty() && options.distancesBy != by) throw ArgError("The locate table and the distance table share one set of colours: --distances " + options.distancesBy + " does not go with --locate " + by, "(--locate)");
-			if (!options.componentsBy.empty() && options.componentsBy != by) throw ArgError("The locate table and the component table share one set of colours: --components " + options.componentsBy + " does not go with --locate " + by, "(--locate)");
-			if (!options.superbubblesBy.empty() && options.superbubblesBy != by) throw ArgError("The locate table and the superbubble table share one set of colours: --superbubbles " + options.superbubblesBy + " does not go with --locate " + by, "(--locate)");
-			if (!options.anchorsBy.empty() && options.anchorsBy != by) throw ArgError("The locate table and the anchor table share one set of colours: --anchors " + options.anchorsBy + " does not go with --locate " + by, "(--locate)");
-			if (options.locateIn.empty()) throw ArgError("The locate table needs a query: --locate-in <fasta file>", "(--locate)");
-			if (!locateOutSet) options.locateFile = "de_bruijn.locate.tsv";
-			if (options.locateFile.empty()) throw ArgError("The locate table needs a file name", "(--locate-out)");
-			if (locateWalksSet && options.locateWalksFile.empty()) throw ArgError("The locate walks need a file name", "(--locate-walks)");
-		}
-		else if (locateOutSet || locateWalksSet || !options.locateIn.empty())
-		{
-			throw ArgError("This argument needs --locate <file|sequence>", locateOutSet ? "(--locate-out)" : locateWalksSet ? "(--locate-walks)" : "(--locate-in)");
-		}
+		// every table beside every other, each into a file of its own, on one GPU; the complaints are looked for in the tables' order
+		namespace GF = TwoPaCo::GraphFormat;
+		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE}, false, false, false, false,
+			{0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
+		GF::CheckTableOptions(tables, rules);
+		options.tables = tables.request;
+		optionsSet = optionsSet || options.tables.Any();
 
 		if (runTests)
 		{

@@ -1,7 +1,8 @@
 // devicegraph.h -- the tables of the compacted graph, built on the device (include/twopaco_hip.h, the tpc_segments_* groups) and
 // fetched into the structs of graphformat.h.  One layer for both programs: graphdump, which loads the device library with dlopen,
-// and twopaco, which links it.  What differs between them stays with them: their timers, their [timing] lines, and the text they
-// throw when an entry point fails (Api::check is the caller's).  Nothing here knows which program calls it.
+// and twopaco, which links it.  What differs between them stays with them: their timers, their [timing] lines (StageObserver), the
+// text they throw when an entry point fails (Api::check is the caller's) or a stage disagrees with them (StageWording), the order of
+// their stages, and when they fetch the event table.  Nothing here knows which program calls it.
 #ifndef _DEVICE_GRAPH_H_
 #define _DEVICE_GRAPH_H_
 
@@ -12,6 +13,7 @@
 
 #include "../../include/twopaco_hip.h"
 #include "graphformat.h"
+#include "tablerequest.h"
 #include "textpack.h"
 
 // The entry points both programs reach through Api, each as tpc_<name>: the one list behind the members, graphdump's dlsym loads
@@ -364,6 +366,118 @@ namespace TwoPaCo
 			}
 
 			return batches;
+		}
+
+		// Where a position of a record is ambiguous, in the packed text's coordinates: what the segment build must not name by.
+		// refusal: thrown when the packed text and the parsed letters are not the same records
+		inline std::vector<uint64_t> AmbiguousPositions(const TwoPaCo::PackedText & text, const GraphFormat::LoadedSequences & loaded, const char * refusal)
+		{
+			if (text.recStart.size() != loaded.body.size()) throw std::runtime_error(refusal);
+			std::vector<uint64_t> ambiguous;
+			for (size_t r = 0; r < loaded.body.size(); r++)
+			{
+				if (text.recLength[r] != loaded.body[r].size()) throw std::runtime_error(refusal);
+				for (uint64_t at : loaded.ambiguous[r]) ambiguous.push_back(text.recStart[r] + at);
+			}
+
+			return ambiguous;
+		}
+
+		// The stages of BuildTables: one per table (GraphFormat::TableId), and the edge index in front of the locate stage
+		const int EDGES = GraphFormat::TABLES;
+		// twopaco's order, and graphdump's: the distance stage before the link stage, as long as graphdump has had both.  Behind the link
+		// and the bubble stage it would find 12 B per link, 4 B per 32 events and, with --bubbles, 24 B per segment and 16 B per bubble
+		// more resident, which a run that just fits the device does not have.
+		const int STAGES_LINKS_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::DISTANCES, GraphFormat::COMPONENTS,
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE};
+		const int STAGES_DISTANCES_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::DISTANCES, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::COMPONENTS,
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE};
+
+		// The caller's clock and [timing] lines.  built: after a stage's build, with the stage and its TPC_K_* (EDGES, then LOCATE
+		// once its batches are through: their kernel time is locateKernelMs, not the last batch's); fetched: after a stage's fetch.
+		struct StageObserver
+		{
+			std::function<void(int stage, int kernel)> built;
+			std::function<void(int stage)> fetched;
+			uint64_t locateBatches;
+			double locateKernelMs;
+			StageObserver() : locateBatches(0), locateKernelMs(0) {}
+		};
+
+		// "<the><noun> stage and the <other> disagree about the <what>": `the` opens the sentence, and the distance stage's other
+		// party is called the caller's way
+		struct StageWording
+		{
+			const char * the;
+			const char * colorsOfDistances;
+		};
+
+		// The wanted stages over the segment table on the device, in `order`, each fetched as far as the files print it
+		// (tablerequest.h: NeedsColorRows, NeedsLinkRows).  counts: tpc_segments_counts; t.map and the queries are the caller's
+		// (MakeColorMap, LoadQueries); linkBits: the link stage runs in any case and its first bits are fetched (the compact text).
+		inline void BuildTables(const Api & api, const GraphFormat::TableRequest & request, const int * order, const uint64_t * counts, bool linkBits, uint64_t batchPositions,
+			const StageWording & wording, GraphFormat::Tables & t, StageObserver & observer)
+		{
+			using namespace GraphFormat;
+			auto agree = [&wording](bool same, const char * noun, const char * other, const char * what)
+			{
+				if (!same) throw std::runtime_error(std::string(wording.the) + noun + " stage and the " + other + " disagree about the " + what);
+			};
+
+			const uint64_t events = counts[0];
+			t.segments = counts[1];
+			for (int at = 0; at < TABLES; at++)
+			{
+				const int stage = order[at];
+				if (stage == COLORS ? !NeedsColorBuild(request) : stage == LINKS ? !NeedsLinkBuild(request) && !linkBits : !request.On(TableId(stage))) continue;
+				switch (stage)
+				{
+				case COLORS:
+					BuildColors(api, t.map);
+					observer.built(stage, TPC_K_COLORS);
+					if (NeedsColorRows(request)) FetchColors(api, t.map, t.segments, t.colors);
+					break;
+				case LINKS:
+					BuildLinks(api);
+					observer.built(stage, TPC_K_LINKS);
+					t.linkRows = FetchLinks(api, events, NeedsLinkRows(request), linkBits, t.links);
+					break;
+				case BUBBLES:
+					BuildBubbles(api);
+					observer.built(stage, TPC_K_BUBBLES);
+					FetchBubbles(api, t.bubbles);
+					break;
+				case DISTANCES:
+					BuildDistances(api);
+					observer.built(stage, TPC_K_DISTANCES);
+					agree(FetchDistances(api, t.map.label.size(), t.segments, t.distances), "distance", wording.colorsOfDistances, "colours or the segments");
+					break;
+				case COMPONENTS:
+					BuildComponents(api);
+					observer.built(stage, TPC_K_COMPONENTS);
+					agree(FetchComponents(api, t.segments, t.colors.Words(), t.components), "component", "segment table", "segments");
+					break;
+				case SUPERBUBBLES:
+					BuildSuperbubbles(api, request.superbubblesMax);
+					observer.built(stage, TPC_K_SUPERBUBBLES);
+					agree(FetchSuperbubbles(api, t.segments, t.colors.Words(), t.superbubbles), "superbubble", "segment table", "segments");
+					break;
+				case ANCHORS:
+					BuildAnchors(api, t.map, request.anchorsRef);
+					observer.built(stage, TPC_K_ANCHORS);
+					agree(FetchAnchors(api, t.map, events, t.segments, t.anchors), "anchor", "colour map", "colours");
+					break;
+				case LOCATE:
+					uint64_t edges[6] = {0, 0, 0, 0, 0, 0};
+					BuildEdges(api, edges);
+					observer.built(EDGES, TPC_K_LOCATE);
+					observer.locateBatches = LocateOnDevice(api, edges, t.map.label.size(), t.segments, t.queryLetters, batchPositions, t.locate, observer.locateKernelMs);
+					observer.built(stage, TPC_K_LOCATE);
+					break;
+				}
+
+				observer.fetched(stage);
+			}
 		}
 	}
 }

@@ -58,15 +58,11 @@ namespace
 		opt.graphThreads = size_t(graphThreads < 1 ? 1 : graphThreads);
 	}
 
-	void SetColors(TwoPaCo::EnumeratorOptions & opt, const char * colorsBy, const char * colorsFile)
-	{
-		opt.colorsBy = colorsBy ? colorsBy : "";
-		opt.colorsFile = colorsFile ? colorsFile : "";
-	}
+	namespace GF = TwoPaCo::GraphFormat;
 
 	void SetLinks(TwoPaCo::EnumeratorOptions & opt, const char * linksFile, int graphCompact)
 	{
-		opt.linksFile = linksFile ? linksFile : "";
+		GF::SetTable(opt.tables, GF::LINKS, 0, linksFile, 0);
 		opt.graphCompact = graphCompact != 0;
 	}
 }
@@ -190,7 +186,7 @@ extern "C"
 		});
 	}
 
-	// the same as tpch_create_enumerator with --colors (EnumeratorOptions::colorsBy ...): colorsBy file | sequence into colorsFile;
+	// the same as tpch_create_enumerator with --colors (EnumeratorOptions::tables): colorsBy file | sequence into colorsFile;
 	// graphFormat may be NULL or empty (no graph); outFile may be empty, then the junction stream is not written
 	void * tpch_create_enumerator_colors(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
@@ -200,12 +196,12 @@ extern "C"
 		{
 			opt.insertTestFirst = testFirst != 0;
 			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
-			SetColors(opt, colorsBy, colorsFile);
-			if (opt.colorsBy.empty()) throw std::runtime_error("The colours must be one of file, sequence");
+			GF::SetTable(opt.tables, GF::COLORS, colorsBy, colorsFile, 0);
+			if (!opt.tables.On(GF::COLORS)) throw std::runtime_error("The colours must be one of file, sequence");
 		});
 	}
 
-	// the same as tpch_create_enumerator_colors with --links / --graph-compact (EnumeratorOptions::linksFile, graphCompact): linksFile
+	// the same as tpch_create_enumerator_colors with --links / --graph-compact (EnumeratorOptions::tables, graphCompact): linksFile
 	// NULL or empty: no link table; colorsBy NULL or empty: no colour table
 	void * tpch_create_enumerator_links(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
@@ -216,13 +212,13 @@ extern "C"
 		{
 			opt.insertTestFirst = testFirst != 0;
 			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
-			SetColors(opt, colorsBy, colorsFile);
+			GF::SetTable(opt.tables, GF::COLORS, colorsBy, colorsFile, 0);
 			SetLinks(opt, linksFile, graphCompact);
-			if (opt.linksFile.empty() && !opt.graphCompact) throw std::runtime_error("One of the link table's file and the compact graph is required");
+			if (!opt.tables.On(GF::LINKS) && !opt.graphCompact) throw std::runtime_error("One of the link table's file and the compact graph is required");
 		});
 	}
 
-	// the same as tpch_create_enumerator_links with --distances (EnumeratorOptions::distancesBy, distancesFile, distancesPhylipFile):
+	// the same as tpch_create_enumerator_links with --distances (EnumeratorOptions::tables):
 	// distancesBy file | sequence into distancesFile, phylipFile NULL or empty: no PHYLIP matrix; linksFile NULL or empty: no link
 	// table; colorsBy NULL or empty: no colour table; autoFilter != 0: `-f auto` (EnumeratorOptions::autoFilterSize, filterBits is
 	// ignored and rounds = 0 lets the plan choose them too, as tpch_create_enumerator_auto)
@@ -236,19 +232,16 @@ extern "C"
 		{
 			opt.insertTestFirst = testFirst != 0;
 			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
-			SetColors(opt, colorsBy, colorsFile);
+			GF::SetTable(opt.tables, GF::COLORS, colorsBy, colorsFile, 0);
 			SetLinks(opt, linksFile, graphCompact);
-			opt.distancesBy = distancesBy ? distancesBy : "";
-			opt.distancesFile = distancesFile ? distancesFile : "";
-			opt.distancesPhylipFile = phylipFile ? phylipFile : "";
-			if (opt.distancesBy.empty() || opt.distancesFile.empty()) throw std::runtime_error("The distance table needs its colours, one of file, sequence, and a file name");
+			if (!distancesBy || !*distancesBy || !distancesFile || !*distancesFile) throw std::runtime_error("The distance table needs its colours, one of file, sequence, and a file name");
+			GF::SetTable(opt.tables, GF::DISTANCES, distancesBy, distancesFile, phylipFile);
 			opt.autoFilterSize = autoFilter != 0;
 			opt.autoRounds = autoFilter != 0 && rounds == 0;
 		});
 	}
 
-	// the same as tpch_create_enumerator_distances with --components instead (EnumeratorOptions::componentsBy, componentsFile,
-	// componentsMembersFile): componentsBy file | sequence into componentsFile, membersFile NULL or empty: no members file
+	// the same as tpch_create_enumerator_distances with --components instead (EnumeratorOptions::tables): componentsBy file | sequence into componentsFile, membersFile NULL or empty: no members file
 	void * tpch_create_enumerator_components(const char ** files, int nfiles, uint64_t k, uint64_t filterBits, uint64_t q, uint64_t rounds,
 		uint64_t threads, uint64_t abundance, const char * tmpDir, const char * outFile, int pinned, uint64_t seed, int device,
 		int testFirst, const char * graphFormat, const char * graphFile, int graphPrefix, int graphThreads, const char * colorsBy, const char * colorsFile,
@@ -258,12 +251,10 @@ extern "C"
 		{
 			opt.insertTestFirst = testFirst != 0;
 			SetGraph(opt, graphFormat, graphFile, graphPrefix, graphThreads);
-			SetColors(opt, colorsBy, colorsFile);
+			GF::SetTable(opt.tables, GF::COLORS, colorsBy, colorsFile, 0);
 			SetLinks(opt, linksFile, graphCompact);
-			opt.componentsBy = componentsBy ? componentsBy : "";
-			opt.componentsFile = componentsFile ? componentsFile : "";
-			opt.componentsMembersFile = membersFile ? membersFile : "";
-			if (opt.componentsBy.empty() || opt.componentsFile.empty()) throw std::runtime_error("The component table needs its colours, one of file, sequence, and a file name");
+			if (!componentsBy || !*componentsBy || !componentsFile || !*componentsFile) throw std::runtime_error("The component table needs its colours, one of file, sequence, and a file name");
+			GF::SetTable(opt.tables, GF::COMPONENTS, componentsBy, componentsFile, membersFile);
 		});
 	}
 

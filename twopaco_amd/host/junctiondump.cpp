@@ -395,36 +395,7 @@ namespace
 		}
 	};
 
-	// --distances beside another table of the same colours: the file names of the distance table, written after that table from the
-	// same walk (or segment build) and the same colour table
-	struct DistancesWanted
-	{
-		bool on;
-		std::string out, phylip;
-		DistancesWanted() : on(false) {}
-	};
-
-	void DumpColors(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
-		const DistancesWanted & also = DistancesWanted())
-	{
-		InputSequences seq;
-		ListSequences(fasta, prefix, seq);
-		EventCollector events;
-		WalkSegments(binFile, fasta, k, events);
-		std::vector<uint32_t> seqEventBegin;
-		EventTable table;
-		events.Table(seq.name.size(), seqEventBegin, table);
-		ColorMap map;
-		MakeColorMap(seq, fasta, bySequence, map);
-		ColorTable colors;
-		ComputeColors(table, k, map.colorOfSequence, map.label.size(), colors);
-		DistanceTable distances;
-		if (also.on) ComputeDistances(table, colors, distances);
-		WriteColors(table, k, map, colors, outPath);
-		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
-	}
-
-	// ---------------------------------------------------------------------------------------- --links and --compact, serial
+	// ---------------------------------------------------------------------------------------- the tables and --compact, serial
 	struct SerialTable
 	{
 		InputSequences seq;
@@ -432,94 +403,53 @@ namespace
 		EventCollector events;
 		std::vector<uint32_t> seqEventBegin;
 		EventTable table;
-		LinkTable links;
 	};
 
-	// the walk's event table and its links; nothing is printed before both are complete
-	void WalkLinks(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bodies, SerialTable & out)
+	// the walk's event table; nothing is printed before it is complete
+	void WalkTable(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bodies, SerialTable & out)
 	{
 		if (bodies) LoadSequences(fasta, prefix, 1, out.seq, out.loaded);
 		else ListSequences(fasta, prefix, out.seq);
 		WalkSegments(binFile, fasta, k, out.events);
 		out.events.Table(out.seq.name.size(), out.seqEventBegin, out.table);
-		ComputeLinks(out.table, out.links);
-	}
-
-	uint64_t CountFirstBits(const EventTable & table)
-	{
-		uint64_t n = 0;
-		for (uint64_t w = 0; w < (table.events + 31) / 32; w++) n += uint64_t(__builtin_popcount(table.first[w]));
-		return n;
-	}
-
-	void DumpLinks(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, const std::string & outPath)
-	{
-		SerialTable t;
-		WalkLinks(binFile, fasta, k, prefix, false, t);
-		WriteLinks(t.table, k, CountFirstBits(t.table), t.links, outPath);
 	}
 
 	void DumpCompact(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix)
 	{
 		SerialTable t;
-		WalkLinks(binFile, fasta, k, prefix, true, t);
-		t.table.linkFirst = t.links.linkFirst.data();
+		WalkTable(binFile, fasta, k, prefix, true, t);
+		LinkTable links;
+		ComputeLinks(t.table, links);
+		t.table.linkFirst = links.linkFirst.data();
 		Out head(false);
 		HeaderLines("gfa1", t.seq, head, true);
 		std::fwrite(head.Text().data(), 1, head.Text().size(), stdout);
 		FormatEvents(t.table, t.seq, t.loaded, k, "gfa1", 1, -1, 0);
 	}
 
-	// --bubbles, serial: the walk, then the three serial statements one after the other
-	void DumpBubbles(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
-		const DistancesWanted & also = DistancesWanted())
+	// The colours of a request, once the input's files and sequences are known; the reference colour of --anchors must be one of them
+	void MakeRequestColors(const TableRequest & request, const InputSequences & seq, const std::vector<std::string> & fasta, ColorMap & map)
 	{
-		SerialTable t;
-		WalkLinks(binFile, fasta, k, prefix, false, t);
-		ColorMap map;
-		MakeColorMap(t.seq, fasta, bySequence, map);
-		ColorTable colors;
-		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
-		BubbleTable bubbles;
-		ComputeBubbles(t.table, t.links, bubbles);
-		DistanceTable distances;
-		if (also.on) ComputeDistances(t.table, colors, distances);
-		WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, outPath);
-		if (also.on) WriteDistanceFiles(k, map, colors.Rows(), distances, also.out, also.phylip);
-	}
-
-	struct ArgError
-	{
-		std::string what, arg;
-		ArgError(const std::string & w, const std::string & a) : what(w), arg(a) {}
-	};
-
-	// --anchors beside another table of the same colours, or alone: the reference colour and the file names (out empty: stdout)
-	struct AnchorsWanted
-	{
-		bool on;
-		uint32_t ref;
-		std::string out, paf;
-		AnchorsWanted() : on(false), ref(0) {}
-	};
-
-	// the reference colour must be one of the map's: known only once the input's files and sequences are
-	void CheckAnchorsRef(const AnchorsWanted & anchors, const ColorMap & map)
-	{
-		if (anchors.on && anchors.ref >= map.label.size())
+		if (!NeedsColorMap(request)) return;
+		MakeColorMap(seq, fasta, request.bySequence, map);
+		if (request.On(ANCHORS) && request.anchorsRef >= map.label.size())
 		{
-			throw ArgError("Value '" + std::to_string(anchors.ref) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--anchors-ref)");
+			throw ArgError("Value '" + std::to_string(request.anchorsRef) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--anchors-ref)");
 		}
 	}
 
-	// --locate beside another table of the same colours, or alone: the query files and the file names (out empty: stdout, walks empty: none)
-	struct LocateWanted
+	// A table request, serial: one walk (with the letters when the edge index reads them), the serial statements the request needs,
+	// then the tables in their order.  A stream the walk refuses prints the walk's error and nothing else.
+	void DumpTables(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, const TableRequest & request)
 	{
-		bool on;
-		std::vector<std::string> in;
-		std::string out, walks;
-		LocateWanted() : on(false) {}
-	};
+		SerialTable t;
+		WalkTable(binFile, fasta, k, prefix, NeedsLetters(request), t);
+		Tables tables;
+		MakeRequestColors(request, t.seq, fasta, tables.map);
+		LoadQueries(request, 1, tables);
+		ComputeTables(t.table, t.loaded, k, request, tables);
+		WriteTables(COLORS, t.table, k, request, t.seq, tables, [](int) {});
+	}
 
 	// Positions of packed query text per device call, whole records: 2^28, or what TWOPACO_LOCATE_BATCH says (tests: a small query in
 	// several batches)
@@ -528,88 +458,6 @@ namespace
 		const char * e = std::getenv("TWOPACO_LOCATE_BATCH");
 		const long long n = e && *e ? std::atoll(e) : 0;
 		return n > 0 ? uint64_t(n) : uint64_t(1) << 28;
-	}
-
-	// --components beside another table of the same colours, or alone: the file names of the component table (out empty: stdout)
-	struct ComponentsWanted
-	{
-		bool on;
-		std::string out, members;
-		ComponentsWanted() : on(false) {}
-	};
-
-	// --superbubbles beside another table of the same colours, or alone: the file names (out empty: stdout) and the bound
-	struct SuperbubblesWanted
-	{
-		bool on;
-		std::string out, members;
-		uint32_t maxInside;
-		SuperbubblesWanted() : on(false), maxInside(62) {}
-	};
-
-	// --components, --superbubbles and / or --anchors, serial, alone or beside --colors / --bubbles / --distances of the same colours: one
-	// walk, the serial statements one after the other, then the tables in the order colours or bubbles, distances, components,
-	// superbubbles, anchors
-	void DumpComponents(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const ComponentsWanted & want,
-		bool colorsToo, bool bubblesToo, const std::string & firstOut, bool distancesToo, const DistancesWanted & distancesTo, const SuperbubblesWanted & super,
-		const AnchorsWanted & anchorsTo = AnchorsWanted(), const LocateWanted & locateTo = LocateWanted())
-	{
-		SerialTable t;
-		WalkLinks(binFile, fasta, k, prefix, locateTo.on, t);   // (the edge index reads the letters)
-		ColorMap map;
-		MakeColorMap(t.seq, fasta, bySequence, map);
-		CheckAnchorsRef(anchorsTo, map);
-		ColorTable colors;
-		ComputeColors(t.table, k, map.colorOfSequence, map.label.size(), colors);
-		BubbleTable bubbles;
-		if (bubblesToo) ComputeBubbles(t.table, t.links, bubbles);
-		DistanceTable distances;
-		if (distancesToo) ComputeDistances(t.table, colors, distances);
-		ComponentTable components;
-		if (want.on) ComputeComponents(t.table, k, t.links, colors, components);
-		SuperbubbleTable superbubbles;
-		if (super.on) ComputeSuperbubbles(t.table, k, t.links, colors, super.maxInside, superbubbles);
-		AnchorTable anchors;
-		if (anchorsTo.on) ComputeAnchors(t.table, k, map.colorOfSequence, map.label.size(), anchorsTo.ref, anchors);
-		InputSequences queries;
-		LocateTable locate;
-		if (locateTo.on)
-		{
-			LoadedSequences queryLetters;
-			LoadSequences(locateTo.in, false, 1, queries, queryLetters);
-			CheckEventTable(t.table, t.loaded, k, 1);
-			EdgeIndex index;
-			BuildEdgeIndex(t.table, t.loaded, k, index);
-			ComputeLocate(index, colors, queryLetters, locate);
-		}
-
-		if (colorsToo) WriteColors(t.table, k, map, colors, firstOut);
-		if (bubblesToo) WriteBubbles(t.table, k, map, colors, t.links.Rows(), bubbles, firstOut);
-		if (distancesToo) WriteDistanceFiles(k, map, colors.Rows(), distances, distancesTo.out, distancesTo.phylip);
-		if (want.on) WriteComponentFiles(t.table, k, map, colors, t.links.Rows(), components, want.out, want.members);
-		if (super.on) WriteSuperbubbleFiles(t.table, k, map, colors, t.links.Rows(), superbubbles, super.out, super.members);
-		if (anchorsTo.on) WriteAnchorFiles(t.table, k, map, t.seq, anchors, anchorsTo.out, anchorsTo.paf);
-		if (locateTo.on) WriteLocateFiles(t.table, k, map, colors, queries, locate, locateTo.out, locateTo.walks);
-	}
-
-	// --distances, serial: the walk, the colour table, then the serial statement of the matrices
-	void DumpDistances(const std::string & binFile, const std::vector<std::string> & fasta, size_t k, bool prefix, bool bySequence, const std::string & outPath,
-		const std::string & phylipPath)
-	{
-		InputSequences seq;
-		ListSequences(fasta, prefix, seq);
-		EventCollector events;
-		WalkSegments(binFile, fasta, k, events);
-		std::vector<uint32_t> seqEventBegin;
-		EventTable table;
-		events.Table(seq.name.size(), seqEventBegin, table);
-		ColorMap map;
-		MakeColorMap(seq, fasta, bySequence, map);
-		ColorTable colors;
-		ComputeColors(table, k, map.colorOfSequence, map.label.size(), colors);
-		DistanceTable distances;
-		ComputeDistances(table, colors, distances);
-		WriteDistanceFiles(k, map, colors.Rows(), distances, outPath, phylipPath);
 	}
 
 	// ---------------------------------------------------------------------------------------- --gpu
@@ -622,15 +470,14 @@ namespace
 	{
 		std::string path, text;
 		uint64_t events, segments, nNamed, deviceBytes, streamBytes, textBytes, tableBytes;
-		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs;
+		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs;
+		double stageMs[TABLES + 1], stageKernelMs[TABLES + 1];  // of the stages of BuildTables: the tables', and EDGES
 		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored, anchorBlocks, anchors;
-		double bubblesKernelMs, bubblesMs, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs, superbubblesKernelMs, superbubblesMs, anchorsKernelMs, anchorsMs;
-		double edgesKernelMs, edgesMs, locateKernelMs, locateMs;
 		uint64_t locateRuns, locateBatches;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
-			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), colorsKernelMs(0), colorsMs(0), linksKernelMs(0), linksMs(0), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0), bubblesKernelMs(0), bubblesMs(0), distancesKernelMs(0), distancesMs(0),
-			componentsKernelMs(0), componentsMs(0), superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), superbubblesKernelMs(0), superbubblesMs(0), anchorsKernelMs(0), anchorsMs(0), edgesKernelMs(0), edgesMs(0), locateKernelMs(0), locateMs(0), locateRuns(0), locateBatches(0), threads(1) {}
+			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), stageMs(), stageKernelMs(), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0),
+			superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), locateRuns(0), locateBatches(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -649,11 +496,12 @@ namespace
 				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu, "
 				"\"edges_kernel_ms\": %.3f, \"edges_ms\": %.3f, \"locate_kernel_ms\": %.3f, \"locate_ms\": %.3f, \"locate_runs\": %llu, \"locate_batches\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
-				(unsigned long long)tableBytes, text.c_str(), textKernelMs, colorsKernelMs, colorsMs, linksKernelMs, linksMs, (unsigned long long)links,
-				(unsigned long long)linkOccurrences, bubblesKernelMs, bubblesMs, (unsigned long long)bubbles, distancesKernelMs, distancesMs, componentsKernelMs, componentsMs,
-				(unsigned long long)components, (unsigned long long)largestComponent, superbubblesKernelMs, superbubblesMs, (unsigned long long)superbubbles,
-				(unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, anchorsKernelMs, anchorsMs, (unsigned long long)anchorBlocks,
-				(unsigned long long)anchors, edgesKernelMs, edgesMs, locateKernelMs, locateMs, (unsigned long long)locateRuns, (unsigned long long)locateBatches);
+				(unsigned long long)tableBytes, text.c_str(), textKernelMs, stageKernelMs[COLORS], stageMs[COLORS], stageKernelMs[LINKS], stageMs[LINKS], (unsigned long long)links,
+				(unsigned long long)linkOccurrences, stageKernelMs[BUBBLES], stageMs[BUBBLES], (unsigned long long)bubbles, stageKernelMs[DISTANCES], stageMs[DISTANCES],
+				stageKernelMs[COMPONENTS], stageMs[COMPONENTS], (unsigned long long)components, (unsigned long long)largestComponent, stageKernelMs[SUPERBUBBLES],
+				stageMs[SUPERBUBBLES], (unsigned long long)superbubbles, (unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, stageKernelMs[ANCHORS],
+				stageMs[ANCHORS], (unsigned long long)anchorBlocks, (unsigned long long)anchors, stageKernelMs[EDGES], stageMs[EDGES], stageKernelMs[LOCATE], stageMs[LOCATE],
+				(unsigned long long)locateRuns, (unsigned long long)locateBatches);
 			std::fclose(f);
 		}
 	};
@@ -709,6 +557,8 @@ namespace
 		void * handle_;
 	};
 
+	const char * const PACKER_DISAGREES = "--gpu: the packer and the parser disagree about the input sequences";
+
 	// The front half of every device path: the stream's bytes and the packed text go up, the device builds the event table of
 	// the stream (name, first sight, the two positions of every event, the events of every sequence).  counts: tpc_segments_counts;
 	// sequences: how many the text holds; t0: when the device stage began.  Throws what the serial walk throws at a stream it refuses.
@@ -736,14 +586,7 @@ namespace
 		t0 = std::chrono::steady_clock::now();
 		TwoPaCo::PackedText text;
 		TwoPaCo::PackFastaFiles(fasta, threads, text);
-		if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-		std::vector<uint64_t> ambiguous;
-		for (size_t r = 0; r < loaded.body.size(); r++)
-		{
-			if (text.recLength[r] != loaded.body[r].size()) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-			for (uint64_t at : loaded.ambiguous[r]) ambiguous.push_back(text.recStart[r] + at);
-		}
-
+		const std::vector<uint64_t> ambiguous = AmbiguousPositions(text, loaded, PACKER_DISAGREES);
 		stats.packMs = MsSince(t0);
 
 		// the device stage
@@ -793,160 +636,64 @@ namespace
 		if (std::getenv("TWOPACO_TIMING")) std::fprintf(stderr, "[timing] %s on device: %.3f ms (kernels %.3f ms)\n", what, ms, kernelMs);
 	}
 
-	// The link table of the table on the device (csrc/tpc_links.hip), fetched: the rows, the first bits, or the number of rows alone.
-	void LinksOnDevice(DeviceLibrary & lib, uint64_t events, bool rows, bool bits, LinkTable & links, DumpStats & stats)
+	// graphdump's clock around the stages of BuildTables: DumpStats and the [timing] lines (the colour table's comes last, after the files)
+	const char * const STAGE_TIMING[TABLES + 1] = {0, "link table", "bubble table", "distance matrices", "component table", "superbubble table", "anchor table", "locate", "edge index"};
+	const StageWording GPU_WORDING = {"--gpu: the ", "colour map"};
+
+	void BuildTablesTimed(DeviceLibrary & lib, const TableRequest & request, const uint64_t * counts, bool linkBits, Tables & tables, DumpStats & stats)
 	{
-		const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-		BuildLinks(lib);
-		stats.linksKernelMs = lib.kernel_ms(lib.ctx, TPC_K_LINKS);
-		stats.links = FetchLinks(lib, events, rows, bits, links);
-		stats.linkOccurrences = links.occurrences;
-		stats.linksMs = MsSince(t0);
-		TimingLine("link table", stats.linksMs, stats.linksKernelMs);
+		std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+		auto close = [&](int stage)
+		{
+			stats.stageMs[stage] = MsSince(last);
+			last = std::chrono::steady_clock::now();
+			if (STAGE_TIMING[stage]) TimingLine(STAGE_TIMING[stage], stats.stageMs[stage], stats.stageKernelMs[stage]);
+		};
+
+		StageObserver observer;
+		observer.built = [&](int stage, int kernel)
+		{
+			stats.stageKernelMs[stage] = stage == LOCATE ? observer.locateKernelMs : lib.kernel_ms(lib.ctx, kernel);
+			if (stage == EDGES) close(stage);
+		};
+		observer.fetched = close;
+		BuildTables(lib, request, STAGES_DISTANCES_FIRST, counts, linkBits, LocateBatchPositions(), GPU_WORDING, tables, observer);
+		stats.links = tables.linkRows;
+		stats.linkOccurrences = tables.links.occurrences;
+		stats.bubbles = tables.bubbles.source.size();
+		stats.components = tables.components.Rows();
+		stats.largestComponent = tables.components.Largest();
+		stats.superbubbles = tables.superbubbles.Rows();
+		stats.superbubbleMembers = tables.superbubbles.members.size();
+		stats.superbubblesUnmirrored = tables.superbubbles.unmirrored;
+		stats.anchorBlocks = tables.anchors.Rows();
+		stats.anchors = tables.anchors.Anchors();
+		stats.locateRuns = tables.locate.Runs();
+		stats.locateBatches = observer.locateBatches;
 	}
 
-	// What a --gpu run instead of -f writes: one of the colour, link and bubble tables into `out`, and / or the distance table and the
-	// component table (alone, or beside the colour or the bubble table of the same colours, written after it).
-	struct TablesWanted
-	{
-		bool colors, links, bubbles, distances, components, superbubbles, bySequence;
-		std::string out, distancesOut, distancesPhylip, componentsOut, componentsMembers, superbubblesOut, superbubblesMembers;
-		uint32_t superbubblesMax;
-		AnchorsWanted anchors;
-		LocateWanted locate;
-	};
-
-	// --colors, --links, --bubbles, --distances with --gpu: one segment build, the table stays on the device, and the stages that are
-	// wanted run there in this order: colours (csrc/tpc_colors.hip), distances over their presence bits (csrc/tpc_distances.hip), links
-	// (csrc/tpc_links.hip), bubbles over the link rows (csrc/tpc_bubbles.hip), components over the link rows and the colour rows
-	// (csrc/tpc_components.hip).  Fetched is what the files print and no more: the event
-	// table for the names and lengths of any rows; --distances alone fetches the two matrices, neither colour rows nor event table.
+	// A table request with --gpu: one segment build, the table stays on the device, and the stages that are wanted run there
+	// (devicegraph.h: BuildTables).  Fetched is what the files print and no more: the event table for the names and lengths of any
+	// rows; --distances alone fetches the two matrices, neither colour rows nor event table.
 	void DumpTablesOnDevice(DeviceLibrary & lib, const std::string & binFile, const std::vector<std::string> & fasta, size_t k, size_t threads,
-		const InputSequences & seq, const LoadedSequences & loaded, const TablesWanted & want, DumpStats & stats)
+		const InputSequences & seq, const LoadedSequences & loaded, const TableRequest & request, DumpStats & stats)
 	{
 		uint64_t counts[6] = {0, 0, 0, 0, 0, 0};
 		size_t sequences = 0;
 		std::chrono::steady_clock::time_point t0;
 		BuildTableOnDevice(lib, binFile, fasta, k, threads, loaded, stats, counts, sequences, t0);
-		ColorMap map;
-		ColorTable colors;
-		const bool colorTable = want.colors || want.bubbles || want.distances || want.components || want.superbubbles || want.locate.on;
-		if (colorTable || want.anchors.on)
-		{
-			MakeColorMap(seq, fasta, want.bySequence, map);
-			if (map.colorOfSequence.size() != sequences) throw std::runtime_error("--gpu: the packer and the parser disagree about the input sequences");
-			CheckAnchorsRef(want.anchors, map);
-		}
-
-		if (colorTable)
-		{
-			const std::chrono::steady_clock::time_point c0 = std::chrono::steady_clock::now();
-			BuildColors(lib, map);
-			stats.colorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COLORS);
-			if (want.colors || want.bubbles || want.components || want.superbubbles || want.locate.on) FetchColors(lib, map, counts[1], colors);
-			stats.colorsMs = MsSince(c0);
-		}
-
-		DistanceTable distances;
-		if (want.distances)
-		{
-			const std::chrono::steady_clock::time_point d0 = std::chrono::steady_clock::now();
-			BuildDistances(lib);
-			stats.distancesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_DISTANCES);
-			if (!FetchDistances(lib, map.label.size(), counts[1], distances)) throw std::runtime_error("--gpu: the distance stage and the colour map disagree about the colours or the segments");
-			stats.distancesMs = MsSince(d0);
-			TimingLine("distance matrices", stats.distancesMs, stats.distancesKernelMs);
-		}
-
-		LinkTable links;
-		if (want.links || want.bubbles || want.components || want.superbubbles) LinksOnDevice(lib, counts[0], want.links || want.bubbles, false, links, stats);
-		BubbleTable bubbles;
-		if (want.bubbles)
-		{
-			const std::chrono::steady_clock::time_point b0 = std::chrono::steady_clock::now();
-			BuildBubbles(lib);
-			stats.bubblesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_BUBBLES);
-			FetchBubbles(lib, bubbles);
-			stats.bubbles = bubbles.source.size();
-			stats.bubblesMs = MsSince(b0);
-			TimingLine("bubble table", stats.bubblesMs, stats.bubblesKernelMs);
-		}
-
-		ComponentTable components;
-		if (want.components)
-		{
-			const std::chrono::steady_clock::time_point p0 = std::chrono::steady_clock::now();
-			BuildComponents(lib);
-			stats.componentsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_COMPONENTS);
-			if (!FetchComponents(lib, counts[1], colors.Words(), components)) throw std::runtime_error("--gpu: the component stage and the segment table disagree about the segments");
-			stats.components = components.Rows();
-			stats.largestComponent = components.Largest();
-			stats.componentsMs = MsSince(p0);
-			TimingLine("component table", stats.componentsMs, stats.componentsKernelMs);
-		}
-
-		SuperbubbleTable superbubbles;
-		if (want.superbubbles)
-		{
-			const std::chrono::steady_clock::time_point p0 = std::chrono::steady_clock::now();
-			BuildSuperbubbles(lib, want.superbubblesMax);
-			stats.superbubblesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_SUPERBUBBLES);
-			if (!FetchSuperbubbles(lib, counts[1], colors.Words(), superbubbles)) throw std::runtime_error("--gpu: the superbubble stage and the segment table disagree about the segments");
-			stats.superbubbles = superbubbles.Rows();
-			stats.superbubbleMembers = superbubbles.members.size();
-			stats.superbubblesUnmirrored = superbubbles.unmirrored;
-			stats.superbubblesMs = MsSince(p0);
-			TimingLine("superbubble table", stats.superbubblesMs, stats.superbubblesKernelMs);
-		}
-
-		AnchorTable anchors;
-		if (want.anchors.on)
-		{
-			// over the event table alone (csrc/tpc_anchors.hip): neither the colour rows nor the link rows are read
-			const std::chrono::steady_clock::time_point a0 = std::chrono::steady_clock::now();
-			BuildAnchors(lib, map, want.anchors.ref);
-			stats.anchorsKernelMs = lib.kernel_ms(lib.ctx, TPC_K_ANCHORS);
-			if (!FetchAnchors(lib, map, counts[0], counts[1], anchors)) throw std::runtime_error("--gpu: the anchor stage and the colour map disagree about the colours");
-			stats.anchorBlocks = anchors.Rows();
-			stats.anchors = anchors.Anchors();
-			stats.anchorsMs = MsSince(a0);
-			TimingLine("anchor table", stats.anchorsMs, stats.anchorsKernelMs);
-		}
-
-		InputSequences queries;
-		LocateTable locate;
-		if (want.locate.on)
-		{
-			// the edge index over the table and the text where they are, the colour rows of the build above (csrc/tpc_locate.hip)
-			const std::chrono::steady_clock::time_point l0 = std::chrono::steady_clock::now();
-			LoadedSequences queryLetters;
-			LoadSequences(want.locate.in, false, threads, queries, queryLetters);
-			uint64_t edges[6] = {0, 0, 0, 0, 0, 0};
-			BuildEdges(lib, edges);
-			stats.edgesKernelMs = lib.kernel_ms(lib.ctx, TPC_K_LOCATE);
-			stats.edgesMs = MsSince(l0);
-			TimingLine("edge index", stats.edgesMs, stats.edgesKernelMs);
-			const std::chrono::steady_clock::time_point l1 = std::chrono::steady_clock::now();
-			stats.locateBatches = LocateOnDevice(lib, edges, map.label.size(), counts[1], queryLetters, LocateBatchPositions(), locate, stats.locateKernelMs);
-			stats.locateRuns = locate.Runs();
-			stats.locateMs = MsSince(l1);
-			TimingLine("locate", stats.locateMs, stats.locateKernelMs);
-		}
-
+		Tables tables;
+		MakeRequestColors(request, seq, fasta, tables.map);
+		if (NeedsColorMap(request) && tables.map.colorOfSequence.size() != sequences) throw std::runtime_error(PACKER_DISAGREES);
+		LoadQueries(request, threads, tables);
+		BuildTablesTimed(lib, request, counts, false, tables, stats);
 		Events held(counts[0], sequences);
-		if (want.colors || want.links || want.bubbles || want.components || want.superbubbles || want.anchors.on || want.locate.on) FetchTable(lib, held);
+		if (NeedsEventTable(request)) FetchTable(lib, held);
 		stats.deviceMs = MsSince(t0);
 		t0 = std::chrono::steady_clock::now();
-		if (want.colors) WriteColors(held.table, k, map, colors, want.out);
-		if (want.links) WriteLinks(held.table, k, counts[1], links, want.out);
-		if (want.bubbles) WriteBubbles(held.table, k, map, colors, links.Rows(), bubbles, want.out);
-		if (want.distances) WriteDistanceFiles(k, map, counts[1], distances, want.distancesOut, want.distancesPhylip);
-		if (want.components) WriteComponentFiles(held.table, k, map, colors, stats.links, components, want.componentsOut, want.componentsMembers);
-		if (want.superbubbles) WriteSuperbubbleFiles(held.table, k, map, colors, stats.links, superbubbles, want.superbubblesOut, want.superbubblesMembers);
-		if (want.anchors.on) WriteAnchorFiles(held.table, k, map, seq, anchors, want.anchors.out, want.anchors.paf);
-		if (want.locate.on) WriteLocateFiles(held.table, k, map, colors, queries, locate, want.locate.out, want.locate.walks);
+		WriteTables(COLORS, held.table, k, request, seq, tables, [](int) {});
 		stats.formatMs = MsSince(t0);
-		if (want.colors) TimingLine("colour table", stats.colorsMs, stats.colorsKernelMs);
+		if (request.On(COLORS)) TimingLine("colour table", stats.stageMs[COLORS], stats.stageKernelMs[COLORS]);
 	}
 
 	// The device path of gfa1 / gfa2 / fasta.  `out` holds what main printed so far (the header lines).  The formatter of
@@ -990,11 +737,11 @@ namespace
 		Events held(counts[0], sequences);
 		stats.indexMs = FetchTable(lib, held);
 		EventTable & table = held.table;
-		LinkTable links;
+		Tables tables;
 		if (compact)
 		{
-			LinksOnDevice(lib, counts[0], false, true, links, stats);
-			table.linkFirst = links.linkFirst.data();
+			BuildTablesTimed(lib, TableRequest(), counts, true, tables, stats);
+			table.linkFirst = tables.links.linkFirst.data();
 		}
 
 		stats.deviceMs = MsSince(t0) - stats.indexMs;
@@ -1099,13 +846,10 @@ int main(int argc, char * argv[])
 {
 	try
 	{
-		std::string binFile, format, colorsBy, colorsOut, linksOut, bubblesBy, bubblesOut, distancesBy, distancesOut, distancesPhylip, componentsBy, componentsOut, componentsMembers, superbubblesBy, superbubblesOut, superbubblesMembers, anchorsBy, anchorsOut, anchorsPaf, locateBy, locateOut, locateWalks;
-		std::vector<std::string> locateIn;
-		bool locateOutSet = false, locateWalksSet = false;
+		std::string binFile, format;
 		std::vector<std::string> fasta;
-		bool colorsOutSet = false, textSet = false, links = false, linksOutSet = false, compact = false, bubblesOutSet = false, distancesOutSet = false, distancesPhylipSet = false, componentsOutSet = false, componentsMembersSet = false, superbubblesOutSet = false, superbubblesMembersSet = false, superbubblesMaxSet = false;
-		uint32_t superbubblesMax = 62, anchorsRef = 0;
-		bool anchorsRefSet = false, anchorsOutSet = false, anchorsPafSet = false;
+		TableOptions tables;
+		bool textSet = false, compact = false;
 		bool prefix = false, haveK = false, haveFormat = false, haveFile = false, gpu = false, textOnDevice = false;
 		int device = 0;
 		size_t k = 25, threads = 16;
@@ -1113,7 +857,7 @@ int main(int argc, char * argv[])
 		for (int i = 1; i < argc; i++)
 		{
 			const std::string a = argv[i];
-			auto value = [&](const char * id) -> std::string
+			auto value = [&](const std::string & id) -> std::string
 			{
 				if (i + 1 >= argc) throw ArgError("Missing a value for this argument!", id);
 				return argv[++i];
@@ -1150,75 +894,8 @@ int main(int argc, char * argv[])
 				textOnDevice = v == "device";
 				textSet = true;
 			}
-			else if (a == "--colors")
-			{
-				colorsBy = value("(--colors)");
-				if (colorsBy != "file" && colorsBy != "sequence") throw ArgError("Value '" + colorsBy + "' does not meet constraint: file|sequence", "Argument: (--colors)");
-			}
-			else if (a == "--colors-out") { colorsOut = value("(--colors-out)"); colorsOutSet = true; }
-			else if (a == "--links") links = true;
-			else if (a == "--links-out") { linksOut = value("(--links-out)"); linksOutSet = true; }
 			else if (a == "--compact") compact = true;
-			else if (a == "--bubbles")
-			{
-				bubblesBy = value("(--bubbles)");
-				if (bubblesBy != "file" && bubblesBy != "sequence") throw ArgError("Value '" + bubblesBy + "' does not meet constraint: file|sequence", "Argument: (--bubbles)");
-			}
-			else if (a == "--bubbles-out") { bubblesOut = value("(--bubbles-out)"); bubblesOutSet = true; }
-			else if (a == "--distances")
-			{
-				distancesBy = value("(--distances)");
-				if (distancesBy != "file" && distancesBy != "sequence") throw ArgError("Value '" + distancesBy + "' does not meet constraint: file|sequence", "Argument: (--distances)");
-			}
-			else if (a == "--distances-out") { distancesOut = value("(--distances-out)"); distancesOutSet = true; }
-			else if (a == "--distances-phylip") { distancesPhylip = value("(--distances-phylip)"); distancesPhylipSet = true; }
-			else if (a == "--components")
-			{
-				componentsBy = value("(--components)");
-				if (componentsBy != "file" && componentsBy != "sequence") throw ArgError("Value '" + componentsBy + "' does not meet constraint: file|sequence", "Argument: (--components)");
-			}
-			else if (a == "--components-out") { componentsOut = value("(--components-out)"); componentsOutSet = true; }
-			else if (a == "--components-members") { componentsMembers = value("(--components-members)"); componentsMembersSet = true; }
-			else if (a == "--superbubbles")
-			{
-				superbubblesBy = value("(--superbubbles)");
-				if (superbubblesBy != "file" && superbubblesBy != "sequence") throw ArgError("Value '" + superbubblesBy + "' does not meet constraint: file|sequence", "Argument: (--superbubbles)");
-			}
-			else if (a == "--superbubbles-out") { superbubblesOut = value("(--superbubbles-out)"); superbubblesOutSet = true; }
-			else if (a == "--superbubbles-members") { superbubblesMembers = value("(--superbubbles-members)"); superbubblesMembersSet = true; }
-			else if (a == "--superbubbles-max")
-			{
-				const std::string v = value("(--superbubbles-max)");
-				char * end = 0;
-				const long n = std::strtol(v.c_str(), &end, 10);
-				if (v.empty() || *end || n < 2 || n > 62) throw ArgError("Value '" + v + "' does not meet constraint: an integer 2 .. 62", "Argument: (--superbubbles-max)");
-				superbubblesMax = uint32_t(n);
-				superbubblesMaxSet = true;
-			}
-			else if (a == "--anchors")
-			{
-				anchorsBy = value("(--anchors)");
-				if (anchorsBy != "file" && anchorsBy != "sequence") throw ArgError("Value '" + anchorsBy + "' does not meet constraint: file|sequence", "Argument: (--anchors)");
-			}
-			else if (a == "--locate")
-			{
-				locateBy = value("(--locate)");
-				if (locateBy != "file" && locateBy != "sequence") throw ArgError("Value '" + locateBy + "' does not meet constraint: file|sequence", "Argument: (--locate)");
-			}
-			else if (a == "--locate-in") locateIn.push_back(value("(--locate-in)"));
-			else if (a == "--locate-out") { locateOut = value("(--locate-out)"); locateOutSet = true; }
-			else if (a == "--locate-walks") { locateWalks = value("(--locate-walks)"); locateWalksSet = true; }
-			else if (a == "--anchors-out") { anchorsOut = value("(--anchors-out)"); anchorsOutSet = true; }
-			else if (a == "--anchors-paf") { anchorsPaf = value("(--anchors-paf)"); anchorsPafSet = true; }
-			else if (a == "--anchors-ref")
-			{
-				const std::string v = value("(--anchors-ref)");
-				char * end = 0;
-				const long long n = std::strtoll(v.c_str(), &end, 10);
-				if (v.empty() || *end || n < 0 || n > 0x7FFFFFFFll) throw ArgError("Value '" + v + "' does not meet constraint: a colour index", "Argument: (--anchors-ref)");
-				anchorsRef = uint32_t(n);
-				anchorsRefSet = true;
-			}
+			else if (ParseTableOption(a, value, "Argument: ", tables)) continue;
 			else if (a == "-k" || a == "--kvalue")
 			{
 				const std::string v = value("(--kvalue)");
@@ -1239,90 +916,20 @@ int main(int argc, char * argv[])
 			else throw ArgError("Couldn't find match for argument", "(" + a + ")");
 		}
 
-		const bool colors = !colorsBy.empty(), bubbles = !bubblesBy.empty(), distances = !distancesBy.empty(), components = !componentsBy.empty();
-		const bool superbubbles = !superbubblesBy.empty();
-		const bool anchors = !anchorsBy.empty();
-		const bool locate = !locateBy.empty();
-		if (locate && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--locate)");
-		if (locate && colors && colorsBy != locateBy) throw ArgError("The locate table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && bubbles && bubblesBy != locateBy) throw ArgError("The locate table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && distances && distancesBy != locateBy) throw ArgError("The locate table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && components && componentsBy != locateBy) throw ArgError("The locate table and the component table share one set of colours: --components " + componentsBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && superbubbles && superbubblesBy != locateBy) throw ArgError("The locate table and the superbubble table share one set of colours: --superbubbles " + superbubblesBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && anchors && anchorsBy != locateBy) throw ArgError("The locate table and the anchor table share one set of colours: --anchors " + anchorsBy + " does not go with --locate " + locateBy, "(--locate)");
-		if (locate && links) throw ArgError("The locate table and the link table are written one at a time: not with --links", "(--locate)");
-		if (locate && compact) throw ArgError("The locate table and the compact text are written one at a time: not with --compact", "(--locate)");
-		if (locate && textSet) throw ArgError("The locate table is formatted by the host: not with --locate", "(--text)");
-		if (locate && locateIn.empty()) throw ArgError("The locate table needs a query: --locate-in <fasta file>", "(--locate)");
-		if (!locateIn.empty() && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-in)");
-		if (locateOutSet && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-out)");
-		if (locateWalksSet && !locate) throw ArgError("This argument needs --locate <file|sequence>", "(--locate-walks)");
-		if (locateWalksSet && locateWalks.empty()) throw ArgError("The locate walks need a file name", "(--locate-walks)");
-		if (anchors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--anchors)");
-		if (anchors && colors && colorsBy != anchorsBy) throw ArgError("The anchor table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
-		if (anchors && bubbles && bubblesBy != anchorsBy) throw ArgError("The anchor table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
-		if (anchors && distances && distancesBy != anchorsBy) throw ArgError("The anchor table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
-		if (anchors && components && componentsBy != anchorsBy) throw ArgError("The anchor table and the component table share one set of colours: --components " + componentsBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
-		if (anchors && superbubbles && superbubblesBy != anchorsBy) throw ArgError("The anchor table and the superbubble table share one set of colours: --superbubbles " + superbubblesBy + " does not go with --anchors " + anchorsBy, "(--anchors)");
-		if (anchors && links) throw ArgError("The anchor table and the link table are written one at a time: not with --links", "(--anchors)");
-		if (anchors && compact) throw ArgError("The anchor table and the compact text are written one at a time: not with --compact", "(--anchors)");
-		if (anchors && textSet) throw ArgError("The anchor table is formatted by the host: not with --anchors", "(--text)");
-		if (anchorsOutSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-out)");
-		if (anchorsPafSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-paf)");
-		if (anchorsRefSet && !anchors) throw ArgError("This argument needs --anchors <file|sequence>", "(--anchors-ref)");
-		if (anchorsPafSet && anchorsPaf.empty()) throw ArgError("The anchor PAF needs a file name", "(--anchors-paf)");
-		if (superbubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--superbubbles)");
-		if (superbubbles && colors && colorsBy != superbubblesBy) throw ArgError("The superbubble table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
-		if (superbubbles && bubbles && bubblesBy != superbubblesBy) throw ArgError("The superbubble table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
-		if (superbubbles && distances && distancesBy != superbubblesBy) throw ArgError("The superbubble table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
-		if (superbubbles && components && componentsBy != superbubblesBy) throw ArgError("The superbubble table and the component table share one set of colours: --components " + componentsBy + " does not go with --superbubbles " + superbubblesBy, "(--superbubbles)");
-		if (superbubbles && links) throw ArgError("The superbubble table and the link table are written one at a time: not with --links", "(--superbubbles)");
-		if (superbubbles && compact) throw ArgError("The superbubble table and the compact text are written one at a time: not with --compact", "(--superbubbles)");
-		if (superbubbles && textSet) throw ArgError("The superbubble table is formatted by the host: not with --superbubbles", "(--text)");
-		if (superbubblesOutSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-out)");
-		if (superbubblesMembersSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-members)");
-		if (superbubblesMaxSet && !superbubbles) throw ArgError("This argument needs --superbubbles <file|sequence>", "(--superbubbles-max)");
-		if (superbubblesMembersSet && superbubblesMembers.empty()) throw ArgError("The superbubble members need a file name", "(--superbubbles-members)");
-		if (components && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--components)");
-		if (components && colors && colorsBy != componentsBy) throw ArgError("The component table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --components " + componentsBy, "(--components)");
-		if (components && bubbles && bubblesBy != componentsBy) throw ArgError("The component table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --components " + componentsBy, "(--components)");
-		if (components && distances && distancesBy != componentsBy) throw ArgError("The component table and the distance table share one set of colours: --distances " + distancesBy + " does not go with --components " + componentsBy, "(--components)");
-		if (components && links) throw ArgError("The component table and the link table are written one at a time: not with --links", "(--components)");
-		if (components && compact) throw ArgError("The component table and the compact text are written one at a time: not with --compact", "(--components)");
-		if (components && textSet) throw ArgError("The component table is formatted by the host: not with --components", "(--text)");
-		if (componentsOutSet && !components) throw ArgError("This argument needs --components <file|sequence>", "(--components-out)");
-		if (componentsMembersSet && !components) throw ArgError("This argument needs --components <file|sequence>", "(--components-members)");
-		if (componentsMembersSet && componentsMembers.empty()) throw ArgError("The component members need a file name", "(--components-members)");
-		if (distances && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--distances)");
-		// one set of colours per run: the modes are compared before anything else is said about the combination
-		if (distances && colors && colorsBy != distancesBy) throw ArgError("The distance table and the colour table share one set of colours: --colors " + colorsBy + " does not go with --distances " + distancesBy, "(--distances)");
-		if (distances && bubbles && bubblesBy != distancesBy) throw ArgError("The distance table and the bubble table share one set of colours: --bubbles " + bubblesBy + " does not go with --distances " + distancesBy, "(--distances)");
-		if (distances && links) throw ArgError("The distance table and the link table are written one at a time: not with --links", "(--distances)");
-		if (distances && compact) throw ArgError("The distance table and the compact text are written one at a time: not with --compact", "(--distances)");
-		if (distances && textSet) throw ArgError("The distance table is formatted by the host: not with --distances", "(--text)");
-		if (distancesOutSet && !distances) throw ArgError("This argument needs --distances <file|sequence>", "(--distances-out)");
-		if (distancesPhylipSet && !distances) throw ArgError("This argument needs --distances <file|sequence>", "(--distances-phylip)");
-		if (distancesPhylipSet && distancesPhylip.empty()) throw ArgError("The PHYLIP matrix needs a file name", "(--distances-phylip)");
-		if (bubbles && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--bubbles)");
-		if (bubbles && colors) throw ArgError("The bubble table and the colour table are written one at a time: not with --colors", "(--bubbles)");
-		if (bubbles && links) throw ArgError("The bubble table and the link table are written one at a time: not with --links", "(--bubbles)");
-		if (bubbles && compact) throw ArgError("The bubble table and the compact text are written one at a time: not with --compact", "(--bubbles)");
-		if (bubbles && textSet) throw ArgError("The bubble table is formatted by the host: not with --bubbles", "(--text)");
-		if (bubblesOutSet && !bubbles) throw ArgError("This argument needs --bubbles <file|sequence>", "(--bubbles-out)");
-		if (colors && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--colors)");
-		if (colors && textSet) throw ArgError("The colour table is formatted by the host: not with --colors", "(--text)");
-		if (colorsOutSet && !colors) throw ArgError("This argument needs --colors <file|sequence>", "(--colors-out)");
-		if (links && haveFormat) throw ArgError("Mutually exclusive argument already set!", "(--links)");
-		if (links && colors) throw ArgError("The link table and the colour table are written one at a time: not with --colors", "(--links)");
-		if (links && textSet) throw ArgError("The link table is formatted by the host: not with --links", "(--text)");
-		if (linksOutSet && !links) throw ArgError("This argument needs --links", "(--links-out)");
+		// A table instead of -f.  The link table goes with no other, the bubble table not with the colour table, none but the colour
+		// and the link table's own complaint with --compact; the complaints are looked for from the last table back, the link table's last.
+		const unsigned linksBit = 1u << LINKS;
+		const TableCliRules rules = {"Argument: ", {LOCATE, ANCHORS, SUPERBUBBLES, COMPONENTS, DISTANCES, BUBBLES, COLORS, LINKS}, true, haveFormat, compact, textSet,
+			{0, 1u << COLORS, 1u << COLORS | linksBit, linksBit, linksBit, linksBit, linksBit, linksBit}, {false, false, true, true, true, true, true, true}, 1, false, 0};
+		CheckTableOptions(tables, rules);
+		const TableRequest & request = tables.request;
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");
 		if (compact && textOnDevice) throw ArgError("The compact text is formatted by the host: not with --text device", "(--compact)");
 		if (!haveK) throw ArgError("Required argument missing: kvalue", " ");
-		if (!haveFormat && !colors && !links && !bubbles && !distances && !components && !superbubbles && !anchors && !locate) throw ArgError("Required argument missing: format", " ");
+		if (!haveFormat && !request.Any()) throw ArgError("Required argument missing: format", " ");
 		if (!haveFile) throw ArgError("Required argument missing: infile", " ");
 		if (textOnDevice && !gpu) throw ArgError("Value 'device' does not meet constraint: the text is rendered on the device only with --gpu", "Argument: (--text)");
-		const bool needsSequences = colors || links || bubbles || distances || components || superbubbles || anchors || locate || format == "gfa1" || format == "gfa2" || format == "fasta";
+		const bool needsSequences = request.Any() || format == "gfa1" || format == "gfa2" || format == "fasta";
 		if (needsSequences && fasta.empty()) throw ArgError("Required argument missing\n", "Argument: seqfilename");
 
 		DumpStats stats;
@@ -1332,66 +939,16 @@ int main(int argc, char * argv[])
 		const bool deviceText = lib && textOnDevice;
 		stats.text = deviceText ? "device" : "host";
 		Out out(!deviceText && !compact);  // --text device, --compact: the header lines wait until the table is known to be good
-		// --distances beside --colors or --bubbles (the same colours, checked above): that table's walk or segment build and its
-		// colour table serve the distance table too, which is written after it
-		DistancesWanted also;
-		also.on = distances && (colors || bubbles);
-		also.out = distancesOut;
-		also.phylip = distancesPhylip;
-		AnchorsWanted anchorsTo;
-		anchorsTo.on = anchors;
-		anchorsTo.ref = anchorsRef;
-		anchorsTo.out = anchorsOut;
-		anchorsTo.paf = anchorsPaf;
-		LocateWanted locateTo;
-		locateTo.on = locate;
-		locateTo.in = locateIn;
-		locateTo.out = locateOut;
-		locateTo.walks = locateWalks;
-		if ((colors || links || bubbles || distances || components || superbubbles || anchors || locate) && lib)
+		if (request.Any() && lib)
 		{
 			std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
 			InputSequences seq;
 			LoadedSequences loaded;
 			LoadSequences(fasta, prefix, threads, seq, loaded);
 			stats.loadMs = MsSince(t0);
-			TablesWanted want;
-			want.colors = colors;
-			want.links = links;
-			want.bubbles = bubbles;
-			want.distances = distances;
-			want.components = components;
-			want.superbubbles = superbubbles;
-			want.superbubblesOut = superbubblesOut;
-			want.superbubblesMembers = superbubblesMembers;
-			want.superbubblesMax = superbubblesMax;
-			want.anchors = anchorsTo;
-			want.locate = locateTo;
-			want.bySequence = (colors ? colorsBy : bubbles ? bubblesBy : distances ? distancesBy : components ? componentsBy : superbubbles ? superbubblesBy : anchors ? anchorsBy : locateBy) == "sequence";
-			want.componentsOut = componentsOut;
-			want.componentsMembers = componentsMembers;
-			want.out = colors ? colorsOut : links ? linksOut : bubblesOut;
-			want.distancesOut = distancesOut;
-			want.distancesPhylip = distancesPhylip;
-			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, want, stats);
+			DumpTablesOnDevice(*lib, binFile, fasta, k, threads, seq, loaded, request, stats);
 		}
-		else if (components || superbubbles || anchors || locate)
-		{
-			ComponentsWanted wanted;
-			wanted.on = components;
-			wanted.out = componentsOut;
-			wanted.members = componentsMembers;
-			SuperbubblesWanted super;
-			super.on = superbubbles;
-			super.out = superbubblesOut;
-			super.members = superbubblesMembers;
-			super.maxInside = superbubblesMax;
-			DumpComponents(binFile, fasta, k, prefix, (components ? componentsBy : superbubbles ? superbubblesBy : anchors ? anchorsBy : locateBy) == "sequence", wanted, colors, bubbles, colors ? colorsOut : bubblesOut, distances, also, super, anchorsTo, locateTo);
-		}
-		else if (colors) DumpColors(binFile, fasta, k, prefix, colorsBy == "sequence", colorsOut, also);
-		else if (links) DumpLinks(binFile, fasta, k, prefix, linksOut);
-		else if (bubbles) DumpBubbles(binFile, fasta, k, prefix, bubblesBy == "sequence", bubblesOut, also);
-		else if (distances) DumpDistances(binFile, fasta, k, prefix, distancesBy == "sequence", distancesOut, distancesPhylip);
+		else if (request.Any()) DumpTables(binFile, fasta, k, prefix, request);
 		else if (lib)
 		{
 			// the serial branch below, with the walk's serial part done on the device
@@ -1446,12 +1003,12 @@ int main(int argc, char * argv[])
 		std::fflush(stdout);
 		if (e.arg == "Argument: seqfilename")
 		{
-			std::fprintf(stderr, "error: %s for arg %s\n", e.what.c_str(), e.arg.c_str());  // thrown after parsing, graphdump.cpp:669-693
+			std::fprintf(stderr, "error: %s for arg %s\n", e.what(), e.arg.c_str());  // thrown after parsing, graphdump.cpp:669-693
 		}
 		else
 		{
 			std::fprintf(stderr, "PARSE ERROR: %s\n             %s\n\nBrief USAGE: \n   %s  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--] [--version] [-h] <file name>\n\n"
-				"For complete USAGE and HELP type: \n   %s --help\n\n", e.arg.c_str(), e.what.c_str(), argv[0], argv[0]);
+				"For complete USAGE and HELP type: \n   %s --help\n\n", e.arg.c_str(), e.what(), argv[0], argv[0]);
 		}
 
 		return 1;

@@ -341,57 +341,19 @@ namespace TwoPaCo
 				if (graph && options.graphFile.empty()) throw std::runtime_error("The graph needs an output file name");
 				if (graph && sharded) throw std::runtime_error("The graph is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
 				const size_t graphThreads = std::max<size_t>(1, std::min<size_t>(16, options.graphThreads));
-				const bool colors = !options.colorsBy.empty();
-				if (colors && options.colorsBy != "file" && options.colorsBy != "sequence") throw std::runtime_error("The colours must be one of file, sequence");
-				if (colors && options.colorsFile.empty()) throw std::runtime_error("The colour table needs an output file name");
-				if (colors && sharded) throw std::runtime_error("The colour table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				const bool links = !options.linksFile.empty();
-				if (links && sharded) throw std::runtime_error("The link table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				const bool bubbles = !options.bubblesFile.empty();
-				if (bubbles && options.bubblesBy != "file" && options.bubblesBy != "sequence") throw std::runtime_error("The bubble table's colours must be one of file, sequence");
-				if (bubbles && colors && options.bubblesBy != options.colorsBy) throw std::runtime_error("The bubble table and the colour table share one set of colours: both by file or both by sequence");
-				if (bubbles && sharded) throw std::runtime_error("The bubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				const bool distances = !options.distancesFile.empty();
-				if (distances && options.distancesBy != "file" && options.distancesBy != "sequence") throw std::runtime_error("The distance table's colours must be one of file, sequence");
-				if (distances && colors && options.distancesBy != options.colorsBy) throw std::runtime_error("The distance table and the colour table share one set of colours: both by file or both by sequence");
-				if (distances && bubbles && options.distancesBy != options.bubblesBy) throw std::runtime_error("The distance table and the bubble table share one set of colours: both by file or both by sequence");
-				if (distances && sharded) throw std::runtime_error("The distance table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				if (!distances && !options.distancesPhylipFile.empty()) throw std::runtime_error("The PHYLIP matrix is written with the distance table only");
-				const bool components = !options.componentsFile.empty();
-				if (components && options.componentsBy != "file" && options.componentsBy != "sequence") throw std::runtime_error("The component table's colours must be one of file, sequence");
-				if (components && colors && options.componentsBy != options.colorsBy) throw std::runtime_error("The component table and the colour table share one set of colours: both by file or both by sequence");
-				if (components && bubbles && options.componentsBy != options.bubblesBy) throw std::runtime_error("The component table and the bubble table share one set of colours: both by file or both by sequence");
-				if (components && distances && options.componentsBy != options.distancesBy) throw std::runtime_error("The component table and the distance table share one set of colours: both by file or both by sequence");
-				if (components && sharded) throw std::runtime_error("The component table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				if (!components && !options.componentsMembersFile.empty()) throw std::runtime_error("The component members are written with the component table only");
-				const bool superbubbles = !options.superbubblesFile.empty();
-				if (superbubbles && options.superbubblesBy != "file" && options.superbubblesBy != "sequence") throw std::runtime_error("The superbubble table's colours must be one of file, sequence");
-				if (superbubbles && colors && options.superbubblesBy != options.colorsBy) throw std::runtime_error("The superbubble table and the colour table share one set of colours: both by file or both by sequence");
-				if (superbubbles && bubbles && options.superbubblesBy != options.bubblesBy) throw std::runtime_error("The superbubble table and the bubble table share one set of colours: both by file or both by sequence");
-				if (superbubbles && distances && options.superbubblesBy != options.distancesBy) throw std::runtime_error("The superbubble table and the distance table share one set of colours: both by file or both by sequence");
-				if (superbubbles && components && options.superbubblesBy != options.componentsBy) throw std::runtime_error("The superbubble table and the component table share one set of colours: both by file or both by sequence");
-				if (superbubbles && sharded) throw std::runtime_error("The superbubble table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				if (superbubbles && (options.superbubblesMax < 2 || options.superbubblesMax > 62)) throw std::runtime_error("The superbubble table's largest inside must be 2 .. 62");
-				if (!superbubbles && !options.superbubblesMembersFile.empty()) throw std::runtime_error("The superbubble members are written with the superbubble table only");
-				const bool anchors = !options.anchorsFile.empty();
-				if (anchors && options.anchorsBy != "file" && options.anchorsBy != "sequence") throw std::runtime_error("The anchor table's colours must be one of file, sequence");
-				if (anchors && colors && options.anchorsBy != options.colorsBy) throw std::runtime_error("The anchor table and the colour table share one set of colours: both by file or both by sequence");
-				if (anchors && bubbles && options.anchorsBy != options.bubblesBy) throw std::runtime_error("The anchor table and the bubble table share one set of colours: both by file or both by sequence");
-				if (anchors && distances && options.anchorsBy != options.distancesBy) throw std::runtime_error("The anchor table and the distance table share one set of colours: both by file or both by sequence");
-				if (anchors && components && options.anchorsBy != options.componentsBy) throw std::runtime_error("The anchor table and the component table share one set of colours: both by file or both by sequence");
-				if (anchors && superbubbles && options.anchorsBy != options.superbubblesBy) throw std::runtime_error("The anchor table and the superbubble table share one set of colours: both by file or both by sequence");
-				if (anchors && sharded) throw std::runtime_error("The anchor table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				if (!anchors && !options.anchorsPafFile.empty()) throw std::runtime_error("The anchor PAF is written with the anchor table only");
-				const bool locate = !options.locateFile.empty();
-				if (locate && options.locateBy != "file" && options.locateBy != "sequence") throw std::runtime_error("The locate table's colours must be one of file, sequence");
-				if (locate && options.locateIn.empty()) throw std::runtime_error("The locate table needs the FASTA files of the queries");
-				for (const std::string * by : { &options.colorsBy, &options.bubblesBy, &options.distancesBy, &options.componentsBy, &options.superbubblesBy, &options.anchorsBy })
+				// (the colours of the tables are one set by construction, and file or sequence: tablerequest.h)
+				const GraphFormat::TableRequest & tables = options.tables;
+				for (int t = 0; t < GraphFormat::TABLES; t++)
 				{
-					if (locate && !by->empty() && *by != options.locateBy) throw std::runtime_error("The locate table and the other tables share one set of colours: all by file or all by sequence");
+					const GraphFormat::TableRequest::File & file = tables.table[t];
+					const GraphFormat::TableRow & row = GraphFormat::TABLE_ROWS[t];
+					if (t == GraphFormat::LOCATE && file.on && tables.locateIn.empty()) throw std::runtime_error("The locate table needs the FASTA files of the queries");
+					if (file.on && file.out.empty()) throw std::runtime_error(GraphFormat::TableNoun(t) + " needs an output file name");
+					if (file.on && sharded) throw std::runtime_error(GraphFormat::TableNoun(t) + " is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
+					if (t == GraphFormat::SUPERBUBBLES && file.on && (tables.superbubblesMax < 2 || tables.superbubblesMax > 62)) throw std::runtime_error("The superbubble table's largest inside must be 2 .. 62");
+					if (!file.on && !file.second.empty()) throw std::runtime_error(std::string(row.secondNoun) + (row.secondPlural ? " are" : " is") + " written with the " + row.noun + " table only");
 				}
 
-				if (locate && sharded) throw std::runtime_error("The locate table is written by one GPU only: every rank of a sharded run holds its own piece of the junction stream");
-				if (!locate && !options.locateWalksFile.empty()) throw std::runtime_error("The locate walks are written with the locate table only");
 				if (options.graphCompact && options.graphFormat != "gfa1") throw std::runtime_error("The compact graph is gfa1 with every link once: it needs the graph format gfa1");
 				if (options.graphCompact && options.graphTextOnDevice) throw std::runtime_error("The compact graph is formatted by the host: not with the text rendered on the device");
 
@@ -526,7 +488,7 @@ namespace TwoPaCo
 				std::string graphLoadError;
 				std::thread graphLoad;
 				struct ThreadJoiner graphLoadJoiner{graphLoad};
-				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors || locate)
+				if (graph || tables.Any())
 				{
 					graphLoad = std::thread([&]()
 					{
@@ -1024,7 +986,7 @@ namespace TwoPaCo
 				}
 
 				timer.Lap("write junction stream");
-				if (graph || colors || links || bubbles || distances || components || superbubbles || anchors || locate) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
+				if (graph || tables.Any()) WriteGraph(nothing, text, vertexLength, graphThreads, options, fileName, graphLoad, graphLoadError, graphSeq, graphLoaded, timer);
 				logStream << "True marks count: " << occurence << std::endl;
 				logStream << "Edges construction time: " << time(0) - mark << std::endl;
 				logStream << std::string(80, '-') << std::endl;
@@ -1033,66 +995,34 @@ namespace TwoPaCo
 		private:
 			// --graph: the segment table from the stream tpc_emit_stream left on the device, fetched as the event table, formatted
 			// into options.graphFile.  What the walk of graphdump would throw is thrown here, before the file is created.
-			// --colors: the same table, built once for both, grouped by segment on the device and written to options.colorsFile.
-			// --bubbles: the colour rows and the link table of the same build, then the bubble stage (csrc/tpc_bubbles.hip) over the
-			// link rows where they lie; written to options.bubblesFile after the graph and the link file.
-			// --distances: the colour build of the same table, then the distance stage (csrc/tpc_distances.hip) over the presence bits
-			// where they lie; options.distancesFile and the PHYLIP file are written last of all, both or neither (WriteDistanceFiles), so that
-			// a step that throws leaves no file of theirs.
-			// --components: the colour build and the link build of the same table, then the component stage (csrc/tpc_components.hip) over
-			// the link rows and the colour rows where they lie; options.componentsFile and the members file are written after the
-			// distance files, both or neither (WriteComponentFiles).
-			// --superbubbles: the same two builds, then the superbubble stage (csrc/tpc_superbubbles.hip) over the link rows' arcs and the
-			// colour rows; options.superbubblesFile and the members file are written after the component files, both or neither
-			// (WriteSuperbubbleFiles).
-			// --anchors: the anchor stage (csrc/tpc_anchors.hip) over the event table of the same build and the colour map alone;
-			// options.anchorsFile and the PAF file are written after the superbubble files, both or neither (WriteAnchorFiles).
-			// --locate: the edge index and the lookups (csrc/tpc_locate.hip) over the event table, the text and the colour rows of the same
-			// build, the queries in batches of whole records; options.locateFile and the walks file are written last of all, both or
-			// neither (WriteLocateFiles).
+			// options.tables: the stages over the same segment build, built once for all (devicegraph.h: BuildTables), or, with nothing
+			// dispatched, the serial statements over the empty table (tablerequest.h: ComputeTables).  Everything that can fail comes
+			// before the first file is written; the files are the graph, then the tables in their order, each table's two files both
+			// or neither (tablerequest.h: WriteTables).
 			void WriteGraph(bool nothing, const PackedText & text, size_t k, size_t threads, const EnumeratorOptions & options, const std::vector<std::string> & fileName,
 				std::thread & load, const std::string & loadError, const GraphFormat::InputSequences & seq, const GraphFormat::LoadedSequences & loaded, PhaseTimer & timer)
 			{
-				const bool graph = !options.graphFormat.empty(), colors = !options.colorsBy.empty(), links = !options.linksFile.empty(), compact = graph && options.graphCompact;
-				const bool bubbles = !options.bubblesFile.empty(), distances = !options.distancesFile.empty(), components = !options.componentsFile.empty();
-				const bool superbubbles = !options.superbubblesFile.empty(), anchors = !options.anchorsFile.empty(), locate = !options.locateFile.empty();
-				const bool colorRows = colors || bubbles || distances || components || superbubbles || locate;
-				const bool bySequence = (colors ? options.colorsBy : bubbles ? options.bubblesBy : distances ? options.distancesBy : components ? options.componentsBy :
-					superbubbles ? options.superbubblesBy : anchors ? options.anchorsBy : options.locateBy) == "sequence";
+				using namespace GraphFormat;
+				const TableRequest & request = options.tables;
+				const bool graph = !options.graphFormat.empty(), compact = graph && options.graphCompact;
+				const char * const disagree = "The packer and the parser disagree about the input sequences";
 				if (load.joinable()) load.join();
 				if (!loadError.empty()) throw std::runtime_error(loadError);
-				if (text.recStart.size() != loaded.body.size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
-				std::vector<uint64_t> ambiguous;
-				for (size_t r = 0; r < loaded.body.size(); r++)
-				{
-					if (text.recLength[r] != loaded.body[r].size()) throw std::runtime_error("The packer and the parser disagree about the input sequences");
-					for (uint64_t at : loaded.ambiguous[r]) ambiguous.push_back(text.recStart[r] + at);
-				}
-
+				const std::vector<uint64_t> ambiguous = DeviceGraph::AmbiguousPositions(text, loaded, disagree);
 				const size_t sequences = text.recStart.size();
-				GraphFormat::ColorMap map;
-				GraphFormat::ColorTable colorTable;
-				GraphFormat::LinkTable linkTable;
-				GraphFormat::BubbleTable bubbleTable;
-				GraphFormat::DistanceTable distanceTable;
-				GraphFormat::ComponentTable componentTable;
-				GraphFormat::SuperbubbleTable superbubbleTable;
-				GraphFormat::AnchorTable anchorTable;
-				GraphFormat::LocateTable locateTable;
-				GraphFormat::InputSequences querySeq;
-				GraphFormat::LoadedSequences queryLetters;
-				if (locate) GraphFormat::LoadSequences(options.locateIn, false, threads, querySeq, queryLetters);
-				auto anchorColors = [&]()
+				Tables tables;
+				LoadQueries(request, threads, tables);
+				auto makeColorMap = [&]()
 				{
-					if (!colorRows) GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-					if (map.colorOfSequence.size() != sequences) throw std::runtime_error("The packer and the parser disagree about the input sequences");
-					if (options.anchorsRef >= map.label.size())
+					if (!NeedsColorMap(request)) return;
+					MakeColorMap(seq, fileName, request.bySequence, tables.map);
+					if (tables.map.colorOfSequence.size() != sequences) throw std::runtime_error(disagree);
+					if (request.On(ANCHORS) && request.anchorsRef >= tables.map.label.size())
 					{
-						throw std::runtime_error("The anchor table's reference colour is " + std::to_string(options.anchorsRef) + ", there are " + std::to_string(map.label.size()) + " colours");
+						throw std::runtime_error("The anchor table's reference colour is " + std::to_string(request.anchorsRef) + ", there are " + std::to_string(tables.map.label.size()) + " colours");
 					}
 				};
 
-				uint64_t segments = 0, linkRows = 0;
 				DeviceGraph::Events held(0, sequences);
 				const std::vector<uint32_t> noBits(1, 0);
 				const uint32_t * linkFirst = compact ? noBits.data() : 0;
@@ -1100,37 +1030,16 @@ namespace TwoPaCo
 				{
 					// nothing dispatched: an empty stream and no text on the device.  No event, no segment, no side: the serial statements
 					// over the empty table give the headers, the colours and two matrices of zeros
-					if (colorRows)
-					{
-						GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-						GraphFormat::ComputeColors(held.table, k, map.colorOfSequence, map.label.size(), colorTable);
-					}
-
-					if (links || bubbles || components || superbubbles) GraphFormat::ComputeLinks(held.table, linkTable);
-					if (bubbles) GraphFormat::ComputeBubbles(held.table, linkTable, bubbleTable);
-					if (distances) GraphFormat::ComputeDistances(held.table, colorTable, distanceTable);
-					if (components) GraphFormat::ComputeComponents(held.table, k, linkTable, colorTable, componentTable);
-					if (superbubbles) GraphFormat::ComputeSuperbubbles(held.table, k, linkTable, colorTable, options.superbubblesMax, superbubbleTable);
-					if (anchors)
-					{
-						anchorColors();
-						GraphFormat::ComputeAnchors(held.table, k, map.colorOfSequence, map.label.size(), options.anchorsRef, anchorTable);
-					}
-
-					if (locate)
-					{
-						GraphFormat::EdgeIndex index;
-						GraphFormat::BuildEdgeIndex(held.table, loaded, k, index);
-						GraphFormat::ComputeLocate(index, colorTable, queryLetters, locateTable);
-					}
+					makeColorMap();
+					ComputeTables(held.table, loaded, k, request, tables);
 				}
 				else
 				{
 					const DeviceGraph::Api api = LinkedApi();
 					const bool timing = std::getenv("TWOPACO_TIMING") != 0;
-					auto kernelLine = [&](const char * name, int which)
+					auto kernelLine = [&](const std::string & name, double ms)
 					{
-						if (timing) std::cerr << "[timing]   " << name << ": " << tpc_kernel_ms(ctx_, which) << " ms" << std::endl;
+						if (timing) std::cerr << "[timing]   " << name << ": " << ms << " ms" << std::endl;
 					};
 
 					Check(tpc_segments_build_resident(ctx_, int(k), text.recStart.data(), text.recLength.data(), uint32_t(sequences), ambiguous.data(), ambiguous.size()), "segments_build");
@@ -1140,217 +1049,70 @@ namespace TwoPaCo
 					Check(tpc_segments_counts(ctx_, counts), "segments_counts");
 					Check(tpc_segments_error(ctx_, &errorSlot, &errorKind), "segments_error");
 					timer.Lap("segment table");
-					kernelLine("segments_kernel_ms", TPC_K_SEGMENTS);
+					kernelLine("segments_kernel_ms", tpc_kernel_ms(ctx_, TPC_K_SEGMENTS));
 					if (errorKind != TPC_SEG_OK)
 					{
 						throw std::runtime_error(errorKind == TPC_SEG_ID_TOO_LARGE ? "A vertex id is too large, cannot generate GFA" : "The input is corrupted");
 					}
 
 					held.table.events = counts[0];
-					segments = counts[1];
-					// Everything that can fail on the device comes before the first file is written: a step that throws leaves no table's
-					// file behind (the graph file removes itself).  --graph-text device keeps the table on the device: what the tables'
-					// files print of it is fetched piece by piece, the names and the positions alone.
+					// What the files print of the event table is fetched before the stages: all of it where the host formats the graph;
+					// with --graph-text device, which keeps the table on the device, the names and the positions alone (and the sequences'
+					// ranges for the anchors).
 					const bool onDevice = graph && options.graphTextOnDevice;
-					bool fetched = false;
-					auto fetchTable = [&]()
+					if (!onDevice && (graph || NeedsEventTable(request)))
 					{
 						DeviceGraph::FetchNames(api, held);
 						DeviceGraph::FetchFirst(api, held);
 						DeviceGraph::FetchPositions(api, held);
 						DeviceGraph::FetchSequences(api, held);
 						timer.Lap("segment table fetch");
-						fetched = true;
+					}
+					else if (onDevice && NeedsEventTable(request))
+					{
+						if (counts[0]) DeviceGraph::FetchNames(api, held);
+						if (counts[0]) DeviceGraph::FetchPositions(api, held);
+						if (request.On(ANCHORS)) DeviceGraph::FetchSequences(api, held);
+					}
+
+					makeColorMap();
+					// twopaco's clock around the stages: a lap after every build and every fetch, the kernels' time after the build's
+					static const char * const lap[TABLES + 1] = {"segment colours", "segment links", "segment bubbles", "segment distances", "segment components",
+						"segment superbubbles", "segment anchors", "locate", "edge index"};
+					DeviceGraph::StageObserver observer;
+					observer.built = [&](int stage, int kernel)
+					{
+						timer.Lap(lap[stage]);
+						kernelLine(std::string(stage == DeviceGraph::EDGES ? "edges" : TABLE_ROWS[stage].name) + "_kernel_ms", stage == LOCATE ? observer.locateKernelMs : timing ? tpc_kernel_ms(ctx_, kernel) : 0);
 					};
-
-					if (colorRows)
+					observer.fetched = [&](int stage)
 					{
-						// --colors: the events grouped by segment on the device (csrc/tpc_colors.hip); the rows' names and lengths come from
-						// the fetched event table
-						if (!onDevice) fetchTable();
-						else if (counts[0])
-						{
-							DeviceGraph::FetchNames(api, held);
-							DeviceGraph::FetchPositions(api, held);
-						}
-
-						GraphFormat::MakeColorMap(seq, fileName, bySequence, map);
-						if (map.colorOfSequence.size() != sequences) throw std::runtime_error("The packer and the parser disagree about the input sequences");
-						DeviceGraph::BuildColors(api, map);
-						timer.Lap("segment colours");
-						kernelLine("colors_kernel_ms", TPC_K_COLORS);
-						DeviceGraph::FetchColors(api, map, segments, colorTable);
-						timer.Lap("segment colours fetch");
-					}
-
-					if ((links || compact) && !fetched && !onDevice) fetchTable();
-					if (links || compact || bubbles || components || superbubbles)
-					{
-						// --links / the compact graph / --bubbles / --components: the distinct links found on the device (csrc/tpc_links.hip), before the graph
-						// is written (the compact text needs their first bits); the rows' names come from name[]
-						DeviceGraph::BuildLinks(api);
-						timer.Lap("segment links");
-						kernelLine("links_kernel_ms", TPC_K_LINKS);
-						linkRows = DeviceGraph::FetchLinks(api, counts[0], links, compact, linkTable);
-						if (links && held.name.empty() && counts[0]) DeviceGraph::FetchNames(api, held);
-						timer.Lap("segment links fetch");
-						if (compact) linkFirst = linkTable.linkFirst.data();
-					}
-
-					if (bubbles)
-					{
-						// over the link rows where they lie (csrc/tpc_bubbles.hip); the arms' names, lengths and colours are --colors'
-						DeviceGraph::BuildBubbles(api);
-						timer.Lap("segment bubbles");
-						kernelLine("bubbles_kernel_ms", TPC_K_BUBBLES);
-						DeviceGraph::FetchBubbles(api, bubbleTable);
-						timer.Lap("segment bubbles fetch");
-					}
-
-					if (distances)
-					{
-						// over the presence bits where they lie (csrc/tpc_distances.hip); fetched are the matrices alone
-						DeviceGraph::BuildDistances(api);
-						timer.Lap("segment distances");
-						kernelLine("distances_kernel_ms", TPC_K_DISTANCES);
-						if (!DeviceGraph::FetchDistances(api, map.label.size(), segments, distanceTable))
-						{
-							throw std::runtime_error("The distance stage and the colour table disagree about the colours or the segments");
-						}
-
-						timer.Lap("segment distances fetch");
-					}
-
-					if (components)
-					{
-						// over the link rows and the colour rows where they lie (csrc/tpc_components.hip); the roots' names are --colors'
-						DeviceGraph::BuildComponents(api);
-						timer.Lap("segment components");
-						kernelLine("components_kernel_ms", TPC_K_COMPONENTS);
-						if (!DeviceGraph::FetchComponents(api, segments, colorTable.Words(), componentTable))
-						{
-							throw std::runtime_error("The component stage and the segment table disagree about the segments");
-						}
-
-						timer.Lap("segment components fetch");
-					}
-
-					if (superbubbles)
-					{
-						// over the link rows' arcs and the colour rows where they lie (csrc/tpc_superbubbles.hip); the sides' names are --colors'
-						DeviceGraph::BuildSuperbubbles(api, options.superbubblesMax);
-						timer.Lap("segment superbubbles");
-						kernelLine("superbubbles_kernel_ms", TPC_K_SUPERBUBBLES);
-						if (!DeviceGraph::FetchSuperbubbles(api, segments, colorTable.Words(), superbubbleTable))
-						{
-							throw std::runtime_error("The superbubble stage and the segment table disagree about the segments");
-						}
-
-						timer.Lap("segment superbubbles fetch");
-					}
-
-					if (anchors)
-					{
-						// over the event table where it lies (csrc/tpc_anchors.hip); the files print names, positions and sequences of events
-						if (!onDevice)
-						{
-							if (!fetched) fetchTable();
-						}
-						else
-						{
-							if (counts[0] && held.name.empty()) DeviceGraph::FetchNames(api, held);
-							if (counts[0] && held.begin.empty()) DeviceGraph::FetchPositions(api, held);
-							DeviceGraph::FetchSequences(api, held);
-						}
-
-						anchorColors();
-						DeviceGraph::BuildAnchors(api, map, options.anchorsRef);
-						timer.Lap("segment anchors");
-						kernelLine("anchors_kernel_ms", TPC_K_ANCHORS);
-						if (!DeviceGraph::FetchAnchors(api, map, counts[0], segments, anchorTable))
-						{
-							throw std::runtime_error("The anchor stage and the colour map disagree about the colours");
-						}
-
-						timer.Lap("segment anchors fetch");
-					}
-
-					if (locate)
-					{
-						// over the event table, the text and the colour rows where they lie (csrc/tpc_locate.hip); the walks print the rows' names
-						uint64_t edges[6] = {0, 0, 0, 0, 0, 0};
-						DeviceGraph::BuildEdges(api, edges);
-						timer.Lap("edge index");
-						kernelLine("edges_kernel_ms", TPC_K_LOCATE);
-						double kernelMs = 0;
-						DeviceGraph::LocateOnDevice(api, edges, map.label.size(), segments, queryLetters, uint64_t(1) << 28, locateTable, kernelMs);
-						timer.Lap("locate");
-						if (timing) std::cerr << "[timing]   locate_kernel_ms: " << kernelMs << " ms" << std::endl;
-					}
-
+						if (stage != LOCATE) timer.Lap((std::string(lap[stage]) + " fetch").c_str());
+					};
+					const DeviceGraph::StageWording wording = {"The ", "colour table"};
+					DeviceGraph::BuildTables(api, request, DeviceGraph::STAGES_LINKS_FIRST, counts, compact, uint64_t(1) << 28, wording, tables, observer);
+					if (compact) linkFirst = tables.links.linkFirst.data();
 					if (graph && onDevice) WriteGraphOnDevice(options, seq, loaded, timer);
-					else if (graph && !fetched) fetchTable();
 				}
 
 				// the files: the graph, then the tables.  (With nothing dispatched the colour table is written before the graph.)
-				auto writeColors = [&]()
+				auto written = [&](int id) { timer.Lap((std::string(TABLE_ROWS[id].noun) + " table writing").c_str()); };
+				if (nothing && request.On(COLORS))
 				{
-					GraphFormat::WriteColors(held.table, k, map, colorTable, options.colorsFile);
-					timer.Lap("colour table writing");
-				};
+					WriteTable(COLORS, held.table, k, request, seq, tables);
+					written(COLORS);
+				}
 
-				if (colors && nothing) writeColors();
 				if (graph && (nothing || !options.graphTextOnDevice))
 				{
-					GraphFormat::EventTable table = held.table;
+					EventTable table = held.table;
 					table.linkFirst = linkFirst;   // given: the compact gfa1
-					GraphFormat::CheckEventTable(table, loaded, k, threads);
-					GraphFormat::WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
+					CheckEventTable(table, loaded, k, threads);
+					WriteGraphFile(table, seq, loaded, k, options.graphFormat, threads, options.graphFile);
 					timer.Lap("graph formatting + writing");
 				}
 
-				if (colors && !nothing) writeColors();
-				if (links)
-				{
-					GraphFormat::WriteLinks(held.table, k, segments, linkTable, options.linksFile);
-					timer.Lap("link table writing");
-				}
-
-				if (bubbles)
-				{
-					GraphFormat::WriteBubbles(held.table, k, map, colorTable, linkRows, bubbleTable, options.bubblesFile);
-					timer.Lap("bubble table writing");
-				}
-
-				if (distances)
-				{
-					GraphFormat::WriteDistanceFiles(k, map, segments, distanceTable, options.distancesFile, options.distancesPhylipFile);
-					timer.Lap("distance table writing");
-				}
-
-				if (components)
-				{
-					GraphFormat::WriteComponentFiles(held.table, k, map, colorTable, linkRows, componentTable, options.componentsFile, options.componentsMembersFile);
-					timer.Lap("component table writing");
-				}
-
-				if (superbubbles)
-				{
-					GraphFormat::WriteSuperbubbleFiles(held.table, k, map, colorTable, linkRows, superbubbleTable, options.superbubblesFile, options.superbubblesMembersFile);
-					timer.Lap("superbubble table writing");
-				}
-
-				if (anchors)
-				{
-					GraphFormat::WriteAnchorFiles(held.table, k, map, seq, anchorTable, options.anchorsFile, options.anchorsPafFile);
-					timer.Lap("anchor table writing");
-				}
-
-				if (locate)
-				{
-					GraphFormat::WriteLocateFiles(held.table, k, map, colorTable, querySeq, locateTable, options.locateFile, options.locateWalksFile);
-					timer.Lap("locate table writing");
-				}
+				WriteTables(nothing ? LINKS : COLORS, held.table, k, request, seq, tables, written);
 			}
 
 			// the entry points of devicegraph.h at their linked addresses, on this enumerator's context and with its Check

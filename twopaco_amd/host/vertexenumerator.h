@@ -28,6 +28,7 @@
 #include "junctionapi.h"
 #include "seed.h"
 #include "streamfastaparser.h"
+#include "tablerequest.h"
 
 namespace TwoPaCo
 {
@@ -71,65 +72,15 @@ namespace TwoPaCo
 		// false: the event table is fetched and the text formatted by graphThreads host threads.  true: the text is rendered on
 		// the device and only written here (tpc_segments_text_plan / _text_write); the same bytes
 		bool graphTextOnDevice;
-		// The segment colour table (graphformat.h: WriteColors; `graphdump --colors` writes the same bytes for the junction stream
-		// of this run): colorsBy = file | sequence (empty: off) -- colour c is the c-th input file or the c-th sequence -- into
-		// colorsFile.  The events are grouped by segment on the device (tpc_segments_colors_build) over the segment table --graph
-		// uses, built once for both.  One GPU.
-		std::string colorsBy;
-		std::string colorsFile;
-		// The link table (graphformat.h: WriteLinks; `graphdump --links` writes the same bytes for the junction stream of this run):
-		// linksFile (empty: off).  The distinct links are found on the device (tpc_segments_links_build) over the same segment
-		// table.  graphCompact (graphFormat gfa1, host text only): the graph file is the compact gfa1 of `graphdump -f gfa1
-		// --compact` -- no per-sequence S lines, no C lines, every link once -- from the same link stage.  One GPU.
-		std::string linksFile;
+		// The tables of the same graph (tablerequest.h: which tables, their colours -- the c-th input file or the c-th sequence, one set
+		// for all of them --, their files, the bound of the superbubbles, the reference colour of the anchors, the query files of
+		// --locate): each file byte for byte what `graphdump --<table>` writes for the junction stream of this run.  Every table wanted
+		// needs a file name.  The stages run on the device over the segment table --graph uses, built once for all
+		// (devicegraph.h: BuildTables); a run where nothing was dispatched computes them over the empty table (ComputeTables).  One GPU.
+		GraphFormat::TableRequest tables;
+		// graphFormat gfa1, host text only: the graph file is the compact gfa1 of `graphdump -f gfa1 --compact` -- no per-sequence S
+		// lines, no C lines, every link once -- from the link stage of the tables.
 		bool graphCompact;
-		// The simple bubbles of the graph (graphformat.h: WriteBubbles; `graphdump --bubbles` writes the same bytes for the junction
-		// stream of this run): bubblesFile (empty: off), bubblesBy = "file" | "sequence" the colours of the arms' presence columns --
-		// the same as colorsBy when both are given.  Found on the device (tpc_segments_bubbles_build) over the colour rows and the
-		// link table of the same segment table.  One GPU.
-		std::string bubblesBy;
-		std::string bubblesFile;
-		// The genome distance matrices (graphformat.h: WriteDistances; `graphdump --distances` writes the same bytes for the junction
-		// stream of this run): distancesFile (empty: off), distancesBy = "file" | "sequence" -- the same as colorsBy and bubblesBy
-		// when those are given -- and distancesPhylipFile (empty: off) for the PHYLIP square matrix of Jaccard distances over edges.
-		// Summed on the device (tpc_segments_distances_build) over the colour build of the same segment table.  One GPU.
-		std::string distancesBy;
-		std::string distancesFile;
-		std::string distancesPhylipFile;
-		// The connected components of the graph (graphformat.h: WriteComponents; `graphdump --components` writes the same bytes for the
-		// junction stream of this run): componentsFile (empty: off), componentsBy = "file" | "sequence" -- the same as colorsBy,
-		// bubblesBy and distancesBy when those are given -- and componentsMembersFile (empty: off) for the component of every segment.
-		// Found on the device (tpc_segments_components_build) over the link build and the colour build of the same segment table.
-		// One GPU.
-		std::string componentsBy;
-		std::string componentsFile;
-		std::string componentsMembersFile;
-		// The bounded superbubbles of the graph (graphformat.h: WriteSuperbubbles; `graphdump --superbubbles` writes the same bytes for
-		// the junction stream of this run): superbubblesFile (empty: off), superbubblesBy = "file" | "sequence" -- the same as the
-		// other tables' when those are given --, superbubblesMembersFile (empty: off) for the inside sides of every row and
-		// superbubblesMax, the largest inside reported (2 .. 62).  Found on the device (tpc_segments_superbubbles_build) over the link
-		// build and the colour build of the same segment table.  One GPU.
-		std::string superbubblesBy;
-		std::string superbubblesFile;
-		std::string superbubblesMembersFile;
-		uint32_t superbubblesMax = 62;
-		// The anchor blocks against a reference colour (graphformat.h: WriteAnchors; `graphdump --anchors` writes the same bytes for the
-		// junction stream of this run): anchorsFile (empty: off), anchorsBy = "file" | "sequence" -- the same as the other tables' when
-		// those are given --, anchorsRef, the index of the reference colour, and anchorsPafFile (empty: off) for the blocks as PAF.
-		// Found on the device (tpc_segments_anchors_build) over the event table of the same segment build.  One GPU.
-		std::string anchorsBy;
-		std::string anchorsFile;
-		std::string anchorsPafFile;
-		uint32_t anchorsRef = 0;
-		// The query records of locateIn looked up in the graph window by window (graphformat.h: WriteLocate; `graphdump --locate` writes
-		// the same bytes for the junction stream of this run): locateFile (empty: off), locateBy = "file" | "sequence" -- the same as the
-		// other tables' when those are given --, locateIn, the FASTA files of the queries, and locateWalksFile (empty: off) for the
-		// runs.  The edge index and the lookups run on the device (tpc_segments_edges_build, tpc_segments_locate) over the event table
-		// and the colour rows of the same segment build.  One GPU.
-		std::string locateBy;
-		std::string locateFile;
-		std::string locateWalksFile;
-		std::vector<std::string> locateIn;
 		// `-f auto`: CreateEnumerator ignores its filterSize argument.  The text is uploaded first, the device sketches its distinct
 		// canonical (k+1)-mers (tpc_distinct_sketch), filterplan.h turns the estimate into the filter size -- capped at half of the
 		// device memory free at that moment, or at TWOPACO_FILTER_CAP_BYTES -- and only then are the hash tables drawn and the
