@@ -67,7 +67,8 @@ enum {
     TPC_K_SUPERBUBBLES = 23, /* tpc_segments_superbubbles_build: the adjacency lists, the bounded search per entrance and the report (no counterpart in the reference) */
     TPC_K_ANCHORS = 24,     /* tpc_segments_anchors_build: the keys, their sort, mates, heads and tails, the blocks and the per-colour sums (no counterpart in the reference) */
     TPC_K_LOCATE = 25,      /* tpc_segments_edges_build / tpc_segments_locate, whichever ran last: the stage on the stream from its first kernel to its last (no counterpart in the reference) */
-    TPC_K_COUNT = 26
+    TPC_K_CLASSES = 26,     /* tpc_segments_classes_build: the set of rows keyed by their presence words, the numbering and the per-class sums (no counterpart in the reference) */
+    TPC_K_COUNT = 27
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -883,6 +884,59 @@ int tpc_segments_locate_fetch_runs(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32
 int tpc_segments_locate_fetch_records(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint64_t *windows, uint64_t *found, uint64_t *forward, uint64_t *runs);
 int tpc_segments_locate_fetch_shared(tpc_ctx *ctx, uint64_t s0, uint64_t n, uint64_t *counts_host /* [n x colours] */);
 
+/* The COLOUR CLASSES of the compacted graph (csrc/tpc_classes.hip): the distinct sets of colours that segments have -- which genomes
+ * share sequence that nobody else has, and how much.  No counterpart in the reference; ComputeClasses of
+ * twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The definition, over the colour table of the
+ * last tpc_segments_colors_build:
+ *   ROW              a row of the colour table, 'N'-named segments included.
+ *   CLASS            the rows whose presence words are all equal.  Its FIRST is its smallest row.
+ *   CLASS ID         classes are numbered from 0, ascending by first: the order in which gfa1 first prints a segment of each.
+ *   PER ROW          class[r].
+ *   PER CLASS p      first[p]; segments[p]; length[p], the sum of the segments' lengths in bases; edges[p], the sum of end - begin of
+ *                    each row's first event, the weight of the distance matrices (length - k per segment); occurrences[p], the sum of
+ *                    the colour rows' occurrences; presence[p], the W words every row of the class holds; n_colors[p], their popcount.
+ *                    The sums are 64-bit.
+ *   PER n THAT OCCURS  the number of classes with n_colors == n, and the sums of their segments and edges (the sets).
+ *   CONSEQUENCES     the segments[p] sum to the rows; the segments of the classes with n_colors == n sum to the colour table's
+ *                    histogram bin n; segments[i][j] and edges[i][j] of the distance matrices are the sums of segments[p] and edges[p]
+ *                    over the classes that hold both colours; no class is empty, because every row has an occurrence.
+ *   EXACT            integers, commutative sums and a smallest row: the result depends neither on the schedule nor on the hash.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this; tpc_segments_counts and the colour, link,
+ * bubble, distance, component and other outputs are what they were, in any order of the builds.
+ *   tpc_segments_classes_build           an open-addressed set of rows with a power-of-two number of slots, at least 2 S: a row hashes
+ *                                        its W words to 64 bits, claims an empty slot with a compare-and-swap or is decided against the
+ *                                        words of the row a slot holds, and steps over the slots of other classes (the words decide,
+ *                                        the hash only finds the home slot).  One thread per row while W <= 8, one wave per row beyond;
+ *                                        while W <= 2 the words are the key and no row is read twice.  The smallest row per slot, one
+ *                                        flag per row that is it, one scan for the ids, then the sums, folded per wave.  Every probe
+ *                                        loop is counted and ends within `slots` steps; a set too small for the classes (only with the
+ *                                        option test_classes_slots_log2) is an error text ("segment classes: gave up ...") from kernels
+ *                                        that end normally.  Also refused with an error text: no segment table, a table whose
+ *                                        tpc_segments_error kind is not TPC_SEG_OK, no colour table, 2^31 segments or more, buffers
+ *                                        beyond the free device memory; the context stays usable.  Kept until the next segment, colour
+ *                                        or class build: 4 B per row, per class 4 B of first, 32 B of sums and 4 W B of presence, and
+ *                                        24 B x (colours + 1) of sets.  During the call 8 B per row of remembered slots and flags and
+ *                                        4 B per slot (12 B while W <= 2).  TPC_K_CLASSES times the stage on the stream from its first
+ *                                        kernel to its last, the host's one wait for the class count included, as TPC_K_COMPONENTS
+ *                                        times the component stage.  Options (tests, each for the next build only; see
+ *                                        tpc_set_option): test_classes_slots_log2, test_classes_hash_bits, test_classes_grid,
+ *                                        test_classes_wide.
+ *   tpc_segments_classes_info            info[0] classes, [1] rows, [2] the segments of the largest class, [3] the probes that met a
+ *                                        slot of another class (depends on the schedule: it shows that the chain path ran), [4] the
+ *                                        stage's device bytes at their peak
+ *   tpc_segments_classes_fetch_members   class[r] of rows [r0, r0 + n) to the host
+ *   tpc_segments_classes_fetch_rows      first / segments / length / edges / occurrences of classes [p0, p0 + n)
+ *   tpc_segments_classes_fetch_presence  the n x W presence words of classes [p0, p0 + n), row-major (n_colors is their popcount)
+ *   tpc_segments_classes_fetch_sets      classes / segments / edges by number of colours, colours + 1 entries each (0 where no class has n)
+ * A range outside a table is refused with an error text. */
+int tpc_segments_classes_build(tpc_ctx *ctx);
+int tpc_segments_classes_info(tpc_ctx *ctx, uint64_t *info /* [5]: classes, rows, segments of the largest class, probes past another class, peak device bytes */);
+int tpc_segments_classes_fetch_members(tpc_ctx *ctx, uint64_t r0, uint64_t n, uint32_t *class_host);
+int tpc_segments_classes_fetch_rows(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *first_host, uint64_t *segments_host, uint64_t *length_host, uint64_t *edges_host,
+                                    uint64_t *occurrences_host);
+int tpc_segments_classes_fetch_presence(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *words_host /* [n x W] */);
+int tpc_segments_classes_fetch_sets(tpc_ctx *ctx, uint64_t *classes_host, uint64_t *segments_host, uint64_t *edges_host /* [n_colors + 1] each */);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -943,6 +997,15 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      (csrc/tpc_pass1_anyq.hip) for every q, so that they can be checked on the goldens with q <= 16
  *   test_links_slots_log2  tests only: the next tpc_segments_links_build takes 2^n slots for its link set instead of sizing it by
  *                      the occurrences (0 = by the occurrences), so that long probe chains and a full set can be reached
+ *   test_classes_slots_log2  tests only, the next tpc_segments_classes_build alone: 2^n slots (n = 1 .. 31) for its set of rows instead
+ *                      of sizing it by the rows (0 = by the rows), so that long chains, a set that is exactly full and a set that is
+ *                      too small ("segment classes: gave up ...", an error return from kernels that end normally) can be reached
+ *   test_classes_hash_bits   tests only, the next tpc_segments_classes_build alone: only the low n bits of a row's hash are used,
+ *                      n = 0 .. 64 (negative = all 64, the default), so that different keys share a home slot
+ *   test_classes_grid  tests only, the next tpc_segments_classes_build alone: at most n workgroups per kernel of the stage (0 = by
+ *                      the rows), so that a table of a few thousand rows makes every workgroup stride several times
+ *   test_classes_wide  tests only, the next tpc_segments_classes_build alone: 1 forces the wave-per-row form at any W, 2 the
+ *                      thread-per-row form (0 = by W)
  *   test_distances_chunk_words  tests only: the next tpc_segments_distances_build stages n column words (64 rows each) per chunk
  *                      instead of its own 64 (0 = its own; more than 64 is refused), so that a table of a few hundred rows crosses
  *                      chunk borders and ends in a partial chunk

@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25}
+           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25, "classes": 26}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -43,7 +43,9 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_anchors_build", "tpc_segments_anchors_info", "tpc_segments_anchors_fetch_mates", "tpc_segments_anchors_fetch_rows",
                "tpc_segments_anchors_fetch_shared",
                "tpc_segments_edges_build", "tpc_segments_edges_info", "tpc_segments_locate", "tpc_segments_locate_info", "tpc_segments_locate_fetch_hits",
-               "tpc_segments_locate_fetch_runs", "tpc_segments_locate_fetch_records", "tpc_segments_locate_fetch_shared"]
+               "tpc_segments_locate_fetch_runs", "tpc_segments_locate_fetch_records", "tpc_segments_locate_fetch_shared",
+               "tpc_segments_classes_build", "tpc_segments_classes_info", "tpc_segments_classes_fetch_members", "tpc_segments_classes_fetch_rows",
+               "tpc_segments_classes_fetch_presence", "tpc_segments_classes_fetch_sets"]
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -213,6 +215,12 @@ def hip():
         L.tpc_segments_locate_fetch_runs.argtypes = [p, u64, u64, p, p, p, p, p]
         L.tpc_segments_locate_fetch_records.argtypes = [p, u64, u64, p, p, p, p]
         L.tpc_segments_locate_fetch_shared.argtypes = [p, u64, u64, p]
+        L.tpc_segments_classes_build.argtypes = [p]
+        L.tpc_segments_classes_info.argtypes = [p, p]
+        L.tpc_segments_classes_fetch_members.argtypes = [p, u64, u64, p]
+        L.tpc_segments_classes_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p]
+        L.tpc_segments_classes_fetch_presence.argtypes = [p, u64, u64, p]
+        L.tpc_segments_classes_fetch_sets.argtypes = [p, p, p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -424,7 +432,10 @@ class Context:
 
     def set_option(self, name, value):
         """tpc_set_option: the tuning knobs and the tests-only options of include/twopaco_hip.h, among them test_links_slots_log2,
-        test_distances_chunk_words and test_components_step_limit (the step bound of the next segments_components_build, 0 = its own)."""
+        test_distances_chunk_words, test_components_step_limit (the step bound of the next segments_components_build, 0 = its own) and, each
+        for the next segments_classes_build alone, test_classes_slots_log2 (2^n slots, 0 = by the rows), test_classes_hash_bits (the low n
+        bits of the hash, 0 .. 64, negative = all), test_classes_grid (workgroups per kernel, 0 = by the rows) and test_classes_wide (1 = a
+        wave per row, 2 = a thread per row, 0 = by the words)."""
         self._ck(hip().tpc_set_option(self._h, name.encode(), int(value)))
 
     def stat(self, name):
@@ -840,6 +851,47 @@ class Context:
         out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
         self._ck(hip().tpc_segments_components_fetch_presence(self._h, p0, n, out.ctypes.data))
         return out
+
+    def segments_classes_build(self):
+        """The colour classes (csrc/tpc_classes.hip) over the colour table of the last segments_colors_build.  Returns
+        segments_classes_info()."""
+        self._ck(hip().tpc_segments_classes_build(self._h))
+        return self.segments_classes_info()
+
+    def segments_classes_info(self):
+        """dict: classes, rows, largest (segments of the largest class), collisions (probes that met a slot of another class; depends on
+        the schedule), peak_bytes (device memory of the stage)."""
+        c = np.zeros(5, dtype=np.uint64)
+        self._ck(hip().tpc_segments_classes_info(self._h, c.ctypes.data))
+        return dict(zip(("classes", "rows", "largest", "collisions", "peak_bytes"), (int(x) for x in c)))
+
+    def segments_classes_fetch_members(self, r0=0, n=None):
+        """class[r] of rows [r0, r0 + n) as uint32; n = None: to the last row."""
+        n = self.segments_classes_info()["rows"] - r0 if n is None else n
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        self._ck(hip().tpc_segments_classes_fetch_members(self._h, r0, n, out.ctypes.data))
+        return out
+
+    def segments_classes_fetch_rows(self, p0=0, n=None):
+        """(first as uint32; segments, length, edges, occurrences as uint64) of classes [p0, p0 + n); n = None: to the last."""
+        n = self.segments_classes_info()["classes"] - p0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32)] + [np.zeros(max(n, 0), dtype=np.uint64) for _ in range(4)]
+        self._ck(hip().tpc_segments_classes_fetch_rows(self._h, p0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_classes_fetch_presence(self, p0=0, n=None):
+        """uint32 [n, W] presence words of classes [p0, p0 + n), W as of the colour table; n = None: to the last."""
+        n = self.segments_classes_info()["classes"] - p0 if n is None else n
+        out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
+        self._ck(hip().tpc_segments_classes_fetch_presence(self._h, p0, n, out.ctypes.data))
+        return out
+
+    def segments_classes_fetch_sets(self):
+        """(classes, segments, edges) as uint64 [colours + 1] each: by number of colours, 0 where no class has that many."""
+        n = self.segments_colors_info()["colors"] + 1
+        out = [np.zeros(n, dtype=np.uint64) for _ in range(3)]
+        self._ck(hip().tpc_segments_classes_fetch_sets(self._h, *[a.ctypes.data for a in out]))
+        return tuple(out)
 
     def segments_superbubbles_build(self, max_inside=62):
         """The bounded superbubbles (csrc/tpc_superbubbles.hip) over the link table of the last segments_links_build and the colour table

@@ -395,6 +395,11 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "test_locate_grid")) { c->opt_locate_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }  // tests only: workgroups of the edge index's tile kernels
     if (!strcmp(name, "test_distances_chunk_words")) { c->opt_distances_chunk_words = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 20)); return 0; }  // tests only: chunk length of the next tpc_segments_distances_build
     if (!strcmp(name, "test_components_step_limit")) { c->opt_components_step_limit = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 0x7FFFFFFF)); return 0; }  // tests only: step bound of the next tpc_segments_components_build
+    // tests only, each for the next tpc_segments_classes_build alone: slots of the set, kept hash bits (negative: all), workgroups, the row form
+    if (!strcmp(name, "test_classes_slots_log2")) { c->opt_classes_slots_log2 = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 64)); return 0; }
+    if (!strcmp(name, "test_classes_hash_bits")) { c->opt_classes_hash_bits = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 65)); return 0; }
+    if (!strcmp(name, "test_classes_grid")) { c->opt_classes_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }
+    if (!strcmp(name, "test_classes_wide")) { c->opt_classes_wide = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 3)); return 0; }
     if (!strcmp(name, "test_fail_mallocs")) { tpc_test_fail_mallocs.store(value > 0 ? (int)value : 0); return 0; }  // process-wide, tests only
     return fail(c, -1, "unknown option %s", name);
 }

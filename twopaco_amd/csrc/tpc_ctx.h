@@ -13,6 +13,7 @@
 //   tpc_anchors.hip       the anchor blocks against a reference colour (tpc_segments_anchors_*), kernels and entry points
 //   tpc_locate.hip        the edge index and the location of a query text in it (tpc_segments_edges_*, tpc_segments_locate_*), kernels and entry points
 //   tpc_edgehash.h        the two-strand rolling hash of an edge, shared by tpc_sketch.hip and tpc_locate.hip
+//   tpc_classes.hip       the colour classes over the colour table (tpc_segments_classes_*), kernels and entry points
 //   tpc_stage.h           what the eight stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
 //   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
@@ -211,6 +212,22 @@ struct tpc_ctx {
         uint32_t n_colors = 0;
         bool valid = false;
     } loc;
+    // colour classes (tpc_segments_classes_*, tpc_classes.hip) of the last tpc_segments_classes_build
+    struct Classes {
+        uint32_t *class_of = nullptr;        // device, [n_rows]: the class id of every row
+        uint32_t *first = nullptr;           // device, [n_classes]: the smallest row of every class
+        unsigned long long *sums = nullptr;  // device, [4][n_classes]: segments, length, edges, occurrences
+        uint32_t *presence = nullptr;        // device, [n_classes][words]
+        unsigned long long *sets = nullptr;  // device, [3][n_colors + 1]: classes, segments, edges by number of colours
+        uint64_t n_classes = 0, n_rows = 0, largest = 0, met = 0, peak_bytes = 0;
+        uint32_t words = 0, n_colors = 0;
+        bool valid = false;
+    } cls;
+    // options test_classes_* (tests only), each for the next tpc_segments_classes_build alone
+    int opt_classes_slots_log2 = 0;          // slots of the class set, 0 = by the rows
+    int opt_classes_hash_bits = -1;          // low bits of the row's hash that are kept, -1 = all 64
+    int opt_classes_grid = 0;                // at most this many workgroups per kernel, 0 = by the rows
+    int opt_classes_wide = 0;                // 1 = a wave per row, 2 = a thread per row, 0 = by the words
     int opt_edges_slots_log2 = 0;            // option test_edges_slots_log2 (tests only): slots of the edge index, 0 = by the edges
     int opt_edges_hash_bits = 0;             // option test_edges_hash_bits (tests only): bits of the edge's hash that are kept, 0 = all 64
     int opt_locate_grid = 0;                 // option test_locate_grid (tests only): at most this many workgroups of the tile kernels, 0 = by the CUs
@@ -331,7 +348,7 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these nine and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these ten and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
@@ -340,6 +357,7 @@ void superbubbles_drop(tpc_ctx *c);
 void anchors_drop(tpc_ctx *c);
 void edges_drop(tpc_ctx *c);
 void locate_drop(tpc_ctx *c);
+void classes_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

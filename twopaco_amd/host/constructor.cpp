@@ -47,7 +47,11 @@
 // --locate file|sequence --locate-in Q.fa [--locate-in ...] [--locate-out F] [--locate-walks F]: the records of the query files looked
 // up in the graph window by window -- found, where, on which strand, in which colours -- as TSV, byte for byte what `graphdump
 // --locate` writes, and asked for, the runs as a walks file (csrc/tpc_locate.hip builds the edge index and looks the queries up on
-// the device; combines with everything above; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// the device; combines with everything above; the other tables must name the same colours; its files are written after the anchor files);
+// --classes file|sequence [--classes-out F] [--classes-members F]: the colour classes of the same graph -- the distinct sets of colours
+// and the segments that have each -- as TSV of integers, byte for byte what `graphdump --classes` writes, and asked for, the class of
+// every segment (csrc/tpc_classes.hip groups the colour rows on the device; combines with everything above from one segment and colour
+// build; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -106,6 +110,7 @@ namespace
 			<< "               [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>]" << std::endl
 			<< "               [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>]" << std::endl
 			<< "               [--locate <file|sequence> --locate-in <file name> ... [--locate-out <file name>] [--locate-walks <file name>]]" << std::endl
+			<< "               [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -157,7 +162,12 @@ namespace
 			<< "       --locate: also look every (k+1)-mer of the records of the --locate-in FASTA files up in the graph and write per record its valid" << std::endl
 			<< "               windows, those found, those found forward, the runs they form and per colour (by file or by sequence, as --colors) the" << std::endl
 			<< "               hits in segments of that colour as TSV to --locate-out (default de_bruijn.locate.tsv).  --locate-walks: also the runs," << std::endl
-			<< "               one line each: the query's interval and the segment's.  Combines with all tables above (the same colours).  One GPU only." << std::endl;
+			<< "               one line each: the query's interval and the segment's.  Combines with all tables above (the same colours).  One GPU only." << std::endl
+			<< "       --classes: also write the colour classes of the graph as TSV to --classes-out (default de_bruijn.classes.tsv): the distinct sets" << std::endl
+			<< "               of colours (by file or by sequence, as --colors) that segments have, numbered in the order gfa1 first prints a segment of" << std::endl
+			<< "               each.  Per class the name of its first segment, its segments, bases, edges, occurrences, number of colours and presence" << std::endl
+			<< "               bits; in front the classes, segments and edges by number of colours.  --classes-members: also the class of every segment," << std::endl
+			<< "               one line per segment.  Combines with all tables above (the same colours); written last.  One GPU only." << std::endl;
 	}
 }
 
@@ -310,8 +320,8 @@ int main(int argc, char * argv[])
 
 		// every table beside every other, each into a file of its own, on one GPU; the complaints are looked for in the tables' order
 		namespace GF = TwoPaCo::GraphFormat;
-		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE}, false, false, false, false,
-			{0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
+		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE, GF::CLASSES}, false, false, false, false,
+			{0, 0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
 		GF::CheckTableOptions(tables, rules);
 		options.tables = tables.request;
 		optionsSet = optionsSet || options.tables.Any();

@@ -33,7 +33,8 @@
 	X(segments_superbubbles_fetch_presence) \
 	X(segments_anchors_build) X(segments_anchors_info) X(segments_anchors_fetch_mates) X(segments_anchors_fetch_rows) X(segments_anchors_fetch_shared) \
 	X(segments_edges_build) X(segments_edges_info) X(segments_locate) X(segments_locate_info) X(segments_locate_fetch_runs) X(segments_locate_fetch_records) \
-	X(segments_locate_fetch_shared)
+	X(segments_locate_fetch_shared) \
+	X(segments_classes_build) X(segments_classes_info) X(segments_classes_fetch_members) X(segments_classes_fetch_rows) X(segments_classes_fetch_presence)
 
 namespace TwoPaCo
 {
@@ -225,6 +226,34 @@ namespace TwoPaCo
 			return true;
 		}
 
+		// The colour classes (csrc/tpc_classes.hip), grouped over the presence words of the colour build where they lie.
+		inline void BuildClasses(const Api & api)
+		{
+			api.check(api.segments_classes_build(api.ctx), "segments_classes_build");
+		}
+
+		// ... fetched: the members, the rows and their presence words (the per-n sets are the writer's to sum).  false, and nothing
+		// fetched, when the stage saw other segments than the caller
+		inline bool FetchClasses(const Api & api, uint64_t rows, size_t words, GraphFormat::ClassTable & out)
+		{
+			uint64_t info[5] = {0, 0, 0, 0, 0};
+			api.check(api.segments_classes_info(api.ctx, info), "segments_classes_info");
+			if (info[1] != rows) return false;
+			const size_t n = size_t(info[0]);
+			out.classOf.resize(rows);
+			out.first.resize(n);
+			out.segments.resize(n);
+			out.length.resize(n);
+			out.edges.resize(n);
+			out.occurrences.resize(n);
+			out.presence.resize(n * words);
+			api.check(api.segments_classes_fetch_members(api.ctx, 0, rows, out.classOf.data()), "segments_classes_fetch_members");
+			api.check(api.segments_classes_fetch_rows(api.ctx, 0, n, out.first.data(), out.segments.data(), out.length.data(), out.edges.data(), out.occurrences.data()),
+				"segments_classes_fetch_rows");
+			api.check(api.segments_classes_fetch_presence(api.ctx, 0, n, out.presence.data()), "segments_classes_fetch_presence");
+			return true;
+		}
+
 		// The bounded superbubbles (csrc/tpc_superbubbles.hip), searched over the link rows' arcs, presence ORed over the colour rows.
 		inline void BuildSuperbubbles(const Api & api, uint32_t maxInside)
 		{
@@ -389,9 +418,9 @@ namespace TwoPaCo
 		// and the bubble stage it would find 12 B per link, 4 B per 32 events and, with --bubbles, 24 B per segment and 16 B per bubble
 		// more resident, which a run that just fits the device does not have.
 		const int STAGES_LINKS_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::DISTANCES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES};
 		const int STAGES_DISTANCES_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::DISTANCES, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES};
 
 		// The caller's clock and [timing] lines.  built: after a stage's build, with the stage and its TPC_K_* (EDGES, then LOCATE
 		// once its batches are through: their kernel time is locateKernelMs, not the last batch's); fetched: after a stage's fetch.
@@ -466,6 +495,11 @@ namespace TwoPaCo
 					BuildAnchors(api, t.map, request.anchorsRef);
 					observer.built(stage, TPC_K_ANCHORS);
 					agree(FetchAnchors(api, t.map, events, t.segments, t.anchors), "anchor", "colour map", "colours");
+					break;
+				case CLASSES:
+					BuildClasses(api);
+					observer.built(stage, TPC_K_CLASSES);
+					agree(FetchClasses(api, t.segments, t.colors.Words(), t.classes), "class", "segment table", "segments");
 					break;
 				case LOCATE:
 					uint64_t edges[6] = {0, 0, 0, 0, 0, 0};

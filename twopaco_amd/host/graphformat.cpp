@@ -5,6 +5,7 @@
 #include <cerrno>
 #include <condition_variable>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -1060,6 +1061,151 @@ namespace TwoPaCo
 			try
 			{
 				WriteComponents(t, k, map, colors, links, c, path);
+			}
+			catch (...)
+			{
+				if (!membersPath.empty()) ::unlink(membersPath.c_str());
+				throw;
+			}
+		}
+
+		void ComputeClasses(const EventTable & t, size_t k, const ColorTable & colors, ClassTable & out)
+		{
+			const size_t rows = colors.Rows(), words = colors.Words();
+			if (colors.occurrences.size() != rows || colors.presence.size() != rows * words) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			out = ClassTable();
+			out.classOf.resize(rows);
+			std::map<std::vector<uint32_t>, uint32_t> classOfKey;
+			for (size_t r = 0; r < rows; r++)
+			{
+				const uint32_t e0 = colors.firstEvent[r];
+				if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				const std::vector<uint32_t> key(colors.presence.begin() + r * words, colors.presence.begin() + (r + 1) * words);
+				// rows come in ascending order: a key's first row opens its class, so the ids ascend by first
+				const std::pair<std::map<std::vector<uint32_t>, uint32_t>::iterator, bool> at = classOfKey.insert(std::make_pair(key, uint32_t(out.first.size())));
+				if (at.second)
+				{
+					out.first.push_back(uint32_t(r));
+					out.segments.push_back(0);
+					out.length.push_back(0);
+					out.edges.push_back(0);
+					out.occurrences.push_back(0);
+					out.presence.insert(out.presence.end(), key.begin(), key.end());
+				}
+
+				const uint32_t p = at.first->second;
+				const uint64_t weight = uint64_t(t.end[e0]) - t.begin[e0];
+				out.classOf[r] = p;
+				out.segments[p] += 1;
+				out.length[p] += weight + k;
+				out.edges[p] += weight;
+				out.occurrences[p] += colors.occurrences[r];
+			}
+		}
+
+		namespace
+		{
+			void CheckClasses(const EventTable & t, const ColorTable & colors, const ClassTable & c)
+			{
+				const size_t rows = colors.Rows(), words = colors.Words(), n = c.Rows();
+				if (c.classOf.size() != rows || c.segments.size() != n || c.length.size() != n || c.edges.size() != n || c.occurrences.size() != n || c.presence.size() != n * words)
+				{
+					throw std::runtime_error("class table: the arrays do not agree about the rows, the classes and the colours");
+				}
+
+				for (uint32_t e0 : colors.firstEvent)
+				{
+					if (e0 >= t.events) throw std::runtime_error("colour table: a row's first event lies outside the event table");
+				}
+
+				for (uint32_t p : c.classOf)
+				{
+					if (p >= n) throw std::runtime_error("class table: a row lies in no class");
+				}
+
+				for (uint32_t r : c.first)
+				{
+					if (r >= rows) throw std::runtime_error("class table: a first row lies outside the segments");
+				}
+			}
+		}
+
+		void WriteClasses(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, const ClassTable & c, const std::string & path)
+		{
+			CheckClasses(t, colors, c);
+			if (map.label.size() != colors.colors) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			const size_t words = colors.Words(), n = c.Rows(), digits = size_t((colors.colors + 3) / 4);
+			// classes, segments and edges by number of colours: computed here from the rows, whichever source they have
+			std::vector<uint32_t> held(n, 0);
+			std::vector<uint64_t> setClasses(colors.colors + 1, 0), setSegments(colors.colors + 1, 0), setEdges(colors.colors + 1, 0);
+			for (size_t p = 0; p < n; p++)
+			{
+				if (c.segments[p] == 0) throw std::runtime_error("class table: a class holds no segment");
+				for (size_t w = 0; w < words; w++) held[p] += uint32_t(__builtin_popcount(c.presence[p * words + w]));
+				if (held[p] > colors.colors) throw std::runtime_error("class table: a class holds more colours than there are");
+				setClasses[held[p]] += 1;
+				setSegments[held[p]] += c.segments[p];
+				setEdges[held[p]] += c.edges[p];
+			}
+
+			WriteStreamed(path, "class table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-classes\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(colors.colors) +
+					"\tsegments=" + std::to_string(colors.Rows()) + "\tclasses=" + std::to_string(n) + "\n";
+				for (uint64_t col = 0; col < colors.colors; col++) buf += "#color\t" + std::to_string(col) + "\t" + map.label[col] + "\n";
+				for (uint64_t held_n = 0; held_n <= colors.colors; held_n++)
+				{
+					if (setClasses[held_n])
+					{
+						buf += "#sets\t" + std::to_string(held_n) + "\t" + std::to_string(setClasses[held_n]) + "\t" + std::to_string(setSegments[held_n]) + "\t" + std::to_string(setEdges[held_n]) + "\n";
+					}
+				}
+
+				for (size_t p = 0; p < n; p++)
+				{
+					buf += std::to_string(p);
+					buf += '\t';
+					buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[c.first[p]]])));
+					for (uint64_t value : {c.segments[p], c.length[p], c.edges[p], c.occurrences[p], uint64_t(held[p])})
+					{
+						buf += '\t';
+						buf += std::to_string(value);
+					}
+
+					const uint32_t * bits = &c.presence[p * words];
+					buf += '\t';
+					for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(bits[j >> 3] >> (4 * (j & 7))) & 15u];
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteClassMembers(const EventTable & t, size_t k, const ColorTable & colors, const ClassTable & c, const std::string & path)
+		{
+			CheckClasses(t, colors, c);
+			if (path.empty()) throw std::runtime_error("The class members need a file name");
+			WriteStreamed(path, "class members", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-class-members\t1\tk=" + std::to_string(k) + "\tsegments=" + std::to_string(colors.Rows()) + "\tclasses=" + std::to_string(c.Rows()) + "\n";
+				for (size_t r = 0; r < colors.Rows(); r++)
+				{
+					buf += std::to_string(static_cast<long long>(Magnitude(t.name[colors.firstEvent[r]])));
+					buf += '\t';
+					buf += std::to_string(c.classOf[r]);
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteClassFiles(const EventTable & t, size_t k, const ColorMap & map, const ColorTable & colors, const ClassTable & c, const std::string & path,
+			const std::string & membersPath)
+		{
+			if (!membersPath.empty()) WriteClassMembers(t, k, colors, c, membersPath);
+			try
+			{
+				WriteClasses(t, k, map, colors, c, path);
 			}
 			catch (...)
 			{

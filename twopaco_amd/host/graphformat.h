@@ -505,6 +505,46 @@ namespace TwoPaCo
 		void WriteComponentFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const ComponentTable & components,
 			const std::string & path, const std::string & membersPath);
 
+		// ---------------------------------------------------------------------------------------- the colour classes
+		// Which segments share their set of genomes (include/twopaco_hip.h, the tpc_segments_classes_* group, states the definition
+		// in the same words).  ROW: a row of the colour table, 'N'-named segments included.  CLASS: the rows whose presence words are
+		// all equal; its FIRST is its smallest row.  CLASS ID: classes are numbered from 0, ascending by first, the order in which
+		// gfa1 first prints a segment of each.  Per class: first, segments, length (the sum of the segments' lengths in bases), edges
+		// (the sum of end - begin of each row's first event, the weight of the distance matrices), occurrences (the sum of the colour
+		// rows' occurrences), presence (the words every row of the class holds) and n_colors, its popcount.  The sums are 64-bit.
+		// The segments of all classes sum to the rows, those of the classes of n colours to the colour table's "#hist n", and the
+		// distance matrices are the sums of segments and edges over the classes that hold both colours.  The arrays come from
+		// ComputeClasses below -- the serial statement -- or from the device (csrc/tpc_classes.hip); WriteClasses and
+		// WriteClassMembers print either as the same bytes.
+		struct ClassTable
+		{
+			std::vector<uint32_t> classOf;                                     // [rows]
+			std::vector<uint32_t> first;                                       // [classes]
+			std::vector<uint64_t> segments, length, edges, occurrences;        // [classes]
+			std::vector<uint32_t> presence;                                    // [classes][colors.Words()]
+			size_t Rows() const { return first.size(); }
+			uint64_t Largest() const { return segments.empty() ? 0 : *std::max_element(segments.begin(), segments.end()); }
+		};
+
+		// The definition stated with std:: containers: an ordered map from the presence words of a row to its class, filled in row
+		// order, so that the ids ascend by first; then the sums.  `colors` is the colour table of `table`.
+		void ComputeClasses(const EventTable & table, size_t k, const ColorTable & colors, ClassTable & out);
+
+		// The TSV text: "#twopaco-classes\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tclasses=<P>", the colour table's
+		// "#color" lines, "#sets\t<n>\t<classes>\t<segments>\t<edges>" for every number of colours n that a class has, ascending, then
+		// one line per class: id, the name of the first segment, segments, length, edges, occurrences, n_colors and presence as hex (as
+		// the colour table prints it).  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteClasses(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const ClassTable & classes, const std::string & path);
+
+		// The members: "#twopaco-class-members\t1\tk=<k>\tsegments=<S>\tclasses=<P>", then "<name>\t<id>" per row in row order, into
+		// the file `path`.
+		void WriteClassMembers(const EventTable & table, size_t k, const ColorTable & colors, const ClassTable & classes, const std::string & path);
+
+		// Both files of the class table, or neither: the members first when membersPath is given, then the TSV (to stdout when path
+		// is empty); when the TSV cannot be written the members file is removed again before the error is thrown.
+		void WriteClassFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const ClassTable & classes, const std::string & path,
+			const std::string & membersPath);
+
 		// ---------------------------------------------------------------------------------------- the superbubbles
 		// Where the genomes differ, beyond two alleles (include/twopaco_hip.h, the tpc_segments_superbubbles_* group, states the
 		// definition in the same words; Onodera, Sadakane and Shibuya 2013).  Rows, sides (code = row * 2 + minus, rev(code) = code ^ 1),

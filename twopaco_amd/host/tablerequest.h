@@ -20,7 +20,7 @@ namespace TwoPaCo
 	namespace GraphFormat
 	{
 		// in the order the tables are written
-		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, TABLES };
+		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, CLASSES, TABLES };
 
 		enum Reads { NOTHING, BUILD, ROWS };  // of a device stage: not read, built and read where it lies, its rows fetched for the files
 
@@ -47,6 +47,7 @@ namespace TwoPaCo
 			{"superbubbles", "superbubble", true, "members", "The superbubble members", true, "--superbubbles-max", ROWS, BUILD, true, false},
 			{"anchors", "anchor", true, "paf", "The anchor PAF", false, "--anchors-ref", NOTHING, NOTHING, true, false},
 			{"locate", "locate", true, "walks", "The locate walks", true, "--locate-in", ROWS, NOTHING, true, true},
+			{"classes", "class", true, "members", "The class members", true, 0, ROWS, NOTHING, true, false},
 		};
 
 		struct TableRequest
@@ -272,6 +273,7 @@ namespace TwoPaCo
 			SuperbubbleTable superbubbles;
 			AnchorTable anchors;
 			LocateTable locate;
+			ClassTable classes;
 			InputSequences queries;         // of request.locateIn
 			LoadedSequences queryLetters;
 			uint64_t segments, linkRows;    // the rows of the colour table and of the link table, fetched or not
@@ -303,6 +305,8 @@ namespace TwoPaCo
 				BuildEdgeIndex(table, loaded, k, index);
 				ComputeLocate(index, t.colors, t.queryLetters, t.locate);
 			}
+
+			if (request.On(CLASSES)) ComputeClasses(table, k, t.colors, t.classes);
 		}
 
 		// One table's files, if it is wanted
@@ -320,6 +324,7 @@ namespace TwoPaCo
 			case SUPERBUBBLES: WriteSuperbubbleFiles(table, k, t.map, t.colors, t.linkRows, t.superbubbles, f.out, f.second); break;
 			case ANCHORS: WriteAnchorFiles(table, k, t.map, seq, t.anchors, f.out, f.second); break;
 			case LOCATE: WriteLocateFiles(table, k, t.map, t.colors, t.queries, t.locate, f.out, f.second); break;
+			case CLASSES: WriteClassFiles(table, k, t.map, t.colors, t.classes, f.out, f.second); break;
 			}
 		}
 

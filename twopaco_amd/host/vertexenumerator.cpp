@@ -1078,7 +1078,7 @@ namespace TwoPaCo
 					makeColorMap();
 					// twopaco's clock around the stages: a lap after every build and every fetch, the kernels' time after the build's
 					static const char * const lap[TABLES + 1] = {"segment colours", "segment links", "segment bubbles", "segment distances", "segment components",
-						"segment superbubbles", "segment anchors", "locate", "edge index"};
+						"segment superbubbles", "segment anchors", "locate", "segment classes", "edge index"};
 					DeviceGraph::StageObserver observer;
 					observer.built = [&](int stage, int kernel)
 					{
