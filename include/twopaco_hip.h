@@ -68,7 +68,8 @@ enum {
     TPC_K_ANCHORS = 24,     /* tpc_segments_anchors_build: the keys, their sort, mates, heads and tails, the blocks and the per-colour sums (no counterpart in the reference) */
     TPC_K_LOCATE = 25,      /* tpc_segments_edges_build / tpc_segments_locate, whichever ran last: the stage on the stream from its first kernel to its last (no counterpart in the reference) */
     TPC_K_CLASSES = 26,     /* tpc_segments_classes_build: the set of rows keyed by their presence words, the numbering and the per-class sums (no counterpart in the reference) */
-    TPC_K_COUNT = 27
+    TPC_K_TRACKS = 27,      /* tpc_segments_tracks_build: the row of every event, the heads, their scan, the intervals and the sums (no counterpart in the reference) */
+    TPC_K_COUNT = 28
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -937,6 +938,62 @@ int tpc_segments_classes_fetch_rows(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint3
 int tpc_segments_classes_fetch_presence(tpc_ctx *ctx, uint64_t p0, uint64_t n, uint32_t *words_host /* [n x W] */);
 int tpc_segments_classes_fetch_sets(tpc_ctx *ctx, uint64_t *classes_host, uint64_t *segments_host, uint64_t *edges_host /* [n_colors + 1] each */);
 
+/* The PRESENCE TRACKS of the input sequences (csrc/tpc_tracks.hip): for every stretch of every sequence, which colours share it -- the
+ * colour rows projected onto the sequences' coordinates, neighbouring occurrences of equal presence merged into one interval.  No
+ * counterpart in the reference; ComputeTracks of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested
+ * against.  The definition, over the event table of the last tpc_segments_build_* and the colour table of the last
+ * tpc_segments_colors_build:
+ *   EVENT, ROW, COLOUR, PRESENCE, N_COLORS  those of the colour table.  row(e) is the row of event e, seq(e) its sequence,
+ *                    colour(e) = color_of_seq[seq(e)].
+ *   SELECTED         with only == 0xFFFFFFFF every event is selected; otherwise the events with colour(e) == only.
+ *   CONTINUES        a selected event e continues e - 1 when seq(e) == seq(e - 1) and the W presence words of row(e) and row(e - 1)
+ *                    are all equal.  The words decide: equal n_colors is not enough, equal rows is a shortcut.
+ *   SHARED JUNCTIONS consecutive events of one sequence share their junction: end[e - 1] == begin[e].
+ *   INTERVAL         a maximal run first .. last of selected events in which each continues the one before it.  It stands for the
+ *                    (k+1)-mers that start at positions [begin[first], end[last]) of its sequence, in bases
+ *                    [begin[first], end[last] + k).  events = last - first + 1, edges = end[last] - begin[first]; its presence and
+ *                    n_colors are those of row(first).  Intervals are reported ascending by first.
+ *   TILING           the intervals of one sequence tile [begin[its first event], end[its last event]) with no gap and no overlap.  Two
+ *                    sequences never share an interval, even with the same colour and the same presence at the border.  A sequence
+ *                    without events has no interval.  'N'-named segments are rows of their own, as everywhere else.
+ *   PER COLOUR c     64-bit sums over the intervals whose sequence has colour c: intervals[c]; edges[c]; core_edges[c], the edges of
+ *                    the intervals with n_colors == C; private_edges[c], those with n_colors == 1.  With only == c the other colours'
+ *                    entries are 0.  With one colour in all, core and private coincide.
+ *   PER DEPTH n      0 .. C: depth_intervals[n] and depth_edges[n] over all reported intervals.
+ *   CONSEQUENCES     edges[c] equals the sum of end - begin over the events of colour c: ref_edges of the anchor table with ref = c.
+ *                    The per-depth edges sum to the per-colour edges.  With only == c the rows are exactly the rows of the
+ *                    all-colours table whose sequence has colour c, in the same order.
+ *   EXACT            integers and commutative sums: nothing depends on the schedule.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this; tpc_segments_counts and every other stage's
+ * arrays are what they were, in any order of the builds.
+ *   tpc_segments_tracks_build        the row of every event (as the colour stage finds it), then per event its sequence, its colour,
+ *                                    whether it is selected and whether it is a head (does not continue): one thread per event while
+ *                                    W <= 8, one wave per event beyond; one exclusive scan over the heads numbers the intervals (its
+ *                                    total is the host's one wait); a head writes first_event and row, a tail last_event; the sums by
+ *                                    one thread per interval, neighbouring lanes of one colour folded into one vector atomic per
+ *                                    sum by the run's leader and those of one n_colors likewise, the bins in LDS while there are at
+ *                                    most 512 colours.  color_of_seq [n_rec] and n_colors: THAT THIS IS THE MAP THE
+ *                                    COLOUR TABLE WAS BUILT WITH IS THE CALLER'S PROMISE; only the colour count can be checked.
+ *                                    Refused with an error text that begins "segment tracks:", the context staying usable: no segment
+ *                                    table, a table whose tpc_segments_error kind is not TPC_SEG_OK, no colour table or one of another
+ *                                    colour count, a colour >= n_colors, only_color >= n_colors and not 0xFFFFFFFF, buffers beyond the
+ *                                    free device memory.  Kept until the next segment, colour or track build: 12 B per interval and
+ *                                    48 B per colour (+ 16 B); during the call 12 B per event, 4 B per name of the first-sight table,
+ *                                    4 B per sequence and the scan's scratch.  TPC_K_TRACKS times the stage on the stream from its
+ *                                    first kernel to its last, the wait for the interval count included.  Option (tests, the next
+ *                                    build only; see tpc_set_option): test_tracks_grid.
+ *   tpc_segments_tracks_info         info[0] intervals, [1] selected events, [2] colours, [3] only (0xFFFFFFFF: all), [4] the stage's
+ *                                    device bytes at their peak
+ *   tpc_segments_tracks_fetch_rows   first_event / last_event / row of intervals [i0, i0 + n)
+ *   tpc_segments_tracks_fetch_colors intervals / edges / core_edges / private_edges per colour, n_colors entries each
+ *   tpc_segments_tracks_fetch_depth  intervals / edges per number of colours, n_colors + 1 entries each (0 where no interval has n)
+ * A range outside the table is refused with an error text. */
+int tpc_segments_tracks_build(tpc_ctx *ctx, const uint32_t *color_of_seq /* [n_rec] */, uint32_t n_colors, uint32_t only_color /* 0xFFFFFFFF: all */);
+int tpc_segments_tracks_info(tpc_ctx *ctx, uint64_t *info /* [5]: intervals, selected events, colours, only, peak device bytes */);
+int tpc_segments_tracks_fetch_rows(tpc_ctx *ctx, uint64_t i0, uint64_t n, uint32_t *first_event, uint32_t *last_event, uint32_t *row);
+int tpc_segments_tracks_fetch_colors(tpc_ctx *ctx, uint64_t *intervals, uint64_t *edges, uint64_t *core_edges, uint64_t *private_edges /* [n_colors] each */);
+int tpc_segments_tracks_fetch_depth(tpc_ctx *ctx, uint64_t *intervals, uint64_t *edges /* [n_colors + 1] each */);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -1006,6 +1063,8 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *                      the rows), so that a table of a few thousand rows makes every workgroup stride several times
  *   test_classes_wide  tests only, the next tpc_segments_classes_build alone: 1 forces the wave-per-row form at any W, 2 the
  *                      thread-per-row form (0 = by W)
+ *   test_tracks_grid   tests only, the next tpc_segments_tracks_build alone: at most n workgroups per kernel of the stage (0 = by the
+ *                      events), so that a table of a few thousand events makes every workgroup stride several times
  *   test_distances_chunk_words  tests only: the next tpc_segments_distances_build stages n column words (64 rows each) per chunk
  *                      instead of its own 64 (0 = its own; more than 64 is refused), so that a table of a few hundred rows crosses
  *                      chunk borders and ends in a partial chunk

@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25, "classes": 26}
+           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25, "classes": 26, "tracks": 27}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -45,7 +45,10 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_edges_build", "tpc_segments_edges_info", "tpc_segments_locate", "tpc_segments_locate_info", "tpc_segments_locate_fetch_hits",
                "tpc_segments_locate_fetch_runs", "tpc_segments_locate_fetch_records", "tpc_segments_locate_fetch_shared",
                "tpc_segments_classes_build", "tpc_segments_classes_info", "tpc_segments_classes_fetch_members", "tpc_segments_classes_fetch_rows",
-               "tpc_segments_classes_fetch_presence", "tpc_segments_classes_fetch_sets"]
+               "tpc_segments_classes_fetch_presence", "tpc_segments_classes_fetch_sets",
+               "tpc_segments_tracks_build", "tpc_segments_tracks_info", "tpc_segments_tracks_fetch_rows", "tpc_segments_tracks_fetch_colors",
+               "tpc_segments_tracks_fetch_depth"]
+TRACKS_ALL = 0xFFFFFFFF  # only_color of tpc_segments_tracks_build: every colour
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
 _hip = None
@@ -221,6 +224,11 @@ def hip():
         L.tpc_segments_classes_fetch_rows.argtypes = [p, u64, u64, p, p, p, p, p]
         L.tpc_segments_classes_fetch_presence.argtypes = [p, u64, u64, p]
         L.tpc_segments_classes_fetch_sets.argtypes = [p, p, p, p]
+        L.tpc_segments_tracks_build.argtypes = [p, p, u32, u32]
+        L.tpc_segments_tracks_info.argtypes = [p, p]
+        L.tpc_segments_tracks_fetch_rows.argtypes = [p, u64, u64, p, p, p]
+        L.tpc_segments_tracks_fetch_colors.argtypes = [p, p, p, p, p]
+        L.tpc_segments_tracks_fetch_depth.argtypes = [p, p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -939,6 +947,41 @@ class Context:
         out = np.zeros((max(n, 0), self.segments_colors_info()["words"]), dtype=np.uint32)
         self._ck(hip().tpc_segments_superbubbles_fetch_presence(self._h, b0, n, out.ctypes.data))
         return out
+
+    def segments_tracks_build(self, color_of_seq, n_colors, only=None):
+        """The presence tracks (csrc/tpc_tracks.hip) over the table of the last segments_build and the colour table of the last
+        segments_colors_build, which the caller promises was built with the same color_of_seq; only: one colour, None = all.  The
+        option test_tracks_grid (set_option) caps the workgroups per kernel for the next build alone.  Returns segments_tracks_info()."""
+        col = np.ascontiguousarray(color_of_seq, dtype=np.uint32)
+        self._ck(hip().tpc_segments_tracks_build(self._h, col.ctypes.data if col.size else None, n_colors, TRACKS_ALL if only is None else only))
+        return self.segments_tracks_info()
+
+    def segments_tracks_info(self):
+        """dict: intervals, selected (events), colors, only (None: all colours), peak_bytes (device memory of the stage)."""
+        c = np.zeros(5, dtype=np.uint64)
+        self._ck(hip().tpc_segments_tracks_info(self._h, c.ctypes.data))
+        d = dict(zip(("intervals", "selected", "colors", "only", "peak_bytes"), (int(x) for x in c)))
+        d["only"] = None if d["only"] == TRACKS_ALL else d["only"]
+        return d
+
+    def segments_tracks_fetch_rows(self, i0=0, n=None):
+        """(first_event, last_event, row) of intervals [i0, i0 + n) as uint32; n = None: to the last interval."""
+        n = self.segments_tracks_info()["intervals"] - i0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(3)]
+        self._ck(hip().tpc_segments_tracks_fetch_rows(self._h, i0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_tracks_fetch_colors(self):
+        """(intervals, edges, core_edges, private_edges) per colour as uint64 [colors]."""
+        out = [np.zeros(self.segments_tracks_info()["colors"], dtype=np.uint64) for _ in range(4)]
+        self._ck(hip().tpc_segments_tracks_fetch_colors(self._h, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_tracks_fetch_depth(self):
+        """(intervals, edges) per number of colours as uint64 [colors + 1], 0 where no interval has that many."""
+        out = [np.zeros(self.segments_tracks_info()["colors"] + 1, dtype=np.uint64) for _ in range(2)]
+        self._ck(hip().tpc_segments_tracks_fetch_depth(self._h, *[a.ctypes.data for a in out]))
+        return tuple(out)
 
     def segments_anchors_build(self, color_of_seq, n_colors, ref_color=0):
         """The anchor blocks (csrc/tpc_anchors.hip) of every other colour against ref_color, over the table of the last segments_build,

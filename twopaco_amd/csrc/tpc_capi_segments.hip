@@ -29,6 +29,7 @@ void text_plan_drop(tpc_ctx *c)
 //   colours, links      <- components       (joined by the link rows, summed over the colour rows)
 //   colours, links      <- superbubbles     (searched over the link rows' arcs, presence ORed over the colour rows)
 //   colours             <- classes          (the colour rows grouped by their presence words)
+//   colours             <- tracks           (the colour rows projected onto the sequences' events)
 //   segments <- anchors                     (paired and chained over the event table alone)
 //   segments <- edges   <- locate           (the index holds positions of the build's text and rows; a locate holds hits in that index)
 //   segments <- the graph text's plan
@@ -40,6 +41,7 @@ namespace tpch {
 
 void distances_drop(tpc_ctx *c) { free_all({c->dst.mat}); c->dst = {}; }
 void classes_drop(tpc_ctx *c) { free_all({c->cls.class_of, c->cls.first, c->cls.sums, c->cls.presence, c->cls.sets}); c->cls = {}; }
+void tracks_drop(tpc_ctx *c) { free_all({c->trk.rows, c->trk.sums}); c->trk = {}; }
 void components_drop(tpc_ctx *c) { free_all({c->cmp.component, c->cmp.root, c->cmp.sums, c->cmp.presence}); c->cmp = {}; }
 void superbubbles_drop(tpc_ctx *c)
 {
@@ -50,7 +52,7 @@ void locate_drop(tpc_ctx *c) { free_all({c->loc.hit, c->loc.row, c->loc.runs, c-
 void edges_drop(tpc_ctx *c) { locate_drop(c); free_all({c->edg.slots, c->edg.g0}); c->edg = {}; }
 void anchors_drop(tpc_ctx *c) { free_all({c->anc.mate, c->anc.rows, c->anc.sums}); c->anc = {}; }
 void bubbles_drop(tpc_ctx *c) { free_all({c->bub.rows, c->bub.sides, c->bub.hist}); c->bub = {}; }
-void colors_drop(tpc_ctx *c) { distances_drop(c); components_drop(c); superbubbles_drop(c); classes_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
+void colors_drop(tpc_ctx *c) { distances_drop(c); components_drop(c); superbubbles_drop(c); classes_drop(c); tracks_drop(c); free_all({c->col.rows, c->col.presence, c->col.hist}); c->col = {}; }
 void links_drop(tpc_ctx *c) { bubbles_drop(c); components_drop(c); superbubbles_drop(c); free_all({c->lnk.rows, c->lnk.first}); c->lnk = {}; }
 
 }  // namespace tpch

@@ -14,6 +14,7 @@
 //   tpc_locate.hip        the edge index and the location of a query text in it (tpc_segments_edges_*, tpc_segments_locate_*), kernels and entry points
 //   tpc_edgehash.h        the two-strand rolling hash of an edge, shared by tpc_sketch.hip and tpc_locate.hip
 //   tpc_classes.hip       the colour classes over the colour table (tpc_segments_classes_*), kernels and entry points
+//   tpc_tracks.hip        the presence tracks: the colour rows projected onto the sequences' coordinates (tpc_segments_tracks_*), kernels and entry points
 //   tpc_stage.h           what the eight stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
 //   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
@@ -228,6 +229,15 @@ struct tpc_ctx {
     int opt_classes_hash_bits = -1;          // low bits of the row's hash that are kept, -1 = all 64
     int opt_classes_grid = 0;                // at most this many workgroups per kernel, 0 = by the rows
     int opt_classes_wide = 0;                // 1 = a wave per row, 2 = a thread per row, 0 = by the words
+    // presence tracks (tpc_segments_tracks_*, tpc_tracks.hip) of the last tpc_segments_tracks_build
+    struct Tracks {
+        uint32_t *rows = nullptr;            // device, [3][n_intervals]: first_event, last_event, row
+        unsigned long long *sums = nullptr;  // device, [4][n_colors]: intervals, edges, core_edges, private_edges; then [2][n_colors + 1]: depth_intervals, depth_edges
+        uint64_t n_intervals = 0, selected = 0, peak_bytes = 0;
+        uint32_t n_colors = 0, only = 0;
+        bool valid = false;
+    } trk;
+    int opt_tracks_grid = 0;                 // option test_tracks_grid (tests only), for the next tpc_segments_tracks_build alone: at most this many workgroups per kernel, 0 = by the events
     int opt_edges_slots_log2 = 0;            // option test_edges_slots_log2 (tests only): slots of the edge index, 0 = by the edges
     int opt_edges_hash_bits = 0;             // option test_edges_hash_bits (tests only): bits of the edge's hash that are kept, 0 = all 64
     int opt_locate_grid = 0;                 // option test_locate_grid (tests only): at most this many workgroups of the tile kernels, 0 = by the CUs
@@ -348,7 +358,7 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these ten and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these eleven and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
@@ -358,6 +368,7 @@ void anchors_drop(tpc_ctx *c);
 void edges_drop(tpc_ctx *c);
 void locate_drop(tpc_ctx *c);
 void classes_drop(tpc_ctx *c);
+void tracks_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

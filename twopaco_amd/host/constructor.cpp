@@ -51,7 +51,11 @@
 // --classes file|sequence [--classes-out F] [--classes-members F]: the colour classes of the same graph -- the distinct sets of colours
 // and the segments that have each -- as TSV of integers, byte for byte what `graphdump --classes` writes, and asked for, the class of
 // every segment (csrc/tpc_classes.hip groups the colour rows on the device; combines with everything above from one segment and colour
-// build; the other tables must name the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// build; the other tables must name the same colours; its files are written after the locate files);
+// --tracks file|sequence [--tracks-of N] [--tracks-out F] [--tracks-bedgraph F]: the presence tracks of the input sequences -- for
+// every stretch of every sequence the colours that share it -- as TSV of integers, byte for byte what `graphdump --tracks` writes, and
+// asked for, a bedGraph of the number of colours (csrc/tpc_tracks.hip projects the colour rows onto the events on the device; combines
+// with everything above from one segment and colour build; the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -111,6 +115,7 @@ namespace
 			<< "               [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>]" << std::endl
 			<< "               [--locate <file|sequence> --locate-in <file name> ... [--locate-out <file name>] [--locate-walks <file name>]]" << std::endl
 			<< "               [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>]" << std::endl
+			<< "               [--tracks <file|sequence>] [--tracks-of <integer>] [--tracks-out <file name>] [--tracks-bedgraph <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -167,7 +172,13 @@ namespace
 			<< "               of colours (by file or by sequence, as --colors) that segments have, numbered in the order gfa1 first prints a segment of" << std::endl
 			<< "               each.  Per class the name of its first segment, its segments, bases, edges, occurrences, number of colours and presence" << std::endl
 			<< "               bits; in front the classes, segments and edges by number of colours.  --classes-members: also the class of every segment," << std::endl
-			<< "               one line per segment.  Combines with all tables above (the same colours); written last.  One GPU only." << std::endl;
+			<< "               one line per segment.  Combines with all tables above (the same colours).  One GPU only." << std::endl
+			<< "       --tracks: also write the presence tracks of the input sequences as TSV to --tracks-out (default de_bruijn.tracks.tsv): for every" << std::endl
+			<< "               stretch of every sequence the colours (by file or by sequence, as --colors) that share it, neighbouring segment occurrences" << std::endl
+			<< "               of equal presence merged into one interval: sequence, begin, end, occurrences, number of colours and presence bits; in" << std::endl
+			<< "               front per colour its intervals, edges, core and private edges, and the intervals and edges by number of colours." << std::endl
+			<< "               --tracks-of: the sequences of this one colour only.  --tracks-bedgraph: also the number of colours per interval as" << std::endl
+			<< "               bedGraph.  Combines with all tables above (the same colours); written last.  One GPU only." << std::endl;
 	}
 }
 
@@ -320,8 +331,8 @@ int main(int argc, char * argv[])
 
 		// every table beside every other, each into a file of its own, on one GPU; the complaints are looked for in the tables' order
 		namespace GF = TwoPaCo::GraphFormat;
-		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE, GF::CLASSES}, false, false, false, false,
-			{0, 0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
+		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE, GF::CLASSES, GF::TRACKS}, false, false, false, false,
+			{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
 		GF::CheckTableOptions(tables, rules);
 		options.tables = tables.request;
 		optionsSet = optionsSet || options.tables.Any();

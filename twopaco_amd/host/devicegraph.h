@@ -34,7 +34,8 @@
 	X(segments_anchors_build) X(segments_anchors_info) X(segments_anchors_fetch_mates) X(segments_anchors_fetch_rows) X(segments_anchors_fetch_shared) \
 	X(segments_edges_build) X(segments_edges_info) X(segments_locate) X(segments_locate_info) X(segments_locate_fetch_runs) X(segments_locate_fetch_records) \
 	X(segments_locate_fetch_shared) \
-	X(segments_classes_build) X(segments_classes_info) X(segments_classes_fetch_members) X(segments_classes_fetch_rows) X(segments_classes_fetch_presence)
+	X(segments_classes_build) X(segments_classes_info) X(segments_classes_fetch_members) X(segments_classes_fetch_rows) X(segments_classes_fetch_presence) \
+	X(segments_tracks_build) X(segments_tracks_info) X(segments_tracks_fetch_rows) X(segments_tracks_fetch_colors) X(segments_tracks_fetch_depth)
 
 namespace TwoPaCo
 {
@@ -254,6 +255,37 @@ namespace TwoPaCo
 			return true;
 		}
 
+		// The presence tracks (csrc/tpc_tracks.hip): the colour rows of the colour build projected onto the events of the table on the device.
+		inline void BuildTracks(const Api & api, const GraphFormat::ColorMap & map, uint32_t only)
+		{
+			api.check(api.segments_tracks_build(api.ctx, map.colorOfSequence.data(), uint32_t(map.label.size()), only), "segments_tracks_build");
+		}
+
+		// ... fetched: the intervals and the sums.  false, and nothing fetched, when the stage saw other colours than the caller
+		inline bool FetchTracks(const Api & api, const GraphFormat::ColorMap & map, uint64_t segments, GraphFormat::TrackTable & out)
+		{
+			uint64_t info[5] = {0, 0, 0, 0, 0};
+			api.check(api.segments_tracks_info(api.ctx, info), "segments_tracks_info");
+			if (info[2] != map.label.size()) return false;
+			const size_t n = size_t(info[0]);
+			out.colors = info[2];
+			out.only = uint32_t(info[3]);
+			out.segments = segments;
+			out.firstEvent.resize(n);
+			out.lastEvent.resize(n);
+			out.row.resize(n);
+			out.intervals.resize(size_t(out.colors));
+			out.edges.resize(size_t(out.colors));
+			out.coreEdges.resize(size_t(out.colors));
+			out.privateEdges.resize(size_t(out.colors));
+			out.depthIntervals.resize(size_t(out.colors) + 1);
+			out.depthEdges.resize(size_t(out.colors) + 1);
+			api.check(api.segments_tracks_fetch_rows(api.ctx, 0, n, out.firstEvent.data(), out.lastEvent.data(), out.row.data()), "segments_tracks_fetch_rows");
+			api.check(api.segments_tracks_fetch_colors(api.ctx, out.intervals.data(), out.edges.data(), out.coreEdges.data(), out.privateEdges.data()), "segments_tracks_fetch_colors");
+			api.check(api.segments_tracks_fetch_depth(api.ctx, out.depthIntervals.data(), out.depthEdges.data()), "segments_tracks_fetch_depth");
+			return true;
+		}
+
 		// The bounded superbubbles (csrc/tpc_superbubbles.hip), searched over the link rows' arcs, presence ORed over the colour rows.
 		inline void BuildSuperbubbles(const Api & api, uint32_t maxInside)
 		{
@@ -418,9 +450,9 @@ namespace TwoPaCo
 		// and the bubble stage it would find 12 B per link, 4 B per 32 events and, with --bubbles, 24 B per segment and 16 B per bubble
 		// more resident, which a run that just fits the device does not have.
 		const int STAGES_LINKS_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::DISTANCES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS};
 		const int STAGES_DISTANCES_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::DISTANCES, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS};
 
 		// The caller's clock and [timing] lines.  built: after a stage's build, with the stage and its TPC_K_* (EDGES, then LOCATE
 		// once its batches are through: their kernel time is locateKernelMs, not the last batch's); fetched: after a stage's fetch.
@@ -500,6 +532,11 @@ namespace TwoPaCo
 					BuildClasses(api);
 					observer.built(stage, TPC_K_CLASSES);
 					agree(FetchClasses(api, t.segments, t.colors.Words(), t.classes), "class", "segment table", "segments");
+					break;
+				case TRACKS:
+					BuildTracks(api, t.map, request.tracksOf);
+					observer.built(stage, TPC_K_TRACKS);
+					agree(FetchTracks(api, t.map, t.segments, t.tracks), "track", "colour map", "colours");
 					break;
 				case LOCATE:
 					uint64_t edges[6] = {0, 0, 0, 0, 0, 0};

@@ -1214,6 +1214,217 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeTracks(const EventTable & t, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t nColors, const ColorTable & colors, uint32_t only,
+			TrackTable & out)
+		{
+			(void)k;
+			const uint32_t ALL = TrackTable::ALL;
+			if (nColors == 0) throw std::runtime_error("track table: at least one colour is required");
+			if (only != ALL && only >= nColors) throw std::runtime_error("track table: the one colour is " + std::to_string(only) + ", there are " + std::to_string(nColors) + " colours");
+			if (colorOfSequence.size() != t.sequences) throw std::runtime_error("track table: the colour of every sequence is required");
+			for (uint32_t c : colorOfSequence)
+			{
+				if (c >= nColors) throw std::runtime_error("track table: a sequence has the colour " + std::to_string(c) + ", there are " + std::to_string(nColors) + " colours");
+			}
+
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			const size_t rows = colors.Rows(), words = colors.Words();
+			if (colors.colors != nColors || colors.nColors.size() != rows || colors.presence.size() != rows * words) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+			out = TrackTable();
+			out.colors = nColors;
+			out.segments = rows;
+			out.only = only;
+			out.intervals.assign(nColors, 0);
+			out.edges.assign(nColors, 0);
+			out.coreEdges.assign(nColors, 0);
+			out.privateEdges.assign(nColors, 0);
+			out.depthIntervals.assign(nColors + 1, 0);
+			out.depthEdges.assign(nColors + 1, 0);
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			uint32_t seen = 0, rowBefore = 0;
+			size_t sequence = 0;
+			auto close = [&]()
+			{
+				// the sums of the interval that ends at out.lastEvent.back()
+				const uint32_t first = out.firstEvent.back(), last = out.lastEvent.back(), n = colors.nColors[out.row.back()];
+				const uint32_t c = colorOfSequence[sequence];
+				const uint64_t edges = uint64_t(t.end[last]) - t.begin[first];
+				if (n > nColors) throw std::runtime_error("colour table: a row holds more colours than there are");
+				out.intervals[c] += 1;
+				out.edges[c] += edges;
+				if (n == nColors) out.coreEdges[c] += edges;
+				if (n == 1) out.privateEdges[c] += edges;
+				out.depthIntervals[n] += 1;
+				out.depthEdges[n] += edges;
+			};
+
+			bool open = false;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				bool begins = false;
+				while (e >= t.seqEventBegin[sequence + 1])
+				{
+					if (open) close();
+					open = false;
+					++sequence;
+					begins = true;
+				}
+
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator at = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				uint32_t row = 0;
+				if (at == rowOf.end())
+				{
+					row = seen++;
+					if (name < FRESH) rowOf[name] = row;
+				}
+				else row = at->second;
+
+				if (row >= rows) throw std::runtime_error("track table: the colour table holds fewer rows than the events have segments");
+				const bool selected = only == ALL || colorOfSequence[sequence] == only;
+				if (selected)
+				{
+					const bool continues = open && !begins && std::equal(colors.presence.begin() + size_t(row) * words, colors.presence.begin() + size_t(row + 1) * words,
+						colors.presence.begin() + size_t(rowBefore) * words);
+					if (continues) out.lastEvent.back() = uint32_t(e);
+					else
+					{
+						if (open) close();
+						out.firstEvent.push_back(uint32_t(e));
+						out.lastEvent.push_back(uint32_t(e));
+						out.row.push_back(row);
+						open = true;
+					}
+				}
+
+				rowBefore = row;
+			}
+
+			if (open) close();
+		}
+
+		namespace
+		{
+			// one interval as the writers print it
+			struct TrackLine
+			{
+				uint32_t sequence, nColors;
+				uint64_t begin, end, events;
+			};
+
+			void CheckTracks(const EventTable & t, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & a)
+			{
+				const size_t n = a.Rows();
+				if (a.lastEvent.size() != n || a.row.size() != n || a.intervals.size() != a.colors || a.edges.size() != a.colors || a.coreEdges.size() != a.colors ||
+					a.privateEdges.size() != a.colors || a.depthIntervals.size() != a.colors + 1 || a.depthEdges.size() != a.colors + 1 || map.label.size() != a.colors ||
+					colors.colors != a.colors || (a.only != TrackTable::ALL && a.only >= a.colors))
+				{
+					throw std::runtime_error("track table: the arrays do not agree about the intervals and the colours");
+				}
+
+				if (colors.nColors.size() != colors.Rows() || colors.presence.size() != colors.Rows() * colors.Words()) throw std::runtime_error("colour table: the arrays do not agree about the rows and the colours");
+				if (map.colorOfSequence.size() != t.sequences || seq.name.size() != t.sequences || seq.length.size() != t.sequences)
+				{
+					throw std::runtime_error("track table: the colour, the name and the length of every sequence are required");
+				}
+
+				if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+				for (size_t i = 0; i < n; i++)
+				{
+					if (a.firstEvent[i] > a.lastEvent[i] || a.lastEvent[i] >= t.events || a.row[i] >= colors.Rows() || t.end[a.lastEvent[i]] < t.begin[a.firstEvent[i]])
+					{
+						throw std::runtime_error("track table: an interval lies outside the event table");
+					}
+				}
+			}
+
+			TrackLine MakeTrackLine(const EventTable & t, const ColorTable & colors, const TrackTable & a, size_t i)
+			{
+				TrackLine line;
+				const uint32_t first = a.firstEvent[i], last = a.lastEvent[i];
+				line.sequence = uint32_t(std::upper_bound(t.seqEventBegin, t.seqEventBegin + t.sequences + 1, first) - t.seqEventBegin - 1);
+				line.begin = t.begin[first];
+				line.end = t.end[last];
+				line.events = uint64_t(last) - first + 1;
+				line.nColors = colors.nColors[a.row[i]];
+				return line;
+			}
+		}
+
+		void WriteTracks(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & a, const std::string & path)
+		{
+			CheckTracks(t, map, seq, colors, a);
+			const size_t words = colors.Words(), digits = size_t((colors.colors + 3) / 4);
+			WriteStreamed(path, "track table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-tracks\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(a.colors) +
+					"\tsegments=" + std::to_string(a.segments) + "\tof=" + (a.only == TrackTable::ALL ? std::string("all") : std::to_string(a.only)) + "\tintervals=" +
+					std::to_string(a.Rows()) + "\n";
+				for (uint64_t c = 0; c < a.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+				for (size_t s = 0; s < seq.name.size(); s++)
+				{
+					buf += "#sequence\t" + std::to_string(s) + "\t" + std::to_string(map.colorOfSequence[s]) + "\t" + std::to_string(seq.length[s]) + "\t" + seq.name[s] + "\n";
+					flushIfLarge();
+				}
+
+				for (uint64_t c = 0; c < a.colors; c++)
+				{
+					if (a.only != TrackTable::ALL && c != a.only) continue;
+					buf += "#genome\t" + std::to_string(c) + "\t" + std::to_string(a.intervals[c]) + "\t" + std::to_string(a.edges[c]) + "\t" + std::to_string(a.coreEdges[c]) + "\t" +
+						std::to_string(a.privateEdges[c]) + "\n";
+				}
+
+				for (uint64_t n = 0; n <= a.colors; n++)
+				{
+					if (a.depthIntervals[n]) buf += "#depth\t" + std::to_string(n) + "\t" + std::to_string(a.depthIntervals[n]) + "\t" + std::to_string(a.depthEdges[n]) + "\n";
+				}
+
+				for (size_t i = 0; i < a.Rows(); i++)
+				{
+					const TrackLine line = MakeTrackLine(t, colors, a, i);
+					buf += std::to_string(line.sequence) + "\t" + std::to_string(line.begin) + "\t" + std::to_string(line.end) + "\t" + std::to_string(line.events) + "\t" +
+						std::to_string(line.nColors) + "\t";
+					const uint32_t * bits = &colors.presence[size_t(a.row[i]) * words];
+					for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(bits[j >> 3] >> (4 * (j & 7))) & 15u];
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteTracksBedGraph(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & a,
+			const std::string & path)
+		{
+			CheckTracks(t, map, seq, colors, a);
+			if (path.empty()) throw std::runtime_error("The track bedGraph needs a file name");
+			WriteStreamed(path, "track bedGraph", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "track type=bedGraph name=\"n_colors\" description=\"twopaco tracks k=" + std::to_string(k) + " by=" + (map.bySequence ? "sequence" : "file") + "\"\n";
+				for (size_t i = 0; i < a.Rows(); i++)
+				{
+					const TrackLine line = MakeTrackLine(t, colors, a, i);
+					buf += seq.name[line.sequence] + "\t" + std::to_string(line.begin) + "\t" + std::to_string(line.end) + "\t" + std::to_string(line.nColors) + "\n";
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteTrackFiles(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & a, const std::string & path,
+			const std::string & bedGraphPath)
+		{
+			if (!bedGraphPath.empty()) WriteTracksBedGraph(t, k, map, seq, colors, a, bedGraphPath);
+			try
+			{
+				WriteTracks(t, k, map, seq, colors, a, path);
+			}
+			catch (...)
+			{
+				if (!bedGraphPath.empty()) ::unlink(bedGraphPath.c_str());
+				throw;
+			}
+		}
+
 		void ComputeSuperbubbles(const EventTable & t, size_t k, const LinkTable & links, const ColorTable & colors, uint32_t maxInside, SuperbubbleTable & out)
 		{
 			(void)k;

@@ -545,6 +545,53 @@ namespace TwoPaCo
 		void WriteClassFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, const ClassTable & classes, const std::string & path,
 			const std::string & membersPath);
 
+		// ---------------------------------------------------------------------------------------- the presence tracks
+		// Which colours share each stretch of every sequence (include/twopaco_hip.h, the tpc_segments_tracks_* group, states the
+		// definition in the same words).  row(e), seq(e) and colour(e) = colorOfSequence[seq(e)] are those of the colour table.  With
+		// only == ALL every event is SELECTED, otherwise those with colour(e) == only.  A selected event e CONTINUES e - 1 when both lie
+		// in one sequence and the presence words of their rows are all equal.  An INTERVAL is a maximal run firstEvent .. lastEvent of
+		// selected events each continuing the one before; it stands for the (k+1)-mers that start at [begin[first], end[last]) of its
+		// sequence, in bases [begin[first], end[last] + k); its presence and n_colors are those of row(first).  Intervals ascend by
+		// firstEvent and tile every sequence's events.  Per colour: intervals, edges (end[last] - begin[first] summed), coreEdges
+		// (n_colors == C) and privateEdges (n_colors == 1); per depth n = 0 .. C: depthIntervals and depthEdges.  The arrays come from
+		// ComputeTracks below -- the serial statement -- or from the device (csrc/tpc_tracks.hip); the writers print either as the same
+		// bytes.
+		struct TrackTable
+		{
+			static const uint32_t ALL = 0xFFFFFFFFu;                           // only: every colour
+			uint64_t colors, segments;
+			uint32_t only;
+			std::vector<uint32_t> firstEvent, lastEvent, row;                  // [intervals]
+			std::vector<uint64_t> intervals, edges, coreEdges, privateEdges;   // [colors]
+			std::vector<uint64_t> depthIntervals, depthEdges;                  // [colors + 1]
+			TrackTable() : colors(0), segments(0), only(ALL) {}
+			size_t Rows() const { return firstEvent.size(); }
+		};
+
+		// The definition as a plain loop over the events: the row of every event by a hash map from |name|, as ComputeColors numbers
+		// them.  `colors` is the colour table of `table` under colorOfSequence.  The table must be one whose walk did not fail; every
+		// sequence needs a colour below nColors, and only < nColors or ALL (std::runtime_error otherwise).  No device dependency.
+		void ComputeTracks(const EventTable & table, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t nColors, const ColorTable & colors, uint32_t only,
+			TrackTable & out);
+
+		// The TSV text: "#twopaco-tracks\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tof=<c|all>\tintervals=<I>", the colour
+		// table's "#color" lines, the anchor table's "#sequence" lines, "#genome\t<c>\t<intervals>\t<edges>\t<core_edges>\t
+		// <private_edges>" for every selected colour, zeros included, "#depth\t<n>\t<intervals>\t<edges>" for every n that occurs, then
+		// one line per interval: sequence (0-based), begin, end ((k+1)-mer starts, half-open), events, n_colors and presence as hex (as
+		// the colour table prints it).  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteTracks(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & tracks,
+			const std::string & path);
+
+		// bedGraph into the file `path`: the track line, then "<name>\t<begin>\t<end>\t<n_colors>" per interval in the table's order,
+		// not merged further; sequences are named as the anchor PAF names them.
+		void WriteTracksBedGraph(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & tracks,
+			const std::string & path);
+
+		// Both files, or neither: the bedGraph first when bedGraphPath is given, then the TSV (to stdout when path is empty); when the
+		// TSV cannot be written the bedGraph file is removed again before the error is thrown.
+		void WriteTrackFiles(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const TrackTable & tracks,
+			const std::string & path, const std::string & bedGraphPath);
+
 		// ---------------------------------------------------------------------------------------- the superbubbles
 		// Where the genomes differ, beyond two alleles (include/twopaco_hip.h, the tpc_segments_superbubbles_* group, states the
 		// definition in the same words; Onodera, Sadakane and Shibuya 2013).  Rows, sides (code = row * 2 + minus, rev(code) = code ^ 1),

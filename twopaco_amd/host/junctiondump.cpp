@@ -11,7 +11,8 @@
 //             |  --anchors file|sequence [--anchors-ref <colour>] [--anchors-out <path>] [--anchors-paf <path>]
 //             |  --locate file|sequence --locate-in <q.fa> [--locate-in ...] [--locate-out <path>] [--locate-walks <path>]
 //             |  --classes file|sequence [--classes-out <path>] [--classes-members <path>]
-//             (the last eight instead of -f)
+//             |  --tracks file|sequence [--tracks-of <colour>] [--tracks-out <path>] [--tracks-bedgraph <path>]
+//             (the last nine instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -93,7 +94,13 @@
 // defines them -- as TSV of integers (graphformat.h: WriteClasses) and, asked for, the class of every segment (WriteClassMembers).
 // Without --gpu the serial walk, then ComputeColors and ComputeClasses; with --gpu the colour stage and the class stage over one
 // segment build (csrc/tpc_classes.hip); the bytes are the same.  It goes with what --colors goes with, and with --colors, of the
-// same colours, and is written after every other table; not with -f, --links, --bubbles or --text.
+// same colours, and is written after every other table but the track table; not with -f, --links, --bubbles or --text.
+// --tracks file|sequence [--tracks-of <colour>] [--tracks-out <path>] [--tracks-bedgraph <path>] (an addition; instead of -f): the
+// presence tracks -- for every stretch of every input sequence the colours that share it, neighbouring occurrences of equal presence
+// merged into one interval; include/twopaco_hip.h defines them -- as TSV of integers (graphformat.h: WriteTracks) and, asked for, as
+// bedGraph of the number of colours (WriteTracksBedGraph).  Without --gpu the serial walk, then ComputeColors and ComputeTracks; with
+// --gpu the colour stage and the track stage over one segment build (csrc/tpc_tracks.hip); the bytes are the same.  It goes with
+// what --classes goes with, and with --classes, of the same colours, and is written last; not with -f, --links, --bubbles or --text.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -443,6 +450,11 @@ namespace
 		{
 			throw ArgError("Value '" + std::to_string(request.anchorsRef) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--anchors-ref)");
 		}
+
+		if (request.On(TRACKS) && request.tracksOf != TrackTable::ALL && request.tracksOf >= map.label.size())
+		{
+			throw ArgError("Value '" + std::to_string(request.tracksOf) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--tracks-of)");
+		}
 	}
 
 	// A table request, serial: one walk (with the letters when the edge index reads them), the serial statements the request needs,
@@ -480,11 +492,11 @@ namespace
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs;
 		double stageMs[TABLES + 1], stageKernelMs[TABLES + 1];  // of the stages of BuildTables: the tables', and EDGES
 		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored, anchorBlocks, anchors;
-		uint64_t locateRuns, locateBatches, classes, largestClass;
+		uint64_t locateRuns, locateBatches, classes, largestClass, trackIntervals;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
 			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), stageMs(), stageKernelMs(), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0),
-			superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), locateRuns(0), locateBatches(0), classes(0), largestClass(0), threads(1) {}
+			superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), locateRuns(0), locateBatches(0), classes(0), largestClass(0), trackIntervals(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -502,7 +514,8 @@ namespace
 				"\"superbubbles_kernel_ms\": %.3f, \"superbubbles_ms\": %.3f, \"superbubbles\": %llu, \"superbubble_members\": %llu, \"superbubbles_unmirrored\": %llu, "
 				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu, "
 				"\"edges_kernel_ms\": %.3f, \"edges_ms\": %.3f, \"locate_kernel_ms\": %.3f, \"locate_ms\": %.3f, \"locate_runs\": %llu, \"locate_batches\": %llu, "
-				"\"classes_kernel_ms\": %.3f, \"classes_ms\": %.3f, \"classes\": %llu, \"largest_class\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"classes_kernel_ms\": %.3f, \"classes_ms\": %.3f, \"classes\": %llu, \"largest_class\": %llu, "
+				"\"tracks_kernel_ms\": %.3f, \"tracks_ms\": %.3f, \"track_intervals\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, stageKernelMs[COLORS], stageMs[COLORS], stageKernelMs[LINKS], stageMs[LINKS], (unsigned long long)links,
 				(unsigned long long)linkOccurrences, stageKernelMs[BUBBLES], stageMs[BUBBLES], (unsigned long long)bubbles, stageKernelMs[DISTANCES], stageMs[DISTANCES],
@@ -510,7 +523,7 @@ namespace
 				stageMs[SUPERBUBBLES], (unsigned long long)superbubbles, (unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, stageKernelMs[ANCHORS],
 				stageMs[ANCHORS], (unsigned long long)anchorBlocks, (unsigned long long)anchors, stageKernelMs[EDGES], stageMs[EDGES], stageKernelMs[LOCATE], stageMs[LOCATE],
 				(unsigned long long)locateRuns, (unsigned long long)locateBatches, stageKernelMs[CLASSES], stageMs[CLASSES], (unsigned long long)classes,
-				(unsigned long long)largestClass);
+				(unsigned long long)largestClass, stageKernelMs[TRACKS], stageMs[TRACKS], (unsigned long long)trackIntervals);
 			std::fclose(f);
 		}
 	};
@@ -646,7 +659,7 @@ namespace
 	}
 
 	// graphdump's clock around the stages of BuildTables: DumpStats and the [timing] lines (the colour table's comes last, after the files)
-	const char * const STAGE_TIMING[TABLES + 1] = {0, "link table", "bubble table", "distance matrices", "component table", "superbubble table", "anchor table", "locate", "class table", "edge index"};
+	const char * const STAGE_TIMING[TABLES + 1] = {0, "link table", "bubble table", "distance matrices", "component table", "superbubble table", "anchor table", "locate", "class table", "track table", "edge index"};
 	const StageWording GPU_WORDING = {"--gpu: the ", "colour map"};
 
 	void BuildTablesTimed(DeviceLibrary & lib, const TableRequest & request, const uint64_t * counts, bool linkBits, Tables & tables, DumpStats & stats)
@@ -681,6 +694,7 @@ namespace
 		stats.locateBatches = observer.locateBatches;
 		stats.classes = tables.classes.Rows();
 		stats.largestClass = tables.classes.Largest();
+		stats.trackIntervals = tables.tracks.Rows();
 	}
 
 	// A table request with --gpu: one segment build, the table stays on the device, and the stages that are wanted run there
@@ -774,7 +788,7 @@ namespace
 	// ---------------------------------------------------------------------------------------- command line
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>] [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>] [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>] [--tracks <file|sequence>] [--tracks-of <integer>] [--tracks-out <file name>] [--tracks-bedgraph <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -856,6 +870,16 @@ namespace
 			"     for all; this table is written last); not with --links, --bubbles or --text.\n\n"
 			"   --classes-out <file name>\n     with --classes: write the table there instead of to the standard output\n\n"
 			"   --classes-members <file name>\n     with --classes: also write the class of every segment there, one line per segment\n\n"
+			"   --tracks <file|sequence>\n     instead of -f: the presence tracks of the input sequences as TSV of integers -- for every stretch of every sequence\n"
+			"     the colours of --colors that share it.  Neighbouring segment occurrences of equal presence are one interval: sequence\n"
+			"     (0-based), begin and end (the (k+1)-mers that start in [begin, end); in bases [begin, end + k)), occurrences, number of\n"
+			"     colours and presence bits; in front the colours, the sequences, per colour its intervals, edges and the edges all\n"
+			"     colours (core) or only this one (private) hold, and the intervals and edges by number of colours.  Needs -k and -s.\n"
+			"     With --gpu the intervals are found on the device.  Goes with what --classes goes with, and with --classes, of the same\n"
+			"     colours (one walk for all; this table is written last); not with --links, --bubbles or --text.\n\n"
+			"   --tracks-of <integer>\n     with --tracks: the intervals of the sequences of this one colour only (default: all colours)\n\n"
+			"   --tracks-out <file name>\n     with --tracks: write the table there instead of to the standard output\n\n"
+			"   --tracks-bedgraph <file name>\n     with --tracks: also write the number of colours per interval there as bedGraph\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -938,8 +962,9 @@ int main(int argc, char * argv[])
 		// A table instead of -f.  The link table goes with no other, the bubble table not with the colour table, the class table with
 		// what the colour table goes with, none but the colour, the class and the link table's own complaint with --compact; the complaints are looked for from the last table back, the link table's last.
 		const unsigned linksBit = 1u << LINKS;
-		const TableCliRules rules = {"Argument: ", {CLASSES, LOCATE, ANCHORS, SUPERBUBBLES, COMPONENTS, DISTANCES, BUBBLES, COLORS, LINKS}, true, haveFormat, compact, textSet,
-			{0, 1u << COLORS, 1u << COLORS | linksBit, linksBit, linksBit, linksBit, linksBit, linksBit, 1u << BUBBLES | linksBit}, {false, false, true, true, true, true, true, true, false}, 1, false, 0};
+		const TableCliRules rules = {"Argument: ", {TRACKS, CLASSES, LOCATE, ANCHORS, SUPERBUBBLES, COMPONENTS, DISTANCES, BUBBLES, COLORS, LINKS}, true, haveFormat, compact, textSet,
+			{0, 1u << COLORS, 1u << COLORS | linksBit, linksBit, linksBit, linksBit, linksBit, linksBit, 1u << BUBBLES | linksBit, 1u << BUBBLES | linksBit},
+			{false, false, true, true, true, true, true, true, false, false}, 1, false, 0};
 		CheckTableOptions(tables, rules);
 		const TableRequest & request = tables.request;
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");

@@ -20,7 +20,7 @@ namespace TwoPaCo
 	namespace GraphFormat
 	{
 		// in the order the tables are written
-		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, CLASSES, TABLES };
+		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, CLASSES, TRACKS, TABLES };
 
 		enum Reads { NOTHING, BUILD, ROWS };  // of a device stage: not read, built and read where it lies, its rows fetched for the files
 
@@ -48,6 +48,7 @@ namespace TwoPaCo
 			{"anchors", "anchor", true, "paf", "The anchor PAF", false, "--anchors-ref", NOTHING, NOTHING, true, false},
 			{"locate", "locate", true, "walks", "The locate walks", true, "--locate-in", ROWS, NOTHING, true, true},
 			{"classes", "class", true, "members", "The class members", true, 0, ROWS, NOTHING, true, false},
+			{"tracks", "track", true, "bedgraph", "The track bedGraph", false, "--tracks-of", ROWS, NOTHING, true, false},
 		};
 
 		struct TableRequest
@@ -62,8 +63,9 @@ namespace TwoPaCo
 			File table[TABLES];
 			bool bySequence;                    // the colours of all tables: the input's sequences, or its files
 			uint32_t superbubblesMax, anchorsRef;
+			uint32_t tracksOf;                  // the one colour of the track table, TrackTable::ALL: every colour
 			std::vector<std::string> locateIn;  // the FASTA files of the queries
-			TableRequest() : bySequence(false), superbubblesMax(62), anchorsRef(0) {}
+			TableRequest() : bySequence(false), superbubblesMax(62), anchorsRef(0), tracksOf(TrackTable::ALL) {}
 
 			bool On(TableId t) const { return table[t].on; }
 			bool Any() const
@@ -181,6 +183,7 @@ namespace TwoPaCo
 			if (a == "--superbubbles-max") o.request.superbubblesMax = uint32_t(ParseBounded(value(tag), 2, 62, "an integer 2 .. 62", constraintTag + tag));
 			else if (a == "--anchors-ref") o.request.anchorsRef = uint32_t(ParseBounded(value(tag), 0, 0x7FFFFFFFll, "a colour index", constraintTag + tag));
 			else if (a == "--locate-in") o.request.locateIn.push_back(value(tag));
+			else if (a == "--tracks-of") o.request.tracksOf = uint32_t(ParseBounded(value(tag), 0, 0x7FFFFFFFll, "a colour index", constraintTag + tag));
 			for (int t = 0; t < TABLES; t++)
 			{
 				const TableRow & row = TABLE_ROWS[t];
@@ -256,6 +259,11 @@ namespace TwoPaCo
 				{
 					throw ArgError("Value '" + std::to_string(r.anchorsRef) + "' does not meet constraint: a colour index below " + std::to_string(rules.inputFiles), "(--anchors-ref)");
 				}
+
+				if (t == TRACKS && rules.inputFiles && o.by[t] == "file" && r.tracksOf != TrackTable::ALL && r.tracksOf >= rules.inputFiles)
+				{
+					throw ArgError("Value '" + std::to_string(r.tracksOf) + "' does not meet constraint: a colour index below " + std::to_string(rules.inputFiles), "(--tracks-of)");
+				}
 			}
 
 			for (int t = TABLES; t-- > 0;) if (r.table[t].on && TABLE_ROWS[t].colours) r.bySequence = o.by[t] == "sequence";
@@ -274,6 +282,7 @@ namespace TwoPaCo
 			AnchorTable anchors;
 			LocateTable locate;
 			ClassTable classes;
+			TrackTable tracks;
 			InputSequences queries;         // of request.locateIn
 			LoadedSequences queryLetters;
 			uint64_t segments, linkRows;    // the rows of the colour table and of the link table, fetched or not
@@ -307,6 +316,7 @@ namespace TwoPaCo
 			}
 
 			if (request.On(CLASSES)) ComputeClasses(table, k, t.colors, t.classes);
+			if (request.On(TRACKS)) ComputeTracks(table, k, t.map.colorOfSequence, t.map.label.size(), t.colors, request.tracksOf, t.tracks);
 		}
 
 		// One table's files, if it is wanted
@@ -325,6 +335,7 @@ namespace TwoPaCo
 			case ANCHORS: WriteAnchorFiles(table, k, t.map, seq, t.anchors, f.out, f.second); break;
 			case LOCATE: WriteLocateFiles(table, k, t.map, t.colors, t.queries, t.locate, f.out, f.second); break;
 			case CLASSES: WriteClassFiles(table, k, t.map, t.colors, t.classes, f.out, f.second); break;
+			case TRACKS: WriteTrackFiles(table, k, t.map, seq, t.colors, t.tracks, f.out, f.second); break;
 			}
 		}
 

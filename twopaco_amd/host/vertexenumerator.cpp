@@ -1021,6 +1021,11 @@ namespace TwoPaCo
 					{
 						throw std::runtime_error("The anchor table's reference colour is " + std::to_string(request.anchorsRef) + ", there are " + std::to_string(tables.map.label.size()) + " colours");
 					}
+
+					if (request.On(TRACKS) && request.tracksOf != TrackTable::ALL && request.tracksOf >= tables.map.label.size())
+					{
+						throw std::runtime_error("The track table's one colour is " + std::to_string(request.tracksOf) + ", there are " + std::to_string(tables.map.label.size()) + " colours");
+					}
 				};
 
 				DeviceGraph::Events held(0, sequences);
@@ -1072,13 +1077,13 @@ namespace TwoPaCo
 					{
 						if (counts[0]) DeviceGraph::FetchNames(api, held);
 						if (counts[0]) DeviceGraph::FetchPositions(api, held);
-						if (request.On(ANCHORS)) DeviceGraph::FetchSequences(api, held);
+						if (request.On(ANCHORS) || request.On(TRACKS)) DeviceGraph::FetchSequences(api, held);
 					}
 
 					makeColorMap();
 					// twopaco's clock around the stages: a lap after every build and every fetch, the kernels' time after the build's
 					static const char * const lap[TABLES + 1] = {"segment colours", "segment links", "segment bubbles", "segment distances", "segment components",
-						"segment superbubbles", "segment anchors", "locate", "segment classes", "edge index"};
+						"segment superbubbles", "segment anchors", "locate", "segment classes", "segment tracks", "edge index"};
 					DeviceGraph::StageObserver observer;
 					observer.built = [&](int stage, int kernel)
 					{
