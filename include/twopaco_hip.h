@@ -69,7 +69,8 @@ enum {
     TPC_K_LOCATE = 25,      /* tpc_segments_edges_build / tpc_segments_locate, whichever ran last: the stage on the stream from its first kernel to its last (no counterpart in the reference) */
     TPC_K_CLASSES = 26,     /* tpc_segments_classes_build: the set of rows keyed by their presence words, the numbering and the per-class sums (no counterpart in the reference) */
     TPC_K_TRACKS = 27,      /* tpc_segments_tracks_build: the row of every event, the heads, their scan, the intervals and the sums (no counterpart in the reference) */
-    TPC_K_COUNT = 28
+    TPC_K_VARIANTS = 28,    /* tpc_segments_variants_build: the walks, their scan, the sorts by row and mask, the alleles, presence and sites (no counterpart in the reference) */
+    TPC_K_COUNT = 29
 };
 
 /* Context on HIP device `device`.  Fails (non-zero) when no GPU / device is present:
@@ -994,6 +995,70 @@ int tpc_segments_tracks_fetch_rows(tpc_ctx *ctx, uint64_t i0, uint64_t n, uint32
 int tpc_segments_tracks_fetch_colors(tpc_ctx *ctx, uint64_t *intervals, uint64_t *edges, uint64_t *core_edges, uint64_t *private_edges /* [n_colors] each */);
 int tpc_segments_tracks_fetch_depth(tpc_ctx *ctx, uint64_t *intervals, uint64_t *edges /* [n_colors + 1] each */);
 
+/* The VARIANTS (csrc/tpc_variants.hip): which allele every genome carries through every superbubble.  No counterpart in the reference;
+ * ComputeVariants of twopaco_amd/host/graphformat.h is the serial statement the kernels are tested against.  The definition, over the
+ * event table of the last tpc_segments_build_*, its colour table, its link table and the superbubble table built with max_inside M:
+ *   EVENT, ROW, SIDE, COLOUR  row(e), side(e) = row(e) * 2 + (name[e] < 0), rev(side) = side ^ 1, seq(e) and colour(e) =
+ *                    color_of_seq[seq(e)] as in the groups above.  Superbubble row b has entrance[b], exit[b] and its members, the inside
+ *                    sides in ascending code.
+ *   WALK             for an event e and a direction d: d = + (0) visits e, e + 1, .. reading side(x); d = - (1) visits e, e - 1, ..
+ *                    reading rev(side(x)), the same sequence read on its other strand.  A walk never leaves the events of seq(e).
+ *   TRAVERSAL        a walk (e, d) is a traversal of row b when its first side read is entrance[b], every following side is a member of
+ *                    b until the side read is exit[b] -- that event is its `last` -- and it reaches last before its sequence ends.  A
+ *                    walk that runs out of sequence is not a traversal (a contig end inside the superbubble).  A walk that reads a side
+ *                    that is neither a member nor the exit is not one either and is counted in STRAYS (0 by the matching property).  By
+ *                    acyclicity a traversal reads at most inside[b] members: every walk is bounded by M + 1 steps.  Every event starts
+ *                    at most two traversals: + for the row whose entrance is side(e), - for the row whose entrance is rev(side(e)); a
+ *                    side is the entrance of at most one row.  Traversals are numbered in the order (e, d), + before -.  Per
+ *                    traversal: start, last, d, row, mask (bit i set when member i of the row's member list was read) and edges =
+ *                    |begin[hi] - end[lo]| with lo, hi the smaller and larger of start and last: the sum of the weights of the members
+ *                    read, 0 for a walk straight from entrance to exit.
+ *   ALLELE           two traversals of one row are the same allele iff their masks are equal (in an acyclic set of arcs the vertices of
+ *                    a path determine the path).  Per allele: row, mask, sides = popcount(mask), edges (equal for all its
+ *                    traversals), traversals (64-bit), first (its smallest traversal), presence (W words: the colours with such a
+ *                    traversal) and n_colors.  Alleles are numbered ascending by (row, first).
+ *   SITE             a superbubble row with at least one traversal: its alleles are allele_offset[b] .. allele_offset[b + 1], its
+ *                    traversals their sum.  The histogram counts the sites by their number of alleles.  alleles[b] <= paths[b].
+ *   REFERENCE        with ref_color != 0xFFFFFFFF: ref_allele[b] is the allele (its number among all alleles) of the smallest traversal
+ *                    of b whose colour(start) == ref_color, all ones without one; ref_traversals[b] counts such traversals.
+ *   EXACT            integers, minima, ORs and commutative sums: nothing depends on the schedule.
+ * Separate from the builds and opt-in: a context that never calls it holds none of this; every other stage's arrays are what they
+ * were, in any order of the builds.
+ *   tpc_segments_variants_build      the side of every event, a map from entrance to row, one thread per (event, direction) that walks
+ *                                    at most M + 1 steps inside its sequence's events and finds each member's bit by a binary search
+ *                                    in the row's members; one scan compacts the traversals in order; two stable radix sorts order
+ *                                    them by (row, mask), so that an allele is a run, its first traversal the run's head and its
+ *                                    count the run's length; one more sort numbers the alleles by (row, first); presence by atomicOr,
+ *                                    the reference by atomicMin and atomicAdd per site.  No loop is unbounded.  color_of_seq [n_rec]
+ *                                    and n_colors must be those of the colour build (the caller's promise; the count is checked).
+ *                                    Refused with an error text that begins "segment variants:", the context staying usable: no
+ *                                    segment, colour, link or superbubble table, a segment table that holds the walk's error, a colour
+ *                                    >= n_colors, ref_color >= n_colors and not 0xFFFFFFFF, 2^31 events or more (two walks per event
+ *                                    are numbered in 32 bits, which also covers 2^32 - 1 events), buffers beyond the free device
+ *                                    memory.  Kept until the next segment, colour, link, superbubble or variant build: 28 B per
+ *                                    traversal, 36 B + 4 W B per allele, 24 B per superbubble row; during the call 44 B per event
+ *                                    and 52 B per traversal more.  TPC_K_VARIANTS times the stage on the stream from its first
+ *                                    kernel to its last, its three waits for the counts included.  Option (tests, the next build
+ *                                    only; see tpc_set_option): test_variants_grid.
+ *   tpc_segments_variants_info       info[0] sites, [1] alleles, [2] traversals, [3] strays, [4] the stage's device bytes at their
+ *                                    peak, [5] colours, [6] ref_color (0xFFFFFFFF: none), [7] histogram bins (the most alleles of a
+ *                                    site + 1), [8] superbubble rows
+ *   tpc_segments_variants_fetch_traversals  start / last / d / row / edges / mask of traversals [t0, t0 + n)
+ *   tpc_segments_variants_fetch_alleles     row / sides / edges / first / n_colors / mask / traversals of alleles [a0, a0 + n)
+ *   tpc_segments_variants_fetch_presence    the W = ceil(colours / 32) presence words of alleles [a0, a0 + n)
+ *   tpc_segments_variants_fetch_sites       of superbubble rows [b0, b0 + n): allele_offset (n + 1 entries), traversals, ref_allele,
+ *                                           ref_traversals
+ *   tpc_segments_variants_fetch_hist        sites by number of alleles, info[7] entries
+ * A range outside the table is refused with an error text. */
+int tpc_segments_variants_build(tpc_ctx *ctx, const uint32_t *color_of_seq /* [n_rec] */, uint32_t n_colors, uint32_t ref_color /* 0xFFFFFFFF: none */);
+int tpc_segments_variants_info(tpc_ctx *ctx, uint64_t *info /* [9] */);
+int tpc_segments_variants_fetch_traversals(tpc_ctx *ctx, uint64_t t0, uint64_t n, uint32_t *start, uint32_t *last, uint32_t *dir, uint32_t *row, uint32_t *edges, uint64_t *mask);
+int tpc_segments_variants_fetch_alleles(tpc_ctx *ctx, uint64_t a0, uint64_t n, uint32_t *row, uint32_t *sides, uint32_t *edges, uint32_t *first, uint32_t *n_colors, uint64_t *mask,
+                                        uint64_t *traversals);
+int tpc_segments_variants_fetch_presence(tpc_ctx *ctx, uint64_t a0, uint64_t n, uint32_t *words_host /* [n x W] */);
+int tpc_segments_variants_fetch_sites(tpc_ctx *ctx, uint64_t b0, uint64_t n, uint32_t *allele_offset /* [n + 1] */, uint64_t *traversals, uint32_t *ref_allele, uint64_t *ref_traversals);
+int tpc_segments_variants_fetch_hist(tpc_ctx *ctx, uint64_t *sites_host /* [info[7]] */);
+
 /* ---- parity taps (debug; used by tests/) ---------------------------------------------- */
 uint64_t tpc_filter_words(const tpc_ctx *ctx);               /* 2^L/32 + 1, concurrentbitvector.cpp:12 (sharded: 2^L/32/world) */
 int tpc_filter_download(tpc_ctx *ctx, uint32_t *words_host); /* tpc_filter_words words       */
@@ -1064,6 +1129,8 @@ double tpc_kernel_ms(const tpc_ctx *ctx, int which);
  *   test_classes_wide  tests only, the next tpc_segments_classes_build alone: 1 forces the wave-per-row form at any W, 2 the
  *                      thread-per-row form (0 = by W)
  *   test_tracks_grid   tests only, the next tpc_segments_tracks_build alone: at most n workgroups per kernel of the stage (0 = by the
+ *                      events), so that a table of a few thousand events makes every workgroup stride several times
+ *   test_variants_grid tests only, the next tpc_segments_variants_build alone: at most n workgroups per kernel of the stage (0 = by the
  *                      events), so that a table of a few thousand events makes every workgroup stride several times
  *   test_distances_chunk_words  tests only: the next tpc_segments_distances_build stages n column words (64 rows each) per chunk
  *                      instead of its own 64 (0 = its own; more than 64 is refused), so that a table of a few hundred rows crosses

@@ -13,7 +13,7 @@ DISTANCES_TILE = 32  # TPC_DISTANCES_TILE of csrc/tpc_ctx.h, what Context.stat("
                      # the Gram kernel owns; here for the tests' parametrisation, and tests/test_gpu_distances.py holds the two equal
 KERNELS = {"fused": 12, "filter_reset": 0, "insert": 1, "query": 2, "compact": 3, "filter2": 4, "scan2": 5, "sort": 6, "emit": 7, "split": 8,
            "shard_hash": 9, "shard_apply": 10, "stream": 11, "lookup": 13, "combine": 14, "segments": 15, "segtext": 16, "sketch": 17, "colors": 18, "links": 19, "bubbles": 20,
-           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25, "classes": 26, "tracks": 27}
+           "distances": 21, "components": 22, "superbubbles": 23, "anchors": 24, "locate": 25, "classes": 26, "tracks": 27, "variants": 28}
 
 # every symbol include/twopaco_hip.h declares
 HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_params", "tpc_seq_upload",
@@ -47,7 +47,10 @@ HIP_SYMBOLS = ["tpc_ctx_create", "tpc_ctx_destroy", "tpc_last_error", "tpc_set_p
                "tpc_segments_classes_build", "tpc_segments_classes_info", "tpc_segments_classes_fetch_members", "tpc_segments_classes_fetch_rows",
                "tpc_segments_classes_fetch_presence", "tpc_segments_classes_fetch_sets",
                "tpc_segments_tracks_build", "tpc_segments_tracks_info", "tpc_segments_tracks_fetch_rows", "tpc_segments_tracks_fetch_colors",
-               "tpc_segments_tracks_fetch_depth"]
+               "tpc_segments_tracks_fetch_depth",
+               "tpc_segments_variants_build", "tpc_segments_variants_info", "tpc_segments_variants_fetch_traversals", "tpc_segments_variants_fetch_alleles",
+               "tpc_segments_variants_fetch_presence", "tpc_segments_variants_fetch_sites", "tpc_segments_variants_fetch_hist"]
+VARIANTS_NONE = 0xFFFFFFFF  # ref_color of tpc_segments_variants_build: no reference; ref_allele: no traversal of the reference
 TRACKS_ALL = 0xFFFFFFFF  # only_color of tpc_segments_tracks_build: every colour
 SEGMENT_ERRORS = {0: None, 1: "The input is corrupted", 2: "A vertex id is too large, cannot generate GFA"}  # TPC_SEG_*: what graphdump's serial walk throws
 
@@ -229,6 +232,13 @@ def hip():
         L.tpc_segments_tracks_fetch_rows.argtypes = [p, u64, u64, p, p, p]
         L.tpc_segments_tracks_fetch_colors.argtypes = [p, p, p, p, p]
         L.tpc_segments_tracks_fetch_depth.argtypes = [p, p, p]
+        L.tpc_segments_variants_build.argtypes = [p, p, u32, u32]
+        L.tpc_segments_variants_info.argtypes = [p, p]
+        L.tpc_segments_variants_fetch_traversals.argtypes = [p, u64, u64, p, p, p, p, p, p]
+        L.tpc_segments_variants_fetch_alleles.argtypes = [p, u64, u64, p, p, p, p, p, p, p]
+        L.tpc_segments_variants_fetch_presence.argtypes = [p, u64, u64, p]
+        L.tpc_segments_variants_fetch_sites.argtypes = [p, u64, u64, p, p, p, p]
+        L.tpc_segments_variants_fetch_hist.argtypes = [p, p]
         L.tpc_distinct_sketch.argtypes = [p, ci, p, p]
         L.tpc_host_alloc.argtypes = [ctypes.POINTER(p), u64]
         L.tpc_host_free.argtypes = [p]
@@ -982,6 +992,57 @@ class Context:
         out = [np.zeros(self.segments_tracks_info()["colors"] + 1, dtype=np.uint64) for _ in range(2)]
         self._ck(hip().tpc_segments_tracks_fetch_depth(self._h, *[a.ctypes.data for a in out]))
         return tuple(out)
+
+    def segments_variants_build(self, color_of_seq, n_colors, ref=None):
+        """The variants (csrc/tpc_variants.hip) over the table of the last segments_build and the colour, link and superbubble tables
+        built over it, the colour table with the same color_of_seq (the caller's promise); ref: the reference colour, None = none.
+        The option test_variants_grid (set_option) caps the workgroups per kernel for the next build alone.  Returns segments_variants_info()."""
+        col = np.ascontiguousarray(color_of_seq, dtype=np.uint32)
+        self._ck(hip().tpc_segments_variants_build(self._h, col.ctypes.data if col.size else None, n_colors, VARIANTS_NONE if ref is None else ref))
+        return self.segments_variants_info()
+
+    def segments_variants_info(self):
+        """dict: sites, alleles, traversals, strays, peak_bytes, colors, ref (None: no reference), hist_bins, superbubbles."""
+        c = np.zeros(9, dtype=np.uint64)
+        self._ck(hip().tpc_segments_variants_info(self._h, c.ctypes.data))
+        d = dict(zip(("sites", "alleles", "traversals", "strays", "peak_bytes", "colors", "ref", "hist_bins", "superbubbles"), (int(x) for x in c)))
+        d["ref"] = None if d["ref"] == VARIANTS_NONE else d["ref"]
+        return d
+
+    def segments_variants_fetch_traversals(self, t0=0, n=None):
+        """(start, last, d, row, edges as uint32, mask as uint64) of traversals [t0, t0 + n); n = None: to the last one."""
+        n = self.segments_variants_info()["traversals"] - t0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(5)] + [np.zeros(max(n, 0), dtype=np.uint64)]
+        self._ck(hip().tpc_segments_variants_fetch_traversals(self._h, t0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_variants_fetch_alleles(self, a0=0, n=None):
+        """(row, sides, edges, first, n_colors as uint32, mask, traversals as uint64) of alleles [a0, a0 + n); n = None: to the last one."""
+        n = self.segments_variants_info()["alleles"] - a0 if n is None else n
+        out = [np.zeros(max(n, 0), dtype=np.uint32) for _ in range(5)] + [np.zeros(max(n, 0), dtype=np.uint64) for _ in range(2)]
+        self._ck(hip().tpc_segments_variants_fetch_alleles(self._h, a0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_variants_fetch_presence(self, a0=0, n=None):
+        """The presence words of alleles [a0, a0 + n) as uint32 [n, W]; n = None: to the last one."""
+        info = self.segments_variants_info()
+        n = info["alleles"] - a0 if n is None else n
+        out = np.zeros((max(n, 0), (info["colors"] + 31) // 32), dtype=np.uint32)
+        self._ck(hip().tpc_segments_variants_fetch_presence(self._h, a0, n, out.ctypes.data))
+        return out
+
+    def segments_variants_fetch_sites(self, b0=0, n=None):
+        """(allele_offset uint32 [n + 1], traversals uint64, ref_allele uint32, ref_traversals uint64) of superbubble rows [b0, b0 + n)."""
+        n = self.segments_variants_info()["superbubbles"] - b0 if n is None else n
+        out = [np.zeros(max(n, 0) + 1, dtype=np.uint32), np.zeros(max(n, 0), dtype=np.uint64), np.zeros(max(n, 0), dtype=np.uint32), np.zeros(max(n, 0), dtype=np.uint64)]
+        self._ck(hip().tpc_segments_variants_fetch_sites(self._h, b0, n, *[a.ctypes.data for a in out]))
+        return tuple(out)
+
+    def segments_variants_fetch_hist(self):
+        """The sites by their number of alleles as uint64 [hist_bins]."""
+        out = np.zeros(self.segments_variants_info()["hist_bins"], dtype=np.uint64)
+        self._ck(hip().tpc_segments_variants_fetch_hist(self._h, out.ctypes.data))
+        return out
 
     def segments_anchors_build(self, color_of_seq, n_colors, ref_color=0):
         """The anchor blocks (csrc/tpc_anchors.hip) of every other colour against ref_color, over the table of the last segments_build,

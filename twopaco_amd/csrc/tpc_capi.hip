@@ -401,6 +401,7 @@ int tpc_set_option(tpc_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "test_classes_grid")) { c->opt_classes_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }
     if (!strcmp(name, "test_classes_wide")) { c->opt_classes_wide = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 3)); return 0; }
     if (!strcmp(name, "test_tracks_grid")) { c->opt_tracks_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }  // tests only: workgroups per kernel of the next tpc_segments_tracks_build
+    if (!strcmp(name, "test_variants_grid")) { c->opt_variants_grid = value > 0 ? (int)std::min<int64_t>(value, 1 << 20) : 0; return 0; }  // tests only: workgroups per kernel of the next tpc_segments_variants_build
     if (!strcmp(name, "test_fail_mallocs")) { tpc_test_fail_mallocs.store(value > 0 ? (int)value : 0); return 0; }  // process-wide, tests only
     return fail(c, -1, "unknown option %s", name);
 }

@@ -30,6 +30,7 @@ void text_plan_drop(tpc_ctx *c)
 //   colours, links      <- superbubbles     (searched over the link rows' arcs, presence ORed over the colour rows)
 //   colours             <- classes          (the colour rows grouped by their presence words)
 //   colours             <- tracks           (the colour rows projected onto the sequences' events)
+//   superbubbles        <- variants         (the sequences walked through the superbubble rows and their member lists)
 //   segments <- anchors                     (paired and chained over the event table alone)
 //   segments <- edges   <- locate           (the index holds positions of the build's text and rows; a locate holds hits in that index)
 //   segments <- the graph text's plan
@@ -43,8 +44,14 @@ void distances_drop(tpc_ctx *c) { free_all({c->dst.mat}); c->dst = {}; }
 void classes_drop(tpc_ctx *c) { free_all({c->cls.class_of, c->cls.first, c->cls.sums, c->cls.presence, c->cls.sets}); c->cls = {}; }
 void tracks_drop(tpc_ctx *c) { free_all({c->trk.rows, c->trk.sums}); c->trk = {}; }
 void components_drop(tpc_ctx *c) { free_all({c->cmp.component, c->cmp.root, c->cmp.sums, c->cmp.presence}); c->cmp = {}; }
+void variants_drop(tpc_ctx *c)
+{
+    free_all({c->var.trv, c->var.trv_mask, c->var.all, c->var.all64, c->var.presence, c->var.site_off, c->var.ref_allele, c->var.site64, c->var.hist});
+    c->var = {};
+}
 void superbubbles_drop(tpc_ctx *c)
 {
+    variants_drop(c);
     free_all({c->sbb.off, c->sbb.heads, c->sbb.exit_of, c->sbb.u32, c->sbb.u64, c->sbb.presence, c->sbb.member_off, c->sbb.members});
     c->sbb = {};
 }

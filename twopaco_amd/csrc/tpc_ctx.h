@@ -15,6 +15,7 @@
 //   tpc_edgehash.h        the two-strand rolling hash of an edge, shared by tpc_sketch.hip and tpc_locate.hip
 //   tpc_classes.hip       the colour classes over the colour table (tpc_segments_classes_*), kernels and entry points
 //   tpc_tracks.hip        the presence tracks: the colour rows projected onto the sequences' coordinates (tpc_segments_tracks_*), kernels and entry points
+//   tpc_variants.hip      the variants: the sequences walked through the superbubbles, grouped into alleles (tpc_segments_variants_*), kernels and entry points
 //   tpc_stage.h           what the eight stages above share on the host side: preconditions, the free-memory refusal, temporaries, the planar fetch
 //   tpc_segrows.h         the row of every event, rebuilt by the colour, link, bubble and component stages: its owner and the device helpers over it
 //   tpc_sketch.hip        the distinct-edge sketch behind `-f auto` (tpc_distinct_sketch), kernel and entry point
@@ -237,6 +238,22 @@ struct tpc_ctx {
         uint32_t n_colors = 0, only = 0;
         bool valid = false;
     } trk;
+    // variants (tpc_segments_variants_*, tpc_variants.hip) of the last tpc_segments_variants_build
+    struct Variants {
+        uint32_t *trv = nullptr;             // device, [5][n_trav]: start, last, d, row, edges
+        unsigned long long *trv_mask = nullptr;  // device, [n_trav]
+        uint32_t *all = nullptr;             // device, [5][n_all]: row, sides, edges, first, n_colors
+        unsigned long long *all64 = nullptr; // device, [2][n_all]: mask, traversals
+        uint32_t *presence = nullptr;        // device, [n_all][words]
+        uint32_t *site_off = nullptr;        // device, [n_sbb + 1]: the first allele of every superbubble row
+        uint32_t *ref_allele = nullptr;      // device, [n_sbb]: all ones for none
+        unsigned long long *site64 = nullptr;  // device, [2][n_sbb]: traversals, ref_traversals
+        unsigned long long *hist = nullptr;  // device, [hist_bins]: the sites by their number of alleles
+        uint64_t n_trav = 0, n_all = 0, n_sbb = 0, sites = 0, strays = 0, hist_bins = 0, peak_bytes = 0;
+        uint32_t n_colors = 0, words = 0, ref = 0;
+        bool valid = false;
+    } var;
+    int opt_variants_grid = 0;               // option test_variants_grid (tests only), for the next tpc_segments_variants_build alone: at most this many workgroups per kernel, 0 = by the events
     int opt_tracks_grid = 0;                 // option test_tracks_grid (tests only), for the next tpc_segments_tracks_build alone: at most this many workgroups per kernel, 0 = by the events
     int opt_edges_slots_log2 = 0;            // option test_edges_slots_log2 (tests only): slots of the edge index, 0 = by the edges
     int opt_edges_hash_bits = 0;             // option test_edges_hash_bits (tests only): bits of the edge's hash that are kept, 0 = all 64
@@ -358,7 +375,7 @@ bool part_hash_supported(const tpc_ctx *c);
 bool plan_query(const tpc_ctx *c, uint64_t lo, uint64_t hi, bool gated, TpcQPlan &pl);
 int compact_mask(tpc_ctx *c, const uint32_t *m);
 void stream_part_release(tpc_ctx *c);   // tpc_capi_pass2.hip
-void colors_drop(tpc_ctx *c);           // these eleven and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
+void colors_drop(tpc_ctx *c);           // these twelve and segments_drop: tpc_capi_segments.hip, where who drops whom is written once
 void links_drop(tpc_ctx *c);
 void bubbles_drop(tpc_ctx *c);
 void distances_drop(tpc_ctx *c);
@@ -369,6 +386,7 @@ void edges_drop(tpc_ctx *c);
 void locate_drop(tpc_ctx *c);
 void classes_drop(tpc_ctx *c);
 void tracks_drop(tpc_ctx *c);
+void variants_drop(tpc_ctx *c);
 
 #define HIPCHK(c, expr)                                                                         \
     do {                                                                                        \

@@ -1,5 +1,5 @@
-// tpc_stage.h -- what the stages over the segment table (tpc_colors.hip, tpc_links.hip, tpc_bubbles.hip, tpc_distances.hip, tpc_components.hip, tpc_superbubbles.hip, tpc_anchors.hip, tpc_locate.hip, tpc_classes.hip, tpc_tracks.hip) share
-// on the host side.  `noun` is the stage's name in its error texts: "colours", "links", "bubbles", "distances", "components", "superbubbles", "anchors", "edges", "locate", "classes", "tracks".  Every including unit
+// tpc_stage.h -- what the stages over the segment table (tpc_colors.hip, tpc_links.hip, tpc_bubbles.hip, tpc_distances.hip, tpc_components.hip, tpc_superbubbles.hip, tpc_anchors.hip, tpc_locate.hip, tpc_classes.hip, tpc_tracks.hip, tpc_variants.hip) share
+// on the host side.  `noun` is the stage's name in its error texts: "colours", "links", "bubbles", "distances", "components", "superbubbles", "anchors", "edges", "locate", "classes", "tracks", "variants".  Every including unit
 // gets its own copy (anonymous namespace), as of tpc_segrows.h: the library exports none of it.
 #pragma once
 #include "tpc_ctx.h"

@@ -55,7 +55,11 @@
 // --tracks file|sequence [--tracks-of N] [--tracks-out F] [--tracks-bedgraph F]: the presence tracks of the input sequences -- for
 // every stretch of every sequence the colours that share it -- as TSV of integers, byte for byte what `graphdump --tracks` writes, and
 // asked for, a bedGraph of the number of colours (csrc/tpc_tracks.hip projects the colour rows onto the events on the device; combines
-// with everything above from one segment and colour build; the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
+// with everything above from one segment and colour build; the same colours; its files are written after the class files);
+// --variants file|sequence [--variants-ref N] [--variants-out F] [--variants-vcf F]: the alleles every genome walks through every
+// superbubble as TSV of integers, byte for byte what `graphdump --variants` writes, and with a reference colour, as VCF 4.2
+// (csrc/tpc_variants.hip walks the events on the device; combines with everything above from one segment, colour, link and
+// superbubble build; the same colours; its files are written last).  Errors go to stderr as "\nError: <what>\n", exit code 1
 // (reference constructor.cpp:179-188).
 #include <algorithm>
 #include <cmath>
@@ -116,6 +120,7 @@ namespace
 			<< "               [--locate <file|sequence> --locate-in <file name> ... [--locate-out <file name>] [--locate-walks <file name>]]" << std::endl
 			<< "               [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>]" << std::endl
 			<< "               [--tracks <file|sequence>] [--tracks-of <integer>] [--tracks-out <file name>] [--tracks-bedgraph <file name>]" << std::endl
+			<< "               [--variants <file|sequence>] [--variants-ref <integer>] [--variants-out <file name>] [--variants-vcf <file name>]" << std::endl
 			<< "               <fasta files with genomes> ..." << std::endl
 			<< "       -f auto: the filter size (and, without -r, the rounds) from a count of the input's distinct edges taken on the GPU" << std::endl
 			<< "               (one GPU; not with --load-filter or --test)" << std::endl
@@ -178,7 +183,13 @@ namespace
 			<< "               of equal presence merged into one interval: sequence, begin, end, occurrences, number of colours and presence bits; in" << std::endl
 			<< "               front per colour its intervals, edges, core and private edges, and the intervals and edges by number of colours." << std::endl
 			<< "               --tracks-of: the sequences of this one colour only.  --tracks-bedgraph: also the number of colours per interval as" << std::endl
-			<< "               bedGraph.  Combines with all tables above (the same colours); written last.  One GPU only." << std::endl;
+			<< "               bedGraph.  Combines with all tables above (the same colours).  One GPU only." << std::endl
+			<< "       --variants: also write the alleles the genomes walk through the superbubbles as TSV to --variants-out (default" << std::endl
+			<< "               de_bruijn.variants.tsv): every sequence walked through every superbubble (--superbubbles-max) on both strands, the walks" << std::endl
+			<< "               that read the same inside sides are one allele: site, entrance, exit, allele, traversals, sides, edges, number of colours," << std::endl
+			<< "               presence bits, the span of its first traversal and whether it is the reference's.  --variants-ref: the reference colour." << std::endl
+			<< "               --variants-vcf: with a reference, also VCF 4.2 on the reference's coordinates, one sample per colour, not normalised." << std::endl
+			<< "               Combines with all tables above (the same colours); written last.  One GPU only." << std::endl;
 	}
 }
 
@@ -331,8 +342,8 @@ int main(int argc, char * argv[])
 
 		// every table beside every other, each into a file of its own, on one GPU; the complaints are looked for in the tables' order
 		namespace GF = TwoPaCo::GraphFormat;
-		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE, GF::CLASSES, GF::TRACKS}, false, false, false, false,
-			{0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
+		const GF::TableCliRules rules = {"", {GF::COLORS, GF::LINKS, GF::BUBBLES, GF::DISTANCES, GF::COMPONENTS, GF::SUPERBUBBLES, GF::ANCHORS, GF::LOCATE, GF::CLASSES, GF::TRACKS, GF::VARIANTS}, false, false, false, false,
+			{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, {false, false, false, false, false, false, false, false, false, false, false}, options.gpus, true, fileName.size()};
 		GF::CheckTableOptions(tables, rules);
 		options.tables = tables.request;
 		optionsSet = optionsSet || options.tables.Any();

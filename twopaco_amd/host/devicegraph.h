@@ -35,7 +35,9 @@
 	X(segments_edges_build) X(segments_edges_info) X(segments_locate) X(segments_locate_info) X(segments_locate_fetch_runs) X(segments_locate_fetch_records) \
 	X(segments_locate_fetch_shared) \
 	X(segments_classes_build) X(segments_classes_info) X(segments_classes_fetch_members) X(segments_classes_fetch_rows) X(segments_classes_fetch_presence) \
-	X(segments_tracks_build) X(segments_tracks_info) X(segments_tracks_fetch_rows) X(segments_tracks_fetch_colors) X(segments_tracks_fetch_depth)
+	X(segments_tracks_build) X(segments_tracks_info) X(segments_tracks_fetch_rows) X(segments_tracks_fetch_colors) X(segments_tracks_fetch_depth) \
+	X(segments_variants_build) X(segments_variants_info) X(segments_variants_fetch_traversals) X(segments_variants_fetch_alleles) X(segments_variants_fetch_presence) \
+	X(segments_variants_fetch_sites)
 
 namespace TwoPaCo
 {
@@ -286,6 +288,44 @@ namespace TwoPaCo
 			return true;
 		}
 
+		// The variants (csrc/tpc_variants.hip): every sequence walked through the superbubbles of the superbubble build on the device.
+		inline void BuildVariants(const Api & api, const GraphFormat::ColorMap & map, uint32_t ref)
+		{
+			api.check(api.segments_variants_build(api.ctx, map.colorOfSequence.data(), uint32_t(map.label.size()), ref), "segments_variants_build");
+		}
+
+		// ... fetched: the traversals, the alleles with their presence words and the sites.  false, and nothing fetched, when the stage
+		// saw other colours or superbubbles than the caller
+		inline bool FetchVariants(const Api & api, const GraphFormat::ColorMap & map, uint64_t segments, size_t superbubbles, GraphFormat::VariantTable & out)
+		{
+			uint64_t info[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+			api.check(api.segments_variants_info(api.ctx, info), "segments_variants_info");
+			if (info[5] != map.label.size() || info[8] != superbubbles) return false;
+			const size_t alleles = size_t(info[1]), n = size_t(info[2]), words = size_t((info[5] + 31) / 32);
+			out.colors = info[5];
+			out.segments = segments;
+			out.strays = info[3];
+			out.ref = uint32_t(info[6]);
+			for (std::vector<uint32_t> * v : {&out.start, &out.last, &out.dir, &out.row, &out.edges}) v->resize(n);
+			out.mask.resize(n);
+			for (std::vector<uint32_t> * v : {&out.alleleRow, &out.sides, &out.alleleEdges, &out.first, &out.nColors}) v->resize(alleles);
+			out.alleleMask.resize(alleles);
+			out.traversals.resize(alleles);
+			out.presence.resize(alleles * words);
+			out.alleleOffset.resize(superbubbles + 1);
+			out.refAllele.resize(superbubbles);
+			out.siteTraversals.resize(superbubbles);
+			out.refTraversals.resize(superbubbles);
+			api.check(api.segments_variants_fetch_traversals(api.ctx, 0, n, out.start.data(), out.last.data(), out.dir.data(), out.row.data(), out.edges.data(), out.mask.data()),
+				"segments_variants_fetch_traversals");
+			api.check(api.segments_variants_fetch_alleles(api.ctx, 0, alleles, out.alleleRow.data(), out.sides.data(), out.alleleEdges.data(), out.first.data(), out.nColors.data(),
+				out.alleleMask.data(), out.traversals.data()), "segments_variants_fetch_alleles");
+			api.check(api.segments_variants_fetch_presence(api.ctx, 0, alleles, out.presence.data()), "segments_variants_fetch_presence");
+			api.check(api.segments_variants_fetch_sites(api.ctx, 0, superbubbles, out.alleleOffset.data(), out.siteTraversals.data(), out.refAllele.data(), out.refTraversals.data()),
+				"segments_variants_fetch_sites");
+			return true;
+		}
+
 		// The bounded superbubbles (csrc/tpc_superbubbles.hip), searched over the link rows' arcs, presence ORed over the colour rows.
 		inline void BuildSuperbubbles(const Api & api, uint32_t maxInside)
 		{
@@ -450,9 +490,9 @@ namespace TwoPaCo
 		// and the bubble stage it would find 12 B per link, 4 B per 32 events and, with --bubbles, 24 B per segment and 16 B per bubble
 		// more resident, which a run that just fits the device does not have.
 		const int STAGES_LINKS_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::DISTANCES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS, GraphFormat::VARIANTS};
 		const int STAGES_DISTANCES_FIRST[GraphFormat::TABLES] = {GraphFormat::COLORS, GraphFormat::DISTANCES, GraphFormat::LINKS, GraphFormat::BUBBLES, GraphFormat::COMPONENTS,
-			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS};
+			GraphFormat::SUPERBUBBLES, GraphFormat::ANCHORS, GraphFormat::LOCATE, GraphFormat::CLASSES, GraphFormat::TRACKS, GraphFormat::VARIANTS};
 
 		// The caller's clock and [timing] lines.  built: after a stage's build, with the stage and its TPC_K_* (EDGES, then LOCATE
 		// once its batches are through: their kernel time is locateKernelMs, not the last batch's); fetched: after a stage's fetch.
@@ -490,7 +530,7 @@ namespace TwoPaCo
 			for (int at = 0; at < TABLES; at++)
 			{
 				const int stage = order[at];
-				if (stage == COLORS ? !NeedsColorBuild(request) : stage == LINKS ? !NeedsLinkBuild(request) && !linkBits : !request.On(TableId(stage))) continue;
+				if (stage == COLORS ? !NeedsColorBuild(request) : stage == LINKS ? !NeedsLinkBuild(request) && !linkBits : stage == SUPERBUBBLES ? !NeedsSuperbubbleBuild(request) : !request.On(TableId(stage))) continue;
 				switch (stage)
 				{
 				case COLORS:
@@ -537,6 +577,11 @@ namespace TwoPaCo
 					BuildTracks(api, t.map, request.tracksOf);
 					observer.built(stage, TPC_K_TRACKS);
 					agree(FetchTracks(api, t.map, t.segments, t.tracks), "track", "colour map", "colours");
+					break;
+				case VARIANTS:
+					BuildVariants(api, t.map, request.variantsRef);
+					observer.built(stage, TPC_K_VARIANTS);
+					agree(FetchVariants(api, t.map, t.segments, t.superbubbles.Rows(), t.variants), "variant", "colour map", "colours or the superbubbles");
 					break;
 				case LOCATE:
 					uint64_t edges[6] = {0, 0, 0, 0, 0, 0};

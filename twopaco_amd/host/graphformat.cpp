@@ -1700,6 +1700,397 @@ namespace TwoPaCo
 			}
 		}
 
+		void ComputeVariants(const EventTable & t, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t nColors, const ColorTable & colors, const SuperbubbleTable & b,
+			uint32_t ref, VariantTable & out)
+		{
+			(void)k;
+			const uint32_t NONE = VariantTable::NONE;
+			if (nColors == 0) throw std::runtime_error("variant table: at least one colour is required");
+			if (ref != NONE && ref >= nColors) throw std::runtime_error("variant table: the reference colour is " + std::to_string(ref) + ", there are " + std::to_string(nColors) + " colours");
+			if (colorOfSequence.size() != t.sequences) throw std::runtime_error("variant table: the colour of every sequence is required");
+			for (uint32_t c : colorOfSequence)
+			{
+				if (c >= nColors) throw std::runtime_error("variant table: a sequence has the colour " + std::to_string(c) + ", there are " + std::to_string(nColors) + " colours");
+			}
+
+			if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+			CheckSuperbubbles(t, colors, b);
+			const size_t rows = colors.Rows(), words = size_t((nColors + 31) / 32), nb = b.Rows();
+			out = VariantTable();
+			out.colors = nColors;
+			out.segments = rows;
+			out.ref = ref;
+			// the side and the sequence of every event
+			const int64_t FRESH = int64_t(1) << 34;
+			std::unordered_map<int64_t, uint32_t> rowOf;
+			std::vector<uint32_t> side(t.events), sequenceOf(t.events);
+			uint32_t seen = 0;
+			size_t sequence = 0;
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				while (e >= t.seqEventBegin[sequence + 1]) ++sequence;
+				const int64_t name = Magnitude(t.name[e]);
+				std::unordered_map<int64_t, uint32_t>::const_iterator at = name >= FRESH ? rowOf.end() : rowOf.find(name);
+				uint32_t row = 0;
+				if (at == rowOf.end())
+				{
+					row = seen++;
+					if (name < FRESH) rowOf[name] = row;
+				}
+				else row = at->second;
+
+				if (row >= rows) throw std::runtime_error("variant table: the colour table holds fewer rows than the events have segments");
+				side[e] = row * 2 + (t.name[e] < 0 ? 1u : 0u);
+				sequenceOf[e] = uint32_t(sequence);
+			}
+
+			std::unordered_map<uint32_t, uint32_t> rowOfEntrance;
+			for (size_t r = 0; r < nb; r++) rowOfEntrance[b.entrance[r]] = uint32_t(r);
+			// both walks of every event
+			for (uint64_t e = 0; e < t.events; e++)
+			{
+				for (uint32_t d = 0; d < 2; d++)
+				{
+					std::unordered_map<uint32_t, uint32_t>::const_iterator at = rowOfEntrance.find(side[e] ^ d);
+					if (at == rowOfEntrance.end()) continue;
+					const uint32_t r = at->second;
+					const uint32_t * members = b.members.data() + b.memberOffset[r];
+					const uint32_t inside = b.inside[r];
+					const uint64_t lowest = t.seqEventBegin[sequenceOf[e]], beyond = t.seqEventBegin[sequenceOf[e] + 1];
+					uint64_t mask = 0, x = e;
+					bool reached = false;
+					for (uint32_t step = 0; step <= b.maxInside && !reached; step++)
+					{
+						if (d ? x == lowest : x + 1 == beyond) break;   // the sequence ends inside the superbubble
+						x = d ? x - 1 : x + 1;
+						const uint32_t read = side[x] ^ d;
+						if (read == b.exit[r]) { reached = true; break; }
+						const uint32_t * m = std::lower_bound(members, members + inside, read);
+						if (m == members + inside || *m != read) { out.strays += 1; break; }
+						mask |= uint64_t(1) << (m - members);
+					}
+
+					if (!reached) continue;
+					const uint64_t lo = std::min(e, x), hi = std::max(e, x);
+					out.start.push_back(uint32_t(e));
+					out.last.push_back(uint32_t(x));
+					out.dir.push_back(d);
+					out.row.push_back(r);
+					out.mask.push_back(mask);
+					out.edges.push_back(t.begin[hi] >= t.end[lo] ? t.begin[hi] - t.end[lo] : t.end[lo] - t.begin[hi]);
+				}
+			}
+
+			// the alleles: (row, mask) -> its traversals, in the order (row, first)
+			const size_t n = out.Traversals();
+			std::map<std::pair<uint32_t, uint64_t>, uint32_t> found;   // -> first
+			for (size_t i = 0; i < n; i++) found.insert(std::make_pair(std::make_pair(out.row[i], out.mask[i]), uint32_t(i)));
+			std::vector<std::pair<uint32_t, uint32_t> > order;         // (row, first)
+			for (const auto & f : found) order.push_back(std::make_pair(f.first.first, f.second));
+			std::sort(order.begin(), order.end());
+			const size_t alleles = order.size();
+			std::map<std::pair<uint32_t, uint64_t>, uint32_t> alleleOf;
+			out.alleleOffset.assign(nb + 1, 0);
+			for (size_t a = 0; a < alleles; a++)
+			{
+				const uint32_t first = order[a].second;
+				alleleOf[std::make_pair(out.row[first], out.mask[first])] = uint32_t(a);
+				out.alleleRow.push_back(out.row[first]);
+				out.alleleMask.push_back(out.mask[first]);
+				out.sides.push_back(uint32_t(__builtin_popcountll(out.mask[first])));
+				out.alleleEdges.push_back(out.edges[first]);
+				out.first.push_back(first);
+				out.alleleOffset[out.row[first] + 1] += 1;
+			}
+
+			for (size_t r = 0; r < nb; r++) out.alleleOffset[r + 1] += out.alleleOffset[r];
+			out.traversals.assign(alleles, 0);
+			out.nColors.assign(alleles, 0);
+			out.presence.assign(alleles * words, 0);
+			out.refAllele.assign(nb, NONE);
+			out.siteTraversals.assign(nb, 0);
+			out.refTraversals.assign(nb, 0);
+			for (size_t i = 0; i < n; i++)
+			{
+				const uint32_t a = alleleOf[std::make_pair(out.row[i], out.mask[i])], c = colorOfSequence[sequenceOf[out.start[i]]], r = out.row[i];
+				out.traversals[a] += 1;
+				out.siteTraversals[r] += 1;
+				out.presence[a * words + c / 32] |= 1u << (c % 32);
+				if (c == ref)
+				{
+					if (out.refTraversals[r] == 0) out.refAllele[r] = a;
+					out.refTraversals[r] += 1;
+				}
+			}
+
+			for (size_t a = 0; a < alleles; a++)
+			{
+				for (size_t w = 0; w < words; w++) out.nColors[a] += uint32_t(__builtin_popcount(out.presence[a * words + w]));
+			}
+		}
+
+		namespace
+		{
+			void CheckVariants(const EventTable & t, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const SuperbubbleTable & b, const VariantTable & v)
+			{
+				CheckSuperbubbles(t, colors, b);
+				const size_t n = v.Traversals(), a = v.Alleles(), nb = b.Rows(), words = colors.Words();
+				if (v.last.size() != n || v.dir.size() != n || v.row.size() != n || v.edges.size() != n || v.mask.size() != n || v.alleleRow.size() != a || v.sides.size() != a ||
+					v.alleleEdges.size() != a || v.nColors.size() != a || v.alleleMask.size() != a || v.traversals.size() != a || v.presence.size() != a * words ||
+					v.alleleOffset.size() != nb + 1 || v.alleleOffset[0] != 0 || v.alleleOffset[nb] != a || v.refAllele.size() != nb || v.siteTraversals.size() != nb ||
+					v.refTraversals.size() != nb || map.label.size() != v.colors || colors.colors != v.colors || (v.ref != VariantTable::NONE && v.ref >= v.colors))
+				{
+					throw std::runtime_error("variant table: the arrays do not agree about the traversals, the alleles, the sites and the colours");
+				}
+
+				if (map.colorOfSequence.size() != t.sequences || seq.name.size() != t.sequences || seq.length.size() != t.sequences)
+				{
+					throw std::runtime_error("variant table: the colour, the name and the length of every sequence are required");
+				}
+
+				if (!t.seqEventBegin || t.seqEventBegin[0] != 0 || t.seqEventBegin[t.sequences] != t.events) throw std::runtime_error("event table: the sequences' event ranges do not cover the events");
+				for (size_t i = 0; i < n; i++)
+				{
+					if (v.start[i] >= t.events || v.last[i] >= t.events || v.row[i] >= nb || v.dir[i] > 1) throw std::runtime_error("variant table: a traversal lies outside the tables");
+				}
+
+				for (size_t r = 0; r < nb; r++)
+				{
+					if (v.alleleOffset[r + 1] < v.alleleOffset[r] || (v.refAllele[r] != VariantTable::NONE && (v.refAllele[r] < v.alleleOffset[r] || v.refAllele[r] >= v.alleleOffset[r + 1])))
+					{
+						throw std::runtime_error("variant table: a site's alleles are not its own");
+					}
+				}
+
+				for (size_t i = 0; i < a; i++)
+				{
+					if (v.first[i] >= n || v.alleleRow[i] >= nb) throw std::runtime_error("variant table: an allele lies outside the tables");
+				}
+			}
+
+			// the span of traversal i: its sequence and the positions [begin, end) in bases
+			struct VariantSpan
+			{
+				uint32_t sequence;
+				uint64_t begin, end;
+			};
+
+			VariantSpan MakeVariantSpan(const EventTable & t, size_t k, const VariantTable & v, size_t i)
+			{
+				const uint32_t lo = std::min(v.start[i], v.last[i]), hi = std::max(v.start[i], v.last[i]);
+				VariantSpan span;
+				span.sequence = uint32_t(std::upper_bound(t.seqEventBegin, t.seqEventBegin + t.sequences + 1, lo) - t.seqEventBegin - 1);
+				span.begin = t.end[lo];
+				span.end = uint64_t(t.begin[hi]) + k;
+				return span;
+			}
+
+			void AppendPresence(std::string & buf, const uint32_t * bits, size_t digits)
+			{
+				for (size_t j = 0; j < digits; j++) buf += "0123456789abcdef"[(bits[j >> 3] >> (4 * (j & 7))) & 15u];
+			}
+
+			// the letters of a span as stored, every letter other than A C G T an N
+			std::string SpanLetters(const LoadedSequences & loaded, const VariantSpan & span)
+			{
+				if (span.sequence >= loaded.body.size() || span.end > loaded.body[span.sequence].size() || span.begin > span.end)
+				{
+					throw std::runtime_error("variant table: a traversal lies outside the letters of its sequence");
+				}
+
+				std::string s = loaded.body[span.sequence].substr(size_t(span.begin), size_t(span.end - span.begin));
+				for (char & ch : s) if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T') ch = 'N';
+				return s;
+			}
+
+			std::string ReverseComplementN(const std::string & s)
+			{
+				std::string r(s.rbegin(), s.rend());
+				for (char & ch : r) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : 'N';
+				return r;
+			}
+		}
+
+		void WriteVariants(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const SuperbubbleTable & b,
+			const VariantTable & v, const std::string & path)
+		{
+			CheckVariants(t, map, seq, colors, b, v);
+			const size_t words = colors.Words(), digits = size_t((colors.colors + 3) / 4), nb = b.Rows();
+			std::map<uint32_t, uint64_t> byAlleles;
+			for (size_t r = 0; r < nb; r++) if (v.alleleOffset[r + 1] > v.alleleOffset[r]) byAlleles[v.alleleOffset[r + 1] - v.alleleOffset[r]] += 1;
+			WriteStreamed(path, "variant table", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "#twopaco-variants\t1\tby=" + std::string(map.bySequence ? "sequence" : "file") + "\tk=" + std::to_string(k) + "\tcolors=" + std::to_string(v.colors) +
+					"\tsegments=" + std::to_string(v.segments) + "\tsuperbubbles=" + std::to_string(nb) + "\tmax_inside=" + std::to_string(b.maxInside) + "\tref=" +
+					(v.ref == VariantTable::NONE ? std::string("none") : std::to_string(v.ref)) + "\tsites=" + std::to_string(v.Sites()) + "\talleles=" + std::to_string(v.Alleles()) +
+					"\ttraversals=" + std::to_string(v.Traversals()) + "\n";
+				for (uint64_t c = 0; c < v.colors; c++) buf += "#color\t" + std::to_string(c) + "\t" + map.label[c] + "\n";
+				for (size_t s = 0; s < seq.name.size(); s++)
+				{
+					buf += "#sequence\t" + std::to_string(s) + "\t" + std::to_string(map.colorOfSequence[s]) + "\t" + std::to_string(seq.length[s]) + "\t" + seq.name[s] + "\n";
+					flushIfLarge();
+				}
+
+				for (const auto & bin : byAlleles) buf += "#alleles\t" + std::to_string(bin.first) + "\t" + std::to_string(bin.second) + "\n";
+				for (size_t r = 0; r < nb; r++)
+				{
+					for (uint32_t a = v.alleleOffset[r]; a < v.alleleOffset[r + 1]; a++)
+					{
+						const VariantSpan span = MakeVariantSpan(t, k, v, v.first[a]);
+						buf += std::to_string(r);
+						buf += '\t';
+						AppendSide(buf, t, colors, b.entrance[r]);
+						buf += '\t';
+						AppendSide(buf, t, colors, b.exit[r]);
+						for (uint64_t value : {uint64_t(a - v.alleleOffset[r]), v.traversals[a], uint64_t(v.sides[a]), uint64_t(v.alleleEdges[a]), uint64_t(v.nColors[a])})
+						{
+							buf += '\t';
+							buf += std::to_string(value);
+						}
+
+						buf += '\t';
+						AppendPresence(buf, &v.presence[size_t(a) * words], digits);
+						buf += "\t" + std::to_string(span.sequence) + "\t" + std::to_string(span.begin) + "\t" + std::to_string(span.end) + "\t" + (v.dir[v.first[a]] ? "-" : "+") + "\t" +
+							(v.ref != VariantTable::NONE && v.refAllele[r] == a ? "1" : "0") + "\n";
+					}
+
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteVariantsVcf(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const LoadedSequences & loaded, const ColorTable & colors,
+			const SuperbubbleTable & b, const VariantTable & v, const std::string & path)
+		{
+			CheckVariants(t, map, seq, colors, b, v);
+			if (path.empty()) throw std::runtime_error("The variant VCF needs a file name");
+			if (v.ref == VariantTable::NONE) throw std::runtime_error("The variant VCF needs a reference colour");
+			if (k == 0) throw std::runtime_error("The variant VCF needs k above 0");
+			const size_t words = colors.Words(), nb = b.Rows();
+			// the reference traversal of every site: the smallest one that starts in the reference colour
+			std::vector<uint32_t> refTraversal(nb, VariantTable::NONE);
+			for (size_t i = v.Traversals(); i-- > 0;)
+			{
+				const VariantSpan span = MakeVariantSpan(t, k, v, i);
+				if (map.colorOfSequence[span.sequence] == v.ref) refTraversal[v.row[i]] = uint32_t(i);
+			}
+
+			struct Record
+			{
+				uint32_t sequence, site;
+				uint64_t pos;
+				bool operator < (const Record & o) const { return sequence != o.sequence ? sequence < o.sequence : pos != o.pos ? pos < o.pos : site < o.site; }
+			};
+
+			std::vector<Record> records;
+			for (size_t r = 0; r < nb; r++)
+			{
+				const uint32_t a0 = v.alleleOffset[r], a1 = v.alleleOffset[r + 1];
+				if (refTraversal[r] == VariantTable::NONE || v.refAllele[r] == VariantTable::NONE || a1 - a0 < 2) continue;
+				// (equal edges below k + 1 cannot be in a graph of all (k+1)-mers; under an abundance cut they are, and take the anchored form)
+				bool equal = v.alleleEdges[a0] >= k + 1;
+				for (uint32_t a = a0; a < a1; a++) equal = equal && v.alleleEdges[a] == v.alleleEdges[a0];
+				const VariantSpan span = MakeVariantSpan(t, k, v, refTraversal[r]);
+				const Record record = {span.sequence, uint32_t(r), span.begin + k + (equal ? 1 : 0)};
+				records.push_back(record);
+			}
+
+			std::sort(records.begin(), records.end());
+			WriteStreamed(path, "variant VCF", [&](std::string & buf, const std::function<void()> & flushIfLarge)
+			{
+				buf += "##fileformat=VCFv4.2\n##source=twopaco variants k=" + std::to_string(k) + " by=" + (map.bySequence ? "sequence" : "file") + " ref=" + std::to_string(v.ref) +
+					" max_inside=" + std::to_string(b.maxInside) + "\n";
+				for (size_t s = 0; s < seq.name.size(); s++)
+				{
+					if (map.colorOfSequence[s] == v.ref) buf += "##contig=<ID=" + seq.name[s] + ",length=" + std::to_string(seq.length[s]) + ">\n";
+				}
+
+				buf += "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Traversals of each ALT allele\">\n"
+					"##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Traversals of the site\">\n"
+					"##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Colours with a traversal of the site\">\n"
+					"##INFO=<ID=INS,Number=1,Type=Integer,Description=\"Sides inside the superbubble\">\n"
+					"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Alleles the colour walks\">\n"
+					"#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
+				for (const std::string & label : map.label)
+				{
+					buf += '\t';
+					for (char ch : label) buf += static_cast<unsigned char>(ch) <= ' ' ? '_' : ch;
+				}
+
+				buf += '\n';
+				for (const Record & record : records)
+				{
+					const size_t r = record.site;
+					const uint32_t a0 = v.alleleOffset[r], a1 = v.alleleOffset[r + 1], refAllele = v.refAllele[r], refDir = v.dir[refTraversal[r]];
+					// the record's alleles: the reference's first, then the others in allele order
+					std::vector<uint32_t> local(1, refAllele);
+					for (uint32_t a = a0; a < a1; a++) if (a != refAllele) local.push_back(a);
+					uint32_t least = v.alleleEdges[a0];
+					bool equal = v.alleleEdges[a0] >= k + 1;
+					for (uint32_t a = a0; a < a1; a++)
+					{
+						equal = equal && v.alleleEdges[a] == v.alleleEdges[a0];
+						least = std::min(least, v.alleleEdges[a]);
+					}
+
+					buf += seq.name[record.sequence] + "\t" + std::to_string(record.pos) + "\tsb" + std::to_string(r) + "\t";
+					std::vector<uint32_t> present(words, 0);
+					for (size_t i = 0; i < local.size(); i++)
+					{
+						const uint32_t a = local[i], from = i == 0 ? refTraversal[r] : v.first[a];
+						std::string letters = SpanLetters(loaded, MakeVariantSpan(t, k, v, from));
+						if (v.dir[from] != refDir) letters = ReverseComplementN(letters);
+						const uint64_t edges = v.alleleEdges[a];
+						if (letters.size() != edges + k) throw std::runtime_error("variant table: an allele's span is not its edges and k letters");
+						const std::string text = equal ? letters.substr(k, size_t(edges - k)) : letters.substr(k - 1, size_t(edges + 1 - std::min<uint64_t>(k, least)));
+						if (text.empty()) throw std::runtime_error("variant table: an allele of a record spells nothing");
+						buf += text;
+						buf += i == 0 ? '\t' : i + 1 < local.size() ? ',' : '\t';
+						for (size_t w = 0; w < words; w++) present[w] |= v.presence[size_t(a) * words + w];
+					}
+
+					buf += ".\t.\tAC=";
+					for (size_t i = 1; i < local.size(); i++) buf += std::to_string(v.traversals[local[i]]) + (i + 1 < local.size() ? "," : "");
+					uint32_t ns = 0;
+					for (uint32_t w : present) ns += uint32_t(__builtin_popcount(w));
+					buf += ";AN=" + std::to_string(v.siteTraversals[r]) + ";NS=" + std::to_string(ns) + ";INS=" + std::to_string(b.inside[r]) + "\tGT";
+					for (uint64_t c = 0; c < v.colors; c++)
+					{
+						std::string gt;
+						for (size_t i = 0; i < local.size(); i++)
+						{
+							if (v.presence[size_t(local[i]) * words + c / 32] >> (c % 32) & 1u) gt += (gt.empty() ? "" : "/") + std::to_string(i);
+						}
+
+						buf += "\t" + (gt.empty() ? std::string(".") : gt);
+					}
+
+					buf += '\n';
+					flushIfLarge();
+				}
+			});
+		}
+
+		void WriteVariantFiles(const EventTable & t, size_t k, const ColorMap & map, const InputSequences & seq, const LoadedSequences * loaded, const ColorTable & colors,
+			const SuperbubbleTable & b, const VariantTable & v, const std::string & path, const std::string & vcfPath)
+		{
+			if (!vcfPath.empty())
+			{
+				if (!loaded) throw std::runtime_error("The variant VCF needs the letters of the input");
+				WriteVariantsVcf(t, k, map, seq, *loaded, colors, b, v, vcfPath);
+			}
+
+			try
+			{
+				WriteVariants(t, k, map, seq, colors, b, v, path);
+			}
+			catch (...)
+			{
+				if (!vcfPath.empty()) ::unlink(vcfPath.c_str());
+				throw;
+			}
+		}
+
 		void ComputeAnchors(const EventTable & t, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t colors, uint32_t ref, AnchorTable & out)
 		{
 			(void)k;

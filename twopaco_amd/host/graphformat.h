@@ -643,6 +643,75 @@ namespace TwoPaCo
 		void WriteSuperbubbleFiles(const EventTable & table, size_t k, const ColorMap & map, const ColorTable & colors, uint64_t links, const SuperbubbleTable & superbubbles,
 			const std::string & path, const std::string & membersPath);
 
+		// ---------------------------------------------------------------------------------------- the variants
+		// Which allele every genome carries through every superbubble, what it spells and where it lies (include/twopaco_hip.h, the
+		// tpc_segments_variants_* group, states the definition in the same words).  side(e) = row(e) * 2 + (name[e] < 0).  A WALK (e, d)
+		// visits e, e + 1, .. reading side(x) (d = 0, '+') or e, e - 1, .. reading side(x) ^ 1 (d = 1, '-') and never leaves the events
+		// of seq(e).  It is a TRAVERSAL of superbubble row b when its first side is entrance[b] and every following side is a member of
+		// b until one is exit[b], at the event `last`, within maxInside + 1 steps.  A walk that reads a side that is neither counts in
+		// `strays`.  Traversals are numbered by (e, d), '+' first; mask has bit i set when member i of the row was read; edges =
+		// |begin[hi] - end[lo]| over lo, hi = the smaller and larger of start and last.  An ALLELE is the traversals of one row with one
+		// mask, its `first` the smallest of them; alleles ascend by (row, first).  A SITE is a row with a traversal: alleleOffset[b] ..
+		// alleleOffset[b + 1] are its alleles.  With a reference colour ref != NONE, refAllele[b] is the allele of the smallest
+		// traversal of b that starts in a sequence of that colour (NONE without one), refTraversals[b] their number.  The arrays come
+		// from ComputeVariants below -- the serial statement -- or from the device (csrc/tpc_variants.hip); the writers print either as
+		// the same bytes.
+		struct VariantTable
+		{
+			static const uint32_t NONE = 0xFFFFFFFFu;                          // ref: no reference; refAllele[]: no traversal of the reference
+			uint64_t colors, segments, strays;
+			uint32_t ref;
+			std::vector<uint32_t> start, last, dir, row, edges;                // [traversals]
+			std::vector<uint64_t> mask;                                        // [traversals]
+			std::vector<uint32_t> alleleRow, sides, alleleEdges, first, nColors; // [alleles]
+			std::vector<uint64_t> alleleMask, traversals;                      // [alleles]
+			std::vector<uint32_t> presence;                                    // [alleles][colors.Words()]
+			std::vector<uint32_t> alleleOffset;                                // [superbubbles + 1]
+			std::vector<uint32_t> refAllele;                                   // [superbubbles]
+			std::vector<uint64_t> siteTraversals, refTraversals;               // [superbubbles]
+			VariantTable() : colors(0), segments(0), strays(0), ref(NONE) {}
+			size_t Traversals() const { return start.size(); }
+			size_t Alleles() const { return first.size(); }
+			size_t Sites() const
+			{
+				size_t n = 0;
+				for (size_t b = 0; b + 1 < alleleOffset.size(); b++) n += alleleOffset[b + 1] > alleleOffset[b] ? 1 : 0;
+				return n;
+			}
+		};
+
+		// The definition as plain loops: the side of every event by a hash map from |name|, as ComputeColors numbers the rows, a map
+		// from entrance to row, both walks of every event, an ordered map from (row, mask) to the allele.  `colors` and `superbubbles`
+		// are the tables of `table`.  Every sequence needs a colour below nColors, and ref < nColors or NONE (std::runtime_error
+		// otherwise).  No device dependency.
+		void ComputeVariants(const EventTable & table, size_t k, const std::vector<uint32_t> & colorOfSequence, uint64_t nColors, const ColorTable & colors,
+			const SuperbubbleTable & superbubbles, uint32_t ref, VariantTable & out);
+
+		// The TSV text: "#twopaco-variants\t1\tby=<file|sequence>\tk=<k>\tcolors=<C>\tsegments=<S>\tsuperbubbles=<B>\tmax_inside=<M>\t
+		// ref=<R|none>\tsites=<..>\talleles=<..>\ttraversals=<..>", the colour table's "#color" lines, the anchor table's "#sequence"
+		// lines, "#alleles\t<n>\t<sites>" for every number of alleles a site has, ascending, then one line per allele: site (the
+		// superbubble row), entrance and exit each as |name| and strand, allele (from 0 within the site), traversals, sides, edges,
+		// n_colors, presence as hex, then sequence (0-based), begin, end (bases, half-open) and strand of its first traversal, and
+		// is_ref.  Integers and hex only.  To stdout (path empty) or into the file `path` (removed again when writing fails).
+		void WriteVariants(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const ColorTable & colors, const SuperbubbleTable & superbubbles,
+			const VariantTable & variants, const std::string & path);
+
+		// VCF 4.2 into the file `path`; needs a reference colour and the letters.  One record per site that has a traversal of the
+		// reference and at least two alleles, ordered by (reference sequence, POS, site); ID sb<site>; REF the reference allele, read
+		// from the reference traversal's own span, ALT the others in allele order, each spelled from its first traversal and turned to
+		// the reference traversal's stored orientation; letters other than A C G T print as N.  Alleles of equal edges E >= k + 1 are
+		// span[k : E] at POS = end[lo] + k + 1 (smaller equal edges exist only under an abundance cut); otherwise span[k - 1 : edges + k - min(k, Dmin)] at POS = end[lo] + k.  INFO: AC
+		// (traversals per ALT), AN (the site's traversals), NS (colours with a traversal), INS (inside).  One sample per colour,
+		// labelled as the PHYLIP matrix labels it; GT: the record's allele indices the colour walks, ascending, joined by '/', or '.'.
+		// No further normalisation.
+		void WriteVariantsVcf(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const LoadedSequences & loaded, const ColorTable & colors,
+			const SuperbubbleTable & superbubbles, const VariantTable & variants, const std::string & path);
+
+		// Both files, or neither: the VCF first when vcfPath is given, then the TSV (to stdout when path is empty); when the TSV cannot
+		// be written the VCF is removed again before the error is thrown.  loaded: may be 0 when vcfPath is empty.
+		void WriteVariantFiles(const EventTable & table, size_t k, const ColorMap & map, const InputSequences & seq, const LoadedSequences * loaded, const ColorTable & colors,
+			const SuperbubbleTable & superbubbles, const VariantTable & variants, const std::string & path, const std::string & vcfPath);
+
 		// ---------------------------------------------------------------------------------------- the anchor blocks
 		// Where the sequence a colour shares with a reference colour lies in both (include/twopaco_hip.h, the tpc_segments_anchors_*
 		// group, states the definition in the same words).  count[r][c]: the events of row r in sequences of colour c.  An event e of

@@ -12,7 +12,8 @@
 //             |  --locate file|sequence --locate-in <q.fa> [--locate-in ...] [--locate-out <path>] [--locate-walks <path>]
 //             |  --classes file|sequence [--classes-out <path>] [--classes-members <path>]
 //             |  --tracks file|sequence [--tracks-of <colour>] [--tracks-out <path>] [--tracks-bedgraph <path>]
-//             (the last nine instead of -f)
+//             |  --variants file|sequence [--variants-ref <colour>] [--variants-out <path>] [--variants-vcf <path>] [--superbubbles-max <n>]
+//             (the last ten instead of -f)
 // Formats (reference line numbers):
 //   seq    "chr pos id" per junction occurrence, file order (:160-168)
 //   group  occurrences of the same junction id on one line, lines ordered by their first position (:122-158)
@@ -100,7 +101,14 @@
 // merged into one interval; include/twopaco_hip.h defines them -- as TSV of integers (graphformat.h: WriteTracks) and, asked for, as
 // bedGraph of the number of colours (WriteTracksBedGraph).  Without --gpu the serial walk, then ComputeColors and ComputeTracks; with
 // --gpu the colour stage and the track stage over one segment build (csrc/tpc_tracks.hip); the bytes are the same.  It goes with
-// what --classes goes with, and with --classes, of the same colours, and is written last; not with -f, --links, --bubbles or --text.
+// what --classes goes with, and with --classes, of the same colours, and is written after every other table but the variant table;
+// not with -f, --links, --bubbles or --text.
+// --variants file|sequence [--variants-ref <colour>] [--variants-out <path>] [--variants-vcf <path>] (an addition; instead of -f): the
+// alleles every genome walks through every superbubble -- include/twopaco_hip.h defines walk, traversal, allele and site -- as TSV of
+// integers (graphformat.h: WriteVariants) and, with a reference colour, as VCF 4.2 (WriteVariantsVcf).  Without --gpu the serial walk,
+// then ComputeColors, ComputeLinks, ComputeSuperbubbles and ComputeVariants; with --gpu the colour, link, superbubble and variant stages
+// over one segment build (csrc/tpc_variants.hip); the bytes are the same.  It goes with what --tracks goes with, and with --tracks, of
+// the same colours, and is written last; not with -f, --links, --bubbles or --text.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -455,6 +463,11 @@ namespace
 		{
 			throw ArgError("Value '" + std::to_string(request.tracksOf) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--tracks-of)");
 		}
+
+		if (request.On(VARIANTS) && request.variantsRef != VariantTable::NONE && request.variantsRef >= map.label.size())
+		{
+			throw ArgError("Value '" + std::to_string(request.variantsRef) + "' does not meet constraint: a colour index below " + std::to_string(map.label.size()), "Argument: (--variants-ref)");
+		}
 	}
 
 	// A table request, serial: one walk (with the letters when the edge index reads them), the serial statements the request needs,
@@ -466,6 +479,7 @@ namespace
 		Tables tables;
 		MakeRequestColors(request, t.seq, fasta, tables.map);
 		LoadQueries(request, 1, tables);
+		if (NeedsLetters(request)) tables.letters = &t.loaded;
 		ComputeTables(t.table, t.loaded, k, request, tables);
 		WriteTables(COLORS, t.table, k, request, t.seq, tables, [](int) {});
 	}
@@ -492,11 +506,11 @@ namespace
 		double loadMs, packMs, deviceMs, kernelMs, indexMs, formatMs, textKernelMs;
 		double stageMs[TABLES + 1], stageKernelMs[TABLES + 1];  // of the stages of BuildTables: the tables', and EDGES
 		uint64_t links, linkOccurrences, bubbles, components, largestComponent, superbubbles, superbubbleMembers, superbubblesUnmirrored, anchorBlocks, anchors;
-		uint64_t locateRuns, locateBatches, classes, largestClass, trackIntervals;
+		uint64_t locateRuns, locateBatches, classes, largestClass, trackIntervals, variantAlleles;
 		size_t threads;
 		DumpStats() : path("host"), text("host"), events(0), segments(0), nNamed(0), deviceBytes(0), streamBytes(0), textBytes(0), tableBytes(0), loadMs(0), packMs(0),
 			deviceMs(0), kernelMs(0), indexMs(0), formatMs(0), textKernelMs(0), stageMs(), stageKernelMs(), links(0), linkOccurrences(0), bubbles(0), components(0), largestComponent(0),
-			superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), locateRuns(0), locateBatches(0), classes(0), largestClass(0), trackIntervals(0), threads(1) {}
+			superbubbles(0), superbubbleMembers(0), superbubblesUnmirrored(0), anchorBlocks(0), anchors(0), locateRuns(0), locateBatches(0), classes(0), largestClass(0), trackIntervals(0), variantAlleles(0), threads(1) {}
 
 		// TWOPACO_GRAPHDUMP_STATS=<file>: one JSON object (never on stderr, whose bytes are compared with the reference's)
 		void Write() const
@@ -515,7 +529,8 @@ namespace
 				"\"anchors_kernel_ms\": %.3f, \"anchors_ms\": %.3f, \"anchor_blocks\": %llu, \"anchors\": %llu, "
 				"\"edges_kernel_ms\": %.3f, \"edges_ms\": %.3f, \"locate_kernel_ms\": %.3f, \"locate_ms\": %.3f, \"locate_runs\": %llu, \"locate_batches\": %llu, "
 				"\"classes_kernel_ms\": %.3f, \"classes_ms\": %.3f, \"classes\": %llu, \"largest_class\": %llu, "
-				"\"tracks_kernel_ms\": %.3f, \"tracks_ms\": %.3f, \"track_intervals\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
+				"\"tracks_kernel_ms\": %.3f, \"tracks_ms\": %.3f, \"track_intervals\": %llu, "
+				"\"variants_kernel_ms\": %.3f, \"variants_ms\": %.3f, \"variant_alleles\": %llu}\n", path.c_str(), (unsigned long long)events, (unsigned long long)segments, (unsigned long long)nNamed, deviceMs, kernelMs, loadMs,
 				packMs, indexMs, formatMs, (unsigned long long)threads, (unsigned long long)deviceBytes, (unsigned long long)streamBytes, (unsigned long long)textBytes,
 				(unsigned long long)tableBytes, text.c_str(), textKernelMs, stageKernelMs[COLORS], stageMs[COLORS], stageKernelMs[LINKS], stageMs[LINKS], (unsigned long long)links,
 				(unsigned long long)linkOccurrences, stageKernelMs[BUBBLES], stageMs[BUBBLES], (unsigned long long)bubbles, stageKernelMs[DISTANCES], stageMs[DISTANCES],
@@ -523,7 +538,8 @@ namespace
 				stageMs[SUPERBUBBLES], (unsigned long long)superbubbles, (unsigned long long)superbubbleMembers, (unsigned long long)superbubblesUnmirrored, stageKernelMs[ANCHORS],
 				stageMs[ANCHORS], (unsigned long long)anchorBlocks, (unsigned long long)anchors, stageKernelMs[EDGES], stageMs[EDGES], stageKernelMs[LOCATE], stageMs[LOCATE],
 				(unsigned long long)locateRuns, (unsigned long long)locateBatches, stageKernelMs[CLASSES], stageMs[CLASSES], (unsigned long long)classes,
-				(unsigned long long)largestClass, stageKernelMs[TRACKS], stageMs[TRACKS], (unsigned long long)trackIntervals);
+				(unsigned long long)largestClass, stageKernelMs[TRACKS], stageMs[TRACKS], (unsigned long long)trackIntervals, stageKernelMs[VARIANTS],
+				stageMs[VARIANTS], (unsigned long long)variantAlleles);
 			std::fclose(f);
 		}
 	};
@@ -659,7 +675,7 @@ namespace
 	}
 
 	// graphdump's clock around the stages of BuildTables: DumpStats and the [timing] lines (the colour table's comes last, after the files)
-	const char * const STAGE_TIMING[TABLES + 1] = {0, "link table", "bubble table", "distance matrices", "component table", "superbubble table", "anchor table", "locate", "class table", "track table", "edge index"};
+	const char * const STAGE_TIMING[TABLES + 1] = {0, "link table", "bubble table", "distance matrices", "component table", "superbubble table", "anchor table", "locate", "class table", "track table", "variant table", "edge index"};
 	const StageWording GPU_WORDING = {"--gpu: the ", "colour map"};
 
 	void BuildTablesTimed(DeviceLibrary & lib, const TableRequest & request, const uint64_t * counts, bool linkBits, Tables & tables, DumpStats & stats)
@@ -695,6 +711,7 @@ namespace
 		stats.classes = tables.classes.Rows();
 		stats.largestClass = tables.classes.Largest();
 		stats.trackIntervals = tables.tracks.Rows();
+		stats.variantAlleles = tables.variants.Alleles();
 	}
 
 	// A table request with --gpu: one segment build, the table stays on the device, and the stages that are wanted run there
@@ -711,6 +728,7 @@ namespace
 		MakeRequestColors(request, seq, fasta, tables.map);
 		if (NeedsColorMap(request) && tables.map.colorOfSequence.size() != sequences) throw std::runtime_error(PACKER_DISAGREES);
 		LoadQueries(request, threads, tables);
+		tables.letters = &loaded;
 		BuildTablesTimed(lib, request, counts, false, tables, stats);
 		Events held(counts[0], sequences);
 		if (NeedsEventTable(request)) FetchTable(lib, held);
@@ -788,7 +806,7 @@ namespace
 	// ---------------------------------------------------------------------------------------- command line
 	void Usage()
 	{
-		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>] [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>] [--tracks <file|sequence>] [--tracks-of <integer>] [--tracks-out <file name>] [--tracks-bedgraph <file name>] [--] [--version] [-h] <file name>\n\n"
+		std::printf("\nUSAGE: \n\n   graphdump  [-k <integer>] [-s <string>] ... -f <seq|group|dot|gfa1|gfa2|fasta> [--prefix] [--gpu [<device>]] [--threads <integer>] [--text <host|device>] [--colors <file|sequence>] [--colors-out <file name>] [--links] [--links-out <file name>] [--compact] [--bubbles <file|sequence>] [--bubbles-out <file name>] [--distances <file|sequence>] [--distances-out <file name>] [--distances-phylip <file name>] [--components <file|sequence>] [--components-out <file name>] [--components-members <file name>] [--superbubbles <file|sequence>] [--superbubbles-out <file name>] [--superbubbles-members <file name>] [--superbubbles-max <integer>] [--anchors <file|sequence>] [--anchors-ref <integer>] [--anchors-out <file name>] [--anchors-paf <file name>] [--classes <file|sequence>] [--classes-out <file name>] [--classes-members <file name>] [--tracks <file|sequence>] [--tracks-of <integer>] [--tracks-out <file name>] [--tracks-bedgraph <file name>] [--variants <file|sequence>] [--variants-ref <integer>] [--variants-out <file name>] [--variants-vcf <file name>] [--] [--version] [-h] <file name>\n\n"
 			"Where: \n\n"
 			"   -k <integer>,  --kvalue <integer>\n     (required)  Value of k\n\n"
 			"   -s <string>,  --seqfile <string>  (accepted multiple times)\n     sequences file name\n\n"
@@ -880,6 +898,18 @@ namespace
 			"   --tracks-of <integer>\n     with --tracks: the intervals of the sequences of this one colour only (default: all colours)\n\n"
 			"   --tracks-out <file name>\n     with --tracks: write the table there instead of to the standard output\n\n"
 			"   --tracks-bedgraph <file name>\n     with --tracks: also write the number of colours per interval there as bedGraph\n\n"
+			"   --variants <file|sequence>\n     instead of -f: the alleles the genomes walk through the superbubbles as TSV of integers -- every sequence is walked\n"
+			"     through every superbubble (of at most --superbubbles-max sides inside) on both strands; the walks from entrance to exit\n"
+			"     that read the same inside sides are one allele.  Per allele: site (the row of --superbubbles), entrance and exit, its\n"
+			"     number within the site, traversals, sides, edges, number of colours and presence bits, the span of its first traversal\n"
+			"     (sequence, begin, end in bases, strand) and whether it is the reference's; in front the colours, the sequences and the\n"
+			"     sites by number of alleles.  Needs -k and -s.  With --gpu the walks and the alleles are found on the device.  Goes with\n"
+			"     what --tracks goes with, and with --tracks, of the same colours (this table is written last); not with --links,\n"
+			"     --bubbles or --text.\n\n"
+			"   --variants-ref <integer>\n     with --variants: the reference colour (default: none)\n\n"
+			"   --variants-out <file name>\n     with --variants: write the table there instead of to the standard output\n\n"
+			"   --variants-vcf <file name>\n     with --variants and --variants-ref: also write VCF 4.2 there, positions on the reference colour's sequences, one\n"
+			"     sample per colour; not normalised (bcftools norm does that)\n\n"
 			"   <file name>\n     (required)  input file name\n\n"
 			"   This utility converts the binary output of TwoPaCo to another format\n\n");
 	}
@@ -962,9 +992,9 @@ int main(int argc, char * argv[])
 		// A table instead of -f.  The link table goes with no other, the bubble table not with the colour table, the class table with
 		// what the colour table goes with, none but the colour, the class and the link table's own complaint with --compact; the complaints are looked for from the last table back, the link table's last.
 		const unsigned linksBit = 1u << LINKS;
-		const TableCliRules rules = {"Argument: ", {TRACKS, CLASSES, LOCATE, ANCHORS, SUPERBUBBLES, COMPONENTS, DISTANCES, BUBBLES, COLORS, LINKS}, true, haveFormat, compact, textSet,
-			{0, 1u << COLORS, 1u << COLORS | linksBit, linksBit, linksBit, linksBit, linksBit, linksBit, 1u << BUBBLES | linksBit, 1u << BUBBLES | linksBit},
-			{false, false, true, true, true, true, true, true, false, false}, 1, false, 0};
+		const TableCliRules rules = {"Argument: ", {VARIANTS, TRACKS, CLASSES, LOCATE, ANCHORS, SUPERBUBBLES, COMPONENTS, DISTANCES, BUBBLES, COLORS, LINKS}, true, haveFormat, compact, textSet,
+			{0, 1u << COLORS, 1u << COLORS | linksBit, linksBit, linksBit, linksBit, linksBit, linksBit, 1u << BUBBLES | linksBit, 1u << BUBBLES | linksBit, 1u << BUBBLES | linksBit},
+			{false, false, true, true, true, true, true, true, false, false, false}, 1, false, 0};
 		CheckTableOptions(tables, rules);
 		const TableRequest & request = tables.request;
 		if (compact && format != "gfa1") throw ArgError("The compact text is gfa1 with every link once: it needs -f gfa1", "(--compact)");

@@ -20,7 +20,7 @@ namespace TwoPaCo
 	namespace GraphFormat
 	{
 		// in the order the tables are written
-		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, CLASSES, TRACKS, TABLES };
+		enum TableId { COLORS, LINKS, BUBBLES, DISTANCES, COMPONENTS, SUPERBUBBLES, ANCHORS, LOCATE, CLASSES, TRACKS, VARIANTS, TABLES };
 
 		enum Reads { NOTHING, BUILD, ROWS };  // of a device stage: not read, built and read where it lies, its rows fetched for the files
 
@@ -49,6 +49,7 @@ namespace TwoPaCo
 			{"locate", "locate", true, "walks", "The locate walks", true, "--locate-in", ROWS, NOTHING, true, true},
 			{"classes", "class", true, "members", "The class members", true, 0, ROWS, NOTHING, true, false},
 			{"tracks", "track", true, "bedgraph", "The track bedGraph", false, "--tracks-of", ROWS, NOTHING, true, false},
+			{"variants", "variant", true, "vcf", "The variant VCF", false, "--variants-ref", ROWS, BUILD, true, true},
 		};
 
 		struct TableRequest
@@ -64,8 +65,9 @@ namespace TwoPaCo
 			bool bySequence;                    // the colours of all tables: the input's sequences, or its files
 			uint32_t superbubblesMax, anchorsRef;
 			uint32_t tracksOf;                  // the one colour of the track table, TrackTable::ALL: every colour
+			uint32_t variantsRef;               // the reference colour of the variant table, VariantTable::NONE: none
 			std::vector<std::string> locateIn;  // the FASTA files of the queries
-			TableRequest() : bySequence(false), superbubblesMax(62), anchorsRef(0), tracksOf(TrackTable::ALL) {}
+			TableRequest() : bySequence(false), superbubblesMax(62), anchorsRef(0), tracksOf(TrackTable::ALL), variantsRef(VariantTable::NONE) {}
 
 			bool On(TableId t) const { return table[t].on; }
 			bool Any() const
@@ -92,6 +94,8 @@ namespace TwoPaCo
 		inline bool NeedsLinkBuild(const TableRequest & r) { return ReadsAtLeast(r, &TableRow::linkStage, BUILD); }
 		inline bool NeedsLinkRows(const TableRequest & r) { return ReadsAtLeast(r, &TableRow::linkStage, ROWS); }
 		inline bool NeedsColorMap(const TableRequest & r) { return NeedsColorBuild(r) || r.On(ANCHORS); }
+		// the superbubble table is built for its own files and for the variant table, which walks the genomes through its rows
+		inline bool NeedsSuperbubbleBuild(const TableRequest & r) { return r.On(SUPERBUBBLES) || r.On(VARIANTS); }
 		inline bool NeedsEventTable(const TableRequest & r)
 		{
 			for (int t = 0; t < TABLES; t++) if (r.table[t].on && TABLE_ROWS[t].events) return true;
@@ -184,6 +188,7 @@ namespace TwoPaCo
 			else if (a == "--anchors-ref") o.request.anchorsRef = uint32_t(ParseBounded(value(tag), 0, 0x7FFFFFFFll, "a colour index", constraintTag + tag));
 			else if (a == "--locate-in") o.request.locateIn.push_back(value(tag));
 			else if (a == "--tracks-of") o.request.tracksOf = uint32_t(ParseBounded(value(tag), 0, 0x7FFFFFFFll, "a colour index", constraintTag + tag));
+			else if (a == "--variants-ref") o.request.variantsRef = uint32_t(ParseBounded(value(tag), 0, 0x7FFFFFFFll, "a colour index", constraintTag + tag));
 			for (int t = 0; t < TABLES; t++)
 			{
 				const TableRow & row = TABLE_ROWS[t];
@@ -217,7 +222,8 @@ namespace TwoPaCo
 				const std::string flag = std::string("--") + row.name, tag = "(" + flag + ")";
 				if (!file.on)
 				{
-					const bool orphan[3] = {o.outSet[t], o.secondSet[t], o.extraSet[t]};
+					// (--superbubbles-max is the variant table's as well)
+					const bool orphan[3] = {o.outSet[t], o.secondSet[t], o.extraSet[t] && !(t == SUPERBUBBLES && r.table[VARIANTS].on)};
 					const std::string option[3] = {flag + "-out", row.second ? flag + "-" + row.second : "", row.extra ? row.extra : ""};
 					const int first = rules.queryOrphanFirst && t == LOCATE ? 2 : 0;
 					for (int i = 0; i < 3; i++)
@@ -264,6 +270,12 @@ namespace TwoPaCo
 				{
 					throw ArgError("Value '" + std::to_string(r.tracksOf) + "' does not meet constraint: a colour index below " + std::to_string(rules.inputFiles), "(--tracks-of)");
 				}
+
+				if (t == VARIANTS && o.secondSet[t] && !o.extraSet[t]) throw ArgError("The variant VCF needs a reference colour: --variants-ref <integer>", "(" + flag + "-" + row.second + ")");
+				if (t == VARIANTS && rules.inputFiles && o.by[t] == "file" && r.variantsRef != VariantTable::NONE && r.variantsRef >= rules.inputFiles)
+				{
+					throw ArgError("Value '" + std::to_string(r.variantsRef) + "' does not meet constraint: a colour index below " + std::to_string(rules.inputFiles), "(--variants-ref)");
+				}
 			}
 
 			for (int t = TABLES; t-- > 0;) if (r.table[t].on && TABLE_ROWS[t].colours) r.bySequence = o.by[t] == "sequence";
@@ -283,10 +295,12 @@ namespace TwoPaCo
 			LocateTable locate;
 			ClassTable classes;
 			TrackTable tracks;
+			VariantTable variants;
+			const LoadedSequences * letters; // of the input, for the variant VCF: the caller's, 0 when they were not loaded
 			InputSequences queries;         // of request.locateIn
 			LoadedSequences queryLetters;
 			uint64_t segments, linkRows;    // the rows of the colour table and of the link table, fetched or not
-			Tables() : segments(0), linkRows(0) {}
+			Tables() : letters(0), segments(0), linkRows(0) {}
 		};
 
 		inline void LoadQueries(const TableRequest & request, size_t threads, Tables & t)
@@ -305,7 +319,7 @@ namespace TwoPaCo
 			if (request.On(BUBBLES)) ComputeBubbles(table, t.links, t.bubbles);
 			if (request.On(DISTANCES)) ComputeDistances(table, t.colors, t.distances);
 			if (request.On(COMPONENTS)) ComputeComponents(table, k, t.links, t.colors, t.components);
-			if (request.On(SUPERBUBBLES)) ComputeSuperbubbles(table, k, t.links, t.colors, request.superbubblesMax, t.superbubbles);
+			if (NeedsSuperbubbleBuild(request)) ComputeSuperbubbles(table, k, t.links, t.colors, request.superbubblesMax, t.superbubbles);
 			if (request.On(ANCHORS)) ComputeAnchors(table, k, t.map.colorOfSequence, t.map.label.size(), request.anchorsRef, t.anchors);
 			if (request.On(LOCATE))
 			{
@@ -317,6 +331,7 @@ namespace TwoPaCo
 
 			if (request.On(CLASSES)) ComputeClasses(table, k, t.colors, t.classes);
 			if (request.On(TRACKS)) ComputeTracks(table, k, t.map.colorOfSequence, t.map.label.size(), t.colors, request.tracksOf, t.tracks);
+			if (request.On(VARIANTS)) ComputeVariants(table, k, t.map.colorOfSequence, t.map.label.size(), t.colors, t.superbubbles, request.variantsRef, t.variants);
 		}
 
 		// One table's files, if it is wanted
@@ -336,6 +351,7 @@ namespace TwoPaCo
 			case LOCATE: WriteLocateFiles(table, k, t.map, t.colors, t.queries, t.locate, f.out, f.second); break;
 			case CLASSES: WriteClassFiles(table, k, t.map, t.colors, t.classes, f.out, f.second); break;
 			case TRACKS: WriteTrackFiles(table, k, t.map, seq, t.colors, t.tracks, f.out, f.second); break;
+			case VARIANTS: WriteVariantFiles(table, k, t.map, seq, t.letters, t.colors, t.superbubbles, t.variants, f.out, f.second); break;
 			}
 		}
 

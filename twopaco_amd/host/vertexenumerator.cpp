@@ -1011,6 +1011,7 @@ namespace TwoPaCo
 				const std::vector<uint64_t> ambiguous = DeviceGraph::AmbiguousPositions(text, loaded, disagree);
 				const size_t sequences = text.recStart.size();
 				Tables tables;
+				tables.letters = &loaded;
 				LoadQueries(request, threads, tables);
 				auto makeColorMap = [&]()
 				{
@@ -1025,6 +1026,11 @@ namespace TwoPaCo
 					if (request.On(TRACKS) && request.tracksOf != TrackTable::ALL && request.tracksOf >= tables.map.label.size())
 					{
 						throw std::runtime_error("The track table's one colour is " + std::to_string(request.tracksOf) + ", there are " + std::to_string(tables.map.label.size()) + " colours");
+					}
+
+					if (request.On(VARIANTS) && request.variantsRef != VariantTable::NONE && request.variantsRef >= tables.map.label.size())
+					{
+						throw std::runtime_error("The variant table's reference colour is " + std::to_string(request.variantsRef) + ", there are " + std::to_string(tables.map.label.size()) + " colours");
 					}
 				};
 
@@ -1077,13 +1083,13 @@ namespace TwoPaCo
 					{
 						if (counts[0]) DeviceGraph::FetchNames(api, held);
 						if (counts[0]) DeviceGraph::FetchPositions(api, held);
-						if (request.On(ANCHORS) || request.On(TRACKS)) DeviceGraph::FetchSequences(api, held);
+						if (request.On(ANCHORS) || request.On(TRACKS) || request.On(VARIANTS)) DeviceGraph::FetchSequences(api, held);
 					}
 
 					makeColorMap();
 					// twopaco's clock around the stages: a lap after every build and every fetch, the kernels' time after the build's
 					static const char * const lap[TABLES + 1] = {"segment colours", "segment links", "segment bubbles", "segment distances", "segment components",
-						"segment superbubbles", "segment anchors", "locate", "segment classes", "segment tracks", "edge index"};
+						"segment superbubbles", "segment anchors", "locate", "segment classes", "segment tracks", "segment variants", "edge index"};
 					DeviceGraph::StageObserver observer;
 					observer.built = [&](int stage, int kernel)
 					{
